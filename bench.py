@@ -2,13 +2,18 @@
 """Benchmark of the Mip-NeRF hot path on MI355X (contract: see the task statement).
 
     python bench.py --gpus 1 --steps 50 --warmup 5
-    python bench.py --gpus 8                       # re-executes itself under torch.distributed.run, one rank per GPU (RCCL)
+    python bench.py --gpus 1 --full                # + every sub-record, roofline, ceiling, sustained figure and CPU baseline below
+    python bench.py --gpus 1 --dump-outputs DIR    # + the last timed step's outputs as DIR/<name>.npy (float32)
+    python bench.py --gpus 8                       # starts itself under torch.distributed.run, one rank per GPU (RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set up, pre-heat + W warm-up steps, K timed steps, the outputs (--dump-outputs), the
+JSON line.  Everything else described below runs only with --full.
 
 Headline (top level of the JSON line): a "step" is one MipNerf.forward (coarse + fine level) over one batch of synthetic
 lego-like rays resident in HBM: BASELINE.json configs[1] = 4096 rays x (128 + 128) samples, bf16 MLP.
 metric = ray-samples/sec (whole job, all ranks), ray-samples per step = B x N x num_levels.  Ranks shard rays
-(independent, no data-path collective): weak scaling.  The default run (`--mode all`) also carries two sub-records,
+(independent, no data-path collective): weak scaling.  The --full run (`--mode all`) also carries two sub-records,
 each with its own timed region (same barrier + synchronize bracketing, max over ranks) and its own roofline:
 
   "train":  one training step = randomized forward + loss (incl. distloss) + backward + gradient all-reduce (RCCL, one
@@ -36,6 +41,7 @@ FLOP_PER_SAMPLE = 1_220_608          # 2 x 610,304 MAC of the ML
 FLOP_PER_SAMPLE_TRAIN = 3_556_608    # forward + dgrad + wgrad
 CURRENT_ROUND = 6          # profiles/mlp_pmc.json must carry this round's PMC passes (VERDICT r03 hygiene): bump it and re-run scripts/pmc_traffic.sh every round
 PEAK_TFLOPS = {"bf16": 2500.0, "fp32": 157.3}   # MI355X_MICROARCH.md dense MFMA peaks
+MAX_DUMP_BYTES = 60_000_000          # --dump-outputs: data of all arrays together, under 64 MB with the .npy headers
 
 
 def parse_args():
@@ -49,9 +55,14 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-lightning-route", action="store_true", help="train: skip the lightning_route sub-record (PMC passes: its per-level "
                     "launches would mix into the per-kernel means)")
-    ap.add_argument("--mode", default="all", choices=["all", "inference", "train", "render"],
-                    help="all (default): headline inference + train and render sub-records; inference / train / render: "
-                         "only that workload, reported at the top level")
+    ap.add_argument("--full", action="store_true", help="also every measurement beyond the headline: the sub-records (--mode defaults to "
+                    "all), rooflines from instrumented re-runs, the sustained figure, the MFMA ceiling, the CPU baseline, the live parity "
+                    "records and the scale model.  Off: the run times the headline steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step (rank 0) "
+                    "as DIR/<name>.npy, float32; above %d bytes in all, the same seeded sample of rays from every array" % MAX_DUMP_BYTES)
+    ap.add_argument("--mode", default=None, choices=["all", "inference", "train", "render"],
+                    help="all (default with --full): headline inference + train and render sub-records; inference (default without "
+                         "--full) / train / render: only that workload, reported at the top level")
     ap.add_argument("--autograd", action="store_true", help="train: training_step + loss.backward() through the custom "
                     "autograd Functions (what a Lightning loop does) instead of the single native mipnerf_train_step call")
     ap.add_argument("--torch-adam", action="store_true", help="train: torch.optim.Adam on per-tensor gradients "
@@ -67,20 +78,26 @@ def parse_args():
     ap.add_argument("--sustain-seconds", type=float, default=2.0, help="inference: extra steps after the timed region")
     ap.add_argument("--host-rays", action="store_true", help="inference: the 52 B/ray batch comes from pinned host memory every step "
                     "(what the reference's DataLoader hands over): the PCIe-inclusive rate quoted in DESIGN.md, never `value` of the default line")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.mode is None:
+        args.mode = "all" if args.full else "inference"
+    return args
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher environment: become N ranks, one per GPU, under
+    """`python bench.py --gpus N` with N > 1 and no launcher environment: run N ranks, one per GPU, under
     torch.distributed.run on this node (what the reference's train.py does with devices=num_gpus + DDPPlugin,
-    train.py:56-60)."""
+    train.py:56-60) in a child process, and exit with its status."""
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    import subprocess
+    sys.exit(subprocess.call(cmd))
 
 
 class Env:
@@ -201,6 +218,30 @@ def timed(e, step, warmup, steps, return_local=False):
     return dt, out
 
 
+def level_outputs(out):
+    """The per-level outputs of MipNerf.forward (what a caller of the timed step receives), copied to the host as float32."""
+    names = ("rgb", "distance", "acc", "weights", "t_samples")
+    return {f"level{lvl}_{n}": t.detach().float().cpu().numpy() for lvl, ts in enumerate(out) for n, t in zip(names, ts)}
+
+
+def write_outputs(d, arrays, cap=MAX_DUMP_BYTES):
+    """--dump-outputs: every array as d/<name>.npy in float32.  Above `cap` bytes in all, every array whose first axis is the rays keeps
+    the same seeded sample of rays, so that the files of two builds still compare element for element."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > cap:
+        n = max(a.shape[0] for a in arrays.values() if a.ndim)
+        per_row = sum(a.nbytes // n for a in arrays.values() if a.ndim and a.shape[0] == n)
+        keep = max(1, (cap - (total - per_row * n)) // per_row)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: (a[rows] if a.ndim and a.shape[0] == n else a) for k, a in arrays.items()}
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def launch_stats(ctx):
     import ctypes as C
     from mipnerf_pl_amd import _lib as L
@@ -243,32 +284,36 @@ def run_inference(args, e):
         gf = GraphedForward(model, B, True, e.dev)
         for dst, src in zip(gf.static_in, R):
             dst.copy_(src)
-        ref_out = step_eager()
-        got_out = gf.replay()
-        torch.cuda.synchronize()
-        assert all(torch.equal(a, b) for la, lb in zip(got_out, ref_out) for a, b in zip(la, lb)), "graph replay != eager forward"
+        if args.full:
+            ref_out = step_eager()
+            got_out = gf.replay()
+            torch.cuda.synchronize()
+            assert all(torch.equal(a, b) for la, lb in zip(got_out, ref_out) for a, b in zip(la, lb)), "graph replay != eager forward"
 
     def step():
         return gf.replay() if gf is not None else step_eager()
     step()
-    ctx = model.mlp.native(e.dev)
     preheat(step, e)
     for _ in range(args.warmup):
         step()
     dt, out = timed(e, step, 0, args.steps)
-    # launch duration of the MLP kernel: HIP events around every MLP launch (on the launch stream).  Events cannot be read per replay
-    # inside a graph, so when the timed steps were graph replays the SAME K steps run once more as eager launches right behind them,
-    # instrumented (its own barrier-to-barrier time is reported as `eager_ms_per_step`)
-    ctx.set_option(2, 1)
-    if gf is not None and gf.graph:
-        dt_eager, _ = timed(e, step_eager, 0, args.steps)
-    else:
-        dt_eager = None
-        ctx.set_option(2, 0)
+    dump = level_outputs(out) if args.dump_outputs else None
+    dt_eager, tot_ms, nl = None, 0.0, 0
+    if args.full:
+        # launch duration of the MLP kernel: HIP events around every MLP launch (on the launch stream).  Events cannot be read per replay
+        # inside a graph, so when the timed steps were graph replays the SAME K steps run once more as eager launches right behind them,
+        # instrumented (its own barrier-to-barrier time is reported as `eager_ms_per_step`)
+        ctx = model.mlp.native(e.dev)
         ctx.set_option(2, 1)
-        dt, out = timed(e, step, 0, args.steps)       # eager steps: instrument the timed region itself, as in rounds 1-4
-    tot_ms, nl = launch_stats(ctx)
-    ctx.set_option(2, 0)
+        if gf is not None and gf.graph:
+            dt_eager, _ = timed(e, step_eager, 0, args.steps)
+        else:
+            ctx.set_option(2, 0)
+            ctx.set_option(2, 1)
+            dt, out = timed(e, step, 0, args.steps)       # eager steps: instrument the timed region itself, as in rounds 1-4
+            dump = level_outputs(out) if args.dump_outputs else None
+        tot_ms, nl = launch_stats(ctx)
+        ctx.set_option(2, 0)
     assert bool(torch.isfinite(out[-1][0]).all())
     M = B * N
     samples_per_step = B * N * model.num_levels
@@ -288,7 +333,7 @@ def run_inference(args, e):
                                       "replays" if dt_eager is not None else "HIP events around every MLP launch of the timed region")}
     # sustained: keep stepping for >= sustain-seconds; the package settles on its power budget (DVFS)
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         per = max(1, int(0.25 / max(dt / args.steps, 1e-5)))
         t_end = time.perf_counter() + args.sustain_seconds
         while time.perf_counter() < t_end:          # un-instrumented heat-up
@@ -309,7 +354,7 @@ def run_inference(args, e):
         if nl2 > 0:
             tf2 = FLOP_PER_SAMPLE * M / (tot2 / nl2 * 1e-3) / 1e12
             sustained.update({"launch_ms": round(tot2 / nl2, 4), "achieved": round(tf2, 2), "frac": round(tf2 / peak, 4)})
-    ctx.set_option(2, 0)
+        ctx.set_option(2, 0)
     rec = {"value": round(value, 1), "ms_per_step": round(dt / args.steps * 1e3, 4), "steps": args.steps, "warmup": args.warmup,
            "scaling": "weak", "roofline": roofline, "sustained": sustained,
            "config": {"workload": (f"BASELINE.json configs[1]: MipNerf.forward inference, {B} rays x ({N} coarse + {N} fine) "
@@ -319,6 +364,8 @@ def run_inference(args, e):
                       "eager_ms_per_step": None if dt_eager is None else round(dt_eager / args.steps * 1e3, 4),
                       "inputs": "pinned host memory, copied every step (PCIe-inclusive)" if args.host_rays else "resident in HBM",
                       "parallelism": f"ray-split x{e.world} (no data-path collective)"}}
+    if dump is not None:
+        rec["outputs"] = dump
     return rec, (rays_np, params)
 
 
@@ -436,6 +483,7 @@ def run_train(args, e):
     if graphed:
         gstep.allreduce_stats()                              # drop the events of the first (capturing) step
     dt, out, dt_local = timed(e, step, args.warmup, args.steps, return_local=True)
+    dump = {"loss": out[-1][0].detach().float().cpu().numpy()} if args.dump_outputs else None
     assert bool(torch.isfinite(out[-1][0]).all())
     samples_per_step = B * N * model.num_levels
     value = samples_per_step * e.world * args.steps / dt
@@ -470,7 +518,7 @@ def run_train(args, e):
                                 "frac_of_peak": round(traffic / (ms * 1e-3) / 8e12, 4),
                                 "note": "store-everything backprop: 3.73 TFLOP / 20.9 GB = 178 FLOP/B, below the 312 FLOP/B ridge"}
     lightning = None
-    if e.world == 1 and args.precision == "bf16" and not args.autograd and not args.no_lightning_route:
+    if args.full and e.world == 1 and args.precision == "bf16" and not args.autograd and not args.no_lightning_route:
         try:
             lightning = run_lightning_route(args, e, model0.state_dict(), R, gt, N)
             lightning["vs_graphed_step"] = round(lightning["ms_per_step"] / ms, 4)
@@ -488,6 +536,8 @@ def run_train(args, e):
                       "collective_path": bool(graphed and gstep.collective),
                       "lr_schedule": "device" if graphed else "host",
                       "parallelism": f"data-parallel x{e.world}, one {4 * sum(p.numel() for p in model.parameters())} B all-reduce per step"}}
+    if dump is not None:
+        rec["outputs"] = dump
     return rec
 
 
@@ -674,6 +724,7 @@ def run_render(args, e):
     warm = args.warmup if args.mode == "render" else 1
     step()
     dt, out = timed(e, step, warm, frames)           # (a frame is 140 ms of back-to-back launches: no pre-heat needed)
+    dump = {"fine_rgb": out[-1][0].detach().float().cpu().numpy()} if args.dump_outputs else None
     assert bool(torch.isfinite(out[-1][0]).all())
     samples_per_frame = Himg * Wimg * N * system.mip_nerf.num_levels
     ms = dt / frames * 1e3
@@ -688,11 +739,13 @@ def run_render(args, e):
                                    f"over {e.world} rank(s), rgb all-gathered"),
                       "mode": "render", "samples_per_level": N, "frame_rays": Himg * Wimg,
                       "rays_per_gpu_max": shard_bounds(Himg * Wimg, 0, e.world)[1], "parallelism": f"ray-split x{e.world}, all_gather of 12 B/ray"}}
-    if e.world == 1 and N == 128:
+    if args.full and e.world == 1 and N == 128:
         try:
             rec["reference_frame"] = render_reference_frame(args, e, frames)
         except Exception as ex:      # noqa: BLE001  (a sub-record must not take the bench line down)
             rec["reference_frame"] = {"error": f"{type(ex).__name__}: {ex}"}
+    if dump is not None:
+        rec["outputs"] = dump
     return rec
 
 
@@ -1115,29 +1168,35 @@ def main():
         recs["train"] = sub("train", run_train)
     if args.mode in ("all", "render"):
         recs["render"] = sub("render", run_render)
-    if args.mode == "all" and not args.no_fp32 and args.precision == "bf16":
+    if args.full and args.mode == "all" and not args.no_fp32 and args.precision == "bf16":
         recs["fp32"] = sub("fp32", run_fp32_c4)
-    if args.mode == "all" and args.rays == 4096 and args.samples == 128:      # the default (driver) invocation
+    if args.full and args.mode == "all" and args.rays == 4096 and args.samples == 128:      # the default (driver) invocation
         recs["trained_field"] = sub("trained_field", run_trained_field)
         if not args.no_fp32 and args.precision == "bf16":
             recs["variants"] = sub("variants", run_variants)
     ceiling = None
-    if args.mode in ("all", "inference") and args.precision == "bf16" and e.world == 1 and args.ceiling_seconds > 0:
+    if args.full and args.mode in ("all", "inference") and args.precision == "bf16" and e.world == 1 and args.ceiling_seconds > 0:
         try:
             ceiling = run_ceiling(args, e)
         except Exception as ex:  # noqa: BLE001  (a diagnostic must not take the line down)
             ceiling = {"error": f"{type(ex).__name__}: {ex}"}
     head_mode = "inference" if "inference" in recs else args.mode
     head = recs.pop(head_mode)
+    outputs = head.pop("outputs", None)
+    for r in recs.values():
+        r.pop("outputs", None)
     who = rank_report(e)
     cpu = None
-    if e.rank == 0 and e.world == 1 and not args.no_cpu_baseline and inputs is not None:
+    if args.full and e.rank == 0 and e.world == 1 and not args.no_cpu_baseline and inputs is not None:
         cpu = cpu_baseline(args, *inputs)
         if "train" in recs and recs["train"].get("value") and cpu.get("kind") == "reference":
             try:
                 recs["train"]["cpu_baseline"] = cpu_baseline_train(args, *inputs, cpu["cores"])
             except Exception as ex:  # noqa: BLE001  (a baseline must not take the line down)
                 recs["train"]["cpu_baseline"] = {"error": f"{type(ex).__name__}: {ex}"}
+    if e.rank == 0 and args.dump_outputs:
+        names = write_outputs(args.dump_outputs, outputs)
+        print(f"[bench] wrote {len(names)} arrays of the last timed step to {args.dump_outputs}: {' '.join(names)}", file=sys.stderr)
     if e.rank == 0:
         line = {"metric": "ray-samples/sec", "value": head["value"], "unit": "ray-samples/s", "n_gpus": e.world,
                 "steps": head["steps"], "warmup": head["warmup"], "ms_per_step": head["ms_per_step"], "higher_is_better": True,
@@ -1163,7 +1222,7 @@ def main():
         for k, r in recs.items():
             r.update({"metric": "ray-samples/sec", "unit": "ray-samples/s", "n_gpus": e.world, "per_gpu": round(r["value"] / e.world, 1)})
             line[k] = r
-        if e.world == 1 and args.mode == "all" and line.get("train", {}).get("ms_per_step") and line.get("render", {}).get("ms_per_step"):
+        if args.full and e.world == 1 and args.mode == "all" and line.get("train", {}).get("ms_per_step") and line.get("render", {}).get("ms_per_step"):
             # what the builder EXPECTS of the 1 / 2 / 4 / 8 curve, stated before anybody measures it
             try:
                 line["scale_model"] = scale_model(line, measure_one_rank_rccl_allreduce(612740, e.dev), 4 * 612740)

@@ -7,11 +7,12 @@ T=${1:-r05z}
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 rm -f gpurun_out/parity.jsonl
+OUT=$(python -c "import sys; sys.path[:0] = ['.', 'tests']; import gpu_util; print(gpu_util.OUT)")      # where the GPU tests write their records
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -6 | tee gpurun_out/${T}_smoke.txt
 timeout 1500 python -m pytest tests ${PYTEST_X:--x} -q -m gpu 2>&1 | tail -${PYTEST_TAIL:-8} > gpurun_out/${T}_pytest_gpu_tail.txt
 tail -3 gpurun_out/${T}_pytest_gpu_tail.txt
 cp gpurun_out/parity.jsonl gpurun_out/${T}_parity.jsonl
-timeout 900 python bench.py > gpurun_out/${T}_bench.out 2> gpurun_out/${T}_bench.err
+timeout 900 python bench.py --full > $OUT/${T}_bench.out 2> $OUT/${T}_bench.err
 python - $T <<'PY'
 import json, sys
 T = sys.argv[1]
@@ -36,7 +37,7 @@ if [ "${PMC:-1}" = "1" ]; then
   ROUND=5 bash scripts/pmc_traffic.sh 2>&1 | tail -8
   TAG=$T bash scripts/pmc_unbounded_bf16.sh 2>&1 | tail -4
 fi
-MIPNERF_FORCE_COLLECTIVE_PATH=1 timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --sustain-seconds 0 --ceiling-seconds 0 --no-fp32 --preheat-seconds 0.5 2> gpurun_out/${T}_bench_rccl1.err | tail -1 | python -c "
+MIPNERF_FORCE_COLLECTIVE_PATH=1 timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --sustain-seconds 0 --ceiling-seconds 0 --no-fp32 --preheat-seconds 0.5 2> $OUT/${T}_bench_rccl1.err | tail -1 | python -c "
 import sys, json
 l = json.loads(sys.stdin.read())
 print('1-rank RCCL communicator alive: headline graph', l['config']['hip_graph'], l['config']['hip_graph_capture_error'], 'train graph', l['train']['config']['hip_graph'], l['train']['config']['collective_path'], 'allreduce ms', l['train']['ranks']['allreduce_ms'], 'render', l['render']['ms_per_step'])"

@@ -6,11 +6,12 @@ T=${1:-r06z}
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 rm -f gpurun_out/parity.jsonl
+OUT=$(python -c "import sys; sys.path[:0] = ['.', 'tests']; import gpu_util; print(gpu_util.OUT)")      # where the GPU tests write their records
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -6 | tee gpurun_out/${T}_smoke.txt
 timeout 1500 python -m pytest tests ${PYTEST_X:--x} -q -m gpu 2>&1 | tail -${PYTEST_TAIL:-8} > gpurun_out/${T}_pytest_gpu_tail.txt
 tail -3 gpurun_out/${T}_pytest_gpu_tail.txt
 cp gpurun_out/parity.jsonl gpurun_out/${T}_parity.jsonl
-timeout 900 python bench.py > gpurun_out/${T}_bench.out 2> gpurun_out/${T}_bench.err
+timeout 900 python bench.py --full > $OUT/${T}_bench.out 2> $OUT/${T}_bench.err
 python - $T <<'PY'
 import json, sys
 T = sys.argv[1]

@@ -3,7 +3,7 @@
 # the go / no-go micro-kernel (no HBM traffic at all), the in-process MFMA ceilings and rocm-smi on the same box
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
-L=$(timeout 200 python bench.py --mode inference --precision fp32 --rays 8192 --samples 256 --steps 6 --warmup 2 --no-cpu-baseline --sustain-seconds 0 --preheat-seconds 1 2>/dev/null | python -c "
+L=$(timeout 200 python bench.py --full --mode inference --precision fp32 --rays 8192 --samples 256 --steps 6 --warmup 2 --no-cpu-baseline --sustain-seconds 0 --preheat-seconds 1 2>/dev/null | python -c "
 import sys, json
 l = json.loads([x for x in sys.stdin if x.startswith('{')][-1]); print(l['roofline']['launch_ms'])")
 echo "launch_ms $L"

@@ -1,5 +1,6 @@
 """bench.py contract on the GPU box: `python bench.py --gpus N` starts N ranks ITSELF (no launcher), the JSON line carries
-n_gpus = N, the headline plus the train / render sub-records, each with a roofline.  A 1-GPU box cannot run two RCCL
+n_gpus = N; a plain run times the headline alone and can write its outputs; with --full the line carries the headline plus the
+train / render sub-records, each with a roofline.  A 1-GPU box cannot run two RCCL
 ranks (RCCL refuses two ranks per device), so the plumbing test puts both ranks on cuda:0 over gloo
 (MIPNERF_BENCH_SHARE_GPU / MIPNERF_BENCH_BACKEND: test-only knobs)."""
 import json
@@ -27,7 +28,7 @@ def test_bench_refuses_world_size_mismatch():
 
 @pytest.mark.gpu
 def test_bench_self_launches_two_ranks():
-    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rays", "512", "--samples", "32", "--sustain-seconds", "0", "--preheat-seconds", "0.1"],
+    out = _run(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--rays", "512", "--samples", "32", "--sustain-seconds", "0", "--preheat-seconds", "0.1"],
                {"MIPNERF_BENCH_SHARE_GPU": "1", "MIPNERF_BENCH_BACKEND": "gloo"})
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -49,10 +50,10 @@ def test_bench_self_launches_two_ranks():
 @pytest.mark.gpu
 def test_bench_self_launches_eight_ranks_on_the_shared_gpu():
     """the driver's SCALE run goes to N = 8 and no box with more than one GPU was ever available to the builder.  The
-    rank-count-specific host logic -- self re-exec under torch.distributed.run with 8 ranks, the eight contiguous ray shards of the
+    rank-count-specific host logic -- self-launch under torch.distributed.run with 8 ranks, the eight contiguous ray shards of the
     640,000-ray frame (80,000 each) and their gather, eight flat-gradient all-reduces per training step with 1 / 8 folded into Adam, max over
     ranks of the timed regions -- runs here with all eight ranks on cuda:0 over gloo (RCCL refuses two ranks per device)."""
-    out = _run(["--gpus", "8", "--steps", "2", "--warmup", "1", "--rays", "256", "--samples", "32", "--sustain-seconds", "0", "--preheat-seconds", "0.05"],
+    out = _run(["--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--rays", "256", "--samples", "32", "--sustain-seconds", "0", "--preheat-seconds", "0.05"],
                {"MIPNERF_BENCH_SHARE_GPU": "1", "MIPNERF_BENCH_BACKEND": "gloo"}, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -68,7 +69,7 @@ def test_bench_self_launches_eight_ranks_on_the_shared_gpu():
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line():
-    out = _run(["--steps", "3", "--warmup", "1", "--rays", "512", "--samples", "32", "--sustain-seconds", "0.2", "--ceiling-seconds", "0.4", "--preheat-seconds", "0.2"], {})
+    out = _run(["--full", "--steps", "3", "--warmup", "1", "--rays", "512", "--samples", "32", "--sustain-seconds", "0.2", "--ceiling-seconds", "0.4", "--preheat-seconds", "0.2"], {})
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["metric"] == "ray-samples/sec" and line["dtype"] == "bf16"
@@ -99,6 +100,33 @@ def test_bench_single_gpu_line():
     ub = line["fp32"]["unbounded"]["bf16"]
     assert ub.get("finite") is True and ub["frac"] > 0.25 and ub["psnr_vs_fp32_frame_db"] > 45, ub
     assert ub["ms_per_step"] < 0.4 * line["fp32"]["unbounded"]["ms_per_step"], (ub, line["fp32"]["unbounded"])
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: the headline alone (no sub-record, no roofline re-run, no ceiling, no CPU baseline), exactly --steps timed steps, and
+    --dump-outputs writes the last timed step's per-level outputs -- the same bits on a second run with the same arguments."""
+    import numpy as np
+    B, N = 512, 32
+    lines = []
+    for run in ("a", "b"):
+        out = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--rays", str(B), "--samples", str(N), "--preheat-seconds", "0.1",
+                    "--dump-outputs", str(tmp_path / run)], {}, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
+    line = lines[0]
+    assert line["metric"] == "ray-samples/sec" and line["unit"] == "ray-samples/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["config"]["mode"] == "inference" and line["config"]["hip_graph"] is True
+    assert line["ms_per_step"] > 0 and line["value"] == pytest.approx(B * N * 2 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "sustained" not in line and "ceiling" not in line
+    assert not {"train", "render", "fp32", "trained_field", "variants", "scale_model"} & set(line)
+    shapes = {"rgb": (B, 3), "distance": (B,), "acc": (B,), "weights": (B, N), "t_samples": (B, N + 1)}
+    want = sorted(f"level{lvl}_{k}.npy" for lvl in range(2) for k in shapes)
+    assert sorted(os.listdir(tmp_path / "a")) == want and sorted(os.listdir(tmp_path / "b")) == want
+    for name in want:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and a.shape == shapes[name[7:-4]] and np.isfinite(a).all(), name
+        assert np.array_equal(a, b), name
 
 
 @pytest.mark.gpu

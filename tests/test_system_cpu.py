@@ -214,6 +214,31 @@ def test_bench_scale_model_and_pmc_round_rule(tmp_path):
     assert t and t > 12124160 and "round" in src
 
 
+def test_bench_write_outputs_caps_with_one_seeded_sample_of_rays(tmp_path):
+    """bench.py --dump-outputs: float32 files named after the arrays; above the byte cap every array whose first axis is the rays keeps the
+    same seeded rows (the same on every run), the rest is written whole."""
+    import importlib.util
+    import os
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+    arrays = {"level0_rgb": rng.random((1000, 3)), "level0_weights": rng.random((1000, 64)).astype(np.float32), "loss": np.float64(0.5)}
+    assert bench.write_outputs(str(tmp_path / "all"), arrays) == ["level0_rgb", "level0_weights", "loss"]
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in arrays}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["level0_rgb"], arrays["level0_rgb"].astype(np.float32)) and got["loss"] == 0.5
+    cap = 100 * (3 + 64) * 4 + 4
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), arrays, cap=cap)
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert sum(v.nbytes for v in a.values()) <= cap and a["level0_rgb"].shape == (100, 3) and a["level0_weights"].shape == (100, 64)
+    rows = [int(np.flatnonzero((arrays["level0_rgb"].astype(np.float32) == r).all(1))[0]) for r in a["level0_rgb"]]
+    assert rows == sorted(set(rows)) and np.array_equal(a["level0_weights"], arrays["level0_weights"][rows])
+    assert all(np.array_equal(a[k], np.load(tmp_path / "b" / (k + ".npy"))) for k in arrays)
+
+
 def test_unbounded_model_precision_rules_on_the_host():
     """MipNerf(unbounded=True): fp32 unless asked otherwise; bf16 is accepted (inference kernels exist since round 4) and can be switched to on
     a live model; an unknown precision is refused; the 672-wide first layer / skip concat follow from 42 features per degree"""
