@@ -256,6 +256,17 @@ int64_t mipnerf_eval_workspace_floats(int32_t height, int32_t width);
 int mipnerf_eval_errors(int32_t height, int32_t width, const float* pred, const float* gt,
                         float* workspace, float* out_psnr_ssim, void* stream);
 
+/* ---- image bytes (utils/vis.py:save_images): what the reference writes to PNG, as packed uint8 RGB on the device.
+ * mipnerf_visualize_map: visualize_depth (vis.py:83-97) of one map [num_pixels] fp32 (distance or acc) -> out_rgb
+ * [num_pixels, 3]: nan_to_num, min / max over the whole map, (x - min) / max(max - min, 1e-8) in fp32, (uint8)(255 x)
+ * truncated, then the JET row of that value as the reference writes it (OpenCV's BGR LUT stored as RGB).
+ * workspace: mipnerf_visualize_workspace_floats(num_pixels) floats.
+ * mipnerf_image_to_u8: torchvision save_image of an image already clamped by save_image_tensor: x [num_values] fp32 ->
+ * out [num_values] = (uint8)(clamp(x, 0, 1) * 255 + 0.5).  Neither allocates or synchronises (graph-capturable). */
+int64_t mipnerf_visualize_workspace_floats(int64_t num_pixels);
+int mipnerf_visualize_map(int64_t num_pixels, const float* map, float* workspace, uint8_t* out_rgb, void* stream);
+int mipnerf_image_to_u8(int64_t num_values, const float* x, uint8_t* out, void* stream);
+
 /* ---- training side ---------------------------------------------------------------------- */
 /* activations (mip_nerf.py:236-238): raw [M,4] = (raw_rgb, raw_density) -> rgb_sigma [M,4];
  * density_randn [M] (NULL = none): raw_density + density_noise * density_randn first (mip_nerf.py:232-233). */

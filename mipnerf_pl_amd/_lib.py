@@ -74,6 +74,9 @@ SIGNATURES = {
     "mipnerf_generate_rays_f64": (C.c_int, [_I64, _P, _P, _P, C.POINTER(RaysPtrs), _P]),
     "mipnerf_eval_workspace_floats": (_I64, [_I32, _I32]),
     "mipnerf_eval_errors": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _P]),
+    "mipnerf_visualize_workspace_floats": (_I64, [_I64]),
+    "mipnerf_visualize_map": (C.c_int, [_I64, _P, _P, _P, _P]),
+    "mipnerf_image_to_u8": (C.c_int, [_I64, _P, _P, _P]),
     "mipnerf_activate": (C.c_int, [_I64, _P, _F, _F, _P, _F, _P, _P]),
     "mipnerf_volumetric_rendering_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _F, _P, _P]),
     "mipnerf_distloss": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P]),

@@ -41,6 +41,7 @@ UNITS = [
                            "-DMIP_WGRAD_RECOMPUTE_PROBE=" + os.environ.get("MLP_WGRAD_RECOMPUTE_PROBE", "0"),
                            "-DMIP_WGRAD_RECOMPUTE_SCHED=" + os.environ.get("MLP_WGRAD_RECOMPUTE_SCHED", "0")]),
     ("kernels_eval.hip", ["-ffp-contract=off"]),
+    ("kernels_vis.hip", ["-ffp-contract=off"]),
     ("selftest.hip", ["-ffp-contract=off"]),
     ("capi.hip", []),
 ]

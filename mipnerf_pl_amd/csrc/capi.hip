@@ -851,6 +851,23 @@ int mipnerf_eval_errors(int32_t H, int32_t W, const float* pred, const float* gt
     return MIPNERF_OK;
 }
 
+// ---- image bytes (utils/vis.py:save_images) -----------------------------------------------------------------------
+static constexpr int64_t kMaxImageValues = 1LL << 36;     // keeps every grid dimension of kernels_vis.hip below 2^31
+
+int64_t mipnerf_visualize_workspace_floats(int64_t n) { return n > 0 && n <= kMaxImageValues ? mip::visualize_partial_floats(n) : 0; }
+
+int mipnerf_visualize_map(int64_t n, const float* map, float* workspace, uint8_t* out_rgb, void* stream) {
+    if (n < 1 || n > kMaxImageValues || !map || !workspace || !out_rgb) return fail(MIPNERF_E_INVALID, "visualize_map: bad argument");
+    HIP_TRY(mip::launch_visualize_map(n, map, workspace, out_rgb, S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_image_to_u8(int64_t n, const float* x, uint8_t* out, void* stream) {
+    if (n < 1 || n > kMaxImageValues || !x || !out) return fail(MIPNERF_E_INVALID, "image_to_u8: bad argument");
+    HIP_TRY(mip::launch_image_to_u8(n, x, out, S(stream)));
+    return MIPNERF_OK;
+}
+
 // ---- training-side entry points ------------------------------------------------------------------
 int mipnerf_activate(int64_t M, const float* raw, float rgb_padding, float density_bias, const float* density_randn,
                      float density_noise, float* rgb_sigma, void* stream) {

@@ -310,12 +310,13 @@ class RealData360(BaseDataset):
 
 
 class RenderGen(torch.utils.data.Dataset):
-    """render_video.py:19-118: `scales` pyramids of the 120-pose spherical path; item i = Rays [H_i, W_i, k] of camera i."""
+    """render_video.py:19-118: `scales` pyramids of the spherical path of `n_poses` poses (the reference's 120 by default); item i =
+    Rays [H_i, W_i, k] of camera i."""
 
-    def __init__(self, base_focal, base_size, scales=4, device=None):
+    def __init__(self, base_focal, base_size, scales=4, device=None, n_poses=120):
         super().__init__()
         self.near, self.far = 2, 6
-        c2w = create_spheric_poses(4)
+        c2w = create_spheric_poses(4, n_poses)
         records, self.sizes = [], []
         for i in range(scales):
             w, h, f = base_size[0] / 2 ** i, base_size[1] / 2 ** i, base_focal / 2 ** i

@@ -1,0 +1,166 @@
+"""The reference's eval.py loop on the device: test-set PSNR / SSIM and the rgb / distance / acc images of every test view.
+
+Per test image (eval.py:49-79): the fine level of the whole frame from one captured hipGraph (`model.GraphedFrame`, one per image size,
+so a multi-scale test set captures four), PSNR and SSIM in one kernel (`ops.eval_errors`), and -- with `save_image` -- the three PNGs
+of utils/vis.py:save_images made on the device (`ops.image_to_u8`, `ops.visualize_map`): only their bytes cross to the host.
+Same directory layout, file names and metric files as the reference:
+
+    <out_dir>/test/<exp_name>/<base_w / W>/{n:05d}_rgb.png, _dist.png, _acc.png     n advances every `scale` images
+    <out_dir>/test/<exp_name>/psnrs.txt, ssims.txt                                   one space-separated line each
+
+`summarize_results` is utils/metrics.py:128-152 and `generate_video` render_video.py:156-180 (imageio when importable, otherwise an
+animated PNG written by PIL).  The command line is `python -m mipnerf_pl_amd.eval`.
+"""
+from __future__ import annotations
+
+import glob
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+from .rays import Rays
+
+DEFAULT_CHUNK = 12288        # eval.py / render_video.py --chunk_size
+
+
+class FrameEvaluator:
+    """Everything one image size needs: the frame's `GraphedFrame` (or its eager form) and the device buffers of the image bytes."""
+
+    def __init__(self, model, height, width, chunk_size, white_bkgd, device, use_graph=True):
+        from .model import GraphedFrame
+        self.h, self.w = int(height), int(width)
+        n = self.h * self.w
+        self.frame = GraphedFrame(model, n, chunk_size, white_bkgd, device, capture=use_graph)
+        self.vis_ws = torch.empty(ops.visualize_workspace_floats(n), dtype=torch.float32, device=device)
+        self.rgb_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
+        self.dist_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
+        self.acc_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
+
+    def render(self, rays):
+        """Rays [H, W, k] -> fine (rgb [H, W, 3], distance [H, W], acc [H, W]): views of the frame's static outputs."""
+        flat = Rays(*[t.reshape(self.h * self.w, -1) for t in rays])
+        _, rgb, dist = self.frame(flat)
+        return rgb.view(self.h, self.w, 3), dist.view(self.h, self.w), self.frame.acc[-1].view(self.h, self.w)
+
+    def images(self, rgb, dist, acc):
+        """The bytes of the three PNGs of vis.py:save_images, on the device: (rgb, dist, acc) uint8 [H, W, 3]."""
+        ops.image_to_u8(rgb, out=self.rgb_u8)
+        ops.visualize_map(dist, out=self.dist_u8, workspace=self.vis_ws)
+        ops.visualize_map(acc, out=self.acc_u8, workspace=self.vis_ws)
+        return self.rgb_u8, self.dist_u8, self.acc_u8
+
+
+def save_images(rgb_u8, dist_u8, acc_u8, path, idx):
+    """vis.py:save_images with the bytes already made: {idx:05d}_rgb.png, _dist.png, _acc.png under `path`."""
+    from PIL import Image
+    names = []
+    for tag, img in (("rgb", rgb_u8), ("dist", dist_u8), ("acc", acc_u8)):
+        arr = img.cpu().numpy() if torch.is_tensor(img) else np.asarray(img)
+        name = os.path.join(path, "{:05d}_{}.png".format(idx, tag))
+        Image.fromarray(arr).save(name)
+        names.append(name)
+    return names
+
+
+def image_slots(sizes, scale, base_width):
+    """(n, sub-directory) of each image of a test set with image sizes `sizes` [(H, W)]: n advances every `scale` images
+    (eval.py:54-56), the sub-directory is str(int(base_width / W)) (eval.py:76)."""
+    n, out = -1, []
+    for idx, (_, w) in enumerate(sizes):
+        if idx % scale == 0:
+            n += 1
+        out.append((n, str(int(base_width / w))))
+    return out
+
+
+def write_metrics(folder, psnrs, ssims):
+    """psnrs.txt / ssims.txt of eval.py:80-83: the values of one scene as one space-separated line."""
+    os.makedirs(folder, exist_ok=True)
+    for name, values in (("psnrs.txt", psnrs), ("ssims.txt", ssims)):
+        with open(os.path.join(folder, name), "w") as f:
+            f.write(" ".join(str(float(v)) for v in values))
+
+
+def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chunk_size=DEFAULT_CHUNK, white_bkgd=True, use_graph=True,
+             base_size=(800, 800)):
+    """eval.py:main after the checkpoint is loaded: every image of `dataset` (a test split of `datasets.dataset_dict`) rendered by
+    `system.mip_nerf`, PSNR / SSIM recorded, the images written when `save_image`.  Returns (psnrs, ssims) as lists of floats."""
+    if scale not in (1, 4):
+        raise ValueError("scale must be 1 or 4 (eval.py --scale)")
+    model = system.mip_nerf
+    device = next(model.parameters()).device
+    folder = os.path.join(out_dir, "test", exp_name)
+    for i in range(scale):
+        os.makedirs(os.path.join(folder, str(2 ** i)), exist_ok=True)
+    slots = image_slots(dataset.sizes, scale, base_size[0])
+    evaluators, psnrs, ssims = {}, [], []
+    with torch.no_grad():
+        for idx in range(len(dataset)):
+            rays, gt = dataset[idx]
+            h, w = int(gt.shape[0]), int(gt.shape[1])
+            ev = evaluators.get((h, w))
+            if ev is None:
+                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph)
+            rgb, dist, acc = ev.render(rays)
+            psnr, ssim = ops.eval_errors(rgb, gt[..., :3])
+            psnrs.append(psnr.item())
+            ssims.append(ssim.item())
+            if save_image:
+                n, sub = slots[idx]
+                save_images(*ev.images(rgb, dist, acc), os.path.join(folder, sub), n)
+    write_metrics(folder, psnrs, ssims)
+    generate_video(folder)
+    return psnrs, ssims
+
+
+def summarize_results(folder, scene_names, num_buckets):
+    """utils/metrics.py:128-152: 'psnr per bucket | ssim per bucket | average' over the scenes' psnrs.txt / ssims.txt."""
+    results = []
+    for scene in scene_names:
+        values = []
+        for metric in ("psnrs", "ssims"):
+            with open(os.path.join(folder, "test", scene, f"{metric}.txt")) as f:
+                v = np.array([float(s) for s in f.readline().split(" ")])
+            values.append(np.mean(np.reshape(v, [-1, num_buckets]), 0))
+        results.append(np.concatenate(values))
+    avg = np.mean(np.array(results), 0)
+    psnr, ssim = np.mean(np.reshape(avg, [-1, num_buckets]), 1)
+    mse = np.exp(-0.1 * np.log(10.) * psnr)
+    dssim = np.sqrt(1 - ssim)
+    avg_avg = np.exp(np.mean(np.log(np.array([mse, dssim]))))
+    s = [" ".join(f"{x:0.4f}" for x in row) for row in np.reshape(avg, [-1, num_buckets])]
+    s.append(f"{avg_avg:0.4f}")
+    return " | ".join(s)
+
+
+def generate_video(image_path):
+    """render_video.py:156-180: per scale directory 1, 2, 4, ... the *_rgb.png frames in name order, then the same frames reversed,
+    at 40 fps.  With imageio: video_<s>.mov (as the reference); without it: an animated PNG video_<s>.png written by PIL.
+    Returns the written paths."""
+    try:
+        import imageio
+    except ImportError:
+        imageio = None
+    from PIL import Image
+    n_dirs = sum(os.path.isdir(os.path.join(image_path, d)) for d in os.listdir(image_path))
+    written = []
+    for i in range(n_dirs):
+        d = os.path.join(image_path, str(2 ** i))
+        files = sorted(glob.glob(os.path.join(d, "*_rgb.png")))
+        if not files:
+            continue
+        frames = [np.array(Image.open(f)).astype(np.uint8) for f in files]
+        frames += frames[::-1]
+        if imageio is not None:
+            name = os.path.join(d, "video_{}.mov".format(2 ** i))
+            imageio.mimwrite(name, frames, fps=40, quality=10)
+            print("generate video in {}".format(name))
+        else:
+            name = os.path.join(d, "video_{}.png".format(2 ** i))
+            ims = [Image.fromarray(f) for f in frames]
+            ims[0].save(name, save_all=True, append_images=ims[1:], duration=25, loop=0)
+            print("imageio is not installed: generate animated PNG in {}".format(name))
+        written.append(name)
+    return written

@@ -792,10 +792,14 @@ class GraphedFrame:
     views of the static outputs (valid until the next call).
     `lanes` (default 2, env MIPNERF_FRAME_LANES): the chunks are independent, so the capture forks into that many streams that
     take the chunks round-robin, each with its own workspace and per-sample scratch: the small kernels and the kernel boundaries
-    of one lane run while the other lane's MLP kernel owns the CUs."""
+    of one lane run while the other lane's MLP kernel owns the CUs.
+    Every level's acc is kept too: `acc[l]` [n] (fine level: `acc[-1]`), filled by each call next to what it returns.
+    `capture=False` runs the same chunk launches eagerly on every call instead of replaying a graph."""
 
-    def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, lanes: Optional[int] = None):
+    def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, lanes: Optional[int] = None,
+                 capture: bool = True):
         self.model, self.n, self.chunk, self.white_bkgd, self.dev = model, int(num_rays), int(chunk), bool(white_bkgd), device
+        self.capture = bool(capture)
         self.lanes = max(1, int(lanes if lanes is not None else os.environ.get("MIPNERF_FRAME_LANES", "2")))
         self.static_in = Rays(*[torch.zeros(self.n, k, device=device) for k in (3, 3, 3, 1, 1, 1, 1)])
         for k in ("directions", "viewdirs"):
@@ -864,7 +868,10 @@ class GraphedFrame:
             self.graph = None                   # MipNerf.set_precision since the capture: the graph holds the other precision's launches
         if self.graph is None:
             self._captured_precision = self.model.precision
-            self._capture()
+            if self.capture:
+                self._capture()
+            else:
+                self.graph = False
         for dst, src in zip(self.static_in, rays):
             dst.copy_(src)
         if self.graph is False:

@@ -254,6 +254,42 @@ def eval_errors(pred_color, batch_pixels):
     return out[0], out[1]
 
 
+def _u8_out(out, shape, device, name):
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"{name}: `out` must be a contiguous uint8 tensor of shape {tuple(shape)} on {device}")
+    return out
+
+
+def visualize_workspace_floats(num_pixels: int) -> int:
+    return int(L.lib().mipnerf_visualize_workspace_floats(int(num_pixels)))
+
+
+def visualize_map(x, out=None, workspace=None):
+    """utils/vis.py:visualize_depth of a distance / acc map [..., H, W] (any shape; the min / max run over all of it): the uint8 RGB
+    bytes [*x.shape, 3] that the reference writes to its _dist.png / _acc.png.  `out` / `workspace` (visualize_workspace_floats(numel)
+    floats) may be given, e.g. inside a captured graph."""
+    a = _f32c(x, "visualize_map")
+    n = a.numel()
+    out = _u8_out(out, (*a.shape, 3), a.device, "visualize_map")
+    if workspace is None:
+        workspace = torch.empty(visualize_workspace_floats(n), device=a.device, dtype=torch.float32)
+    elif workspace.dtype != torch.float32 or workspace.numel() < visualize_workspace_floats(n):
+        raise ValueError("visualize_map: workspace too small")
+    L.check(L.lib().mipnerf_visualize_map(n, _ptr(a), _ptr(workspace), _ptr(out), _stream()), "visualize_map")
+    return out
+
+
+def image_to_u8(x, out=None):
+    """torchvision save_image after save_image_tensor's clamp (vis.py:46-63) on one image: (uint8)(clamp(x, 0, 1) * 255 + 0.5),
+    elementwise, same shape as x."""
+    a = _f32c(x, "image_to_u8")
+    out = _u8_out(out, a.shape, a.device, "image_to_u8")
+    L.check(L.lib().mipnerf_image_to_u8(a.numel(), _ptr(a), _ptr(out), _stream()), "image_to_u8")
+    return out
+
+
 def selftest() -> str:
     """Run the hardware self-test (MFMA lane layouts, LDS DMA); returns the report, raises on failure."""
     rc = L.lib().mipnerf_selftest(_stream())

@@ -1,0 +1,100 @@
+"""The reference's render_video.py on the device: the spherical camera path rendered at `scale` pyramid levels.
+
+`render_video(system, out_dir, exp_name, scale, ...)` restates render_video.py:run_render: rays of `datasets.RenderGen` (generated on the
+device), each frame from one captured hipGraph per image size (`evaluate.FrameEvaluator`), its rgb / distance / acc PNGs made on the
+device and written to <out_dir>/render_spheric/<exp_name>/<base_w / W>/{i % n_poses:05d}_{rgb,dist,acc}.png, then `generate_video`.
+`n_poses` (not in the reference) shortens the path; the default 120 is the reference's.
+
+    python -m mipnerf_pl_amd.render_video --ckpt CKPT --out_dir OUT --scale 4 [--gen_video_only --render_images_dir DIR]
+"""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from .evaluate import DEFAULT_CHUNK, FrameEvaluator, generate_video, save_images
+
+CAMERA_ANGLE_X = 0.6911112070083618       # render_video.py --camera_angle_x default (Blender's lego)
+
+
+def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_angle_x=CAMERA_ANGLE_X, chunk_size=DEFAULT_CHUNK,
+                 white_bkgd=True, n_poses=120, use_graph=True):
+    """render_video.py:run_render after the checkpoint is loaded.  Returns the output folder."""
+    from .datasets import RenderGen
+    model = system.mip_nerf
+    device = next(model.parameters()).device
+    folder = os.path.join(out_dir, "render_spheric", exp_name)
+    for i in range(scale):
+        os.makedirs(os.path.join(folder, str(2 ** i)), exist_ok=True)
+    focal = .5 * base_size[0] / np.tan(.5 * camera_angle_x)
+    dataset = RenderGen(focal, base_size, scale, device=device, n_poses=n_poses)
+    nums = len(dataset) // scale
+    evaluators = {}
+    with torch.no_grad():
+        for idx in range(len(dataset)):
+            rays = dataset[idx]
+            h, w = dataset.sizes[idx]
+            ev = evaluators.get((h, w))
+            if ev is None:
+                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph)
+            images = ev.images(*ev.render(rays))
+            save_images(*images, os.path.join(folder, str(int(base_size[0] / w))), idx % nums)
+    generate_video(folder)
+    return folder
+
+
+def _bool(s):
+    if str(s).lower() in ("1", "true", "yes", "y"):
+        return True
+    if str(s).lower() in ("0", "false", "no", "n"):
+        return False
+    raise argparse.ArgumentTypeError(f"expected a boolean, got {s!r}")
+
+
+def add_common_args(p):
+    """Flags both command lines share with the reference, and the two of their own (--precision, --no-graph)."""
+    p.add_argument("--ckpt", help="Path to ckpt.")
+    p.add_argument("--out_dir", help="Output directory.", type=str, required=True)
+    p.add_argument("--chunk_size", help="Chunk size for render.", type=int, default=DEFAULT_CHUNK)
+    p.add_argument("--white_bkgd", help="Train set image background color.", type=_bool, default=True)
+    p.add_argument("--base_size", help="source image size: W H", type=int, nargs=2, default=[800, 800])
+    p.add_argument("--precision", help="MLP precision (default: the checkpoint's)", choices=["fp32", "bf16"], default=None)
+    p.add_argument("--no-graph", dest="use_graph", help="render each frame eagerly instead of replaying a captured hipGraph",
+                   action="store_false")
+    return p
+
+
+def build_parser():
+    p = add_common_args(argparse.ArgumentParser(prog="python -m mipnerf_pl_amd.render_video"))
+    p.add_argument("--render_images_dir", help="already render image directory.", type=str, default=None)
+    p.add_argument("--scale", help="must specify nums of scale", type=int, required=True)
+    p.add_argument("--camera_angle_x", help="camera_angle_x in source dataset", type=float, default=CAMERA_ANGLE_X)
+    p.add_argument("--gen_video_only", help="only generate the video of images rendered before", action="store_true")
+    p.add_argument("--n_poses", help="poses on the spherical path", type=int, default=120)
+    return p
+
+
+def load_system(args):
+    """MipNeRFSystem.load_from_checkpoint(--ckpt), with --precision when given (on the host; the caller moves it)."""
+    from .system import MipNeRFSystem
+    kw = {"precision": args.precision} if args.precision else {}
+    return MipNeRFSystem.load_from_checkpoint(args.ckpt, **kw)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.gen_video_only:
+        if args.render_images_dir is None:
+            raise SystemExit("only generate video, you must give the different scale image base dir (--render_images_dir)")
+        return generate_video(args.render_images_dir)
+    system = load_system(args).to(torch.device("cuda")).eval()
+    return render_video(system, args.out_dir, system.hparams["exp_name"], args.scale, base_size=args.base_size,
+                        camera_angle_x=args.camera_angle_x, chunk_size=args.chunk_size, white_bkgd=args.white_bkgd,
+                        n_poses=args.n_poses, use_graph=args.use_graph)
+
+
+if __name__ == "__main__":
+    main()
