@@ -226,6 +226,16 @@ int mipnerf_generate_rays(int64_t num_rays, const float* cameras, const int32_t*
  * arithmetic gets to 1e-4 relative only. */
 int mipnerf_generate_rays_f64(int64_t num_rays, const double* cameras, const int32_t* cam_idx,
                               const int32_t* pix_idx, const mipnerf_rays_out* out, void* stream);
+/* One training batch of an epoch straight into caller-owned buffers (the static inputs of a captured training step):
+ * b = *step - *epoch_base (device int64s, read when the kernel runs, so a replayed graph advances through the epoch);
+ * ray i = global pixel id order[b * batch_size + i] over the concatenation of the `n_images` images of the `cameras` table,
+ * image c found in the int64 table offsets[0..n_images] (pixel counts, cumulative; offsets[0] = 0), pixel id - offsets[c],
+ * the arithmetic of mipnerf_generate_rays; gt[i][0..2] = pixels[id][0..2] (pixels [offsets[n_images]][3] fp32).  Bit-identical
+ * to mipnerf_generate_rays of the same (camera, pixel) pairs.  Rays whose index is past n_order are left unwritten.
+ * No host synchronisation, no allocation: capturable. */
+int mipnerf_gather_train_batch(int64_t batch_size, int64_t n_order, const int64_t* order, int32_t n_images,
+                               const int64_t* offsets, const float* cameras, const float* pixels, const int64_t* step,
+                               const int64_t* epoch_base, const mipnerf_rays_out* out, float* gt, void* stream);
 
 /* ---- unbounded scenes (mip-NeRF 360) --------------------------------------------------------------------------------
  * Correct versions of what the reference's dead code aims at (models/mip.py:106-124 sample_along_rays_360, :38-47 full

@@ -1,0 +1,93 @@
+"""Hyper-parameters of a training run, with the semantics of the reference's YAML configs (configs/*.yaml, configs/config.py).
+
+A configuration is one FLAT dict: nested YAML sections become dotted keys (`train.batch_size`, `nerf.mlp.net_width`).
+`DEFAULTS` is the reference's `configs/lego.yaml` (its train.py's default `--config`; the reference's `default.yaml` is empty), which
+completes `system.DEFAULT_HPARAMS` with the run-level keys (`seed`, `num_gpus`, `exp_name`, `train.batch_type`, `val.*`,
+`checkpoint.resume_path`, ...).  `parse_args` merges, later winning:
+
+    DEFAULTS  <-  --config FILE  <-  trailing KEY VALUE pairs  <-  command-line arguments that are not yet keys
+
+Every leaf value goes through the same rule: `yaml.safe_load` first, then a string is tried with `ast.literal_eval` (falling back to the
+string itself), and a list becomes a tuple.  So the reference's quirks hold here too: `5e-4` (a string to YAML 1.1) becomes 0.0005,
+`None` becomes None, and `append_identity: Ture` stays the string 'Ture' (truthy, as the model reads it).
+"""
+from __future__ import annotations
+
+import argparse
+import ast
+
+DEFAULTS = {
+    'seed': 4, 'num_gpus': 1, 'exp_name': 'lego',
+    'train.batch_size': 3072, 'train.batch_type': 'all_images', 'train.num_work': 4, 'train.randomized': True,
+    'train.white_bkgd': True,
+    'val.batch_size': 1, 'val.batch_type': 'single_image', 'val.num_work': 4, 'val.randomized': False, 'val.white_bkgd': True,
+    'val.check_interval': 10000, 'val.chunk_size': 8192, 'val.sample_num': 4,
+    'nerf.num_samples': 128, 'nerf.num_levels': 2, 'nerf.resample_padding': 0.01, 'nerf.stop_resample_grad': True,
+    'nerf.use_viewdirs': True, 'nerf.disparity': False, 'nerf.ray_shape': 'cone', 'nerf.min_deg_point': 0,
+    'nerf.max_deg_point': 16, 'nerf.deg_view': 4, 'nerf.density_activation': 'softplus', 'nerf.density_noise': 0.0,
+    'nerf.density_bias': -1.0, 'nerf.rgb_activation': 'sigmoid', 'nerf.rgb_padding': 0.001, 'nerf.disable_integration': False,
+    'nerf.append_identity': 'Ture',
+    'nerf.mlp.net_depth': 8, 'nerf.mlp.net_width': 256, 'nerf.mlp.net_depth_condition': 1, 'nerf.mlp.net_width_condition': 128,
+    'nerf.mlp.net_activation': 'relu', 'nerf.mlp.skip_index': 4, 'nerf.mlp.num_rgb_channels': 3, 'nerf.mlp.num_density_channels': 1,
+    'optimizer.lr_init': 0.0005, 'optimizer.lr_final': 5e-06, 'optimizer.lr_delay_steps': 2500, 'optimizer.lr_delay_mult': 0.01,
+    'optimizer.max_steps': 1000000,
+    'loss.disable_multiscale_loss': False, 'loss.coarse_loss_mult': 0.1,
+    'checkpoint.resume_path': None,
+}
+
+
+def parse_value(v):
+    """One leaf: a string through ast.literal_eval when it parses, a list as a tuple."""
+    if isinstance(v, str):
+        try:
+            v = ast.literal_eval(v)
+        except (ValueError, SyntaxError):
+            pass
+    if isinstance(v, list):
+        v = tuple(v)
+    return v
+
+
+def flatten(tree, prefix=""):
+    """Nested dict (a parsed YAML document) -> flat dict of dotted keys with parsed leaves.  None (an empty file) -> {}."""
+    out = {}
+    for k, v in (tree or {}).items():
+        if isinstance(v, dict):
+            out.update(flatten(v, f"{prefix}{k}."))
+        else:
+            out[prefix + str(k)] = parse_value(v)
+    return out
+
+
+def load(path):
+    """The flat configuration of one YAML file."""
+    import yaml
+    with open(path) as f:
+        return flatten(yaml.safe_load(f))
+
+
+def merge_opts(config, opts):
+    """Trailing `KEY VALUE ...` pairs of the command line into `config` (in place); values parsed like file values."""
+    opts = list(opts or [])
+    if len(opts) % 2:
+        raise ValueError(f"opts must be KEY VALUE pairs, got {len(opts)} items: {opts}")
+    for k, v in zip(opts[0::2], opts[1::2]):
+        config[k] = parse_value(v)
+    return config
+
+
+def resolve(args: argparse.Namespace, defaults=None):
+    """The configuration of a parsed command line: defaults, then `args.config`, then `args.opts`, then every other attribute of
+    `args` whose name is not a key yet (so --data_path, --out_dir, --dataset_name land in the dict; a config key is not overridden)."""
+    config = dict(DEFAULTS if defaults is None else defaults)
+    if getattr(args, "config", None) is not None:
+        config.update(load(args.config))
+    merge_opts(config, getattr(args, "opts", None))
+    for k, v in vars(args).items():
+        if k not in config:
+            config[k] = v
+    return config
+
+
+def parse_args(parser: argparse.ArgumentParser, argv=None):
+    return resolve(parser.parse_args(argv))

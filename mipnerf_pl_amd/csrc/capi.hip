@@ -839,6 +839,17 @@ int mipnerf_generate_rays_f64(int64_t n, const double* cameras, const int32_t* c
     return MIPNERF_OK;
 }
 
+int mipnerf_gather_train_batch(int64_t batch_size, int64_t n_order, const int64_t* order, int32_t n_images, const int64_t* offsets,
+                               const float* cameras, const float* pixels, const int64_t* step, const int64_t* epoch_base,
+                               const mipnerf_rays_out* out, float* gt, void* stream) {
+    if (batch_size < 1 || n_order < 0 || n_images < 1 || !order || !offsets || !cameras || !pixels || !step || !epoch_base || !out ||
+        !out->origins || !out->directions || !out->viewdirs || !out->radii || !out->lossmult || !out->near || !out->far || !gt)
+        return fail(MIPNERF_E_INVALID, "gather_train_batch: bad argument");
+    HIP_TRY(mip::launch_gather_train_batch(batch_size, n_order, order, n_images, offsets, cameras, pixels, step, epoch_base, out->origins,
+                                           out->directions, out->viewdirs, out->radii, out->lossmult, out->near, out->far, gt, S(stream)));
+    return MIPNERF_OK;
+}
+
 // ---- evaluation metrics (utils/metrics.py:191-197) ---------------------------------------------------------------
 int64_t mipnerf_eval_workspace_floats(int32_t height, int32_t width) {
     return height > 0 && width > 0 ? mip::eval_errors_partial_floats(height, width) : 0;

@@ -472,17 +472,13 @@ __device__ __forceinline__ void pixel_direction(const T* __restrict__ cam, T x, 
 }
 }  // namespace
 
+// ray `i` of an output batch = pixel `p` (row-major) of camera record `cam`: the per-ray arithmetic k_generate_rays and
+// k_gather_train_batch share, so that both write the same bits for the same pixel
 template <typename T>
-__global__ void __launch_bounds__(256)
-k_generate_rays(int64_t n, const T* __restrict__ cams, const int32_t* __restrict__ cam_idx,
-                const int32_t* __restrict__ pix_idx, float* __restrict__ origins, float* __restrict__ directions,
-                float* __restrict__ viewdirs, float* __restrict__ radii, float* __restrict__ lossmult,
-                float* __restrict__ nearp, float* __restrict__ farp) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const T* cam = cams + (size_t)(cam_idx ? cam_idx[i] : 0) * 32;
+__device__ __forceinline__ void write_ray(const T* __restrict__ cam, int p, int64_t i, float* __restrict__ origins,
+                                          float* __restrict__ directions, float* __restrict__ viewdirs, float* __restrict__ radii,
+                                          float* __restrict__ lossmult, float* __restrict__ nearp, float* __restrict__ farp) {
     const int W = (int)cam[21], H = (int)cam[22];
-    const int p = pix_idx ? pix_idx[i] : (int)i;
     const int yy = p / W, xx = p - yy * W;
     T d[3], dn[3];
     pixel_direction<T>(cam, (T)xx, (T)yy, d);
@@ -503,6 +499,47 @@ k_generate_rays(int64_t n, const T* __restrict__ cams, const int32_t* __restrict
     farp[i] = (float)cam[24];
 }
 
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_generate_rays(int64_t n, const T* __restrict__ cams, const int32_t* __restrict__ cam_idx,
+                const int32_t* __restrict__ pix_idx, float* __restrict__ origins, float* __restrict__ directions,
+                float* __restrict__ viewdirs, float* __restrict__ radii, float* __restrict__ lossmult,
+                float* __restrict__ nearp, float* __restrict__ farp) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const T* cam = cams + (size_t)(cam_idx ? cam_idx[i] : 0) * 32;
+    write_ray<T>(cam, pix_idx ? pix_idx[i] : (int)i, i, origins, directions, viewdirs, radii, lossmult, nearp, farp);
+}
+
+// Batch b of an epoch (datasets.BaseDataset.rays_at of order[b*B : (b+1)*B]) written into caller-owned buffers, with b read
+// from the device: b = *step - *epoch_base.  `step` is advanced by a LATER launch (the scheduled Adam kernel), never by this
+// one, so every block reads the same b.  Ray i: global pixel id order[b*B + i] -> image c = the last c with offsets[c] <= id
+// (torch.searchsorted(offsets, id, right=True) - 1), pixel id - offsets[c], then the arithmetic of k_generate_rays and the
+// gt gather pixels[id].  Rays past the end of `order` (or a batch index outside the epoch) are left unwritten.
+__global__ void __launch_bounds__(256)
+k_gather_train_batch(int64_t B, int64_t n_order, const int64_t* __restrict__ order, int n_images,
+                     const int64_t* __restrict__ offsets, const float* __restrict__ cams, const float* __restrict__ pixels,
+                     const int64_t* __restrict__ step, const int64_t* __restrict__ epoch_base, float* __restrict__ origins,
+                     float* __restrict__ directions, float* __restrict__ viewdirs, float* __restrict__ radii,
+                     float* __restrict__ lossmult, float* __restrict__ nearp, float* __restrict__ farp, float* __restrict__ gt) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const int64_t b = *step - *epoch_base;
+    if (b < 0) return;
+    const int64_t j = b * B + i;
+    if (j >= n_order) return;
+    const int64_t id = order[j];
+    if (id < 0 || id >= offsets[n_images]) return;
+    int lo = 0, hi = n_images - 1;          // invariant: offsets[lo] <= id < offsets[hi + 1]
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (offsets[mid] <= id) lo = mid; else hi = mid - 1;
+    }
+    write_ray<float>(cams + (size_t)lo * 32, (int)(id - offsets[lo]), i, origins, directions, viewdirs, radii, lossmult, nearp, farp);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gt[i * 3 + k] = pixels[id * 3 + k];
+}
+
 hipError_t launch_generate_rays(int64_t n, const float* cams, const int32_t* cam_idx, const int32_t* pix_idx,
                                 float* origins, float* directions, float* viewdirs, float* radii, float* lossmult,
                                 float* nearp, float* farp, hipStream_t st) {
@@ -516,6 +553,14 @@ hipError_t launch_generate_rays_f64(int64_t n, const double* cams, const int32_t
                                     float* nearp, float* farp, hipStream_t st) {
     hipLaunchKernelGGL(k_generate_rays<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, cams, cam_idx, pix_idx,
                        origins, directions, viewdirs, radii, lossmult, nearp, farp);
+    return hipGetLastError();
+}
+hipError_t launch_gather_train_batch(int64_t B, int64_t n_order, const int64_t* order, int n_images, const int64_t* offsets,
+                                     const float* cams, const float* pixels, const int64_t* step, const int64_t* epoch_base,
+                                     float* origins, float* directions, float* viewdirs, float* radii, float* lossmult, float* nearp,
+                                     float* farp, float* gt, hipStream_t st) {
+    hipLaunchKernelGGL(k_gather_train_batch, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B, n_order, order, n_images, offsets,
+                       cams, pixels, step, epoch_base, origins, directions, viewdirs, radii, lossmult, nearp, farp, gt);
     return hipGetLastError();
 }
 }  // namespace mip

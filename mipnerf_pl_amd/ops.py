@@ -234,6 +234,36 @@ def generate_rays(cameras, num_rays=None, cam_idx=None, pix_idx=None):
     return Rays(*out)
 
 
+def gather_train_batch(order, offsets, cameras, pixels, step, epoch_base, rays_out, gt_out):
+    """Batch b = step[0] - epoch_base[0] (both read on the device) of an epoch order, written into `rays_out` (Rays of [B, k] fp32
+    buffers) and `gt_out` [B, 3]: the same bits as `dataset.rays_at(order[b*B:(b+1)*B])` (BaseDataset: `offsets` int64 [n_images + 1],
+    `cameras` [n_images, 32] fp32, `pixels` [P, 3] fp32), with no host synchronisation -- the batch source of a captured training
+    step (train_graph.GraphedTrainStep).  Rays past the end of `order` are left unwritten."""
+    import ctypes as C
+    B = int(gt_out.shape[0])
+    dev = gt_out.device
+
+    def chk(t, name, dtype, shape=None):
+        if not (t.is_cuda and t.device == dev and t.dtype == dtype and t.is_contiguous()):
+            raise ValueError(f"gather_train_batch: {name} must be a contiguous {dtype} tensor on {dev}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"gather_train_batch: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+    chk(gt_out, "gt_out", torch.float32, (B, 3))
+    for k, w in zip(rays_out._fields, (3, 3, 3, 1, 1, 1, 1)):
+        chk(getattr(rays_out, k), k, torch.float32, (B, w))
+    chk(order, "order", torch.int64)
+    chk(offsets, "offsets", torch.int64)
+    chk(cameras, "cameras", torch.float32, (offsets.numel() - 1, 32))
+    chk(pixels, "pixels", torch.float32)
+    chk(step, "step", torch.int64)
+    chk(epoch_base, "epoch_base", torch.int64)
+    rp = L.RaysPtrs(*[t.data_ptr() for t in rays_out])
+    L.check(L.lib().mipnerf_gather_train_batch(B, order.numel(), _ptr(order), offsets.numel() - 1, _ptr(offsets), _ptr(cameras),
+                                               _ptr(pixels), _ptr(step), _ptr(epoch_base), C.byref(rp), _ptr(gt_out), _stream()),
+            "gather_train_batch")
+
+
 def eval_errors(pred_color, batch_pixels):
     """utils/metrics.py:191-197: (psnr, ssim) of one rendered frame, pred/gt [1,H,W,3] (or [H,W,3]) fp32 HIP tensors;
     one fused kernel instead of six conv2d passes.  Returns two 0-d tensors."""

@@ -10,7 +10,8 @@ device memory.  With world_size > 1 the step is two graphs around one eager RCCL
 (SUM; the 1/world mean is folded into the Adam kernel): graph A = draws + forward + backward, graph B = Adam + re-pack.
 
 Inputs live in static buffers (`self.rays`, `self.gt`): write the next batch there (copy_ or device-side ray generation
-straight into them) and call the object.  Returns the static scalars tensor [6] = loss, mse_c, mse_f, distloss_c,
+straight into them) and call the object, or give a `batch_source`: a callable issued first inside the step (inside the captured
+graph) that writes the batch itself, e.g. `ops.gather_train_batch` with the batch index read from the device (train.py).  Returns the static scalars tensor [6] = loss, mse_c, mse_f, distloss_c,
 distloss_f, psnr_fine (valid until the next call).
 """
 from __future__ import annotations
@@ -27,7 +28,7 @@ from .rays import Rays
 
 
 class GraphedTrainStep:
-    def __init__(self, system, optimizer, num_rays: int, device: torch.device, use_graph: bool = True):
+    def __init__(self, system, optimizer, num_rays: int, device: torch.device, use_graph: bool = True, batch_source=None):
         from .optim import FlatAdam
         if not isinstance(optimizer, FlatAdam):
             raise TypeError("GraphedTrainStep needs the flat optimiser (system.fused_adam = True)")
@@ -37,6 +38,7 @@ class GraphedTrainStep:
         self.system, self.model, self.opt = system, model, optimizer
         self.B, self.N, self.dev = int(num_rays), model.num_samples, device
         self.use_graph = bool(use_graph)
+        self.batch_source = batch_source    # optional callable writing self.rays / self.gt on the device, issued first in _fwd_bwd
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # the collective form (graph A, all-reduce on the process group's communicator, graph B) is what every world > 1 run
         # uses; MIPNERF_FORCE_COLLECTIVE_PATH=1 takes it at world 1 too when a process group exists (a 1-rank RCCL
@@ -74,6 +76,8 @@ class GraphedTrainStep:
     # ---- the two halves ------------------------------------------------------------------------------------------------
     def _fwd_bwd(self):
         m, B, N = self.model, self.B, self.N
+        if self.batch_source is not None:
+            self.batch_source()
         t_rand = u_rand = dz = None
         if self.randomized:
             draws = torch.rand(2, B, N + 1, device=self.dev)        # one launch for both draws
