@@ -28,7 +28,7 @@ UNITS = [
     # (source, extra flags)
     ("kernels_ray.hip", ["-ffp-contract=off"]),
     ("kernels_train.hip", ["-ffp-contract=off"]),
-    ("kernels_360.hip", ["-ffp-contract=off"] + (["-DMIP_IPE360_ROW_PAD=" + os.environ["MLP_IPE360_ROW_PAD"]] if os.environ.get("MLP_IPE360_ROW_PAD") else [])),
+    ("kernels_360.hip", ["-ffp-contract=off"]),
     ("kernels_resample_grad.hip", ["-ffp-contract=off"]),
     ("kernels_pack.hip", []),
     ("kernels_mlp_f32.hip", ["-ffp-contract=off"]),
@@ -36,10 +36,7 @@ UNITS = [
     ("mlp_bf16_gen.hip", NO_IEEE + ["-ffp-contract=off"]),    # the fused IPE must round like kernels_ray.hip
     ("mlp_bf16_trainfwd_gen.hip", NO_IEEE + ["-ffp-contract=off"]),
     ("mlp_bf16_dgrad_gen.hip", NO_IEEE),
-    ("kernels_wgrad.hip", ["-DMIP_WGRAD_NT=" + os.environ.get("MLP_WGRAD_NT", "1"), "-DMIP_WGRAD_STAGES=" + os.environ.get("MLP_WGRAD_STAGES", "4"),
-                           "-DMIP_WGRAD_TR=" + os.environ.get("MLP_WGRAD_TR", "0"),
-                           "-DMIP_WGRAD_RECOMPUTE_PROBE=" + os.environ.get("MLP_WGRAD_RECOMPUTE_PROBE", "0"),
-                           "-DMIP_WGRAD_RECOMPUTE_SCHED=" + os.environ.get("MLP_WGRAD_RECOMPUTE_SCHED", "0")]),
+    ("kernels_wgrad.hip", []),
     ("kernels_eval.hip", ["-ffp-contract=off"]),
     ("kernels_vis.hip", ["-ffp-contract=off"]),
     ("selftest.hip", ["-ffp-contract=off"]),
@@ -50,28 +47,7 @@ UNITS = [
 DIAG_LIB = os.path.join(CSRC, "libmipnerf_diag.so")
 DIAG_UNITS = [("kernels_diag.hip", []), ("diag_capi.hip", [])]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall",
-          "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result",
-          # range reduction of the bf16 pipeline's fast sine (raymath.hpp: sin_fast): 1 = two-float fp32, 0 = fp64
-          "-DMIP_SIN_FAST_TWOFLOAT=" + os.environ.get("MLP_SIN_TWOFLOAT", "0"),
-          # wave scans / reductions of the ray-side kernels (raywave.hpp): 1 = DPP row_shr / row_bcast, 0 = __shfl (ds_bpermute)
-          "-DMIP_WAVE_DPP=" + os.environ.get("MLP_WAVE_DPP", "1")]
-
-
-# Timing-experiment knobs whose build gives WRONG results (value = the harmless default).  A stale variable in the environment must not
-# silently produce a product library with wrong gradients: such a build needs MIPNERF_EXPERIMENT_BUILD=1 AND its own MIPNERF_LIB_NAME, and
-# the library it produces refuses mipnerf_create() unless the process sets MIPNERF_ALLOW_EXPERIMENT_LIB=1 (capi.hip).
-WRONG_RESULT_KNOBS = {"MLP_ABLATE_BARRIER": "0", "MLP_ABLATE_WAIT": "0", "MLP_ABLATE_LDA": "0", "MLP_F32R_GEN_ABLATE": "0", "MLP_F32R_ABLATE": "",
-                      "MLP_TRAIN_ABLATE_TMFMA": "0", "MLP_WGRAD_TR": "0", "MLP_TRAIN_SKIP_STORES": "0", "MLP_WGRAD_RECOMPUTE_PROBE": "0",
-                      "MLP_PRE_ABLATE_STORES": "0", "MLP_TRUNK_ABLATE_PRELOADS": "0"}
-
-
-def experiment_flags():
-    """The wrong-result knobs that are switched on, as "NAME=value ..." ("" for a product build); raises when they are set without the opt-in."""
-    on = [f"{k}={os.environ[k]}" for k, d in sorted(WRONG_RESULT_KNOBS.items()) if os.environ.get(k, d) != d]
-    if on and (os.environ.get("MIPNERF_EXPERIMENT_BUILD") != "1" or os.path.basename(LIB) == "libmipnerf_hip.so"):
-        raise RuntimeError("timing-experiment variables are set (" + " ".join(on) + "): they produce WRONG results.  Unset them, or opt in with "
-                           "MIPNERF_EXPERIMENT_BUILD=1 and a MIPNERF_LIB_NAME other than libmipnerf_hip.so")
-    return " ".join(on)
+          "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result"]
 
 
 def hipcc() -> str:
@@ -111,15 +87,12 @@ def variant_units():
     import re
     out = []
     for f in sorted(os.listdir(CSRC)):
-        if re.fullmatch(r"mlp_bf16_gen_v\d+\.hip", f) or re.fullmatch(r"mlp_bf16_trainfwd(_pre)?_gen_v\d+\.hip", f):
-            out.append((f, NO_IEEE + ["-ffp-contract=off"]))
-        elif re.fullmatch(r"(pre_gemm_gen|mlp_bf16_pre_gen|mlp_bf16_fused_gen)_v\d+\.hip", f):      # two-kernel bf16 form of wide encodings (gen_pre_gemm.py)
+        # inference + training-forward kernels, the two- and one-kernel bf16 forms of wide encodings (gen_pre_gemm.py), the register-resident
+        # fp32 kernels (gen_mlp_f32r.py)
+        if re.fullmatch(r"(mlp_bf16_gen|mlp_bf16_trainfwd(_pre)?_gen|pre_gemm_gen|mlp_bf16_pre_gen|mlp_bf16_fused_gen|mlp_f32r_gen)_v\d+\.hip", f):
             out.append((f, NO_IEEE + ["-ffp-contract=off"]))
         elif re.fullmatch(r"mlp_bf16_dgrad_gen_v\d+\.hip", f):
             out.append((f, NO_IEEE))
-        elif re.fullmatch(r"mlp_f32r_gen_v\d+\.hip", f):              # register-resident fp32 kernels (gen_mlp_f32r.py)
-            out.append((f, NO_IEEE + ["-ffp-contract=off"] + (["-DMLP_F32R_ABLATE=" + os.environ["MLP_F32R_ABLATE"]] if os.environ.get("MLP_F32R_ABLATE") else []) +
-                        ["-DMLP_F32R_NAT_NT=" + os.environ.get("MLP_F32R_NAT_NT", "1")]))
     return out
 
 
@@ -149,15 +122,13 @@ def tables_object() -> str:
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
-    experiment_flags()            # refuse BEFORE the generators overwrite the tracked sources with an ablated form
     generate()
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".bin"))]
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_hip.h"))
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_diag.h"))
     stamp = os.path.join(CSRC, ".build_stamp_" + os.path.basename(LIB))
-    exp = experiment_flags()
-    units = UNITS[:-1] + variant_units() + [("capi.hip", ['-DMIPNERF_EXPERIMENT_BUILD="%s"' % exp] if exp else [])]          # capi.hip last
-    dig = _digest(deps, COMMON + sum((f for _, f in units), []) + [f"{k}={v}" for k, v in sorted(os.environ.items()) if k.startswith("MLP_")])
+    units = UNITS[:-1] + variant_units() + UNITS[-1:]          # capi.hip last
+    dig = _digest(deps, COMMON + sum((f for _, f in units), []))
     if not force and os.path.exists(LIB) and os.path.exists(DIAG_LIB) and os.path.exists(stamp) and open(stamp).read() == dig:
         if verbose:
             print(f"[build] {LIB} is up to date")

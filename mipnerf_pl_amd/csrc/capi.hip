@@ -94,11 +94,6 @@ void build_tables(Tables& T, const PlanDesc& P) {
         for (int s = 0; s < op.nsegs; ++s) nk += op.segs[s].nk;
         for (int t = 0; t < op.ntiles; t += 2) {
             const bool pair = t + 1 < op.ntiles;
-            if (kChainOrder) {
-                for (int ks = 0; ks < nk; ++ks) fill_chunk(op, t, ks);
-                if (pair) for (int ks = 0; ks < nk; ++ks) fill_chunk(op, t + 1, ks);
-                continue;
-            }
             for (int ks = 0; ks < nk; ++ks) {
                 fill_chunk(op, t, ks);
                 if (pair) fill_chunk(op, t + 1, ks);
@@ -432,13 +427,6 @@ int mipnerf_variant_arch(int variant, mipnerf_config* cfg, int* has_bf16_trainin
 int mipnerf_create(const mipnerf_config* cfg, mipnerf_ctx** out) {
     using namespace mip::plan;
     if (!cfg || !out) return fail(MIPNERF_E_INVALID, "null argument");
-#ifdef MIPNERF_EXPERIMENT_BUILD
-    // build.py compiled this library with timing-experiment knobs that produce WRONG results (ablated barriers / operand reads /
-    // transposing MFMAs ...): it refuses to serve unless the process says it knows
-    if (!getenv("MIPNERF_ALLOW_EXPERIMENT_LIB"))
-        return fail(MIPNERF_E_UNSUPPORTED, "this library is a timing-experiment build (" MIPNERF_EXPERIMENT_BUILD "): its results are wrong by "
-                                           "construction; set MIPNERF_ALLOW_EXPERIMENT_LIB=1 to time it, or rebuild without those variables");
-#endif
     if (cfg->num_samples < 1 || cfg->num_samples > MIPNERF_MAX_SAMPLES)
         return fail(MIPNERF_E_INVALID, "num_samples must be in [1, %d]", MIPNERF_MAX_SAMPLES);
     if (cfg->num_levels < 1 || cfg->num_levels > 2) return fail(MIPNERF_E_UNSUPPORTED, "num_levels must be 1 or 2");

@@ -25,35 +25,25 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
-from mipnerf_pl_amd.mlp_plan import CHAIN, Plan, Arch  # noqa: E402
+from mipnerf_pl_amd.mlp_plan import Plan, Arch  # noqa: E402
 
-WAVES = int(os.environ.get("MLP_WAVES", "8"))   # wavefronts per workgroup (32 samples each); 4 => two 128-sample workgroups per CU
+WAVES = 8             # wavefronts per workgroup (32 samples each); the 512-wide trunk: 4 (waves_of)
 GROUP = 4 * WAVES     # chunks per ring slot (wave w DMAs chunks 4w..4w+3 of a group)
 SLOTS = 2             # ring slots
-WG_PER_CU = 8 // WAVES
 CHUNK_BYTES = 1024
-PREFETCH = int(os.environ.get("MLP_PREFETCH", "4"))   # A-fragment prefetch distance in chunks (registers A0..)
-ABLATE_BARRIER = os.environ.get("MLP_ABLATE_BARRIER", "0") == "1"   # timing experiments only (wrong results)
-ABLATE_WAIT = os.environ.get("MLP_ABLATE_WAIT", "0") == "1"         # timing experiments only (wrong results)
-ABLATE_LDA = int(os.environ.get("MLP_ABLATE_LDA", "0"))              # N > 0: read only every (N+1)-th A fragment (wrong results)
-# static priority 1 for the second-dispatched half of the workgroup (the arbitration loser on every segment): 0.4722-0.4756 vs
-# 0.4762-0.4773 ms per launch in three alternating A/B pairs (+0.4 %, profiles/r02k_setprio_ab.log); MLP_SETPRIO=0 turns it off
-SETPRIO = os.environ.get("MLP_SETPRIO", "1") == "1"
-# The integrated positional encoding of the NEXT tile computed piecewise in the shadow of this tile's MFMAs (after the last layer
-# that reads the encoding: its LDS area is free from there on) instead of in a VALU-only phase at the start of every tile.
-IPE_SHADOW = os.environ.get("MLP_IPE_SHADOW", "0") == "1"    # measured: -0.56 % cycles, +0.25 % time (profiles/r03f_ipe_shadow_ab.txt): off
-IPE_SHADOW_STRIDE = int(os.environ.get("MLP_IPE_SHADOW_STRIDE", "4"))    # one piece every STRIDE slots
-# trunk kernels of the two-kernel form: pre_x / pre_acc (read once, 1.5 KB per sample) with the non-temporal policy, so that they do not push the weight
-# stream out of the L2: 7.803 / 7.812 / 7.819 vs 7.835 / 7.837 / 7.862 ms per forward in three alternating pairs (-0.4 %, profiles/r04z_trunk_nt_loads_ab.txt)
-PRE_NT = os.environ.get("MLP_PRE_NT_LOADS", "1") == "1"
-# round 6, timing probe for the one-kernel form: the trunk without its 1,536 B/sample of pre_x / pre_acc loads -- the values come
-# from LDS instead (stale weights as X, the bias table as accumulator images).  WRONG results (build.py: WRONG_RESULT_KNOBS)
-ABLATE_PRELOADS = os.environ.get("MLP_TRUNK_ABLATE_PRELOADS", "0") == "1"
+PREFETCH = 4          # A-fragment prefetch distance in chunks (registers A0..)
+# Every kernel gives static priority 1 to the second-dispatched half of the workgroup (the arbitration loser on every segment): 0.4722-0.4756 vs
+# 0.4762-0.4773 ms per launch in three alternating A/B pairs (+0.4 %, profiles/r02k_setprio_ab.log).
+# The trunk kernels of the two-kernel form read pre_x / pre_acc (read once, 1.5 KB per sample) with the non-temporal policy, so that they do not push
+# the weight stream out of the L2: 7.803 / 7.812 / 7.819 vs 7.835 / 7.837 / 7.862 ms per forward in three alternating pairs (-0.4 %,
+# profiles/r04z_trunk_nt_loads_ab.txt).
+# Computing the NEXT tile's integrated positional encoding piecewise in the shadow of this tile's MFMAs measured -0.56 % cycles but +0.25 % time
+# (profiles/r03f_ipe_shadow_ab.txt): it is computed in a VALU-only phase at the start of every tile.
 NE = 3                # rotating registers for LDS-resident B operands (E0..E2)
 # one-kernel form of a wide encoding (Plan.fused): wave-private LDS ring of encoding k-steps (1 KiB each, global_load_lds from the fragment buffer
 # k_cast_ipe_360 writes) and how many k-steps ahead of its MFMAs a k-step's DMA is issued (its B-operand read happens two k-steps ahead)
-FUSED_RING = int(os.environ.get("MLP_FUSED_RING", "8"))
-FUSED_AHEAD = int(os.environ.get("MLP_FUSED_AHEAD", "7"))
+FUSED_RING = 8
+FUSED_AHEAD = 7
 ENC_WAVE_BYTES = 8192  # wave-private LDS: 6 KiB encoding + 2 KiB view encoding
 
 
@@ -116,7 +106,6 @@ def gen_plan_header(plans) -> str:
              ", ".join(str(int(np.prod(s))) for _, s in shapes) + "};")
     L.append(f"constexpr int kNumChunks = {len(plan.chunks)}, kNumTiles = {plan.n_tiles}, kNumOps = {len(plan.ops)};")
     L.append(f"constexpr int kGroupChunks = {GROUP}, kRingSlots = {SLOTS}, kNumGroups = {len(plan.chunks) // GROUP};")
-    L.append(f"constexpr bool kChainOrder = {'true' if CHAIN else 'false'};   // weight-stream order (mlp_plan.CHAIN)")
     L.append("struct SegDesc { int kind, nk, col0, ncols; };            // kind 0 natural, 1 dlayout")
     L.append("struct TileDesc { int wt, bt, row0, nrows, ld; };")
     L.append("// kind 0 hidden, 1 head (last tile = density), 2 colour")
@@ -186,15 +175,10 @@ def build_schedule(plan: Plan):
                 if seg.regset == "enc":
                     return ("lds", ksl * 1024)
                 return ("lds", nenc_lds * 1024 + ksl * 1024)   # view: after the encoding k-steps
-            if CHAIN:
+            for ks in range(op.nk):
                 for w in range(spk):
-                    for ks in range(op.nk):
-                        slots.append(dict(acc=f"acc{pair}{w}", b=bop(ks), panel=len(panels), ks=ks, first_of_ks=True))
-            else:
-                for ks in range(op.nk):
-                    for w in range(spk):
-                        slots.append(dict(acc=f"acc{pair}{w}", b=bop(ks), panel=len(panels), ks=ks, first_of_ks=(w == 0)))
-            panels.append(dict(op=op, t0=t0, t1=t1, first=first, n=len(slots) - first, pair=pair, spk=1 if CHAIN else spk))
+                    slots.append(dict(acc=f"acc{pair}{w}", b=bop(ks), panel=len(panels), ks=ks, first_of_ks=(w == 0)))
+            panels.append(dict(op=op, t0=t0, t1=t1, first=first, n=len(slots) - first, pair=pair, spk=spk))
     return panels, slots
 
 
@@ -288,7 +272,7 @@ __device__ __forceinline__ void epilogue_half(const f32x16& acc, bf16x8& o) {
     }
 }
 
-// (PRE_LD: read-once data of the trunk kernels -- plain or non-temporal loads, build knob MLP_PRE_NT_LOADS)
+// (PRE_LD: read-once data of the trunk kernels -- plain loads, or non-temporal ones where the kernel defines it)
 #ifndef PRE_LD
 #define PRE_LD(ptr) (*(ptr))
 #endif
@@ -428,50 +412,13 @@ __device__ __forceinline__ void ipe_to_lds(const RayIn& R, int64_t sc, int num_s
     }
 }
 
-// The same encoding in PIECES (gen_mlp_bf16.IPE_SHADOW): the generated tile body spreads them over the MFMA slots that follow the
-// last layer reading the encoding, computing the NEXT tile's fragments while this tile's layers 6.. run.  Expression for
-// expression the body of ipe_to_lds above, so both routes write the same bits.
-struct IpeNext { float mx, my, mz, cx, cy, cz; };
-__device__ __forceinline__ void ipe_next_gauss(const RayIn& R, int64_t sc, int num_samples, IpeNext& q) {
-    const int64_t b = sc / num_samples;
-    const int i = (int)(sc - b * num_samples);
-    const float d[3] = {R.dirs[b * 3], R.dirs[b * 3 + 1], R.dirs[b * 3 + 2]};
-    const float o[3] = {R.origins[b * 3], R.origins[b * 3 + 1], R.origins[b * 3 + 2]};
-    const float t0 = R.t[b * (num_samples + 1) + i], t1 = R.t[b * (num_samples + 1) + i + 1];
-    Gauss3 g = conical_frustum_to_gaussian(t0, t1, d, o, R.radii[b]);
-    if (R.disable_integration) g.cov[0] = g.cov[1] = g.cov[2] = 0.0f;
-    q.mx = g.mean[0]; q.my = g.mean[1]; q.mz = g.mean[2]; q.cx = g.cov[0]; q.cy = g.cov[1]; q.cz = g.cov[2];
-}
-template <int KS, int J>
-__device__ __forceinline__ void ipe_next_yd(const RayIn& R, const IpeNext& q, int hi, float& y, float& damp) {
-    auto pick = [](int a, float x, float yy, float z) { return a == 0 ? x : (a == 1 ? yy : z); };
-    constexpr int f0 = KS * 16 + J, f1 = f0 + 8;              // lane-half 0 / 1
-    const int l = hi ? f1 / 3 : f0 / 3;
-    const float m = hi ? pick(f1 % 3, q.mx, q.my, q.mz) : pick(f0 % 3, q.mx, q.my, q.mz);
-    const float cv = hi ? pick(f1 % 3, q.cx, q.cy, q.cz) : pick(f0 % 3, q.cx, q.cy, q.cz);
-    const float scale = (float)(1u << (l + R.min_deg));
-    y = m * scale;
-    const float yv = cv * (scale * scale);
-    damp = exp_fast(-0.5f * yv);
-}
-template <int J>
-__device__ __forceinline__ void ipe_next_sc(float y, float damp, bf16x8& fs, bf16x8& fc) {
-    fs[J] = (__bf16)(damp * sin_fast(y));
-    fc[J] = (__bf16)(damp * sin_fast(y + kHalfPiF));
-}
-template <int KS>
-__device__ __forceinline__ void ipe_next_store(const bf16x8& fs, const bf16x8& fc, char* enc_lane_w) {
-    *reinterpret_cast<bf16x8*>(enc_lane_w + KS * 1024) = fs;
-    *reinterpret_cast<bf16x8*>(enc_lane_w + (KS + 3) * 1024) = fc;
-}
-
 // Ring-group boundary, executed when the A-fragment LOAD cursor enters group g:
 // (1) this wave's share of group g has landed (vmcnt) and all its LDS reads of group g-1 have
 //     returned (lgkmcnt); (2) barrier: both now hold for every wave, so group g is readable and
 //     the slot of group g-1 is free; (3) prefetch group g+1 (or group 0 of the next tile) there.
 #define GROUP_BEGIN(g, nslot)                                                                     \
     do {                                                                                          \
-        if (DMA) asm volatile("WAIT_INSN\n\tBARRIER_INSN" ::: "memory");          \
+        if (DMA) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");          \
         else __syncthreads();                                                                     \
         if ((g) + 1 < kNumGroups) issue_group<DMA>(stream, smem, (g) + 1, (nslot), wave, lane16); \
         else if (has_next) issue_group<DMA>(stream, smem, 0, (nslot), wave, lane16);              \
@@ -493,7 +440,7 @@ DEEP_RING_MACRO = r"""// One wave per SIMD (the 512-wide trunk, gen_mlp_bf16.wav
         if ((g) + kAhead < kNumGroups) issue_group<DMA>(stream, smem, (g) + kAhead, ((g) + kAhead) % kSlots, wave, lane16);      \
         else issue_group<DMA>(stream, smem, (g) + kAhead - kNumGroups, ((g) + kAhead) % kSlots, wave, lane16);                  \
     } while (0)
-// kSlots = kAhead + 2 (MLP_WIDE_SPARE_SLOT=1): group g + kAhead goes into the slot of group g - 2, whose LDS reads returned long ago (every
+// kSlots = kAhead + 2 (the spare slot): group g + kAhead goes into the slot of group g - 2, whose LDS reads returned long ago (every
 // MFMA slot waits for all but its last PREFETCH - 1 reads), so the boundary need not drain this wave's in-flight A-fragment reads of group g - 1
 #define GROUP_BEGIN_DEEP_NODRAIN(g, WAITCNT)                                                                             \
     do {                                                                                                                \
@@ -593,13 +540,6 @@ def count_waits(lines, start, cpw, ngroups):
     return kmax
 
 
-def _shadow_fits(plan: Plan) -> bool:
-    """Three ops behind the last encoding reader with >= 2 x 18 MFMA slots each (gen_kernel places one encoding k-step per op)."""
-    last = max(i for i, op in enumerate(plan.ops) if any(sg.regset == "enc" for sg in op.segs))
-    tail = plan.ops[last + 1:last + 4]
-    return len(tail) == 3 and all(op.nk * len(op.tiles) // 2 >= 18 for op in tail)
-
-
 def waves_of(arch: Arch) -> int:
     """Wavefronts per workgroup.  A layer's input AND output activations live in registers (2 x width/16 k-step fragments of 4 VGPRs): up to 256
     wide that is 128 of the 256 registers a wave has at two waves per SIMD; a 512-wide trunk needs 256 for the activations alone, so its kernel
@@ -614,20 +554,19 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
     assert not fused or (1 < FUSED_AHEAD <= FUSED_RING - 1)
     WAVES = waves_of(plan.arch)                 # (shadow the module defaults: everything below is per kernel)
     wide = max(plan.arch.net_width, plan.arch.net_width_condition) > 256      # one wave per SIMD, 512-register budget
-    # chunks a wave DMAs per ring group.  The one-wave-per-SIMD kernels can take 8 (MLP_WIDE_CPW): a group is then 32 of a wave's MFMAs, so the
+    # chunks a wave DMAs per ring group.  The one-wave-per-SIMD kernels can take 8: a group is then 32 of a wave's MFMAs, so the
     # workgroup meets at a barrier half as often -- with one wave per SIMD nobody covers for a wave parked at the barrier
-    PREFETCH = int(os.environ.get("MLP_WIDE_PREFETCH", globals()["PREFETCH"])) if wide else globals()["PREFETCH"]      # A-fragment read distance (chunks)
-    CPW = int(os.environ.get("MLP_WIDE_CPW", "4")) if wide else 4
+    CPW = 4
     assert CPW in (4, 8)
     GROUP = CPW * WAVES
     WG_PER_CU = 1 if wide else 8 // WAVES
     nreg = max(plan.arch.net_width, plan.arch.net_width_condition) // 16      # k-step fragments of one activation register set
     # Round 6 A/B on the 512-wide trunk (profiles/r06c_w512_group_prefetch_ab.txt, r06d_w512_spare_slot_ab.txt; ms per 524,288 samples): default of round 5
-    # (3 groups in flight, 4 slots) 2.085-2.121; 32-chunk groups (MLP_WIDE_CPW=8: half the barriers) 2.14; A fragments 6 / 8 chunks ahead 2.10 / 2.11;
-    # a spare slot (no LDS drain at the boundaries) with 2 / 4 groups in flight 2.088-2.093 / 2.096-2.104.  None of the ring's knobs is worth more
+    # (3 groups in flight, 4 slots) 2.085-2.121; 32-chunk groups (CPW = 8: half the barriers) 2.14; A fragments 6 / 8 chunks ahead 2.10 / 2.11;
+    # a spare slot (no LDS drain at the boundaries) with 2 / 4 groups in flight 2.088-2.093 / 2.096-2.104.  None of the ring's settings is worth more
     # than 1.3 %: at 128 samples per workgroup the kernel pulls its 4.5-MiB weight stream through L2 -> LDS at 9.6 TB/s chip-wide, which is what bounds it.
-    AHEAD = int(os.environ.get("MLP_WIDE_AHEAD", "2")) if wide else 1         # ring groups in flight (GROUP_BEGIN_DEEP); the 8-wave kernels: 1
-    SPARE = wide and os.environ.get("MLP_WIDE_SPARE_SLOT", "1") == "1"           # one more ring slot than groups in flight: no LDS drain at the group boundaries
+    AHEAD = 2 if wide else 1         # ring groups in flight (GROUP_BEGIN_DEEP); the 8-wave kernels: 1
+    SPARE = wide                     # one more ring slot than groups in flight: no LDS drain at the group boundaries
     SLOTS = (AHEAD + (2 if SPARE else 1)) if wide else globals()["SLOTS"]
     sfx = f"_pre_v{variant}" if pre else (f"_fused_v{variant}" if fused else ("" if variant == 0 else f"_v{variant}"))
     nchunks = len(plan.chunks)
@@ -665,17 +604,11 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
         e(f"namespace v{variant}{'pre' if pre else ('fused' if fused else '')} {{")
     e("typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;")
     e("typedef __attribute__((ext_vector_type(16))) float f32x16;")
-    if pre and ABLATE_PRELOADS:
-        e("extern __shared__ __attribute__((aligned(16))) char smem_probe[];")
-        e("typedef __attribute__((ext_vector_type(4))) float f32x4p_;")
-        e("__device__ __forceinline__ bf16x8 pre_fake(const bf16x8* p) { return *reinterpret_cast<const bf16x8*>(smem_probe + ((unsigned)(size_t)p & 0x7ff0u)); }")
-        e(f"__device__ __forceinline__ f32x4p_ pre_fake(const f32x4p_* p) {{ return *reinterpret_cast<const f32x4p_*>(smem_probe + {ring_bytes} + ((unsigned)(size_t)p & 0x1ff0u)); }}")
-        e("#define PRE_LD(ptr) pre_fake(ptr)")
-    elif pre and PRE_NT:
+    if pre:
         e("#define PRE_LD(ptr) __builtin_nontemporal_load(ptr)")
     # (fused: 29 instead of 136 SGPRs spilled to VGPR lanes and -0.3 % per forward in three alternating pairs, profiles/r06g_fused360_ab.txt;
     #  the ring geometry -- 8 slots / 7 ahead, 8 / 5, 6 / 5 -- is worth nothing: 6.60-6.61 ms all)
-    if wide or (fused and os.environ.get("MLP_FUSED_OPAQUE", "1") == "1"):
+    if wide or fused:
         e("#define MIP_OPAQUE_STREAM_BASE 1")
     e(f"constexpr int kRingBytes = {ring_bytes};")
     e(f"constexpr int kBiasBytes = {nbias_bytes};")
@@ -690,8 +623,7 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
     if wide:
         e(f"constexpr int kAhead = {AHEAD};")
         e(f"constexpr int kSlots = {SLOTS};")
-    e(KERNEL_PREAMBLE.replace("BARRIER_INSN", "s_nop 0" if ABLATE_BARRIER else "s_barrier")
-      .replace("WAIT_INSN", "s_waitcnt lgkmcnt(0)" if ABLATE_WAIT else "s_waitcnt vmcnt(0) lgkmcnt(0)"))
+    e(KERNEL_PREAMBLE)
     if wide:
         e(DEEP_RING_MACRO)
     if fused:
@@ -717,9 +649,7 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
     e("    for (int i = tid; i < kBiasBytes / 16; i += blockDim.x)")
     e("        reinterpret_cast<float4*>(smem + kRingBytes)[i] = reinterpret_cast<const float4*>(bias_tab)[i];")
     e("    __syncthreads();")
-    if SETPRIO:
-        e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // MI355X_MICROARCH.md, two waves per SIMD, item 4")
-    shadow = IPE_SHADOW and nenc == 6 and _shadow_fits(plan)
+    e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // MI355X_MICROARCH.md, two waves per SIMD, item 4")
     if wide:
         e("    if ((int)blockIdx.x < ntiles) {")
         for g in range(AHEAD):
@@ -733,29 +663,17 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
         e("    }")
     else:
         e("    if ((int)blockIdx.x < ntiles) issue_group<DMA>(stream, smem, 0, 0, wave, lane16);")
-    if shadow:
-        e("    if (IPE && (int)blockIdx.x < ntiles) {      // the first tile's encoding; every later one is computed in the previous tile's shadow")
-        e("        const int64_t s_first = (int64_t)blockIdx.x * kTileSamples + wave * 32 + n;")
-        e(f"        ipe_to_lds<{nenc}>(rin, s_first < M ? s_first : M - 1, num_samples, hi, encw + lane16);")
-        e("    }")
     e("    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {")
     e("        const bool has_next = tile + (int)gridDim.x < ntiles;")
     e("        const int64_t s = (int64_t)tile * kTileSamples + wave * 32 + n;")
     e("        const int64_t sc = s < M ? s : M - 1;")
     e("        const int64_t ray = sc / num_samples;")
-    if shadow:
-        e("        const int64_t s_next = (int64_t)(tile + (int)gridDim.x) * kTileSamples + wave * 32 + n;")
-        e("        const int64_t scn = s_next < M ? s_next : M - 1;     // past the end: a valid sample, its encoding is never used")
-        e("        IpeNext ipn;")
-        e("        float ipe_y = 0.0f, ipe_d = 0.0f;")
-        e("        bf16x8 ipe_fs, ipe_fc;")
     if pre or fused:
         e("        issue_encodings<DMA, 0, 0>(nullptr, viewenc + ray * 32 + hi * 8, encw, lane16);")
     else:
         e("        if (IPE) {")
         e(f"            issue_encodings<DMA, {nenc}, {nenc}>(nullptr, viewenc + ray * 32 + hi * 8, encw, lane16);")
-        if not shadow:
-            e(f"            ipe_to_lds<{nenc}>(rin, sc, num_samples, hi, encw + lane16);")
+        e(f"            ipe_to_lds<{nenc}>(rin, sc, num_samples, hi, encw + lane16);")
         e("        } else {")
         e(f"            issue_encodings<DMA, {nenc}, 0>(enc + sc * {a.xyz_dim} + hi * 8, viewenc + ray * 32 + hi * 8, encw, lane16);")
         e("        }")
@@ -777,8 +695,6 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
     def lda(c):
         slot = (c // GROUP) % SLOTS
         off = slot * GROUP * CHUNK_BYTES + (c % GROUP) * CHUNK_BYTES
-        if ABLATE_LDA and (c // PREFETCH) % (ABLATE_LDA + 1) != 0 and c >= PREFETCH:
-            return f"// (ablated) A{c % PREFETCH} = LDA({off});"
         return f"A{c % PREFETCH} = LDA({off});"
 
     # ---- assign E registers to LDS-resident B operands and place their loads -----------------
@@ -872,36 +788,6 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
         last_ring = max(c for c, sl in enumerate(slots) if sl["b"][0] == "ring")
         for i in range(FUSED_AHEAD):      # the next tile's first k-steps (a harmless re-read of this tile's on the last tile)
             side[last_ring].append(f"ENC_DMA({nring + i}, encb_next, {i * 1024}, {2048 + (i % FUSED_RING) * 1024});")
-
-    # ---- the next tile's integrated positional encoding, in pieces, behind the last reader of this tile's encoding ----
-    # One k-step (8 feature pairs + its LDS store) per op, in the FIRST HALF of that op's slots: there most of the op's output
-    # registers are still dead, so the pieces' temporaries (y, damping, two fragments) fit the 256-VGPR budget without spills;
-    # only the six Gaussian moments stay live from the first piece to the last.
-    if shadow:
-        last_enc = max(c for c, sl in enumerate(slots) if sl["b"][0] == "lds" and sl["b"][1] < nenc * 1024)
-        tail_ops = []
-        for pn in panels:
-            op = pn["op"]
-            if pn["first"] > last_enc + 2 and (not tail_ops or tail_ops[-1][0] is not op):
-                tail_ops.append([op, pn["first"], 0])
-            if tail_ops and tail_ops[-1][0] is op:
-                tail_ops[-1][2] = pn["first"] + pn["n"] - tail_ops[-1][1]
-        per_k = []
-        for ks in range(3):
-            ps = []
-            for j in range(8):
-                ps.append(f"ipe_next_yd<{ks}, {j}>(rin, ipn, hi, ipe_y, ipe_d);")
-                ps.append(f"ipe_next_sc<{j}>(ipe_y, ipe_d, ipe_fs, ipe_fc);")
-            ps.append(f"ipe_next_store<{ks}>(ipe_fs, ipe_fc, encw + lane16);")
-            per_k.append(ps)
-        per_k[0].insert(0, "ipe_next_gauss(rin, scn, num_samples, ipn);")
-        regions = [(first, n // 2) for _, first, n in tail_ops[:3]]
-        assert len(regions) == 3 and all(r[1] >= len(per_k[0]) for r in regions), \
-            "IPE_SHADOW needs three ops behind the skip layer with >= 36 MFMA slots each (set MLP_IPE_SHADOW=0 for this shape)"
-        for (first, n), ps in zip(regions, per_k):
-            stride = max(1, min(IPE_SHADOW_STRIDE, n // len(ps)))
-            for pi_, stmt in enumerate(ps):
-                side[first + pi_ * stride].append("if (IPE) { " + stmt + " }")
 
     # ---- tile prologue --------------------------------------------------------------------------
     def group_begin(g, note=""):

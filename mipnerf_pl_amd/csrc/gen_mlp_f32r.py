@@ -30,8 +30,7 @@ from mipnerf_pl_amd.mlp_f32r_plan import GROUP_CHUNKS, NSLOT, RING_SLOTS, F32RPl
 GROUP_BYTES = GROUP_CHUNKS * 1024
 RING_BYTES = RING_SLOTS * GROUP_BYTES
 WAVES = 4
-PIECE_WINDOW = float(os.environ.get("MLP_F32R_PIECE_WINDOW", "0.5"))
-GEN_ABLATE = int(os.environ.get("MLP_F32R_GEN_ABLATE", "0"))      # timing experiments (wrong results): 1 no LDS-DMA, 2 no accumulator images, 4 no thin heads, 8 no ReLU   # fraction of a ring group's k-steps that carry its LDS-DMA pieces
+PIECE_WINDOW = 0.5    # fraction of a ring group's k-steps that carry its LDS-DMA pieces
 TILE_SAMPLES = 32 * WAVES
 
 
@@ -49,13 +48,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // next group needs (the pieces queued at the previous barrier: the ring is RING_SLOTS deep, group g + RING_SLOTS - 1 is in flight while
 // g is read), so vmcnt(K) = "my share of the next group and of the natural blocks queued two barriers ago has landed"; lgkmcnt(0) = my
 // reads of the slot that is about to be refilled have returned; the barrier makes both true for every wave.
-#if defined(MLP_F32R_ABLATE) && MLP_F32R_ABLATE == 1          // timing experiments only (races): no barrier / no waits at all
-#define GROUP_BEGIN(K) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(K) : "memory")
-#elif defined(MLP_F32R_ABLATE) && MLP_F32R_ABLATE == 2
-#define GROUP_BEGIN(K) asm volatile("" ::: "memory")
-#else
 #define GROUP_BEGIN(K) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(K) : "memory")
-#endif
 
 __device__ __forceinline__ float relu1(float x) { return __builtin_fmaxf(x, 0.0f); }
 
@@ -79,13 +72,8 @@ __device__ __forceinline__ void dma_piece(const char* gbase, unsigned lds_addr, 
         : "memory");
 }
 // One piece of a natural block: every lane brings 16 bytes of ITS sample's row: per-lane 64-bit row address + immediate; M0 is the LDS
-// target minus that immediate.  The rows are read once per tile (MLP_F32R_NAT_NT=1: non-temporal, so that hundreds of MB of encodings do
-// not compete with the 2.33-MiB weight stream for the XCD's L2).
-#if defined(MLP_F32R_NAT_NT) && MLP_F32R_NAT_NT
-#define NAT_POLICY " nt"
-#else
-#define NAT_POLICY ""
-#endif
+// target minus that immediate.  The rows are read once per tile (non-temporal, so that hundreds of MB of encodings do not compete with the
+// 2.33-MiB weight stream for the XCD's L2).
 template <int IMM>
 __device__ __forceinline__ void dma_piece_v(const float* row, unsigned m0_val) {
     unsigned keep;
@@ -93,7 +81,7 @@ __device__ __forceinline__ void dma_piece_v(const float* row, unsigned m0_val) {
         "s_mov_b32 %0, m0\n\t"
         "s_mov_b32 m0, %2\n\t"
         "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off offset:%3" NAT_POLICY "\n\t"
+        "global_load_lds_dwordx4 %1, off offset:%3 nt\n\t"
         "s_mov_b32 m0, %0"
         : "=&s"(keep)
         : "v"(row), "s"(m0_val), "n"(IMM)
@@ -139,7 +127,7 @@ class Gen:
         op, blk, j = st["op"], st["blk"], st["j"]
         assert blk.kind == DLAYOUT
         reg = f"{blk.src}[{blk.index}][{j}]"
-        return f"relu1({reg})" if op.in_relu and not (GEN_ABLATE & 8) else reg
+        return f"relu1({reg})" if op.in_relu else reg
 
     def nat_pieces(self, u, nxt, indent="        "):
         """the four LDS-DMA statements of one natural block (the first carries the opaque copy of the wave's LDS base)"""
@@ -272,7 +260,7 @@ class Gen:
                     E(f"        bqn = LDB({un['slot'] * 4096 + (nxt['j'] // 4) * 1024});")
                     nxt_q = key
             # ---- thin head riding on this step
-            for th in (op.thin if not (GEN_ABLATE & 4) or not op.tiles else []):
+            for th in op.thin:
                 for row in range(th.nrows):
                     nm_ = f"thin{oi}_{row}"
                     if st["ks"] % 4 == 0:
@@ -295,18 +283,13 @@ class Gen:
                 at[pos] = at.get(pos, 0) + 1
             for t in range(nt):
                 for _ in range(at.get(t, 0)):
-                    pc = pieces.pop(0)
-                    if not (GEN_ABLATE & 1) or pc.startswith("NEXT"):
-                        E("        " + pc)
+                    E("        " + pieces.pop(0))
                 E(f"        MFMA({op.out}[{t}], a{t // 4}[{t % 4}], b{i % 2});")
             if nt == 0:
                 for _ in range(npc):
-                    pc = pieces.pop(0)
-                    if not (GEN_ABLATE & 1) or pc.startswith("NEXT"):
-                        E("        " + pc)
+                    E("        " + pieces.pop(0))
             for s_ in bias_in.get(i, []):
-                if not (GEN_ABLATE & 2):
-                    E("        " + s_)
+                E("        " + s_)
             if nt:
                 E("        PIN();")
             if nq:

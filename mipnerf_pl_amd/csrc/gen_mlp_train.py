@@ -22,15 +22,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, HERE)
 from mipnerf_pl_amd.mlp_plan import Plan  # noqa: E402
 from mipnerf_pl_amd.mlp_train_plan import GROUP, SLOTS, TrainPlan  # noqa: E402
-from gen_mlp_bf16 import KERNEL_PREAMBLE, SETPRIO  # noqa: E402
+from gen_mlp_bf16 import KERNEL_PREAMBLE  # noqa: E402
 
 WAVES = 8
 CHUNK_BYTES = 1024
-PREFETCH = int(os.environ.get("MLP_TRAIN_PREFETCH", "4"))
-ABLATE_TMFMA = os.environ.get("MLP_TRAIN_ABLATE_TMFMA", "0") == "1"    # timing experiment: no transposing MFMAs (wrong T-blocks)
-# timing experiment: comma-separated forward op indices whose saved-activation T-blocks are neither transposed nor stored
-# ("store every other layer"; the weight-gradient kernel would recompute them: MLP_WGRAD_RECOMPUTE_PROBE).  Wrong gradients.
-SKIP_STORES = {int(x) for x in os.environ.get("MLP_TRAIN_SKIP_STORES", "0").split(",") if x.strip() and os.environ.get("MLP_TRAIN_SKIP_STORES", "0") != "0"}
+PREFETCH = 4
 NE = 3
 
 TRAIN_PREAMBLE = r"""
@@ -45,9 +41,6 @@ __device__ __forceinline__ void store_tfrag(const f32x16& acc, char* blk, unsign
     bf16x8 o;
 #pragma unroll
     for (int r = 0; r < 8; ++r) o[r] = (__bf16)acc[R0 + r];
-#ifdef MLP_TRAIN_ABLATE_STORES      // timing experiment: everything but the store itself (results are wrong)
-    if (lane16 != 0xFFFFFFFFu) { asm volatile("" :: "v"(o)); return; }
-#endif
     // streamed once, read back by another kernel after >2 GB of other traffic: keep it out of the L2's way
     // (measured on MI355X: -5 % forward-with-save, -7 % dgrad vs plain stores)
     __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(blk + (R0 / 8) * 1024 + lane16));
@@ -87,16 +80,6 @@ __device__ __forceinline__ void depilogue_half(const f32x16& acc, unsigned mw, b
     o = v;
 }
 
-// Ring-group boundary with a COUNTED wait.  vmcnt retires in issue order (loads and stores share the counter on
-// gfx9-family parts), and this wave issued exactly K stores (all unconditional) after its 4 DMAs of group g, so
-// vmcnt(K) means "my share of group g has landed" without draining the T-block stores still in flight.
-#define GROUP_BEGIN_K(g, nslot, K)                                                               \
-    do {                                                                                          \
-        asm volatile("s_waitcnt vmcnt(" #K ") lgkmcnt(0)\n\ts_barrier" ::: "memory");              \
-        if ((g) + 1 < kNumGroups) issue_group<DMA>(stream, smem, (g) + 1, (nslot), wave, lane16); \
-        else if (has_next) issue_group<DMA>(stream, smem, 0, (nslot), wave, lane16);              \
-    } while (0)
-
 // one 1-KiB lane-linear DMA (global -> wave-private LDS), per-lane 64-bit source address
 __device__ __forceinline__ void dma_1k(const void* src_lane, char* lds_dst) {
     const unsigned lds_addr = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds_dst;
@@ -133,7 +116,7 @@ def _slot_b(sl):
     return b[1] if isinstance(b, tuple) and b[0] == "reg" else None
 
 
-def place_sides(prog, nchunks, which=""):
+def place_sides(prog, nchunks):
     """Spread each panel's `post` statements (and the next-next panel's `pre`) over the next panel's slots: the
     register work (epilogue, transposing MFMAs, masks) right away, one statement per slot; the T-block STORES evenly
     over the rest of the panel (all 8 waves of a workgroup run in lockstep, so back-to-back stores reach the CU's store
@@ -142,17 +125,12 @@ def place_sides(prog, nchunks, which=""):
     instructions altogether saves 0.18 ms of a 0.77 ms launch, but neither spreading them, nor counted vmcnt waits,
     nor the block layout (scripts/micro/wpattern.hip: the pattern alone sustains 4.9 TB/s) changes the launch time --
     the kernel sits on the power envelope and 3.5 TB/s of HBM writes take their share of it."""
-    spread = os.environ.get("MLP_TRAIN_SPREAD_STORES", "1") in ("1", which)
     side = {c: [] for c in range(nchunks)}
     for pi, pn in enumerate(prog.panels):
         post = prog.panels[pi - 1]["post"] if pi > 0 else []
         pre = prog.panels[pi + 1]["pre"] if pi + 1 < len(prog.panels) else []
         n = pn["n"]
         first = pn["first"]
-        if not spread:
-            for wi, stmt in enumerate(post + pre):
-                side[first + min(2 + wi, n - 1)].append(stmt)
-            continue
         compute = [st for st in post if count_stores(st) == 0]
         stores = [st for st in post if count_stores(st) > 0]
         pos = 2
@@ -184,30 +162,20 @@ def count_stores(stmt: str) -> int:
     return stmt.count("store_tfrag<") + stmt.count("reinterpret_cast<u32x4*>(mask_wave")
 
 
-def emit_tile_body(e, prog, side, nchunks_total, prologue_lines, final_lines, lda,
-                   counted=os.environ.get("MLP_TRAIN_COUNTED_VMCNT", "0") == "1"):
+def emit_tile_body(e, prog, side, nchunks_total, prologue_lines, final_lines, lda):
     """MFMA slots with A prefetch PREFETCH chunks ahead and ring-group boundaries where the load cursor
     enters a new group.  nchunks_total >= len(slots): trailing (padding) groups are still cycled through so
-    that the ring phase is tile-invariant.  Group boundaries g >= 1 wait with vmcnt(K), K = stores this wave
-    issued since the DMA of group g (see GROUP_BEGIN_K); the tile's first boundary drains everything (it also
-    needs the tile-private DMAs issued just before it)."""
+    that the ring phase is tile-invariant.  Every boundary drains the wave's vector memory operations (a counted
+    wait that leaves the T-block stores in flight measured no faster, see place_sides)."""
     nslots = len(prog.slots)
     e("        GROUP_BEGIN(0, 1);")
-    since = 0
 
     def group_begin(g):
-        nonlocal since
-        if counted:
-            assert since <= 60
-            e(f"        GROUP_BEGIN_K({g}, {(g + 1) % SLOTS}, {since});")
-        else:
-            e(f"        GROUP_BEGIN({g}, {(g + 1) % SLOTS});")
-        since = 0
+        e(f"        GROUP_BEGIN({g}, {(g + 1) % SLOTS});")
     for c in range(min(PREFETCH, nslots)):
         e(f"        {lda(c)}")
     for ln in prologue_lines:
         e(f"        {ln}")
-        since += count_stores(ln)
     e("        PIN();")
     cur_op = None
     for c, sl in enumerate(prog.slots):
@@ -225,7 +193,6 @@ def emit_tile_body(e, prog, side, nchunks_total, prologue_lines, final_lines, ld
             e(f"        {lda(lc)}")
         for stmt in side[c]:
             e(f"        {stmt}")
-            since += count_stores(stmt)
         e("        PIN();")
     # groups the load cursor never entered (stream padding): keep the ring protocol going
     first_unentered = (nslots - 1) // GROUP + 1
@@ -306,10 +273,9 @@ def build_fwd_prog(tp: TrainPlan):
                         continue
                     post.append(f"epilogue_half<{relu}, 0>({acc}, {op.out}[{2 * t}]);  /*op{oi}*/")
                     post.append(f"epilogue_half<{relu}, 8>({acc}, {op.out}[{2 * t + 1}]);  /*op{oi}*/")
-                    if hb is not None and oi not in SKIP_STORES:
-                        if not ABLATE_TMFMA:
-                            post_t.append(f"TMFMA0({acc}, {op.out}[{2 * t}], P1);  /*op{oi}*/")
-                            post_t.append(f"MFMA({acc}, {op.out}[{2 * t + 1}], P2);  /*op{oi}*/")
+                    if hb is not None:
+                        post_t.append(f"TMFMA0({acc}, {op.out}[{2 * t}], P1);  /*op{oi}*/")
+                        post_t.append(f"MFMA({acc}, {op.out}[{2 * t + 1}], P2);  /*op{oi}*/")
                         post_late.append(f"store_tfrag<0>({acc}, ht_wave + {(hb + t) * 2048}, lane16);")
                         post_late.append(f"store_tfrag<8>({acc}, ht_wave + {(hb + t) * 2048}, lane16);")
                     if ml is not None:
@@ -372,7 +338,7 @@ def file_header(e, ns, consts):
     e("typedef __attribute__((ext_vector_type(16))) float f32x16;")
     for k, v in consts.items():
         e(f"constexpr int {k} = {v};")
-    e(KERNEL_PREAMBLE.replace("BARRIER_INSN", "s_barrier").replace("WAIT_INSN", "s_waitcnt vmcnt(0) lgkmcnt(0)"))
+    e(KERNEL_PREAMBLE)
     e(TRAIN_PREAMBLE)
     e("constexpr bool DMA = true;")
 
@@ -408,7 +374,7 @@ def gen_trainfwd(tp: TrainPlan, variant: int = 0) -> str:
     # padding: inside the last ring group, or exactly one whole group of zeros (two view layers: 39 groups + 1), begun by an extra GROUP_BEGIN at the tile end
     assert len(prog.slots) == nreal and (nchunks - nreal < GROUP or (nchunks - nreal == GROUP and nreal % GROUP == 0))
     side_e, prologue_e = assign_lds_b(prog, nreal)
-    side = place_sides(prog, nreal, "fwd")
+    side = place_sides(prog, nreal)
     for c in range(nreal):
         side[c] = side_e[c] + side[c]
     check_hazards(prog, side)
@@ -440,8 +406,7 @@ def gen_trainfwd(tp: TrainPlan, variant: int = 0) -> str:
     e("    for (int i = tid; i < kBiasBytes / 16; i += blockDim.x)")
     e("        reinterpret_cast<float4*>(smem + kRingBytes)[i] = reinterpret_cast<const float4*>(bias_tab)[i];")
     e("    __syncthreads();")
-    if SETPRIO:
-        e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // as the inference kernel (gen_mlp_bf16.SETPRIO)")
+    e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // as the inference kernel (gen_mlp_bf16.py)")
     e("    if ((int)blockIdx.x < ntiles) issue_group<DMA>(stream, smem, 0, 0, wave, lane16);")
     e("    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {")
     e("        const bool has_next = tile + (int)gridDim.x < ntiles;")
@@ -554,7 +519,7 @@ def gen_trainfwd_pre(tp: TrainPlan, variant: int) -> str:
     prog = build_fwd_prog(tp)
     assert len(prog.slots) == nreal and (nchunks - nreal < GROUP or (nchunks - nreal == GROUP and nreal % GROUP == 0))
     side_e, prologue_e = assign_lds_b(prog, nreal)
-    side = place_sides(prog, nreal, "fwd")
+    side = place_sides(prog, nreal)
     for c in range(nreal):
         side[c] = side_e[c] + side[c]
     check_hazards(prog, side, preloaded=True)
@@ -585,8 +550,7 @@ def gen_trainfwd_pre(tp: TrainPlan, variant: int) -> str:
     e("    for (int i = tid; i < kBiasBytes / 16; i += blockDim.x)")
     e("        reinterpret_cast<float4*>(smem + kRingBytes)[i] = reinterpret_cast<const float4*>(bias_tab)[i];")
     e("    __syncthreads();")
-    if SETPRIO:
-        e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // as the inference kernel (gen_mlp_bf16.SETPRIO)")
+    e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // as the inference kernel (gen_mlp_bf16.py)")
     e("    if ((int)blockIdx.x < ntiles) issue_group<DMA>(stream, smem, 0, 0, wave, lane16);")
     e("    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {")
     e("        const bool has_next = tile + (int)gridDim.x < ntiles;")
@@ -711,9 +675,8 @@ def build_dgrad_prog(tp: TrainPlan):
                     post.append(f"depilogue_half<false, 0, 0>({acc}, 0u, {op.out}[{2 * t}]);  /*op{oi}*/")
                     post.append(f"depilogue_half<false, 8, 0>({acc}, 0u, {op.out}[{2 * t + 1}]);  /*op{oi}*/")
                 if op.gblock is not None:      # (the bottleneck delta is consumed in registers only)
-                    if not ABLATE_TMFMA:
-                        post_t.append(f"TMFMA0({acc}, {op.out}[{2 * t}], P1);  /*op{oi}*/")
-                        post_t.append(f"MFMA({acc}, {op.out}[{2 * t + 1}], P2);  /*op{oi}*/")
+                    post_t.append(f"TMFMA0({acc}, {op.out}[{2 * t}], P1);  /*op{oi}*/")
+                    post_t.append(f"MFMA({acc}, {op.out}[{2 * t + 1}], P2);  /*op{oi}*/")
                     post_late.append(f"store_tfrag<0>({acc}, gt_wave + {(op.gblock + t) * 2048}, lane16);")
                     post_late.append(f"store_tfrag<8>({acc}, gt_wave + {(op.gblock + t) * 2048}, lane16);")
             pre = []
@@ -738,7 +701,7 @@ def gen_dgrad(tp: TrainPlan, variant: int = 0) -> str:
     assert lds_bytes <= 160 * 1024
     prog = build_dgrad_prog(tp)
     assert len(prog.slots) == nreal
-    side = place_sides(prog, nreal, "dgrad")
+    side = place_sides(prog, nreal)
     check_hazards(prog, side)
     lines = []
     e = lines.append
@@ -759,8 +722,7 @@ def gen_dgrad(tp: TrainPlan, variant: int = 0) -> str:
     e("    const char* priv_lane = privw + lane16;")
     for ln in SELECTORS:
         e("    " + ln)
-    if SETPRIO:
-        e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // as the inference kernel (gen_mlp_bf16.SETPRIO)")
+    e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // as the inference kernel (gen_mlp_bf16.py)")
     e("    if ((int)blockIdx.x < ntiles) issue_group<DMA>(stream, smem, 0, 0, wave, lane16);")
     e("    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {")
     e("        const bool has_next = tile + (int)gridDim.x < ntiles;")

@@ -20,19 +20,11 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace {
-#ifndef MIP_WGRAD_STAGES
-#define MIP_WGRAD_STAGES 4
-#endif
-constexpr int kStages = MIP_WGRAD_STAGES;      // LDS ring depth (build knob MLP_WGRAD_STAGES: 3 / 5 measured no better, profiles/r03aa_wgrad_splits.txt)
+constexpr int kStages = 4;                   // LDS ring depth (3 / 5 measured no better, profiles/r03aa_wgrad_splits.txt)
 constexpr int kStageBytes = 16 * 2048;       // [8 activation blocks | 8 delta blocks] x 2 KiB
 constexpr int kWgradLds = kStages * kStageBytes;
 
-// Every saved-activation / delta block is read exactly once per job: MLP_WGRAD_NT=1 (build knob) marks the stream non-temporal
-#if defined(MIP_WGRAD_NT) && MIP_WGRAD_NT
-#define MIP_WGRAD_LOAD_POLICY " nt"
-#else
-#define MIP_WGRAD_LOAD_POLICY ""
-#endif
+// Every saved-activation / delta block is read exactly once per job: the stream is non-temporal (profiles/r03p_wgrad_nt_ab.log)
 // two 1-KiB DMAs: global (uniform base + lane*16, +1024) -> LDS (uniform dst, +1024)
 __device__ __forceinline__ void dma_block(const char* gbase, char* lbase, unsigned lane16) {
     const unsigned lds_addr = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lbase;
@@ -41,29 +33,14 @@ __device__ __forceinline__ void dma_block(const char* gbase, char* lbase, unsign
         "s_mov_b32 %0, m0\n\t"
         "s_mov_b32 m0, %3\n\t"
         "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2" MIP_WGRAD_LOAD_POLICY "\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:1024" MIP_WGRAD_LOAD_POLICY "\n\t"
+        "global_load_lds_dwordx4 %1, %2 nt\n\t"
+        "global_load_lds_dwordx4 %1, %2 offset:1024 nt\n\t"
         "s_mov_b32 m0, %0"
         : "=&s"(keep)
         : "v"(lane16), "s"(gbase), "s"(lds_addr)
         : "memory");
 }
-// Timing experiment ("natural-layout hand-off"): MLP_WGRAD_TR=1 reads every operand fragment with two transposing
-// ds_read_b64_tr_b16 instead of one ds_read_b128 -- the LDS traffic a weight-gradient kernel would have if the producers stored their
-// k-step registers as they are (lane = sample) and the transposition happened here.  Same bytes, same MFMAs; the RESULTS ARE WRONG
-// (the T-blocks in memory are still transposed): never the default.
-#if defined(MIP_WGRAD_TR) && MIP_WGRAD_TR
-typedef short v4s16 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bf16x8 lds_frag(const char* p) {
-    const v4s16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s16*)(size_t)(p));
-    const v4s16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s16*)(size_t)(p + 8));
-    typedef short v8s16 __attribute__((ext_vector_type(8)));
-    const v8s16 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    return __builtin_bit_cast(bf16x8, v);
-}
-#else
 __device__ __forceinline__ bf16x8 lds_frag(const char* p) { return *reinterpret_cast<const bf16x8*>(p); }
-#endif
 
 // ---- b_src = 1 jobs (pre-GEMM plans, round 5): the B operand is a 32-feature column block of the ROW-MAJOR bf16 encoding [M, xyz_dim]
 // (what k_pre_gemm reads in the training forward): no transposed copy of the 672-wide encoding is ever written.
@@ -84,127 +61,6 @@ __device__ __forceinline__ bf16x8 lds_frag_enc(const char* blk, unsigned enc_lan
     return __builtin_bit_cast(bf16x8, v);
 }
 
-// Timing experiment ("store every other layer, recompute the skipped one here"): MLP_WGRAD_RECOMPUTE_PROBE=<bit mask of
-// job ids>.  The workgroups of those jobs run k_wgrad_recompute_body: a stage carries the instruction mix of the role-flipped recompute
-// job -- wave w owns activation block w of the SKIPPED layer: it forms relu(W[block w, :] a_prev) for the stage's 32 samples (16 k-steps:
-// A = a_prev read from the stage's activation T-blocks with transposing ds_read_b64_tr_b16, B = its 16-KiB slice of W held in 64
-// registers), packs the tile to bf16 -- which IS its B operand of the weight-gradient MFMAs -- and contracts it against all eight delta
-// blocks (16 ds_read_b128 as A operands); the bias gradient of delta block w is 16 VALU adds.  Same HBM bytes per stage as today's job
-// (delta + a_prev); + 16 MFMAs, + 32 transposing LDS reads, + one epilogue per wave and stage.  The operands are whatever the T-blocks
-// hold: the RESULTS ARE WRONG by construction (build.py demands an opt-in).
-#if defined(MIP_WGRAD_RECOMPUTE_PROBE) && MIP_WGRAD_RECOMPUTE_PROBE
-#ifndef MIP_WGRAD_RECOMPUTE_SCHED
-#define MIP_WGRAD_RECOMPUTE_SCHED 0
-#endif
-typedef short v4s16p __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bf16x8 lds_frag_tr(const char* p) {
-    const v4s16p lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s16p*)(size_t)(p));
-    const v4s16p hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s16p*)(size_t)(p + 8));
-    typedef short v8s16p __attribute__((ext_vector_type(8)));
-    const v8s16p v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ void k_wgrad_recompute_body(char* smem, const char* __restrict__ HT, const char* __restrict__ GT, const WgradJob* jp,
-                                                       const int4 wg, int64_t n_wt, int NH, int NG, float* __restrict__ partials, int lane, int wave) {
-    const unsigned lane16 = (unsigned)lane * 16u;
-    const int64_t lo = n_wt * wg.y / wg.z, hi = n_wt * (wg.y + 1) / wg.z;
-    const int nst = (int)(hi - lo);
-    // the job's own activation blocks are the ones the forward no longer stores (MLP_TRAIN_SKIP_STORES): read the NEXT layer's blocks
-    // (8 further on, stored, ordinary relu activations) in their place -- same bytes, operands that toggle like the real ones would
-    const int a_blk = jp->a_blk[wave], b_blk = jp->b_blk[wave] + 8;
-    f32x16 acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-    float bias_sum = 0.0f;
-    bf16x8 wslice[16];                                    // this wave's 32 x 256 slice of the skipped layer's weights (any bits will do)
-#pragma unroll
-    for (int k = 0; k < 16; ++k) wslice[k] = *reinterpret_cast<const bf16x8*>(HT + ((int64_t)(wave * 16 + k) * 64 + lane) * 16);
-    auto issue = [&](int64_t wt, int stage) {
-        char* st = smem + stage * kStageBytes;
-        dma_block(HT + (wt * NH + b_blk) * 2048, st + wave * 2048, lane16);
-        dma_block(GT + (wt * NG + a_blk) * 2048, st + 16384 + wave * 2048, lane16);
-    };
-    if (nst > 0) {
-#pragma unroll
-        for (int s = 0; s < kStages - 1; ++s) issue(lo + (s < nst ? s : nst - 1), s);
-        for (int i = 0; i < nst; ++i) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (kStages - 2)) : "memory");
-            __builtin_amdgcn_s_barrier();
-            const int nxt = i + kStages - 1;
-            issue(lo + (nxt < nst ? nxt : nst - 1), nxt % kStages);
-            const char* st = smem + (i % kStages) * kStageBytes + lane16;
-#if MIP_WGRAD_RECOMPUTE_SCHED == 0
-            // first form (profiles/r05b_*): one accumulator chain, the next operand one k-step ahead
-            f32x16 r0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) r0[r] = 0.0f;
-            bf16x8 t = lds_frag_tr(st);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {                // 16 k-steps over a_prev's 8 blocks x 2 fragments, next operand one step ahead
-                bf16x8 tn = t;
-                if (k + 1 < 16) tn = lds_frag_tr(st + (k + 1) * 1024);
-                r0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t, wslice[k], r0, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                t = tn;
-            }
-            bf16x8 x0, x1;                                // relu + bf16: the recomputed activation block, as B fragments
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                x0[r] = (__bf16)fmaxf(r0[r], 0.0f);
-                x1[r] = (__bf16)fmaxf(r0[r + 8], 0.0f);
-            }
-#else
-            // second form: two accumulator chains (even / odd k-steps), operands four k-steps ahead (a ring of four fragments)
-            f32x16 r0, r1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { r0[r] = 0.0f; r1[r] = 0.0f; }
-            bf16x8 tq[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) tq[k] = lds_frag_tr(st + k * 1024);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const bf16x8 t = tq[k & 3];
-                if (k & 1) r1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t, wslice[k], r1, 0, 0, 0);
-                else r0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t, wslice[k], r0, 0, 0, 0);
-                if (k + 4 < 16) tq[k & 3] = lds_frag_tr(st + (k + 4) * 1024);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            bf16x8 x0, x1;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                x0[r] = (__bf16)fmaxf(r0[r] + r1[r], 0.0f);
-                x1[r] = (__bf16)fmaxf(r0[r + 8] + r1[r + 8], 0.0f);
-            }
-#endif
-            bf16x8 d0 = lds_frag(st + 16384), d1 = lds_frag(st + 16384 + 1024);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {                 // all eight delta blocks against the wave's activation block
-                bf16x8 e0 = d0, e1 = d1;
-                if (j + 1 < 8) { e0 = lds_frag(st + 16384 + (j + 1) * 2048); e1 = lds_frag(st + 16384 + (j + 1) * 2048 + 1024); }
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d0, x0, acc[j], 0, 0, 0);
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d1, x1, acc[j], 0, 0, 0);
-                if (j == wave) {                          // the bias gradient of delta block w: 16 VALU adds per stage
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) bias_sum += (float)d0[r] + (float)d1[r];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                d0 = e0; d1 = e1;
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    float* out = partials + (int64_t)wg.w * kWgradJobFloats + (int64_t)wave * 9 * 1024 + lane * 16;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<float4*>(out + j * 1024 + q * 4) = make_float4(acc[j][4 * q], acc[j][4 * q + 1], acc[j][4 * q + 2], acc[j][4 * q + 3]);
-    out[8 * 1024] = bias_sum;
-}
-#endif
 }  // namespace
 
 // One workgroup's share of one job.  ENC = false: the B blocks are T-blocks of the saved-activation buffer (every job of the standard
@@ -262,10 +118,10 @@ __device__ __forceinline__ void wgrad_body(char* smem, const char* __restrict__ 
                     "s_mov_b32 %0, m0\n\t"
                     "s_mov_b32 m0, %3\n\t"
                     "s_nop 0\n\t"
-                    "global_load_lds_dwordx4 %1, off" MIP_WGRAD_LOAD_POLICY "\n\t"
+                    "global_load_lds_dwordx4 %1, off nt\n\t"
                     "s_add_u32 m0, m0, 1024\n\t"
                     "s_nop 0\n\t"
-                    "global_load_lds_dwordx4 %2, off" MIP_WGRAD_LOAD_POLICY "\n\t"
+                    "global_load_lds_dwordx4 %2, off nt\n\t"
                     "s_mov_b32 m0, %0"
                     : "=&s"(keep)
                     : "v"(p0), "v"(p1), "s"(lds_addr)
@@ -285,10 +141,10 @@ __device__ __forceinline__ void wgrad_body(char* smem, const char* __restrict__ 
                     "s_mov_b32 %0, m0\n\t"
                     "s_mov_b32 m0, %3\n\t"
                     "s_nop 0\n\t"
-                    "global_load_lds_dwordx4 %1, off" MIP_WGRAD_LOAD_POLICY "\n\t"
+                    "global_load_lds_dwordx4 %1, off nt\n\t"
                     "s_add_u32 m0, m0, 1024\n\t"
                     "s_nop 0\n\t"
-                    "global_load_lds_dwordx4 %2, off" MIP_WGRAD_LOAD_POLICY "\n\t"
+                    "global_load_lds_dwordx4 %2, off nt\n\t"
                     "s_mov_b32 m0, %0"
                     : "=&s"(keep)
                     : "v"(p0), "v"(p1), "s"(lds_addr)
@@ -356,12 +212,6 @@ k_mlp_wgrad(const char* __restrict__ HT, const char* __restrict__ GT, const Wgra
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int4 wg = wg_tab[blockIdx.x];                     // job, split, nsplits, partial slot
     const WgradJob* jp = jobs + wg.x;                       // uniform: scalar loads
-#if defined(MIP_WGRAD_RECOMPUTE_PROBE) && MIP_WGRAD_RECOMPUTE_PROBE
-    if ((MIP_WGRAD_RECOMPUTE_PROBE >> wg.x) & 1) {          // timing experiment, workgroup-uniform
-        k_wgrad_recompute_body(smem, HT, GT, jp, wg, n_wt, NH, NG, partials, lane, wave);
-        return;
-    }
-#endif
     if (jp->b_src != 0) {                                   // workgroup-uniform
         if (Ep->row_bytes == 0) wgrad_body<2>(smem, HT, GT, jp, wg, n_wt, NH, NG, partials, Ep, lane, wave);
         else wgrad_body<1>(smem, HT, GT, jp, wg, n_wt, NH, NG, partials, Ep, lane, wave);

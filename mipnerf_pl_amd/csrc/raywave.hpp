@@ -18,18 +18,12 @@ namespace mip {
 // sits on a per-ray dependent chain (compositing -> CDF -> search), so the latency is what they cost.  The DPP forms associate the
 // sums differently from the shuffle trees (row-local prefix, then row totals); the operands are fp32 values widened to double, so
 // the double sums are exact except where magnitudes differ by > 2^29 and the fp32 roundings of the results agree with the shuffle
-// forms except in such corner cases (every golden / fused-vs-stage test runs on these).  MIP_WAVE_DPP=0 restores the shuffles.
-#ifndef MIP_WAVE_DPP
-#define MIP_WAVE_DPP 1
-#endif
-// wave_shr:1 (0x138) and row_bcast:15 / :31 (0x142 / 0x143) exist on the GCN / CDNA family only: a device pass for any other
-// architecture falls back to the shuffle forms instead of failing to assemble (this tree builds gfx950 only; the guard costs nothing)
-#if MIP_WAVE_DPP && defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
-#undef MIP_WAVE_DPP
-#define MIP_WAVE_DPP 0
+// forms except in such corner cases (every golden / fused-vs-stage test runs on these; A/B against the shuffles: profiles/r05a_dpp_graph_ab.txt).
+// wave_shr:1 (0x138) and row_bcast:15 / :31 (0x142 / 0x143) exist on the GCN / CDNA family only
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "raywave.hpp: the wave scans use GCN / CDNA DPP controls; this tree builds gfx950 only"
 #endif
 
-#if MIP_WAVE_DPP
 // lane i <- lane (i - n) within its row of 16 (row_shr:n), lanes without a source get `ident`
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_f32(float ident, float v) {
@@ -88,42 +82,6 @@ __device__ __forceinline__ double wave_sum_f64(double v) { return readlane63(wav
 __device__ __forceinline__ double wave_excl_scan_f64(double v, int lane) {
     return dpp_f64<kDppWaveShr1, 0xf>(wave_incl_scan_dpp(v));
 }
-#else
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// exclusive prefix sum across the 64 lanes; *total = sum over all lanes
-__device__ __forceinline__ float wave_excl_scan(float v, int lane, float* total) {
-    float inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float n = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += n;
-    }
-    *total = __shfl(inc, 63, 64);
-    const float ex = __shfl_up(inc, 1, 64);
-    return lane == 0 ? 0.0f : ex;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_excl_scan_f64(double v, int lane) {
-    double inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double n = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += n;
-    }
-    const double ex = __shfl_up(inc, 1, 64);
-    return lane == 0 ? 0.0 : ex;
-}
-#endif
 
 
 // The per-ray bodies are device functions shared by the stand-alone kernels and by the fused k_composite_resample (one launch

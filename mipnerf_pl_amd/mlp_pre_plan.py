@@ -35,9 +35,9 @@ MAGIC = 0x50524731   # 'PRG1'
 # a 128-sample tile with W0, waves 4-7 the same samples with W_skip[:, 256:], so a tile's encoding comes from HBM once (the second wave finds it
 # in L1 / L2); stream order [k-step][matrix][tile].  Built, parity-green, and SLOWER: 8.56-8.57 ms per forward against 8.27-8.31 (three alternating
 # pairs, profiles/r04y_pre_gemm_split_ab.txt) -- every wave uses half of each ring group, so there is a ring barrier per 16 instead of 32 of its MFMAs
-# and twice the L2 -> LDS weight traffic per sample, which costs more than the second HBM read of the encoding.  Kept as a knob (both forms are
-# generated and checked by tests/test_pre_gemm_cpu.py).
-SPLIT = __import__("os").environ.get("MLP_PRE_SPLIT", "0") == "1"
+# and twice the L2 -> LDS weight traffic per sample, which costs more than the second HBM read of the encoding.  Both forms are generated
+# and checked by tests/test_pre_gemm_cpu.py.
+SPLIT = False
 
 
 def supported(a: Arch) -> bool:

@@ -206,7 +206,7 @@ class NativeContext:
             self._scratch = {}
         t = self._scratch.get(name)
         if t is None or t.numel() < nbytes:
-            # MIPNERF_ZERO_SCRATCH=1: timing experiments whose kernels leave parts of a buffer unwritten (build.py: WRONG_RESULT_KNOBS)
+            # MIPNERF_ZERO_SCRATCH=1: timing experiments whose kernels leave parts of a buffer unwritten (e.g. mipnerf_set_wgrad_splits skipping a job)
             alloc = torch.zeros if os.environ.get("MIPNERF_ZERO_SCRATCH") == "1" else torch.empty
             t = alloc(nbytes, dtype=torch.uint8, device=self.device)
             self._scratch[name] = t

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Interleaved A/B timing of MLP-kernel variants (libmipnerf_hip_<tag>.so built with MLP_* env knobs).
+# Interleaved A/B timing of MLP-kernel variants (libmipnerf_hip_<tag>.so, e.g. two revisions built with MIPNERF_LIB_NAME).
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out

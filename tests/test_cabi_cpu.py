@@ -300,24 +300,57 @@ def test_launch_attribute_caches_are_per_device(lib):
     assert checked >= 10
 
 
-def test_wrong_result_build_knobs_need_an_explicit_opt_in(monkeypatch):
-    """the timing-experiment variables (ablated barriers, transposing reads on untransposed data, ...) give WRONG results; a stale
-    one in the environment must not silently build the product library.  build.py refuses them unless MIPNERF_EXPERIMENT_BUILD=1 AND the
-    output is not libmipnerf_hip.so; the library such a build produces refuses mipnerf_create() without MIPNERF_ALLOW_EXPERIMENT_LIB=1."""
+# Every build-time timing knob the generators, plan modules and build.py once read (rounds 1-6), each at a value other than its old default.
+RETIRED_KNOBS = {
+    "MLP_WAVES": "4", "MLP_PREFETCH": "6", "MLP_ABLATE_BARRIER": "1", "MLP_ABLATE_WAIT": "1", "MLP_ABLATE_LDA": "1", "MLP_SETPRIO": "0",
+    "MLP_IPE_SHADOW": "1", "MLP_IPE_SHADOW_STRIDE": "2", "MLP_PRE_NT_LOADS": "0", "MLP_TRUNK_ABLATE_PRELOADS": "1", "MLP_FUSED_RING": "6",
+    "MLP_FUSED_AHEAD": "5", "MLP_FUSED_OPAQUE": "0", "MLP_WIDE_PREFETCH": "6", "MLP_WIDE_CPW": "8", "MLP_WIDE_AHEAD": "3",
+    "MLP_WIDE_SPARE_SLOT": "0", "MLP_TRAIN_PREFETCH": "6", "MLP_TRAIN_ABLATE_TMFMA": "1", "MLP_TRAIN_SKIP_STORES": "2,4",
+    "MLP_TRAIN_SPREAD_STORES": "0", "MLP_TRAIN_COUNTED_VMCNT": "1", "MLP_F32R_PIECE_WINDOW": "0.25", "MLP_F32R_GEN_ABLATE": "15",
+    "MLP_F32R_ABLATE": "1", "MLP_F32R_NAT_NT": "0", "MLP_PRE_DEPTH": "14", "MLP_PRE_DEPTH_SPLIT": "7", "MLP_PRE_NT_STORES": "0",
+    "MLP_PRE_NT_PASS1": "0", "MLP_PRE_ABLATE_STORES": "1", "MLP_PRE_FORM": "once", "MLP_PRE_ONCE_DEPTH": "7", "MLP_PRE_ONCE_SLOTS": "6",
+    "MLP_PRE_SPLIT": "1", "MLP_CHAIN": "1", "MLP_F32R_GROUP_CHUNKS": "24", "MLP_F32R_RING_SLOTS": "3", "MLP_SIN_TWOFLOAT": "1",
+    "MLP_WAVE_DPP": "0", "MLP_WGRAD_NT": "0", "MLP_WGRAD_STAGES": "3", "MLP_WGRAD_TR": "1", "MLP_WGRAD_RECOMPUTE_PROBE": "1",
+    "MLP_WGRAD_RECOMPUTE_SCHED": "1", "MLP_IPE360_ROW_PAD": "8",
+}
+
+
+def test_the_environment_cannot_change_the_product(tmp_path, monkeypatch):
+    """The product library says one thing whatever shell it is built from: the four generators write byte-identical sources, tables and headers
+    with every retired build knob set, build.py compiles with the same flags, and nothing in the package reads an MLP_* variable."""
+    import importlib
+    import subprocess
+    import sys
+    csrc = os.path.join(REPO, "mipnerf_pl_amd", "csrc")
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("MLP_")}
+    outs = []
+    for env in (clean, {**clean, **RETIRED_KNOBS}):
+        out = tmp_path / f"gen{len(outs)}"
+        out.mkdir()
+        for gen in ("gen_mlp_bf16.py", "gen_mlp_train.py", "gen_mlp_f32r.py", "gen_pre_gemm.py"):
+            subprocess.run([sys.executable, os.path.join(csrc, gen), str(out)], env=env, check=True, stdout=subprocess.DEVNULL)
+        outs.append({f: (out / f).read_bytes() for f in sorted(os.listdir(out))})
+    assert len(outs[0]) >= 30 and sorted(outs[0]) == sorted(outs[1])
+    for f in outs[0]:
+        assert outs[0][f] == outs[1][f], f"{f}: the environment changed a generated file"
+
     from mipnerf_pl_amd import build as b
-    for k in b.WRONG_RESULT_KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    assert b.experiment_flags() == ""
-    monkeypatch.setenv("MLP_WGRAD_TR", "1")
-    with pytest.raises(RuntimeError, match="WRONG results"):
-        b.experiment_flags()
-    monkeypatch.setenv("MIPNERF_EXPERIMENT_BUILD", "1")
-    with pytest.raises(RuntimeError, match="WRONG results"):        # still the product library's name
-        b.experiment_flags()
-    monkeypatch.setattr(b, "LIB", os.path.join(b.CSRC, "libmipnerf_hip_exp.so"))
-    assert b.experiment_flags() == "MLP_WGRAD_TR=1"
-    src = open(os.path.join(REPO, "mipnerf_pl_amd", "csrc", "capi.hip")).read()
-    assert "MIPNERF_ALLOW_EXPERIMENT_LIB" in src and "#ifdef MIPNERF_EXPERIMENT_BUILD" in src
+    flags = (list(b.COMMON), list(b.UNITS))
+    for k, v in RETIRED_KNOBS.items():
+        monkeypatch.setenv(k, v)
+    try:
+        assert (list(importlib.reload(b).COMMON), list(b.UNITS)) == flags
+    finally:
+        monkeypatch.undo()
+        importlib.reload(b)
+
+    readers = []
+    for root, _, files in os.walk(os.path.join(REPO, "mipnerf_pl_amd")):
+        for f in files:
+            if f.endswith((".py", ".hip", ".hpp", ".h", ".c", ".cpp")):
+                src = open(os.path.join(root, f), errors="replace").read()
+                readers += [f"{f}: {m.group(0)}" for m in re.finditer(r"(?:environ|getenv)[^\n]*\bMLP_\w*", src)]
+    assert not readers, readers
 
 
 def test_one_wave_per_simd_kernel_ring_is_consistent():
