@@ -147,6 +147,8 @@ int mipnerf_num_param_tensors(const mipnerf_ctx* ctx);
  * mipnerf_num_param_tensors(ctx) device pointers (24 for the shipped shape) in state_dict order of the reference MLP
  * (mip_nerf.py:19-73): layers.{0..7}.0.{weight,bias}, density_layer.{weight,bias},
  * extra_layer.{weight,bias}, view_layers.0.0.{weight,bias}, color_layer.{weight,bias}.
+ * The bf16 forward stream multiplies the bottleneck into view layer 0 (W_view[:, :W] W_extra, b_view + W_view[:, :W] b_extra), computed
+ * in the same launch with a float64 accumulator in a fixed order: the same parameters always give the same bits.
  * Call after every optimizer step / load_state_dict. */
 int mipnerf_set_params(mipnerf_ctx* ctx, const float* const* params_host, void* stream);
 
@@ -433,10 +435,12 @@ int mipnerf_set_option(mipnerf_ctx* ctx, int option, int value);
 int mipnerf_mlp_launch_stats(mipnerf_ctx* ctx, double* total_ms, int64_t* launches);
 /* Host-only exports of the static plan tables (no GPU needed), used by the CPU tests to
  * prove the C++ plan expansion equals mipnerf_pl_amd/mlp_plan.py.  which: 0 = bf16 stream
- * pack table, 1 = bias table, 2 = fp32 stream pack table (flat parameter indices, -1 = 0),
- * 3 = dgrad (W^T) stream pack table, 4 = wgrad partial -> parameter index table, 5 = wgrad job table.
+ * pack table, 1 = bias table, 2 = fp32 stream pack table (flat parameter indices, -1 = 0) of Plan.build(),
+ * 3 = dgrad (W^T) stream pack table, 4 = wgrad partial -> parameter index table, 5 = wgrad job table,
+ * 6 = pack table and 7 = bias table of the stream the bf16 forward kernels read (Plan.build(fold_view=True): the bottleneck
+ * folded into view layer 0; indices at or past the parameter count address the derived tensors that follow the parameters).
  * Return the element count; copy only when cap is large enough. */
-int64_t mipnerf_debug_table_variant(int variant, int which, int32_t* out_host, int64_t cap);   /* which: 0 bf16 pack, 1 bias, 2 fp32 pack */
+int64_t mipnerf_debug_table_variant(int variant, int which, int32_t* out_host, int64_t cap);   /* which: 0 bf16 pack, 1 bias, 2 fp32 pack, 6 / 7 forward pack / bias */
 int64_t mipnerf_debug_table(int which, int32_t* out_host, int64_t cap);
 int64_t mipnerf_debug_f32net(int32_t* out_host, int64_t cap);
 

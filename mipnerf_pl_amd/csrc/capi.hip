@@ -170,6 +170,23 @@ void build_tables(Tables& T, const PlanDesc& P) {
     }
 }
 
+// The plan of the bf16 forward kernels (inference and training forward-with-save share its stream): the folded ops of the generated
+// header, with the derived tensors (mlp_plan.Plan.derived_shapes) appended to the parameter tensors so that build_tables / encode index
+// them as tensors num_param_tensors and num_param_tensors + 1 (computed by the pack kernel: FoldDesc)
+PlanDesc fwd_desc(const PlanDesc& P) {
+    PlanDesc F = P;
+    F.ops = P.fwd_ops;
+    F.num_ops = P.fwd_num_ops;
+    F.num_chunks = P.fwd_num_chunks;
+    F.num_real_chunks = P.fwd_num_real_chunks;
+    F.num_tiles = P.fwd_num_tiles;
+    if (P.fold) {
+        F.param_numel[F.num_param_tensors++] = P.net_width_cond * (P.net_width + P.view_dim);
+        F.param_numel[F.num_param_tensors++] = P.net_width_cond;
+    }
+    return F;
+}
+
 bool max_deg_span_is_16(const mipnerf_config& cfg) { return cfg.max_deg_point - cfg.min_deg_point == 16 && cfg.min_deg_point >= 0 && cfg.max_deg_point <= 31; }
 
 int off_total(const Tables& T) { return T.total_params; }
@@ -256,13 +273,16 @@ bool pre_tables(PreTables& T, int variant, int nparams) {
 struct mipnerf_ctx {
     mipnerf_config cfg;
     const PlanDesc* P = nullptr;     // the generated architecture variant this context runs (mlp_plan_gen.hpp kPlans)
-    Tables tab;
+    Tables tab;                      // the plan's tables (fp32 kernel)
+    Tables ftab;                     // the bf16 forward kernels' tables (fwd_desc: the bottleneck folded into view layer 0)
     int32_t* d_pack_bf16 = nullptr;
     int32_t* d_pack_f32 = nullptr;
     int32_t* d_bias_idx = nullptr;
-    void* d_stream_bf16 = nullptr;   // kNumChunks * 1 KiB
-    float* d_stream_f32 = nullptr;   // kNumChunks * 2 KiB
-    float* d_bias = nullptr;         // kNumTiles * 32 floats
+    int32_t* d_fwd_bias_idx = nullptr;
+    void* d_stream_bf16 = nullptr;   // fwd_num_chunks * 1 KiB (inference + training forward)
+    float* d_stream_f32 = nullptr;   // num_chunks * 2 KiB
+    float* d_bias = nullptr;         // num_tiles * 32 floats (fp32 kernel)
+    float* d_fwd_bias = nullptr;     // fwd_num_tiles * 32 floats (bf16 forward kernels)
     // register-resident fp32 kernel (variants up to 256 wide): its own weight stream (1-KiB chunks) and aux table
     F32RTables f32r;
     int32_t* d_pack_f32r = nullptr;
@@ -318,7 +338,7 @@ hipError_t launch_bf16_variant(mipnerf_ctx* c, const void* enc, const void* view
     // driving the same context cannot see each other's pointer
     const mip::LaunchBf16Fn fn = mip::kLaunchBf16[c->P->variant];
     if (!fn) return hipErrorInvalidValue;          // fp32-only architecture variant (callers check has_bf16 first)
-    return fn(c->d_stream_bf16, c->d_bias, enc, viewenc, rgb_sigma, raw, M, N, c->cfg.density_bias, c->cfg.rgb_padding,
+    return fn(c->d_stream_bf16, c->d_fwd_bias, enc, viewenc, rgb_sigma, raw, M, N, c->cfg.density_bias, c->cfg.rgb_padding,
               c->grid_limit, dma, rays, dnoise, c->cfg.density_noise, st);
 }
 
@@ -352,7 +372,7 @@ hipError_t launch_trainfwd_variant(mipnerf_ctx* c, const void* enc, const void* 
                                    void* masks, int64_t M, int N, const mip::RayInputs* rays, const float* dnoise, hipStream_t st) {
     const mip::LaunchTrainFwdFn fn = mip::kLaunchTrainFwd[c->P->variant];
     if (!fn) return hipErrorInvalidValue;
-    return fn(c->d_stream_bf16, c->d_bias, enc, viewenc, rgb_sigma, raw, act, masks, M, N, c->cfg.density_bias, c->cfg.rgb_padding,
+    return fn(c->d_stream_bf16, c->d_fwd_bias, enc, viewenc, rgb_sigma, raw, act, masks, M, N, c->cfg.density_bias, c->cfg.rgb_padding,
               c->grid_limit, rays, dnoise, c->cfg.density_noise, st);
 }
 hipError_t launch_dgrad_variant(mipnerf_ctx* c, const float* d_raw, const void* masks, void* delta, int64_t M, hipStream_t st) {
@@ -456,28 +476,33 @@ int mipnerf_create(const mipnerf_config* cfg, mipnerf_ctx** out) {
         return fail(MIPNERF_E_UNSUPPORTED, "no kernels / tables were generated for this MLP shape; generated: %s.  Add the shape to "
                                            "VARIANTS in csrc/gen_mlp_bf16.py and rebuild", have.c_str());
     }
-    if (P->num_param_tensors > mip::kMaxParamTensors)
+    if (P->num_param_tensors + (P->fold ? 2 : 0) > mip::kMaxParamTensors)
         return fail(MIPNERF_E_UNSUPPORTED, "variant has %d parameter tensors, the library handles up to %d", P->num_param_tensors, mip::kMaxParamTensors);
     mipnerf_ctx* c = new mipnerf_ctx();
     c->cfg = *cfg;
     c->P = P;
     build_tables(c->tab, *P);
-    const std::vector<int32_t> e_bf16 = encode(c->tab.pack_bf16, c->tab.tensor_off);
+    build_tables(c->ftab, fwd_desc(*P));
+    const std::vector<int32_t> e_bf16 = encode(c->ftab.pack_bf16, c->ftab.tensor_off);
+    const std::vector<int32_t> e_fbias = encode(c->ftab.bias, c->ftab.tensor_off);
     const std::vector<int32_t> e_f32 = encode(c->tab.pack_f32, c->tab.tensor_off);
     const std::vector<int32_t> e_bias = encode(c->tab.bias, c->tab.tensor_off);
-    const size_t nst = (size_t)P->num_chunks * 512;
+    const size_t nst = (size_t)P->num_chunks * 512, nst_fwd = (size_t)P->fwd_num_chunks * 512;
     hipError_t er = hipSuccess;
     auto chk = [&](hipError_t e) { if (er == hipSuccess) er = e; };
-    chk(hipMalloc(&c->d_pack_bf16, nst * 4));
+    chk(hipMalloc(&c->d_pack_bf16, nst_fwd * 4));
     chk(hipMalloc(&c->d_pack_f32, nst * 4));
     chk(hipMalloc(&c->d_bias_idx, e_bias.size() * 4));
-    chk(hipMalloc(&c->d_stream_bf16, nst * 2));
+    chk(hipMalloc(&c->d_fwd_bias_idx, e_fbias.size() * 4));
+    chk(hipMalloc(&c->d_stream_bf16, nst_fwd * 2));
     chk(hipMalloc(&c->d_stream_f32, nst * 4));
     chk(hipMalloc(&c->d_bias, e_bias.size() * 4));
+    chk(hipMalloc(&c->d_fwd_bias, e_fbias.size() * 4));
     if (er == hipSuccess) {
-        chk(hipMemcpy(c->d_pack_bf16, e_bf16.data(), nst * 4, hipMemcpyHostToDevice));
+        chk(hipMemcpy(c->d_pack_bf16, e_bf16.data(), nst_fwd * 4, hipMemcpyHostToDevice));
         chk(hipMemcpy(c->d_pack_f32, e_f32.data(), nst * 4, hipMemcpyHostToDevice));
         chk(hipMemcpy(c->d_bias_idx, e_bias.data(), e_bias.size() * 4, hipMemcpyHostToDevice));
+        chk(hipMemcpy(c->d_fwd_bias_idx, e_fbias.data(), e_fbias.size() * 4, hipMemcpyHostToDevice));
     }
     if (er != hipSuccess) {
         mipnerf_destroy(c);
@@ -580,6 +605,7 @@ int mipnerf_destroy(mipnerf_ctx* c) {
     if (!c) return MIPNERF_OK;
     (void)hipFree(c->d_pack_bf16); (void)hipFree(c->d_pack_f32); (void)hipFree(c->d_bias_idx);
     (void)hipFree(c->d_stream_bf16); (void)hipFree(c->d_stream_f32); (void)hipFree(c->d_bias);
+    (void)hipFree(c->d_fwd_bias_idx); (void)hipFree(c->d_fwd_bias);
     (void)hipFree(c->d_pack_dgrad); (void)hipFree(c->d_stream_dgrad); (void)hipFree(c->d_jobs); (void)hipFree(c->d_otab);
     (void)hipFree(c->d_wgtab); (void)hipFree(c->d_jobslots); (void)hipFree(c->d_scratch); (void)hipFree(c->d_extra_wT);
     (void)hipFree(c->d_pack_extraT);
@@ -620,10 +646,16 @@ int mipnerf_set_params(mipnerf_ctx* c, const float* const* params_host, void* st
         pp.p[i] = params_host[i];
     }
     const int64_t nst = (int64_t)P.num_chunks * 512;
-    // every stream of the context in ONE launch: bf16 stream, fp32 stream, bias table, and for the trainable variants the
-    // transposed (dgrad) stream and W_extra^T (a gather through an index table like the others)
+    // every stream of the context in ONE launch: bf16 stream, fp32 stream, bias tables, and for the trainable variants the
+    // transposed (dgrad) stream and W_extra^T (a gather through an index table like the others).  The bf16 forward stream and its
+    // bias table read the folded view layer, which the pack kernel computes from the parameters where it meets it (FoldDesc)
     mip::PackSegments sg;
     memset(&sg, 0, sizeof sg);
+    sg.fold.slot = -1;
+    if (P.fold) {
+        const int D = P.net_depth;
+        sg.fold = mip::FoldDesc{P.num_param_tensors, P.net_width, P.net_width + P.view_dim, 2 * D + 4, 2 * D + 5, 2 * D + 2, 2 * D + 3};
+    }
     bool sg_overflow = false;
     auto add = [&](const int32_t* table, int64_t n, void* out, bool bf16) {
         if (sg.n >= mip::kMaxPackSegments) { sg_overflow = true; return; }       // checked BEFORE the arrays are written
@@ -631,9 +663,10 @@ int mipnerf_set_params(mipnerf_ctx* c, const float* const* params_host, void* st
         sg.start[sg.n + 1] = sg.start[sg.n] + n;
         ++sg.n;
     };
-    add(c->d_pack_bf16, nst, c->d_stream_bf16, true);
+    add(c->d_pack_bf16, (int64_t)P.fwd_num_chunks * 512, c->d_stream_bf16, true);
     add(c->d_pack_f32, nst, c->d_stream_f32, false);
     add(c->d_bias_idx, (int64_t)P.num_tiles * 32, c->d_bias, false);
+    add(c->d_fwd_bias_idx, (int64_t)P.fwd_num_tiles * 32, c->d_fwd_bias, false);
     if (has_bf16_train_any(&P)) {
         add(c->d_pack_dgrad, (int64_t)c->tt.n_bchunks * 512, c->d_stream_dgrad, true);
         add(c->d_pack_extraT, (int64_t)P.net_width * P.net_width, c->d_extra_wT, false);
@@ -1616,10 +1649,11 @@ int mipnerf_selftest(void* stream) {
 }
 
 // Host-only debug export of the plan tables (flat parameter indices), used by the CPU tests to prove the
-// C++ expansion equals mlp_plan.py.  which: 0 bf16 pack, 1 bias, 2 fp32 pack.  Returns element count.
+// C++ expansion equals mlp_plan.py.  which: 0 bf16 pack, 1 bias, 2 fp32 pack (Plan.build), 6 / 7 the bf16 pack / bias table of the
+// forward kernels (Plan.build(fold_view=True)).  Returns element count.
 int64_t mipnerf_debug_table_variant(int variant, int which, int32_t* out_host, int64_t cap) {
-    if (variant < 0 || variant >= mip::plan::kNumVariants || which < 0 || which > 5) return -1;
-    if (which >= 3) {               // training tables of the variant (3 dgrad pack, 4 wgrad partial -> parameter, 5 jobs)
+    if (variant < 0 || variant >= mip::plan::kNumVariants || which < 0 || which > 7) return -1;
+    if (which >= 3 && which <= 5) {     // training tables of the variant (3 dgrad pack, 4 wgrad partial -> parameter, 5 jobs)
         TrainTables tt;
         if (!train_tables(tt, variant)) return -1;
         const int32_t* src = which == 3 ? tt.bpack : (which == 4 ? tt.otab : tt.jobs);
@@ -1628,13 +1662,14 @@ int64_t mipnerf_debug_table_variant(int variant, int which, int32_t* out_host, i
         return n;
     }
     Tables T;
-    build_tables(T, mip::plan::kPlans[variant]);
-    const std::vector<int32_t>& v = which == 0 ? T.pack_bf16 : (which == 1 ? T.bias : T.pack_f32);
+    build_tables(T, which >= 6 ? fwd_desc(mip::plan::kPlans[variant]) : mip::plan::kPlans[variant]);
+    const std::vector<int32_t>& v = (which == 0 || which == 6) ? T.pack_bf16 : ((which == 1 || which == 7) ? T.bias : T.pack_f32);
     if (out_host && cap >= (int64_t)v.size()) memcpy(out_host, v.data(), v.size() * 4);
     return (int64_t)v.size();
 }
 
 int64_t mipnerf_debug_table(int which, int32_t* out_host, int64_t cap) {
+    if (which >= 6) return mipnerf_debug_table_variant(0, which, out_host, cap);
     if (which >= 3 && which <= 5) {
         TrainTables tt;
         if (!train_tables(tt)) return -1;

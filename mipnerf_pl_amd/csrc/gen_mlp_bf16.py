@@ -88,7 +88,9 @@ def _ops_table(plan: Plan, name: str):
     return L
 
 
-def gen_plan_header(plans) -> str:
+def gen_plan_header(plans, fplans) -> str:
+    """plans: Plan.build per variant (the fp32 kernel's tables, debug tables 0 / 1 / 2); fplans: the plans the bf16 forward kernels were
+    generated from (Plan.build(fold_view=True)), whose stream and bias table the context packs."""
     plan = plans[0]
     a = plan.arch
     L = []
@@ -118,19 +120,29 @@ def gen_plan_header(plans) -> str:
     L.append("    int num_chunks, num_real_chunks, num_tiles, num_ops;")
     L.append("    const OpDesc* ops;")
     L.append("    int variant;        // index of the generated bf16 inference kernel (launch_mlp_bf16 / launch_mlp_bf16_v<variant>)")
+    L.append("    // the bf16 forward kernels' plan (Plan.build(fold_view=True)): the bottleneck folded into view layer 0, whose tiles read the")
+    L.append("    // derived tensors num_param_tensors (weight, Wc x (W + view_dim)) and num_param_tensors + 1 (bias); fold = 0: fwd_ops == ops")
+    L.append("    int fold, fwd_num_chunks, fwd_num_real_chunks, fwd_num_tiles, fwd_num_ops;")
+    L.append("    const OpDesc* fwd_ops;")
     L.append("};")
     for vi, pl in enumerate(plans):
         L += _ops_table(pl, "kOps" if vi == 0 else f"kOps_v{vi}")
+    for vi, pl in enumerate(fplans):
+        if pl.fold_view:
+            L += _ops_table(pl, "kFwdOps" if vi == 0 else f"kFwdOps_v{vi}")
     L.append(f"constexpr int kNumVariants = {len(plans)};")
     L.append("static const PlanDesc kPlans[kNumVariants] = {")
-    for vi, pl in enumerate(plans):
+    for vi, (pl, fp) in enumerate(zip(plans, fplans)):
         b = pl.arch
         shp = b.param_shapes()
-        assert len(shp) <= 32
+        assert len(shp) + 2 <= 32
         numel = ", ".join(str(int(np.prod(x))) for _, x in shp)
+        ops = 'kOps' if vi == 0 else f'kOps_v{vi}'
+        fops = ('kFwdOps' if vi == 0 else f'kFwdOps_v{vi}') if fp.fold_view else ops
         L.append(f"  {{{b.net_depth}, {b.net_width}, {b.net_depth_condition}, {b.net_width_condition}, {b.skip_index}, {b.num_rgb}, "
                  f"{b.num_density}, {b.xyz_dim}, {b.view_dim}, {int(b.use_viewdirs)}, {b.feat_per_deg}, {len(shp)}, {{{numel}}}, {len(pl.chunks)}, "
-                 f"{pl.n_real_chunks}, {pl.n_tiles}, {len(pl.ops)}, {'kOps' if vi == 0 else f'kOps_v{vi}'}, {vi}}},")
+                 f"{pl.n_real_chunks}, {pl.n_tiles}, {len(pl.ops)}, {ops}, {vi}, "
+                 f"{int(fp.fold_view)}, {len(fp.chunks)}, {fp.n_real_chunks}, {fp.n_tiles}, {len(fp.ops)}, {fops}}},")
     L.append("};")
     L.append("}}  // namespace mip::plan")
     return "\n".join(L) + "\n"
@@ -584,9 +596,10 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
     assert lds_bytes <= 160 * 1024
     panels, slots = build_schedule(plan)
     nreal = len(slots)
-    # padding: inside the last ring group, or exactly one whole group of zeros, begun by an extra GROUP_BEGIN at the tile end (trunk plans; two view layers)
+    # padding: the rest of the last ring group, plus at most one whole group of zeros (trunk plans; two view layers; the folded 128-wide
+    # variant: 10 groups + 8 chunks, padded to 12 groups), each unentered group begun by an extra GROUP_BEGIN at the tile end
     # (4-wave kernels: the stream is padded to mlp_plan.RING_MULTIPLE = 64 chunks = four of their groups; every unentered padding group gets its GROUP_BEGIN)
-    assert nreal == plan.n_real_chunks and (nchunks - nreal < GROUP or (nchunks - nreal == GROUP and nreal % GROUP == 0) or wide)
+    assert nreal == plan.n_real_chunks and (nchunks - nreal < SLOTS * GROUP or wide)
     lines = []
     e = lines.append
     e("// AUTO-GENERATED by gen_mlp_bf16.py from mlp_plan.py -- do not edit by hand.")
@@ -936,11 +949,14 @@ def gen_variants_header(n):
 def main():
     outdir = sys.argv[1] if len(sys.argv) > 1 else HERE
     plans = [Plan.build(a) for a in VARIANTS]
+    # the bf16 inference kernels run the folded plan (the bottleneck multiplied into view layer 0); so does the training forward-with-save
+    # (gen_mlp_train.py), and the two share one packed stream.  The fp32 kernels keep the plain plan.
+    fplans = [Plan.build(a, fold_view=a.bf16_kernels) for a in VARIANTS]
     with open(os.path.join(outdir, "mlp_plan_gen.hpp"), "w") as f:
-        f.write(gen_plan_header(plans))
+        f.write(gen_plan_header(plans, fplans))
     with open(os.path.join(outdir, "mlp_variants_gen.hpp"), "w") as f:
         f.write(gen_variants_header(len(plans)))
-    for vi, plan in enumerate(plans):
+    for vi, plan in enumerate(fplans):
         if not plan.arch.bf16_kernels:
             print(f"variant {vi}: plan tables only (fp32 kernels), {plan.n_real_chunks} chunks, {plan.n_tiles} tiles")
             continue

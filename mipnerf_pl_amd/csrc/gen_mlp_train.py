@@ -371,8 +371,9 @@ def gen_trainfwd(tp: TrainPlan, variant: int = 0) -> str:
     lds_bytes = enc_off + WAVES * enc_wave_bytes
     assert lds_bytes <= 160 * 1024
     prog = build_fwd_prog(tp)
-    # padding: inside the last ring group, or exactly one whole group of zeros (two view layers: 39 groups + 1), begun by an extra GROUP_BEGIN at the tile end
-    assert len(prog.slots) == nreal and (nchunks - nreal < GROUP or (nchunks - nreal == GROUP and nreal % GROUP == 0))
+    # padding: the rest of the last ring group, plus at most one whole group of zeros (two view layers: 35 groups + 1; the folded 128-wide variant:
+    # 10 groups + 8 chunks, padded to 12), each unentered group begun by an extra GROUP_BEGIN at the tile end (emit_tile_body)
+    assert len(prog.slots) == nreal and nchunks - nreal < SLOTS * GROUP
     side_e, prologue_e = assign_lds_b(prog, nreal)
     side = place_sides(prog, nreal)
     for c in range(nreal):
@@ -803,7 +804,7 @@ def train_variants():
                 continue
             if not arch.bf16_kernels:
                 raise NotImplementedError("fp32-only architecture variant")
-            tp = TrainPlan.build(arch)
+            tp = TrainPlan.build(arch, fold_view=True)      # the inference kernel's folded plan: both forward kernels share one stream
             out.append((vi, tp, gen_trainfwd(tp, vi), gen_dgrad(tp, vi)))
         except (NotImplementedError, AssertionError) as ex:
             if vi == 0:

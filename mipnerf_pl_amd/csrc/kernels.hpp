@@ -214,12 +214,21 @@ struct ParamPtrs {
 // table entry: -1 => 0, else (tensor << 20) | element offset
 hipError_t launch_pack(const int32_t* table, int64_t n, const ParamPtrs& ptrs, void* out, bool bf16, hipStream_t st);
 constexpr int kMaxPackSegments = 16;
+// The bottleneck folded into view layer 0 (mlp_plan.fold_params): table entries of tensor `slot` (the Wc x ldv weight
+// [W_view[:, :W] W_extra | W_view[:, W:]]) and `slot + 1` (the bias b_view + W_view[:, :W] b_extra) are computed from the parameters
+// where the pack reads them, with a float64 accumulator in a fixed order; slot = -1: no derived tensors.
+struct FoldDesc {
+    int slot;
+    int W, ldv;                                  // trunk width, in_features of view layer 0 (W + view_dim)
+    int view_w, view_b, extra_w, extra_b;        // parameter tensors
+};
 struct PackSegments {              // several (table -> stream) packs as one launch
     int n;
     int64_t start[kMaxPackSegments + 1];
     const int32_t* table[kMaxPackSegments];
     void* out[kMaxPackSegments];
     int bf16[kMaxPackSegments];
+    FoldDesc fold;
 };
 hipError_t launch_pack_multi(const PackSegments& sg, const ParamPtrs& ptrs, hipStream_t st);
 

@@ -24,6 +24,12 @@ waves of a workgroup (global_load_lds_dwordx4), so each chunk is fetched from L2
 256 samples.  This module defines that order (`chunks`), the index table used to pack the
 fp32 master weights into the bf16 stream, and the bias table layout.
 
+The bf16 forward kernels (inference and the training forward-with-save, one shared stream) run
+`Plan.build(fold_view=True)`: the bottleneck has no activation and only view layer 0 reads it, so
+its weights are multiplied into that layer (`fold_params`).  The head keeps only the density tile
+and view0 reads the trunk output: 1088 chunks per 32 samples instead of 1216 (8 x 256 / 128),
+density and everything derived from it unchanged bit for bit.  The fp32 kernels keep the plain plan.
+
 fp32 kernel (kernels_mlp_f32.hip) keeps activations in LDS in natural feature order and
 uses v_mfma_f32_32x32x2_f32; its packing is the same chunk idea with the natural k map and
 8 fp32 per lane (2 KiB chunks), in [layer][tile][kblock] order (`f32_layers`).
@@ -137,16 +143,25 @@ class Plan:
     pre_gemm: bool = False     # trunk of the two-kernel bf16 form (mlp_pre_plan.py): no encoding segments, layer 0 done elsewhere
     fused: bool = False        # ONE-kernel form of a wide encoding (round 6): layer 0 and the skip layer are k-step-major ops with all 8 output
                                # tiles live, their encoding k-steps streamed global -> wave-private LDS ring -> B operand
+    fold_view: bool = False    # the bottleneck is folded into the first view layer (fold_params): the head is the density tile alone and
+                               # view0 reads the trunk output with the derived weight / bias tensors appended after the real parameters
 
     # ---- construction -----------------------------------------------------------------
     @staticmethod
-    def build(arch: Arch = None, pre_gemm: bool = False, fused: bool = False) -> "Plan":
+    def build(arch: Arch = None, pre_gemm: bool = False, fused: bool = False, fold_view: bool = False) -> "Plan":
         """pre_gemm: the TRUNK of the two-kernel bf16 form used for encodings too wide for the wave-private LDS area (mlp_pre_plan.py):
         layer 0 and the encoding part of the skip layer are a separate k-step-major GEMM kernel; this plan starts at layer 1 with the
         register set X preloaded from memory (bf16(relu(layer 0))) and the skip layer's accumulators initialised from the GEMM's fp32
-        partial sums (Op.pre) instead of the bias."""
+        partial sums (Op.pre) instead of the bias.
+
+        fold_view: extra_layer (the bottleneck) has no activation and only view layer 0 reads it, so
+        W_v[:, :W] (W_e x + b_e) = (W_v[:, :W] W_e) x + W_v[:, :W] b_e: the head keeps only the density tile and view0 multiplies the
+        trunk output with the derived tensors of fold_params (8 x 256 / 128: 1088 chunks instead of 1216).  Only the bf16 forward
+        kernels use it; a plan without view directions is the same either way."""
         a = arch or Arch()
         assert not (pre_gemm and fused)
+        fold_view = bool(fold_view and a.use_viewdirs)
+        assert not (fold_view and (pre_gemm or fused))
         wmax = 256 if (pre_gemm or fused) else 512      # (above 256 the bf16 kernel runs one wave per SIMD: gen_mlp_bf16.waves_of)
         if a.net_width % TILE or a.net_width_condition % TILE or a.net_width > wmax or a.net_width_condition > wmax:
             raise NotImplementedError("MFMA kernels need widths that are multiples of 32 and <= 512 (<= 256 for the two-kernel trunk form)")
@@ -157,7 +172,7 @@ class Plan:
         if not a.use_viewdirs and a.net_width_condition != a.net_width:
             raise NotImplementedError("use_viewdirs=False feeds the trunk output (net_width) to color_layer "
                                       "(net_width_condition inputs): the reference fails unless the two widths are equal")
-        p = Plan(a, pre_gemm=pre_gemm, fused=fused)
+        p = Plan(a, pre_gemm=pre_gemm, fused=fused, fold_view=fold_view)
         encset = "encg" if fused else "enc"
         names = [n for n, _ in a.param_shapes()]
         pid = {n: i for i, n in enumerate(names)}
@@ -190,10 +205,10 @@ class Plan:
         # head: bottleneck (no activation) + density row as an extra tile; without view directions only the density row
         # (extra_layer and view_layers stay unused parameters, mip_nerf.py:99-110)
         tiles = [TileSrc(pid["extra_layer.weight"], pid["extra_layer.bias"], t * TILE, TILE, W)
-                 for t in range(W // TILE)] if a.use_viewdirs else []
+                 for t in range(W // TILE)] if (a.use_viewdirs and not fold_view) else []
         tiles.append(TileSrc(pid["density_layer.weight"], pid["density_layer.bias"], 0, a.num_density, W))
         p.ops.append(Op("head", [Seg(cur, DLAYOUT, W // KSTEP, 0, W)], tiles, False, other))
-        if a.use_viewdirs:
+        if a.use_viewdirs and not fold_view:
             cur, other = other, cur
         Wc = a.net_width_condition
         for i in range(a.net_depth_condition if a.use_viewdirs else 0):
@@ -203,8 +218,8 @@ class Plan:
             else:
                 segs = [Seg(cur, DLAYOUT, Wc // KSTEP, 0, Wc)]
                 ld = Wc
-            tiles = [TileSrc(pid[f"view_layers.{i}.0.weight"], pid[f"view_layers.{i}.0.bias"], t * TILE, TILE, ld)
-                     for t in range(Wc // TILE)]
+            wt, bt = (len(names), len(names) + 1) if (fold_view and i == 0) else (pid[f"view_layers.{i}.0.weight"], pid[f"view_layers.{i}.0.bias"])
+            tiles = [TileSrc(wt, bt, t * TILE, TILE, ld) for t in range(Wc // TILE)]
             p.ops.append(Op(f"view{i}", segs, tiles, True, other))
             cur, other = other, cur
         p.ops.append(Op("color", [Seg(cur, DLAYOUT, Wc // KSTEP, 0, Wc)],
@@ -262,12 +277,32 @@ class Plan:
         raise IndexError
 
     # ---- tables -----------------------------------------------------------------------
+    def derived_shapes(self):
+        """Tensors computed from the parameters (fold_params) that a folded plan indexes after the real ones."""
+        a = self.arch
+        if not self.fold_view:
+            return []
+        return [("fold.view0.weight", (a.net_width_condition, a.net_width + a.view_dim)), ("fold.view0.bias", (a.net_width_condition,))]
+
     def param_offsets(self):
+        """(flat offset of every tensor, number of real parameter values).  A folded plan's derived tensors follow the real ones:
+        their offsets start at that number."""
         offs, o = [], 0
         for _, shp in self.arch.param_shapes():
             offs.append(o)
             o += int(np.prod(shp))
-        return offs, o
+        n = o
+        for _, shp in self.derived_shapes():
+            offs.append(o)
+            o += int(np.prod(shp))
+        return offs, n
+
+    def with_derived(self, flat_params: np.ndarray) -> np.ndarray:
+        """flat parameters followed by the derived tensors this plan indexes (none unless fold_view)."""
+        flat = np.asarray(flat_params, dtype=np.float32).ravel()
+        if not self.fold_view:
+            return flat
+        return np.concatenate([flat, fold_params(self.arch, flat)])
 
     def pack_table(self) -> np.ndarray:
         """int32 [n_chunks, 64, 8]: flat index into the concatenated fp32 parameters of the
@@ -358,6 +393,28 @@ class Plan:
         return np.stack(rows)
 
 
+def fold_params(arch: Arch, flat_params: np.ndarray) -> np.ndarray:
+    """Derived tensors of Plan.build(fold_view=True), flattened: V = [W_v[:, :W] @ W_e | W_v[:, W:]] (Wc x (W + view_dim)) and
+    b = b_v + W_v[:, :W] @ b_e (Wc), computed in float64 and rounded to float32 once (the library computes them on the device with a
+    float64 accumulator: k_pack_multi)."""
+    W, Wc, ldv = arch.net_width, arch.net_width_condition, arch.net_width + arch.view_dim
+    fp = np.asarray(flat_params, dtype=np.float64).ravel()
+    offs, o = {}, 0
+    for n, shp in arch.param_shapes():
+        offs[n] = (o, shp)
+        o += int(np.prod(shp))
+    assert fp.size == o, (fp.size, o)
+
+    def t(n):
+        o0, shp = offs[n]
+        return fp[o0:o0 + int(np.prod(shp))].reshape(shp)
+    Wv, bv, We, be = t("view_layers.0.0.weight"), t("view_layers.0.0.bias"), t("extra_layer.weight"), t("extra_layer.bias")
+    V = np.concatenate([Wv[:, :W] @ We, Wv[:, W:]], axis=1)
+    assert V.shape == (Wc, ldv)
+    b = bv + Wv[:, :W] @ be
+    return np.concatenate([V.ravel(), b]).astype(np.float32)
+
+
 # ---- numpy emulation of the bf16 kernel's dataflow (used by tests, not by the product) -----
 def bf16_round(x: np.ndarray) -> np.ndarray:
     """float32 -> nearest-even bfloat16, returned as float32."""
@@ -377,7 +434,7 @@ def emulate_wave(plan: Plan, flat_params: np.ndarray, enc: np.ndarray, view: np.
     rnd = bf16_round if round_bf16 else (lambda z: z.astype(np.float32))
     ptab = plan.pack_table()
     btab = plan.bias_table()
-    fp = np.concatenate([flat_params.astype(np.float32), np.zeros(1, np.float32)])
+    fp = np.concatenate([plan.with_derived(flat_params), np.zeros(1, np.float32)])
     stream = rnd(fp[ptab])                        # [-1] -> the appended zero
     bias = fp[btab]                               # [tiles, 2, 16]
     lanes_hi = np.repeat(np.arange(2), 32)

@@ -119,14 +119,18 @@ class TrainPlan:
     NE: int = 0                                      # pre-GEMM plans: encoding blocks per wave tile in the fragment buffer
 
     @staticmethod
-    def build(arch: Arch = None, pre_gemm: bool = False) -> "TrainPlan":
+    def build(arch: Arch = None, pre_gemm: bool = False, fold_view: bool = True) -> "TrainPlan":
         """pre_gemm (round 5): the training kernels of the architecture whose encoding is too wide for k_mlp_bf16's wave-private LDS area
         (the unbounded-scene model, 672 features).  Forward-with-save = k_pre_gemm (unchanged: layer 0 and the encoding half of the skip
         layer) + a TRUNK forward-with-save that starts from the preloaded register set X = bf16(relu(layer 0)) -- whose T-blocks and ReLU
         mask it derives from those registers -- and initialises the skip layer's accumulators from k_pre_gemm's partial sums; the dgrad
         stream is the standard one (no gradient flows into the encoding: mip_nerf.py:83-90 concatenates a constant); the two weight
-        matrices that multiply the encoding get weight-gradient jobs whose B blocks are the encoding FRAGMENTS (WJob.b_src = 1)."""
-        fwd = Plan.build(arch or Arch(), pre_gemm=pre_gemm)
+        matrices that multiply the encoding get weight-gradient jobs whose B blocks are the encoding FRAGMENTS (WJob.b_src = 1).
+
+        fold_view: the forward-with-save runs the folded plan (Plan.build(fold_view=True)) like the inference kernel, so both forward kernels
+        compute the same bits; the two-kernel form stays unfolded.  Nothing else depends on it: the bottleneck's output is never saved, and
+        dgrad, the weight-gradient jobs and post_process are the chain rule of the unfolded network either way."""
+        fwd = Plan.build(arch or Arch(), pre_gemm=pre_gemm, fold_view=fold_view and not pre_gemm)
         a = fwd.arch
         if a.net_depth_condition < 1 or (a.net_depth_condition != 1 and pre_gemm):
             raise NotImplementedError("training kernels need at least one view layer (exactly one in the two-kernel form)")
@@ -475,7 +479,7 @@ def emulate_train_tile(tp: TrainPlan, flat_params, enc, view, d_raw, valid, roun
     Returns HT [NH, 2, 64, 8], GT [NG, 2, 64, 8], raw [32, 4]."""
     plan = tp.fwd
     rnd = bf16_round if round_bf16 else (lambda z: z.astype(np.float32))
-    fp = np.concatenate([flat_params.astype(np.float32), np.zeros(1, np.float32)])
+    fp = np.concatenate([plan.with_derived(flat_params), np.zeros(1, np.float32)])      # (a folded plan's derived tensors behind the parameters)
     stream = rnd(fp[plan.pack_table()])
     bias = fp[plan.bias_table()]
 
@@ -536,7 +540,8 @@ def emulate_train_tile(tp: TrainPlan, flat_params, enc, view, d_raw, valid, roun
                 newreg[2 * t] = acc[t, :, 0:8]
                 newreg[2 * t + 1] = acc[t, :, 8:16]
             newreg = rnd(newreg)
-            regs[op.out] = newreg
+            if nto:                 # a density-only head writes no register set
+                regs[op.out] = newreg
             hb, ml = tp.fwd_out[oi]
             for t in range(nto):
                 if hb is not None:

@@ -23,6 +23,6 @@ print("  dur_us", ["%.0f" % x for x in durs])
 for k, v in sorted(acc.items()):
     print(f"  {k}: {sum(v)/len(v):.5g}")
 g = sum(acc["GRBM_GUI_ACTIVE"]) / len(acc["GRBM_GUI_ACTIVE"]) / 8
-print(f"  cycles/XCD {g:.0f}  -> clock {g / (sum(durs)/len(durs)) / 1e3:.3f} GHz ; MFMA-busy frac {1216*8*2*32/g:.3f}")
+print(f"  cycles/XCD {g:.0f}  -> clock {g / (sum(durs)/len(durs)) / 1e3:.3f} GHz ; MFMA-busy frac {1088*8*2*32/g:.3f}  (1088 chunks since the bottleneck fold; 1216 before)")
 PY
 done
