@@ -279,6 +279,23 @@ int64_t mipnerf_visualize_workspace_floats(int64_t num_pixels);
 int mipnerf_visualize_map(int64_t num_pixels, const float* map, float* workspace, uint8_t* out_rgb, void* stream);
 int mipnerf_image_to_u8(int64_t num_values, const float* x, uint8_t* out, void* stream);
 
+/* ---- multi-scale Blender converter (datasets/convert_blender_data.py:34-37 `down2`, 65-81 the level loop): the box pyramid
+ * of num_images RGBA8 frames src_rgba [num_images, H, W, 4]; H and W divisible by 2^(num_levels-1), 1 <= num_levels <=
+ * MIPNERF_MAX_PYRAMID_LEVELS (else MIPNERF_E_INVALID before any launch).  Level 0 is v = float(byte) / 255.f, level j+1 the
+ * float32 mean of each 2x2 block of the UNQUANTISED level j, summed ((p00 + p01) + p10) + p11 (row-major in the block) and
+ * divided by 4, as numpy's mean over axes (1, 3) does.  With H_j = H >> j, W_j = W >> j, PPI = sum_j H_j W_j:
+ *   out_u8   level-major: level j is [num_images, H_j, W_j, 4] at byte offset 4 * num_images * sum_{k<j} H_k W_k; the bytes
+ *            (uint8)(v * 255.f), truncating, that the converter writes to NNN_dj.png.  4 * num_images * PPI bytes.
+ *   out_rgb  (may be NULL) float32 rows [*, 3] in the data set's order: pixel (y, x) of level j of image i is row
+ *            rgb_row_offset + i * PPI + sum_{k<j} H_k W_k + y * W_j + x; the value datasets.py:108-111 makes of the PNG:
+ *            q = float(byte) / 255.f, white_bkgd != 0: q_rgb * q_a + (1.f - q_a) (three roundings), else q_rgb.
+ *   scratch  num_levels > 4 only (else may be NULL): 4 * num_images * (H_3 W_3 + H_4 W_4) floats.
+ * src_rgba, out_u8 and scratch 16-byte aligned.  Does not allocate or synchronise (graph-capturable). */
+#define MIPNERF_MAX_PYRAMID_LEVELS 8
+int mipnerf_box_pyramid(int32_t num_images, int32_t height, int32_t width, int32_t num_levels, const uint8_t* src_rgba,
+                        uint8_t* out_u8, float* out_rgb, int64_t rgb_row_offset, int32_t white_bkgd, float* scratch,
+                        void* stream);
+
 /* ---- training side ---------------------------------------------------------------------- */
 /* activations (mip_nerf.py:236-238): raw [M,4] = (raw_rgb, raw_density) -> rgb_sigma [M,4];
  * density_randn [M] (NULL = none): raw_density + density_noise * density_randn first (mip_nerf.py:232-233). */

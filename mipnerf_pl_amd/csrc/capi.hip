@@ -900,6 +900,22 @@ int mipnerf_image_to_u8(int64_t n, const float* x, uint8_t* out, void* stream) {
     return MIPNERF_OK;
 }
 
+// ---- multi-scale converter (datasets/convert_blender_data.py:34-37, 65-81) ----------------------------------------
+int mipnerf_box_pyramid(int32_t n, int32_t H, int32_t W, int32_t n_levels, const uint8_t* src_rgba, uint8_t* out_u8, float* out_rgb,
+                        int64_t rgb_row_offset, int32_t white_bkgd, float* scratch, void* stream) {
+    if (n_levels < 1 || n_levels > MIPNERF_MAX_PYRAMID_LEVELS) return fail(MIPNERF_E_INVALID, "box_pyramid: n_levels must be in [1, %d]", MIPNERF_MAX_PYRAMID_LEVELS);
+    if (n < 1 || H < 1 || W < 1 || (int64_t)n * H * W > kMaxImageValues / 4) return fail(MIPNERF_E_INVALID, "box_pyramid: bad image count or size");
+    const int T = 1 << (n_levels - 1);
+    if (H % T || W % T) return fail(MIPNERF_E_INVALID, "box_pyramid: %d x %d (H x W) is not divisible by 2^(n_levels-1) = %d", H, W, T);
+    if (!src_rgba || !out_u8 || (n_levels > 4 && !scratch)) return fail(MIPNERF_E_INVALID, "box_pyramid: null argument");
+    if (rgb_row_offset < 0) return fail(MIPNERF_E_INVALID, "box_pyramid: negative row offset");
+    if (((uintptr_t)src_rgba | (uintptr_t)out_u8 | (uintptr_t)scratch) & 15 || ((uintptr_t)out_rgb & 3))
+        return fail(MIPNERF_E_INVALID, "box_pyramid: src, out_u8 and scratch must be 16-byte aligned, out_rgb 4-byte aligned");
+    HIP_TRY(mip::launch_box_pyramid(n, H, W, n_levels, src_rgba, out_u8, out_rgb ? out_rgb + 3 * rgb_row_offset : nullptr, white_bkgd != 0,
+                                    scratch, S(stream)));
+    return MIPNERF_OK;
+}
+
 // ---- training-side entry points ------------------------------------------------------------------
 int mipnerf_activate(int64_t M, const float* raw, float rgb_padding, float density_bias, const float* density_randn,
                      float density_noise, float* rgb_sigma, void* stream) {

@@ -75,12 +75,37 @@ def load_multicam(data_dir, split, white_bkgd=True):
         meta = json.load(fp)[split]
     meta = {k: np.array(meta[k]) for k in meta}
     images = [_composite(_read_image(os.path.join(data_dir, rel)), white_bkgd) for rel in meta["file_path"]]
-    records = []
-    for i in range(len(images)):
-        records.append(ops.camera_record(meta["cam2world"][i].astype(np.float32), float(meta["width"][i]), float(meta["height"][i]),
-                                         float(meta["near"][i]), float(meta["far"][i]),
-                                         pix2cam=meta["pix2cam"][i].astype(np.float32), lossmult=float(meta["lossmult"][i])))
-    return images, records, dict(meta=meta)
+    return images, _multicam_records(meta), dict(meta=meta)
+
+
+def _multicam_records(meta):
+    return [ops.camera_record(meta["cam2world"][i].astype(np.float32), float(meta["width"][i]), float(meta["height"][i]),
+                              float(meta["near"][i]), float(meta["far"][i]),
+                              pix2cam=meta["pix2cam"][i].astype(np.float32), lossmult=float(meta["lossmult"][i]))
+            for i in range(len(meta["file_path"]))]
+
+
+def load_multicam_from_blender(data_dir, split, white_bkgd=True, n_down=4, device=None):
+    """The data set `load_multicam` reads from a converted directory, built from the Blender directory itself: the camera table from
+    the converter's float64 metadata arithmetic (convert_blender_data.split_metadata), the pixel rows [P, 3] from the pyramid kernel
+    (`ops.box_pyramid`: the values the written PNGs would decode and composite to) directly on `device`.  No PNG is written or re-read.
+    Returns (pixels, records, info) with info['sizes'] = the (height, width) of every image."""
+    from . import convert_blender_data as conv
+    if device is None:
+        raise RuntimeError("datasets: the multi-scale pyramid is made by the HIP kernel; need a HIP device (there is no host fallback)")
+    device = torch.device(device)
+    files, cams, angle = conv.read_transforms(data_dir, split)
+    h, w = conv.check_frames(files, n_down)
+    meta = conv.split_metadata(split, cams, h, w, angle, n_down)
+    meta = {k: np.array(meta[k]) for k in meta}
+    sizes = [(int(a), int(b)) for a, b in zip(meta["height"], meta["width"])]
+    ppi = sum(a * b for a, b in sizes[:n_down])
+    pixels = torch.empty(len(files) * ppi, 3, dtype=torch.float32, device=device)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(conv.MAX_WORKERS) as pool, torch.cuda.device(device):
+        for lo, frames in conv.frame_batches(files, h, w, pool):
+            ops.box_pyramid(torch.from_numpy(frames).to(device), n_down, white_bkgd=bool(white_bkgd), out_rgb=pixels, rgb_row_offset=lo * ppi)
+    return pixels, _multicam_records(meta), dict(meta=meta, sizes=sizes)
 
 
 def _unit(v):
@@ -202,16 +227,19 @@ class BaseDataset(torch.utils.data.Dataset):
             assert batch_type == "all_images", "The batch_type can only be all_images with flatten"
         else:
             assert batch_type == "single_image", "The batch_type can only be single_image without flatten"
+        dev = device if device is not None else _default_device()
+        self._load_device = dev                 # for a loader that makes its pixels on the device (Multicam off a Blender directory)
+        self._device_pixels = None
         self.images, records, info = self._load()
         for k, v in info.items():
             setattr(self, k, v)
-        self.n_examples = len(self.images)
+        self.n_examples = len(records)
         self.cameras = torch.stack(records)                                    # [n, 32] host copy of the camera table
-        self.sizes = [(im.shape[0], im.shape[1]) for im in self.images]
+        if self.images is not None:
+            self.sizes = [(im.shape[0], im.shape[1]) for im in self.images]
         self.offsets = np.concatenate([[0], np.cumsum([h * w for h, w in self.sizes])]).astype(np.int64)
         self.device = None
         self._dev = None
-        dev = device if device is not None else _default_device()
         if dev is not None:
             self.to(dev)
 
@@ -223,8 +251,11 @@ class BaseDataset(torch.utils.data.Dataset):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("datasets: rays are generated by the HIP kernel; need a HIP device")
-        flat = np.concatenate([im.reshape(-1, 3) for im in self.images], axis=0)
-        self._dev = dict(cameras=self.cameras.to(device), pixels=torch.from_numpy(flat).to(device),
+        if self._device_pixels is not None:
+            pixels = self._device_pixels = self._device_pixels.to(device)
+        else:
+            pixels = torch.from_numpy(np.concatenate([im.reshape(-1, 3) for im in self.images], axis=0)).to(device)
+        self._dev = dict(cameras=self.cameras.to(device), pixels=pixels,
                          offsets=torch.from_numpy(self.offsets).to(device))
         self.device = device
         return self
@@ -290,13 +321,27 @@ class Blender(BaseDataset):
 
 
 class Multicam(BaseDataset):
-    """Multicam (multi-scale Blender) Dataset (datasets.py:84-168)."""
+    """Multicam (multi-scale Blender) Dataset (datasets.py:84-168).  `data_dir` is a directory written by convert_blender_data -- or
+    a Blender scene directory itself (no `metadata.json`, but `transforms_{split}.json`): then the `n_down` levels of every frame
+    are made on the device at start-up (`from_blender`), `images` is None and the pixels live on the device only."""
 
-    def __init__(self, data_dir, split="train", white_bkgd=True, batch_type="all_images", device=None):
+    def __init__(self, data_dir, split="train", white_bkgd=True, batch_type="all_images", device=None, n_down=4, blender=None):
+        if blender is None:
+            blender = (not os.path.exists(os.path.join(data_dir, "metadata.json"))
+                       and os.path.exists(os.path.join(data_dir, f"transforms_{split}.json")))
+        self.n_down, self.blender = int(n_down), bool(blender)
         super().__init__(data_dir, split, white_bkgd, batch_type, 0, device)
 
+    @classmethod
+    def from_blender(cls, data_dir, split="train", white_bkgd=True, batch_type="all_images", n_down=4, device=None):
+        """The multi-scale data set of a Blender scene directory without a conversion step (see the class)."""
+        return cls(data_dir, split, white_bkgd, batch_type, device=device, n_down=n_down, blender=True)
+
     def _load(self):
-        return load_multicam(self.data_dir, self.split, self.white_bkgd)
+        if not self.blender:
+            return load_multicam(self.data_dir, self.split, self.white_bkgd)
+        self._device_pixels, records, info = load_multicam_from_blender(self.data_dir, self.split, self.white_bkgd, self.n_down, self._load_device)
+        return None, records, info
 
 
 class RealData360(BaseDataset):
@@ -408,4 +453,4 @@ dataset_dict = {
 }
 
 __all__ = ["Blender", "Multicam", "RealData360", "RenderGen", "RayLoader", "dataset_dict", "Rays", "Rays_keys",
-           "create_spheric_poses", "load_blender", "load_multicam", "load_realdata360"]
+           "create_spheric_poses", "load_blender", "load_multicam", "load_multicam_from_blender", "load_realdata360"]

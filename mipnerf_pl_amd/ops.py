@@ -320,6 +320,60 @@ def image_to_u8(x, out=None):
     return out
 
 
+def pyramid_sizes(height: int, width: int, n_levels: int):
+    """[(H >> j, W >> j)] of the converter's levels; ValueError when a level would not halve exactly (the reference crashes in reshape)."""
+    n_levels = int(n_levels)
+    if not 1 <= n_levels <= L.MAX_PYRAMID_LEVELS:
+        raise ValueError(f"box_pyramid: n_levels must be in [1, {L.MAX_PYRAMID_LEVELS}], got {n_levels}")
+    t = 1 << (n_levels - 1)
+    if height < 1 or width < 1 or height % t or width % t:
+        raise ValueError(f"box_pyramid: {height} x {width} (H x W) is not divisible by 2^(n_levels-1) = {t}")
+    return [(height >> j, width >> j) for j in range(n_levels)]
+
+
+def box_pyramid(src_u8, n_levels, white_bkgd=None, out_u8=None, out_rgb=None, rgb_row_offset=0, scratch=None):
+    """convert_blender_data.py:65-81 on a batch of frames.  src_u8 [n, H, W, 4] uint8 RGBA on the device -> (u8_levels, rgb_levels):
+    u8_levels[j] [n, H >> j, W >> j, 4] = the bytes of NNN_dj.png (views of one level-major buffer `out_u8`, 4 * n * PPI bytes, PPI =
+    sum_j (H >> j)(W >> j)); rgb_levels[j] [n, H >> j, W >> j, 3] float32 = what datasets.load_multicam makes of those PNGs, composited
+    over white or not per `white_bkgd`, as strided views of the data set's row order (image-major, level inside the image): rows
+    rgb_row_offset ... rgb_row_offset + n * PPI of `out_rgb` [P, 3].  white_bkgd=None and no `out_rgb`: no rows, rgb_levels is None.
+    `scratch` (n_levels > 4): float32, at least 5 * n * (H >> 3) * (W >> 3) floats.  Given buffers make the call allocation-free (capturable)."""
+    if not src_u8.is_cuda:
+        raise RuntimeError(f"box_pyramid: the MI355X-native path needs HIP device tensors (got {src_u8.device}); there is no CPU fallback")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[-1] != 4:
+        raise TypeError(f"box_pyramid: expected uint8 [n, H, W, 4], got {src_u8.dtype} {tuple(src_u8.shape)}")
+    src = src_u8.contiguous()
+    n, h, w, _ = src.shape
+    sizes = pyramid_sizes(h, w, n_levels)
+    if n < 1:
+        raise ValueError("box_pyramid: no images")
+    ppi = sum(a * b for a, b in sizes)
+    out_u8 = _u8_out(out_u8, (4 * n * ppi,), src.device, "box_pyramid")
+    want_rgb = out_rgb is not None or white_bkgd is not None
+    if want_rgb:
+        if out_rgb is None:
+            out_rgb = torch.empty(rgb_row_offset + n * ppi, 3, dtype=torch.float32, device=src.device)
+        elif (out_rgb.dtype != torch.float32 or out_rgb.dim() != 2 or out_rgb.shape[1] != 3 or not out_rgb.is_contiguous()
+              or out_rgb.device != src.device or rgb_row_offset < 0 or out_rgb.shape[0] < rgb_row_offset + n * ppi):
+            raise ValueError(f"box_pyramid: `out_rgb` must be a contiguous float32 [P, 3] tensor on {src.device} with P >= row offset + {n * ppi}")
+    need = 5 * n * (h >> 3) * (w >> 3) if len(sizes) > 4 else 0
+    if need:
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.float32, device=src.device)
+        elif scratch.dtype != torch.float32 or scratch.numel() < need or not scratch.is_contiguous() or scratch.device != src.device:
+            raise ValueError(f"box_pyramid: scratch must hold {need} float32 values on {src.device}")
+    L.check(L.lib().mipnerf_box_pyramid(n, h, w, len(sizes), _ptr(src), _ptr(out_u8), _ptr(out_rgb) if want_rgb else None, int(rgb_row_offset),
+                                        int(bool(white_bkgd)), _ptr(scratch) if need else None, _stream()), "box_pyramid")
+    u8_levels, rgb_levels, off, row = [], [] if want_rgb else None, 0, int(rgb_row_offset)
+    for hj, wj in sizes:
+        u8_levels.append(out_u8[off:off + 4 * n * hj * wj].view(n, hj, wj, 4))
+        if want_rgb:
+            rgb_levels.append(out_rgb.as_strided((n, hj, wj, 3), (3 * ppi, 3 * wj, 3, 1), 3 * row))
+        off += 4 * n * hj * wj
+        row += hj * wj
+    return u8_levels, rgb_levels
+
+
 def selftest() -> str:
     """Run the hardware self-test (MFMA lane layouts, LDS DMA); returns the report, raises on failure."""
     rc = L.lib().mipnerf_selftest(_stream())

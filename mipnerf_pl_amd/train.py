@@ -19,6 +19,11 @@ monitor='val/psnr', mode='max', save_top_k=2)` of Lightning 1.5 do for `MipNeRFS
 * num_gpus > 1: the command starts one child process per rank (nccl when every rank has its own device, gloo otherwise); rank 0 alone
   logs and writes checkpoints.
 
+`--dataset_name multi_blender` takes either a directory written by `python -m mipnerf_pl_amd.convert_blender_data` or a Blender scene
+directory itself (`--data_path nerf_synthetic/lego`: no metadata.json, but transforms_{split}.json): then the four scales of every frame
+are made on the device at start-up (`datasets.Multicam.from_blender`), no conversion step and no PNG is written; `eval` reads such a
+checkpoint the same way.
+
 `step` in metrics.csv and in checkpoint names is Lightning 1.5's `global_step` at that moment: the 0-based index of the last step taken.
 """
 from __future__ import annotations
@@ -489,7 +494,7 @@ class Trainer:
 # ---------------------------------------------------------------------------------------------------------------------
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m mipnerf_pl_amd.train")
-    p.add_argument("--data_path", help="data path.", type=str, required=True)
+    p.add_argument("--data_path", help="data path (multi_blender: a converted directory, or a Blender scene directory to build the scales on the device).", type=str, required=True)
     p.add_argument("--out_dir", help="Output directory.", type=str, required=True)
     p.add_argument("--dataset_name", help="Single or multi data.", type=str, choices=["multi_blender", "blender"], required=True)
     p.add_argument("--config", help="Path to config file (default: the reference's configs/lego.yaml, built in).", default=None)
