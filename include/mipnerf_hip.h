@@ -296,6 +296,17 @@ int mipnerf_box_pyramid(int32_t num_images, int32_t height, int32_t width, int32
                         uint8_t* out_u8, float* out_rgb, int64_t rgb_row_offset, int32_t white_bkgd, float* scratch,
                         void* stream);
 
+/* ---- box shrink of captured images (LLFF / mip-NeRF-360 `images/` -> what `images_<factor>/` would hold): src
+ * [num_images, height, width, channels] bytes, channels 3 or 4 (a 4th channel is dropped, no compositing), 1 <= factor <=
+ * MIPNERF_MAX_DOWNSCALE_FACTOR, height and width >= factor (else MIPNERF_E_INVALID before any launch).  h = height / factor,
+ * w = width / factor; the height % factor bottom rows and width % factor right columns are ignored.  Per output channel value:
+ * S = the integer sum of the factor x factor source bytes, q = (2 S + factor^2) / (2 factor^2) in integer arithmetic (the box
+ * mean rounded half up to a byte), and out_rgb row rgb_row_offset + (i * h + y) * w + x, float32 [*, 3], gets float(q) / 255.f
+ * (one correctly rounded division).  src 16-byte aligned.  Does not allocate or synchronise (graph-capturable). */
+#define MIPNERF_MAX_DOWNSCALE_FACTOR 16
+int mipnerf_area_downscale(int32_t num_images, int32_t height, int32_t width, int32_t channels, int32_t factor, const uint8_t* src,
+                           float* out_rgb, int64_t rgb_row_offset, void* stream);
+
 /* ---- training side ---------------------------------------------------------------------- */
 /* activations (mip_nerf.py:236-238): raw [M,4] = (raw_rgb, raw_density) -> rgb_sigma [M,4];
  * density_randn [M] (NULL = none): raw_density + density_noise * density_randn first (mip_nerf.py:232-233). */

@@ -17,6 +17,7 @@ FLAG_WHITE_BKGD, FLAG_DISPARITY = 1, 2
 NUM_PARAM_TENSORS = 24
 MAX_SAMPLES = 1024
 MAX_PYRAMID_LEVELS = 8
+MAX_DOWNSCALE_FACTOR = 16
 
 
 class Config(C.Structure):
@@ -80,6 +81,7 @@ SIGNATURES = {
     "mipnerf_visualize_map": (C.c_int, [_I64, _P, _P, _P, _P]),
     "mipnerf_image_to_u8": (C.c_int, [_I64, _P, _P, _P]),
     "mipnerf_box_pyramid": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _I64, _I32, _P, _P]),
+    "mipnerf_area_downscale": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
     "mipnerf_activate": (C.c_int, [_I64, _P, _F, _F, _P, _F, _P, _P]),
     "mipnerf_volumetric_rendering_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _F, _P, _P]),
     "mipnerf_distloss": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P]),

@@ -40,6 +40,7 @@ UNITS = [
     ("kernels_eval.hip", ["-ffp-contract=off"]),
     ("kernels_vis.hip", ["-ffp-contract=off"]),
     ("kernels_pyramid.hip", ["-ffp-contract=off"]),     # q_rgb * q_a + (1 - q_a) rounds three times, as on the host
+    ("kernels_downscale.hip", ["-ffp-contract=off"]),   # float(q) / 255.f stays one rounded division
     ("selftest.hip", ["-ffp-contract=off"]),
     ("capi.hip", []),
 ]

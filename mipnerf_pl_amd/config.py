@@ -5,7 +5,9 @@ A configuration is one FLAT dict: nested YAML sections become dotted keys (`trai
 completes `system.DEFAULT_HPARAMS` with the run-level keys (`seed`, `num_gpus`, `exp_name`, `train.batch_type`, `val.*`,
 `checkpoint.resume_path`, ...).  `parse_args` merges, later winning:
 
-    DEFAULTS  <-  --config FILE  <-  trailing KEY VALUE pairs  <-  command-line arguments that are not yet keys
+    DEFAULTS  <-  [SCENE360_PRESET]  <-  --config FILE  <-  trailing KEY VALUE pairs  <-  command-line arguments that are not yet keys
+
+(the preset only for `--dataset_name llff | realdata360`: captured, unbounded scenes without a white background).
 
 Every leaf value goes through the same rule: `yaml.safe_load` first, then a string is tried with `ast.literal_eval` (falling back to the
 string itself), and a list becomes a tuple.  So the reference's quirks hold here too: `5e-4` (a string to YAML 1.1) becomes 0.0005,
@@ -34,6 +36,11 @@ DEFAULTS = {
     'loss.disable_multiscale_loss': False, 'loss.coarse_loss_mult': 0.1,
     'checkpoint.resume_path': None,
 }
+
+
+# layered over the defaults for the captured-scene data sets: the unbounded model, no white background behind a photograph
+SCENE360_DATASETS = ("llff", "realdata360")
+SCENE360_PRESET = {'nerf.unbounded': True, 'train.white_bkgd': False, 'val.white_bkgd': False, 'exp_name': 'scene360'}
 
 
 def parse_value(v):
@@ -77,9 +84,12 @@ def merge_opts(config, opts):
 
 
 def resolve(args: argparse.Namespace, defaults=None):
-    """The configuration of a parsed command line: defaults, then `args.config`, then `args.opts`, then every other attribute of
-    `args` whose name is not a key yet (so --data_path, --out_dir, --dataset_name land in the dict; a config key is not overridden)."""
+    """The configuration of a parsed command line: defaults (with SCENE360_PRESET over them when `args.dataset_name` is one of
+    SCENE360_DATASETS), then `args.config`, then `args.opts`, then every other attribute of `args` whose name is not a key yet (so
+    --data_path, --out_dir, --dataset_name land in the dict; a config key is not overridden)."""
     config = dict(DEFAULTS if defaults is None else defaults)
+    if getattr(args, "dataset_name", None) in SCENE360_DATASETS:
+        config.update(SCENE360_PRESET)
     if getattr(args, "config", None) is not None:
         config.update(load(args.config))
     merge_opts(config, getattr(args, "opts", None))

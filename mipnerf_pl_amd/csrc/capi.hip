@@ -916,6 +916,19 @@ int mipnerf_box_pyramid(int32_t n, int32_t H, int32_t W, int32_t n_levels, const
     return MIPNERF_OK;
 }
 
+// ---- box shrink of captured images (datasets.load_realdata360 off images/) -------------------------------------------
+int mipnerf_area_downscale(int32_t n, int32_t H, int32_t W, int32_t C, int32_t F, const uint8_t* src, float* out_rgb, int64_t rgb_row_offset,
+                           void* stream) {
+    if (F < 1 || F > MIPNERF_MAX_DOWNSCALE_FACTOR) return fail(MIPNERF_E_INVALID, "area_downscale: factor must be in [1, %d]", MIPNERF_MAX_DOWNSCALE_FACTOR);
+    if (C != 3 && C != 4) return fail(MIPNERF_E_INVALID, "area_downscale: channels must be 3 or 4");
+    if (n < 1 || H < F || W < F || (int64_t)n * H * W > kMaxImageValues / 4) return fail(MIPNERF_E_INVALID, "area_downscale: bad image count or size");
+    if (!src || !out_rgb) return fail(MIPNERF_E_INVALID, "area_downscale: null argument");
+    if (rgb_row_offset < 0) return fail(MIPNERF_E_INVALID, "area_downscale: negative row offset");
+    if (((uintptr_t)src & 15) || ((uintptr_t)out_rgb & 3)) return fail(MIPNERF_E_INVALID, "area_downscale: src must be 16-byte aligned, out_rgb 4-byte aligned");
+    HIP_TRY(mip::launch_area_downscale(n, H, W, C, F, src, out_rgb + 3 * rgb_row_offset, S(stream)));
+    return MIPNERF_OK;
+}
+
 // ---- training-side entry points ------------------------------------------------------------------
 int mipnerf_activate(int64_t M, const float* raw, float rgb_padding, float density_bias, const float* density_randn,
                      float density_noise, float* rgb_sigma, void* stream) {

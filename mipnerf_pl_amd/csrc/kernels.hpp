@@ -245,6 +245,9 @@ hipError_t launch_image_to_u8(int64_t n, const float* x, unsigned char* out, hip
 hipError_t launch_box_pyramid(int64_t n, int h, int w, int n_levels, const unsigned char* src, unsigned char* out_u8, float* out_rgb, int white,
                               float* scratch, hipStream_t st);
 
+// ---- kernels_downscale.hip ----------------------------------------------------------------------
+hipError_t launch_area_downscale(int64_t n, int H, int W, int C, int F, const unsigned char* src, float* out_rgb, hipStream_t st);
+
 // ---- selftest.hip -------------------------------------------------------------------------------
 // returns 0 if the MFMA fragment layouts and the LDS-DMA path behave as the kernels assume;
 // otherwise a bit mask (1: bf16 32x32x16 layout, 2: f32 32x32x2 layout, 4: global_load_lds)

@@ -10,8 +10,10 @@ keys as the reference, so `MipNeRFSystem.setup` / `eval.py` read the same direct
     Blender      `transforms_{split}.json` + RGBA PNGs, white-background compositing        datasets.py:171-263
     Multicam     `metadata.json` of convert_blender_data.py (pix2cam / cam2world / lossmult)  datasets.py:84-168
     RealData360  LLFF `poses_bounds.npy` + `images[_f]/` + COLMAP `sparse/0/cameras.bin`    datasets.py:266-474
-                 (upstream never registers it; here it is `dataset_dict['llff']`)
+                 (upstream never registers it; here it is `dataset_dict['llff']`); a capture with `images/` only is shrunk by
+                 `factor` on the device at start-up (`ops.area_downscale`)
     RenderGen    the spherical render path of render_video.py:19-118 as a camera table
+    PathGen      the interpolated path of utils/vis.py:92-121 (`gen_render_path`) through the poses of a RealData360 split
 
 File parsing and pose algebra are host numpy (they run once); the per-ray arithmetic is the HIP kernel's.
 """
@@ -160,36 +162,96 @@ def read_colmap_pinhole(fname):
     return np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
 
 
-def load_realdata360(data_dir, split, white_bkgd=True, factor=0):
-    """datasets.py:278-345.  `factor` must be > 0 (upstream divides by it at :312 and :335; with the shipped default 0 it
-    produces infinities -- raised here instead).  Every 8th image is the test split."""
+def _image_files(imgdir):
+    return [os.path.join(imgdir, f) for f in sorted(os.listdir(imgdir)) if f.endswith(("JPG", "jpg", "png"))]
+
+
+def _split_indices(n, split):
+    """Indices into the sorted file list: every 8th image is the test split, the others train (datasets.py:325-331)."""
+    idx = np.arange(n)
+    test = idx[::8]
+    return np.array([i for i in idx if i not in test]) if split == "train" else test
+
+
+def realdata360_files(data_dir, split, factor):
+    """(files of `split`, number of files of all splits, shrink): the files of images_<factor>/ when that folder exists (shrink
+    False), else those of images/ (shrink True: `load_realdata360` shrinks them by `factor` on the device).  Sorted by file name;
+    the split is chosen before anything is decoded."""
     if factor <= 0:
         raise ValueError("RealData360 needs factor > 0 (images_<factor>/; datasets.py:312 divides by it)")
     imgdir = os.path.join(data_dir, f"images_{factor}")
-    if not os.path.exists(imgdir):
-        raise ValueError(f"Image folder {imgdir} does not exist.")
-    files = [os.path.join(imgdir, f) for f in sorted(os.listdir(imgdir)) if f.endswith(("JPG", "jpg", "png"))]
-    images = np.stack([_read_image(f) for f in files], axis=0)
+    shrink = not os.path.exists(imgdir)
+    if shrink:
+        if not os.path.exists(os.path.join(data_dir, "images")):
+            raise ValueError(f"Image folder {imgdir} does not exist.")
+        imgdir = os.path.join(data_dir, "images")
+    files = _image_files(imgdir)
+    return [files[i] for i in _split_indices(len(files), split)], len(files), shrink
+
+
+def _read_u8(fname):
+    from PIL import Image
+    with open(fname, "rb") as f:
+        a = np.array(Image.open(f))
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4):
+        raise ValueError(f"{fname}: expected an 8-bit image of 3 or 4 channels, got {a.dtype} {a.shape}")
+    return a
+
+
+def decode_u8(files, workers=16):
+    """`files` decoded on host threads (PIL releases the GIL while it decodes): uint8 [n, H, W, C]; ValueError when they differ in shape."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(int(workers), len(files)))) as pool:
+        frames = list(pool.map(_read_u8, files))
+    for f, a in zip(files, frames):
+        if a.shape != frames[0].shape:
+            raise ValueError(f"{f}: {a.shape} differs from the first image's {frames[0].shape}")
+    return np.stack(frames)
+
+
+def _shrink_on_device(files, factor, device):
+    if device is None:
+        raise RuntimeError("datasets: images/ is shrunk by the HIP kernel; need a HIP device (there is no host fallback)")
+    device = torch.device(device)
+    with torch.cuda.device(device):
+        return ops.area_downscale(torch.from_numpy(decode_u8(files)).to(device), factor)
+
+
+def load_realdata360(data_dir, split, white_bkgd=True, factor=0, device=None):
+    """datasets.py:278-345.  `factor` must be > 0 (upstream divides by it at :312 and :335; with the shipped default 0 it
+    produces infinities -- raised here instead).  Every 8th image is the test split.
+    Without an images_<factor>/ folder but with images/ (a capture as COLMAP leaves it), the split's files of images/ are decoded to
+    bytes, uploaded once and shrunk by `factor` on `device` straight into the pixel table (`ops.area_downscale`: the box mean rounded
+    to a byte, i.e. the pixels an images_<factor>/ folder of those bytes would give); the first return value is then that [P, 3] device
+    tensor and info['sizes'] the (height, width) of every image."""
+    files, n_files, shrink = realdata360_files(data_dir, split, factor)
+    images = None if shrink else np.stack([_read_image(f) for f in _image_files(os.path.join(data_dir, f"images_{factor}"))], axis=0)
     arr = np.load(os.path.join(data_dir, "poses_bounds.npy"))
-    if arr.shape[0] != images.shape[0]:
-        raise RuntimeError(f"Mismatch between imgs {images.shape[0]} and poses {arr.shape[0]}")
+    if arr.shape[0] != n_files:
+        raise RuntimeError(f"Mismatch between imgs {n_files} and poses {arr.shape[0]}")
+    if images is None:
+        pixels = _shrink_on_device(files, factor, device)           # [n_split, h, w, 3] on the device
+        shape = (n_files,) + tuple(pixels.shape[1:])
+    else:
+        pixels, shape = None, images.shape
     poses = arr[:, :-2].reshape(-1, 3, 5).copy()                     # [n, 3, 5] = [R | t | (h, w, f)] in LLFF axis order
     bds = arr[:, -2:].astype(np.float32)
-    poses[:, 0, 4], poses[:, 1, 4] = images.shape[1], images.shape[2]
+    poses[:, 0, 4], poses[:, 1, 4] = shape[1], shape[2]
     poses[:, 2, 4] /= factor
     poses = np.concatenate([poses[:, :, 1:2], -poses[:, :, 0:1], poses[:, :, 2:]], axis=2).astype(np.float32)   # (down,right,back) -> (right,up,back)
     poses = spherify_poses(recenter_poses(poses))
-    idx = np.arange(images.shape[0])
-    test = idx[::8]
-    sel = np.array([i for i in idx if i not in test]) if split == "train" else test
+    sel = _split_indices(n_files, split)
     K = read_colmap_pinhole(os.path.join(data_dir, "sparse", "0", "cameras.bin"))
     K[:2, :] /= factor
     K_inv = np.linalg.inv(K)
     K_inv[1:, :] *= -1
-    h, w = images.shape[1:3]
+    h, w = (int(v) for v in shape[1:3])
     records = [ops.camera_record(poses[i, :3, :4], w, h, float(bds[i, 0]), float(bds[i, 1]), pix2cam=K_inv) for i in sel]
+    info = dict(h=h, w=w, K=K, K_inv=K_inv, bds=bds[sel], camtoworlds=poses[sel][:, :3, :4], focal=poses[0, -1, -1])
+    if pixels is not None:
+        return pixels.view(-1, 3), records, dict(info, sizes=[(h, w)] * len(sel))
     imgs = [np.ascontiguousarray(images[i, ..., :3], dtype=np.float32) for i in sel]
-    return imgs, records, dict(h=h, w=w, K=K, K_inv=K_inv, bds=bds[sel], camtoworlds=poses[sel][:, :3, :4], focal=poses[0, -1, -1])
+    return imgs, records, info
 
 
 def create_spheric_poses(radius, n_poses=120):
@@ -204,6 +266,45 @@ def create_spheric_poses(radius, n_poses=120):
         rot_th = np.array([[np.cos(th), 0, -np.sin(th), 0], [0, 1, 0, 0], [np.sin(th), 0, np.cos(th), 0], [0, 0, 0, 1]])
         out.append((swap @ (rot_th @ rot_phi @ trans))[:3])
     return np.stack(out, 0)
+
+
+def _matrix_to_euler_xyz(m):
+    """Angles in degrees of the extrinsic x, y, z rotations that compose the rotation nearest to `m` [3, 3] (its orthogonal Procrustes
+    projection U V^T, as scipy's Rotation.from_matrix takes a matrix that is only nearly orthogonal): m = Rz(c) Ry(b) Rx(a) -> (a, b, c),
+    b in [-90, 90].  Not meant for b = +-90 (gimbal lock)."""
+    u, _, vt = np.linalg.svd(np.asarray(m, np.float64))
+    if np.linalg.det(u @ vt) < 0:
+        u[:, -1] = -u[:, -1]
+    r = u @ vt
+    return np.degrees([np.arctan2(r[2, 1], r[2, 2]), -np.arcsin(np.clip(r[2, 0], -1.0, 1.0)), np.arctan2(r[1, 0], r[0, 0])])
+
+
+def _euler_xyz_to_matrix(deg):
+    (sa, sb, sc), (ca, cb, cc) = np.sin(np.radians(deg)), np.cos(np.radians(deg))
+    return np.array([[cb * cc, sa * sb * cc - ca * sc, ca * sb * cc + sa * sc],
+                     [cb * sc, sa * sb * sc + ca * cc, ca * sb * sc - sa * cc],
+                     [-sb, sa * cb, ca * cb]])
+
+
+def gen_render_path(c2ws, n_views=30):
+    """utils/vis.py:92-121: a closed path through the poses `c2ws` [N, 3|4, 4] in their order: n_views // 3 poses per consecutive pair
+    (and from the last back to the first), positions and extrinsic-xyz Euler angles in degrees interpolated linearly; an angle more
+    than 180 degrees away from the FIRST pose's has 360 added (upstream's unwrap, whatever the sign).  Float64 [N * (n_views // 3), 4, 4]."""
+    c2ws = np.asarray(c2ws, np.float64)
+    weight = np.linspace(1.0, 0.0, int(n_views) // 3, endpoint=False).reshape(1, -1, 1)
+    angles = []
+    for i, m in enumerate(c2ws):
+        e = _matrix_to_euler_xyz(m[:3, :3])
+        if i:
+            e[np.abs(e - angles[0]) > 180] += 360.0
+        angles.append(e)
+    angles, positions = np.stack(angles)[:, None], c2ws[:, None, :3, 3]
+    angles = (weight * angles + (1.0 - weight) * np.roll(angles, -1, axis=0)).reshape(-1, 3)
+    positions = (weight * positions + (1.0 - weight) * np.roll(positions, -1, axis=0)).reshape(-1, 3)
+    out = np.tile(np.eye(4), (len(angles), 1, 1))
+    for m, e, p in zip(out, angles, positions):
+        m[:3, :3], m[:3, 3] = _euler_xyz_to_matrix(e), p
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -351,7 +452,10 @@ class RealData360(BaseDataset):
         super().__init__(data_dir, split, white_bkgd, batch_type, factor, device)
 
     def _load(self):
-        return load_realdata360(self.data_dir, self.split, self.white_bkgd, self.factor)
+        images, records, info = load_realdata360(self.data_dir, self.split, self.white_bkgd, self.factor, self._load_device)
+        if torch.is_tensor(images):             # made on the device from images/: no host copy
+            self._device_pixels, images = images, None
+        return images, records, info
 
 
 class RenderGen(torch.utils.data.Dataset):
@@ -370,6 +474,9 @@ class RenderGen(torch.utils.data.Dataset):
                 # float64 table -> float64 ray arithmetic on the device, as the reference's numpy (its poses and pix2cam are float64)
                 records.append(ops.camera_record(np.asarray(m, np.float64), w, h, self.near, self.far, pix2cam=pix2cam, dtype=torch.float64))
                 self.sizes.append((int(h), int(w)))
+        self._set_cameras(records, device)
+
+    def _set_cameras(self, records, device):
         self.n_sample = len(records)
         self.cameras = torch.stack(records)
         dev = device if device is not None else _default_device()
@@ -386,6 +493,21 @@ class RenderGen(torch.utils.data.Dataset):
         cam = torch.full((h * w,), int(index), dtype=torch.int32, device=self.device)
         rays = ops.generate_rays(self._cams_dev, cam_idx=cam, pix_idx=torch.arange(h * w, dtype=torch.int32, device=self.device))
         return Rays(*[t.reshape(h, w, -1) for t in rays])
+
+
+class PathGen(RenderGen):
+    """The render path of a captured scene: `gen_render_path` through the poses of `dataset` (a RealData360 split; `poses` [n, 3|4, 4]
+    given: those instead), one float32 camera record per pose built as `load_realdata360` builds the data set's (its size and pix2cam),
+    near / far = the smallest / largest bound of the split.  Item i = Rays [h, w, k] of pose i."""
+
+    def __init__(self, dataset, n_views=30, poses=None, device=None):
+        torch.utils.data.Dataset.__init__(self)
+        self.poses = gen_render_path(dataset.camtoworlds, n_views) if poses is None else np.asarray(poses)
+        self.near, self.far = float(dataset.bds.min()), float(dataset.bds.max())
+        h, w = int(dataset.h), int(dataset.w)
+        self.sizes = [(h, w)] * len(self.poses)
+        self._set_cameras([ops.camera_record(m[:3, :4], w, h, self.near, self.far, pix2cam=dataset.K_inv) for m in self.poses],
+                          device if device is not None else dataset.device)
 
 
 class RayLoader:
@@ -452,5 +574,5 @@ dataset_dict = {
     "realdata360": RealData360,
 }
 
-__all__ = ["Blender", "Multicam", "RealData360", "RenderGen", "RayLoader", "dataset_dict", "Rays", "Rays_keys",
+__all__ = ["Blender", "Multicam", "RealData360", "RenderGen", "PathGen", "gen_render_path", "RayLoader", "dataset_dict", "Rays", "Rays_keys",
            "create_spheric_poses", "load_blender", "load_multicam", "load_multicam_from_blender", "load_realdata360"]

@@ -2,6 +2,9 @@
 
     python -m mipnerf_pl_amd.eval --ckpt CKPT --data DATA_DIR --out_dir OUT --scale 1|4 [--save_image] [--summa_only]
 
+For a checkpoint of a captured scene (`dataset_name` llff / realdata360; `--scale 1`) the defaults follow the checkpoint and the data:
+`--factor` its `factor`, `--white_bkgd` its `val.white_bkgd`, `--base_size` the data set's own (w, h), so the images land in `1/`.
+
 Loads the checkpoint with MipNeRFSystem.load_from_checkpoint, reads the test split of hparams['dataset_name'] through
 datasets.dataset_dict, runs evaluate.evaluate and prints evaluate.summarize_results."""
 from __future__ import annotations
@@ -11,7 +14,7 @@ import argparse
 import torch
 
 from .evaluate import evaluate, summarize_results
-from .render_video import add_common_args, load_system
+from .render_video import add_common_args, flag_given, is_scene360, load_system
 
 
 def build_parser():
@@ -32,10 +35,17 @@ def main(argv=None):
         from .datasets import dataset_dict
         dev = torch.device("cuda", torch.cuda.current_device())
         system = system.to(dev).eval()
+        scene360 = is_scene360(hp)
+        kw = {"factor": args.factor if args.factor is not None else int(hp.get("factor", 4))} if scene360 else {}
         dataset = dataset_dict[hp["dataset_name"]](data_dir=args.data, split="test", white_bkgd=hp["val.white_bkgd"],
-                                                  batch_type=hp["val.batch_type"], device=dev)
+                                                  batch_type=hp["val.batch_type"], device=dev, **kw)
+        white_bkgd, base_size = args.white_bkgd, args.base_size
+        if scene360 and not flag_given(argv, "--white_bkgd"):
+            white_bkgd = bool(hp["val.white_bkgd"])
+        if scene360 and not flag_given(argv, "--base_size"):
+            base_size = (dataset.w, dataset.h)
         evaluate(system, dataset, args.out_dir, exp_name, scale=args.scale, save_image=args.save_image, chunk_size=args.chunk_size,
-                 white_bkgd=args.white_bkgd, use_graph=args.use_graph, base_size=args.base_size)
+                 white_bkgd=white_bkgd, use_graph=args.use_graph, base_size=base_size)
     summary = summarize_results(args.out_dir, [exp_name], args.scale)
     print("PSNR | SSIM | Average")
     print(summary)

@@ -374,6 +374,37 @@ def box_pyramid(src_u8, n_levels, white_bkgd=None, out_u8=None, out_rgb=None, rg
     return u8_levels, rgb_levels
 
 
+def area_downscale(src_u8, factor, out_rgb=None, row_offset=0):
+    """Box shrink of captured images by an integer `factor` F in [1, 16]: src_u8 [n, H, W, C] uint8 on the device, C in {3, 4} (a 4th
+    channel is dropped, no compositing) -> rows row_offset ... row_offset + n * h * w of `out_rgb` [P, 3] float32 (image-major,
+    row-major: the data set's pixel table), h = H // F, w = W // F, the H % F bottom rows and W % F right columns ignored.  Per value:
+    q = (2 S + F F) // (2 F F) of the integer sum S of the F x F source bytes (the box mean rounded half up to a byte), stored as
+    float32(q) / 255: what `datasets._read_image` makes of an images_<F>/ file holding the bytes q.  Returns the written rows as
+    [n, h, w, 3] (a view of `out_rgb`)."""
+    if not src_u8.is_cuda:
+        raise RuntimeError(f"area_downscale: the MI355X-native path needs HIP device tensors (got {src_u8.device}); there is no CPU fallback")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[-1] not in (3, 4):
+        raise TypeError(f"area_downscale: expected uint8 [n, H, W, 3 or 4], got {src_u8.dtype} {tuple(src_u8.shape)}")
+    if isinstance(factor, bool) or int(factor) != factor or not 1 <= int(factor) <= L.MAX_DOWNSCALE_FACTOR:
+        raise ValueError(f"area_downscale: factor must be an integer in [1, {L.MAX_DOWNSCALE_FACTOR}], got {factor!r}")
+    factor = int(factor)
+    src = src_u8.contiguous()
+    if src.data_ptr() % 16:
+        src = src.clone()
+    n, H, W, C = src.shape
+    h, w = H // factor, W // factor
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError(f"area_downscale: no output pixels ({n} images of {H} x {W} at factor {factor})")
+    row_offset = int(row_offset)
+    if out_rgb is None:
+        out_rgb = torch.empty(row_offset + n * h * w, 3, dtype=torch.float32, device=src.device)
+    elif (out_rgb.dtype != torch.float32 or out_rgb.dim() != 2 or out_rgb.shape[1] != 3 or not out_rgb.is_contiguous()
+          or out_rgb.device != src.device or row_offset < 0 or out_rgb.shape[0] < row_offset + n * h * w):
+        raise ValueError(f"area_downscale: `out_rgb` must be a contiguous float32 [P, 3] tensor on {src.device} with P >= row offset + {n * h * w}")
+    L.check(L.lib().mipnerf_area_downscale(n, H, W, C, factor, _ptr(src), _ptr(out_rgb), row_offset, _stream()), "area_downscale")
+    return out_rgb[row_offset:row_offset + n * h * w].view(n, h, w, 3)
+
+
 def selftest() -> str:
     """Run the hardware self-test (MFMA lane layouts, LDS DMA); returns the report, raises on failure."""
     rc = L.lib().mipnerf_selftest(_stream())

@@ -6,6 +6,12 @@ device and written to <out_dir>/render_spheric/<exp_name>/<base_w / W>/{i % n_po
 `n_poses` (not in the reference) shortens the path; the default 120 is the reference's.
 
     python -m mipnerf_pl_amd.render_video --ckpt CKPT --out_dir OUT --scale 4 [--gen_video_only --render_images_dir DIR]
+
+A checkpoint of a captured scene (`dataset_name` llff / realdata360) has no spherical path to fly: `--path interp` (its default) renders
+`datasets.gen_render_path` -- the reference's utils/vis.py path, `--n_views // 3` poses between consecutive poses of the `--split` of
+`--data` and back to the first -- at the data set's own size to <out_dir>/render_path/<exp_name>/1/{i:05d}_{rgb,dist,acc}.png:
+
+    python -m mipnerf_pl_amd.render_video --ckpt CKPT --data DATA_DIR --out_dir OUT --scale 1 [--split test] [--n_views 30]
 """
 from __future__ import annotations
 
@@ -46,6 +52,35 @@ def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_
     return folder
 
 
+def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAULT_CHUNK, white_bkgd=False, use_graph=True):
+    """The interpolated path through the poses of `dataset` (a `datasets.RealData360` split), every frame as in `render_video`.
+    Returns the output folder."""
+    from .datasets import PathGen
+    model = system.mip_nerf
+    device = next(model.parameters()).device
+    folder = os.path.join(out_dir, "render_path", exp_name)
+    os.makedirs(os.path.join(folder, "1"), exist_ok=True)
+    path = PathGen(dataset, n_views, device=device)
+    h, w = path.sizes[0]
+    ev = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph)
+    with torch.no_grad():
+        for idx in range(len(path)):
+            save_images(*ev.images(*ev.render(path[idx])), os.path.join(folder, "1"), idx)
+    generate_video(folder)
+    return folder
+
+
+def is_scene360(hparams):
+    from .config import SCENE360_DATASETS
+    return hparams.get("dataset_name") in SCENE360_DATASETS
+
+
+def flag_given(argv, flag):
+    """Whether `flag` is on the command line `argv` (None: this process's): tells a default from a choice."""
+    import sys
+    return any(a == flag or a.startswith(flag + "=") for a in (sys.argv[1:] if argv is None else argv))
+
+
 def _bool(s):
     if str(s).lower() in ("1", "true", "yes", "y"):
         return True
@@ -61,6 +96,7 @@ def add_common_args(p):
     p.add_argument("--chunk_size", help="Chunk size for render.", type=int, default=DEFAULT_CHUNK)
     p.add_argument("--white_bkgd", help="Train set image background color.", type=_bool, default=True)
     p.add_argument("--base_size", help="source image size: W H", type=int, nargs=2, default=[800, 800])
+    p.add_argument("--factor", help="llff / realdata360 checkpoints: the data set's shrink factor (default: the checkpoint's)", type=int, default=None)
     p.add_argument("--precision", help="MLP precision (default: the checkpoint's)", choices=["fp32", "bf16"], default=None)
     p.add_argument("--no-graph", dest="use_graph", help="render each frame eagerly instead of replaying a captured hipGraph",
                    action="store_false")
@@ -74,6 +110,11 @@ def build_parser():
     p.add_argument("--camera_angle_x", help="camera_angle_x in source dataset", type=float, default=CAMERA_ANGLE_X)
     p.add_argument("--gen_video_only", help="only generate the video of images rendered before", action="store_true")
     p.add_argument("--n_poses", help="poses on the spherical path", type=int, default=120)
+    p.add_argument("--path", help="camera path (default: spheric, or interp for a llff / realdata360 checkpoint)", choices=["spheric", "interp"],
+                   default=None)
+    p.add_argument("--data", help="interp: path to the data whose poses the path runs through.", default=None)
+    p.add_argument("--split", help="interp: the split whose poses the path runs through", choices=["train", "test"], default="test")
+    p.add_argument("--n_views", help="interp: three times the poses per pair of consecutive poses", type=int, default=30)
     return p
 
 
@@ -91,6 +132,18 @@ def main(argv=None):
             raise SystemExit("only generate video, you must give the different scale image base dir (--render_images_dir)")
         return generate_video(args.render_images_dir)
     system = load_system(args).to(torch.device("cuda")).eval()
+    hp = system.hparams
+    if (args.path or ("interp" if is_scene360(hp) else "spheric")) == "interp":
+        from .datasets import RealData360
+        if args.data is None:
+            raise SystemExit("the interp path runs through the poses of a data set: give --data")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dataset = RealData360(args.data, split=args.split, white_bkgd=hp["val.white_bkgd"],
+                              batch_type="all_images" if args.split == "train" else "single_image",
+                              factor=args.factor if args.factor is not None else int(hp.get("factor", 4)), device=dev)
+        return render_path(system, dataset, args.out_dir, hp["exp_name"], n_views=args.n_views, chunk_size=args.chunk_size,
+                           white_bkgd=args.white_bkgd if flag_given(argv, "--white_bkgd") else bool(hp["val.white_bkgd"]),
+                           use_graph=args.use_graph)
     return render_video(system, args.out_dir, system.hparams["exp_name"], args.scale, base_size=args.base_size,
                         camera_angle_x=args.camera_angle_x, chunk_size=args.chunk_size, white_bkgd=args.white_bkgd,
                         n_poses=args.n_poses, use_graph=args.use_graph)

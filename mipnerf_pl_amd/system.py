@@ -120,15 +120,17 @@ class MipNeRFSystem(_Base):
 
     def setup(self, stage=None):   # nerf_system.py:56-68
         from .datasets import dataset_dict
+        from .datasets import RealData360
         dataset = dataset_dict[self.hparams['dataset_name']]
+        kw = {'factor': int(self.hparams.get('factor', 4))} if dataset is RealData360 else {}
         dev = next(self.mip_nerf.parameters()).device          # the datasets live where the model lives
         dev = dev if dev.type == "cuda" else None              # (None: the current HIP device, if any)
         self.train_dataset = dataset(data_dir=self.hparams['data_path'], split='train',
                                      white_bkgd=self.hparams['train.white_bkgd'],
-                                     batch_type=self.hparams['train.batch_type'], device=dev)
+                                     batch_type=self.hparams['train.batch_type'], device=dev, **kw)
         self.val_dataset = dataset(data_dir=self.hparams['data_path'], split='val',
                                    white_bkgd=self.hparams['val.white_bkgd'],
-                                   batch_type=self.hparams['val.batch_type'], device=dev)
+                                   batch_type=self.hparams['val.batch_type'], device=dev, **kw)
 
     def configure_optimizers(self):   # nerf_system.py:70-76
         hp = self.hparams

@@ -1,7 +1,7 @@
 """The reference's train.py without Lightning: `python -m mipnerf_pl_amd.train`.
 
-    python -m mipnerf_pl_amd.train --data_path DATA --out_dir OUT --dataset_name blender|multi_blender [--config FILE]
-        [--precision bf16|fp32] [--no-graph] [--log_every_n_steps 50] [KEY VALUE ...]
+    python -m mipnerf_pl_amd.train --data_path DATA --out_dir OUT --dataset_name blender|multi_blender|llff|realdata360 [--factor 4]
+        [--config FILE] [--precision bf16|fp32] [--no-graph] [--log_every_n_steps 50] [KEY VALUE ...]
 
 What `Trainer(max_steps, val_check_interval, num_sanity_val_steps=1, limit_val_batches=val.sample_num)` + `ModelCheckpoint(save_last=True,
 monitor='val/psnr', mode='max', save_top_k=2)` of Lightning 1.5 do for `MipNeRFSystem` (train.py:31-64), restated as a plain loop:
@@ -23,6 +23,10 @@ monitor='val/psnr', mode='max', save_top_k=2)` of Lightning 1.5 do for `MipNeRFS
 directory itself (`--data_path nerf_synthetic/lego`: no metadata.json, but transforms_{split}.json): then the four scales of every frame
 are made on the device at start-up (`datasets.Multicam.from_blender`), no conversion step and no PNG is written; `eval` reads such a
 checkpoint the same way.
+
+`--dataset_name llff` (= `realdata360`) trains the unbounded-scene model on an LLFF / mip-NeRF-360 capture (`poses_bounds.npy`,
+`sparse/0/cameras.bin`, `images_<factor>/` or, without it, `images/` shrunk by `--factor` on the device at start-up): `config.SCENE360_PRESET`
+(nerf.unbounded, no white background, exp_name scene360) is layered under `--config` and the trailing pairs; `--factor` is stored as hparam `factor`.
 
 `step` in metrics.csv and in checkpoint names is Lightning 1.5's `global_step` at that moment: the 0-based index of the last step taken.
 """
@@ -496,7 +500,8 @@ def build_parser():
     p = argparse.ArgumentParser(prog="python -m mipnerf_pl_amd.train")
     p.add_argument("--data_path", help="data path (multi_blender: a converted directory, or a Blender scene directory to build the scales on the device).", type=str, required=True)
     p.add_argument("--out_dir", help="Output directory.", type=str, required=True)
-    p.add_argument("--dataset_name", help="Single or multi data.", type=str, choices=["multi_blender", "blender"], required=True)
+    p.add_argument("--dataset_name", help="Single or multi data.", type=str, choices=["multi_blender", "blender", "llff", "realdata360"], required=True)
+    p.add_argument("--factor", help="llff / realdata360: read images_<factor>/, or shrink images/ by it on the device.", type=int, default=4)
     p.add_argument("--config", help="Path to config file (default: the reference's configs/lego.yaml, built in).", default=None)
     p.add_argument("--precision", help="MLP precision", choices=["fp32", "bf16"], default="bf16")
     p.add_argument("--no-graph", dest="use_graph", help="run every step eagerly instead of replaying a captured hipGraph",
