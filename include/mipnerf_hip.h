@@ -307,6 +307,47 @@ int mipnerf_box_pyramid(int32_t num_images, int32_t height, int32_t width, int32
 int mipnerf_area_downscale(int32_t num_images, int32_t height, int32_t width, int32_t channels, int32_t factor, const uint8_t* src,
                            float* out_rgb, int64_t rgb_row_offset, void* stream);
 
+/* ---- geometry out of a trained field: density on a lattice, isosurface of any lattice (ABI 6 grows; nothing above changes) ----
+ * A lattice has dims = (nx, ny, nz) points, each >= 2, over the box lo[3] .. hi[3] (HOST arrays, (x, y, z) order); 7 nx ny nz < 2^31
+ * (indices are 32-bit; 512 x 512 x 512 fits), else MIPNERF_E_INVALID before any launch.  Point (i, j, k) has the flat index
+ * (k * ny + j) * nx + i and, per axis, the mean lo + float(i) * h with h = (hi - lo) / float(n - 1), in fp32 without contraction.
+ * mipnerf_density_grid: the field's activated density softplus(raw + density_bias) at an isotropic-per-axis Gaussian on every point:
+ * diagonal covariance cov_scale * h * h / 12 (the variance of a uniform box of side h; cov_scale = 0 is a point query), sigma
+ * [nz, ny, nx] fp32.  The lattice is walked in chunks: encoding rows written from the lattice index (the device code of
+ * mipnerf_integrated_pos_enc, no means or covariances in memory), the MLP path of mipnerf_mlp_forward on a ZERO view encoding (its
+ * colour is dropped), a strided store of the density.  The chunk is what the workspace holds: any size from
+ * mipnerf_density_grid_workspace_bytes(ctx, chunk_points >= 1, precision) on is accepted (16-byte aligned), results do not depend on
+ * it; a chunk past 256 points is cut to whole 256-point tiles.  Both precisions and every MLP shape of the bounded model;
+ * cfg.unbounded = 1: MIPNERF_E_UNSUPPORTED (a lattice in the contracted space is a different question).  Does not allocate or
+ * synchronise (graph-capturable). */
+size_t mipnerf_density_grid_workspace_bytes(const mipnerf_ctx* ctx, int64_t chunk_points, int precision);
+int mipnerf_density_grid(mipnerf_ctx* ctx, const int32_t* dims_host, const float* lo_host, const float* hi_host, float cov_scale,
+                         int precision, float* sigma, void* workspace, size_t workspace_bytes, void* stream);
+/* Marching tetrahedra on the Kuhn split of ANY fp32 device lattice grid [nz, ny, nx] (it need not be a density): every cell is cut
+ * into the six tetrahedra (c, c + e_p0, c + e_p0 + e_p1, c + (1,1,1)), p the permutations of the axes in lexicographic order; 16
+ * sign cases, none ambiguous, face diagonals of neighbouring cells coincide, so a surface that stays off the box is a closed,
+ * consistently oriented 2-manifold.  Where it reaches the box it is cut open, not capped.
+ *   - a point is inside when grid > threshold (NaN and a value equal to the threshold are outside);
+ *   - one vertex per lattice edge whose ends differ; a point owns the 7 edges to its larger neighbours, slots x, y, xy, z, xz, yz,
+ *     xyz (the order of the far end's flat index); position p_in + t (p_out - p_in), t = (threshold - f_in) / (f_out - f_in) in fp32,
+ *     t = 0.5 when that is not finite; vertices ordered by (owning point, slot) = sorted by (smaller end, larger end);
+ *   - faces int32 [F, 3] ordered by (cell, tetrahedron, triangle), wound so that the normal points from inside to outside; the winding
+ *     comes from the sign case and the tetrahedron (that of the triangle through the edge midpoints), never from positions, so a
+ *     triangle that collapses because a lattice value equals the threshold keeps a defined winding and is kept;
+ *   - normals [V, 3]: -grad f normalised; the gradient by central differences at the two ends of the edge (one-sided on the faces of
+ *     the box), interpolated with the same t; (0, 0, 0) where it is zero or not finite;
+ *   - vertex_edges int64 [V, 2]: flat indices of the (inside, outside) ends of each vertex's edge.
+ * Both orders come from exclusive scans, not atomics: two runs give identical bytes.
+ * mipnerf_isosurface_count classifies and scans into `workspace` (mipnerf_isosurface_workspace_bytes, 16-byte aligned), SYNCHRONISES
+ * the stream and returns V and F through host pointers -- it cannot be captured into a hipGraph.  mipnerf_isosurface_emit fills the
+ * caller's buffers (any may be NULL) from the same workspace, grid, dims and threshold; it does not synchronise. */
+size_t mipnerf_isosurface_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int mipnerf_isosurface_count(const int32_t* dims_host, const float* grid, float threshold, void* workspace, size_t workspace_bytes,
+                             int64_t* num_vertices_host, int64_t* num_faces_host, void* stream);
+int mipnerf_isosurface_emit(const int32_t* dims_host, const float* lo_host, const float* hi_host, const float* grid, float threshold,
+                            const void* workspace, size_t workspace_bytes, float* vertices, float* normals, int32_t* faces,
+                            int64_t* vertex_edges, void* stream);
+
 /* ---- training side ---------------------------------------------------------------------- */
 /* activations (mip_nerf.py:236-238): raw [M,4] = (raw_rgb, raw_density) -> rgb_sigma [M,4];
  * density_randn [M] (NULL = none): raw_density + density_noise * density_randn first (mip_nerf.py:232-233). */

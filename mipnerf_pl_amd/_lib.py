@@ -82,6 +82,11 @@ SIGNATURES = {
     "mipnerf_image_to_u8": (C.c_int, [_I64, _P, _P, _P]),
     "mipnerf_box_pyramid": (C.c_int, [_I32, _I32, _I32, _I32, _P, _P, _P, _I64, _I32, _P, _P]),
     "mipnerf_area_downscale": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
+    "mipnerf_density_grid_workspace_bytes": (_SZ, [_P, _I64, C.c_int]),
+    "mipnerf_density_grid": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _F, C.c_int, _P, _P, _SZ, _P]),
+    "mipnerf_isosurface_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "mipnerf_isosurface_count": (C.c_int, [C.POINTER(_I32), _P, _F, _P, _SZ, C.POINTER(_I64), C.POINTER(_I64), _P]),
+    "mipnerf_isosurface_emit": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _F, _P, _SZ, _P, _P, _P, _P, _P]),
     "mipnerf_activate": (C.c_int, [_I64, _P, _F, _F, _P, _F, _P, _P]),
     "mipnerf_volumetric_rendering_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _F, _P, _P]),
     "mipnerf_distloss": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P]),

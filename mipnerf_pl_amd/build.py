@@ -41,6 +41,7 @@ UNITS = [
     ("kernels_vis.hip", ["-ffp-contract=off"]),
     ("kernels_pyramid.hip", ["-ffp-contract=off"]),     # q_rgb * q_a + (1 - q_a) rounds three times, as on the host
     ("kernels_downscale.hip", ["-ffp-contract=off"]),   # float(q) / 255.f stays one rounded division
+    ("kernels_mesh.hip", ["-ffp-contract=off"]),        # lattice means lo + float(i) * h and the shared IPE round as stated in the header
     ("selftest.hip", ["-ffp-contract=off"]),
     ("capi.hip", []),
 ]

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <algorithm>
 #include <vector>
@@ -926,6 +927,115 @@ int mipnerf_area_downscale(int32_t n, int32_t H, int32_t W, int32_t C, int32_t F
     if (rgb_row_offset < 0) return fail(MIPNERF_E_INVALID, "area_downscale: negative row offset");
     if (((uintptr_t)src & 15) || ((uintptr_t)out_rgb & 3)) return fail(MIPNERF_E_INVALID, "area_downscale: src must be 16-byte aligned, out_rgb 4-byte aligned");
     HIP_TRY(mip::launch_area_downscale(n, H, W, C, F, src, out_rgb + 3 * rgb_row_offset, S(stream)));
+    return MIPNERF_OK;
+}
+
+// ---- geometry out of a trained field (kernels_mesh.hip) -----------------------------------------------------------------
+static constexpr size_t kGridViewBytes = 256;                       // one zero view-encoding row [32] of either dtype, 256-aligned
+static inline size_t grid_row_bytes(int precision) { return (size_t)96 * (precision == MIPNERF_PREC_BF16 ? 2 : 4) + 16; }
+
+static int lattice_check(const char* who, const int32_t* dims, const float* lo, const float* hi) {
+    if (!dims || !lo || !hi) return fail(MIPNERF_E_INVALID, "%s: null argument", who);
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 2) return fail(MIPNERF_E_INVALID, "%s: a lattice needs at least 2 points per axis (got %d x %d x %d)", who, dims[0], dims[1], dims[2]);
+        if (!(std::isfinite(lo[a]) && std::isfinite(hi[a]))) return fail(MIPNERF_E_INVALID, "%s: the box is not finite", who);
+    }
+    if (7 * (int64_t)dims[0] * dims[1] * dims[2] >= (1LL << 31))
+        return fail(MIPNERF_E_INVALID, "%s: %d x %d x %d lattice points: indices are 32-bit, 7 nx ny nz must stay below 2^31", who, dims[0], dims[1], dims[2]);
+    return MIPNERF_OK;
+}
+
+size_t mipnerf_density_grid_workspace_bytes(const mipnerf_ctx* c, int64_t chunk_points, int precision) {
+    if (!c || chunk_points < 1 || (precision != MIPNERF_PREC_FP32 && precision != MIPNERF_PREC_BF16)) return 0;
+    return kGridViewBytes + (size_t)chunk_points * grid_row_bytes(precision);
+}
+
+int mipnerf_density_grid(mipnerf_ctx* c, const int32_t* dims, const float* lo, const float* hi, float cov_scale, int precision,
+                         float* sigma, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!c || !sigma || !workspace) return fail(MIPNERF_E_INVALID, "density_grid: null argument");
+    if (int rc = lattice_check("density_grid", dims, lo, hi)) return rc;
+    if (precision != MIPNERF_PREC_FP32 && precision != MIPNERF_PREC_BF16) return fail(MIPNERF_E_INVALID, "density_grid: unknown precision %d", precision);
+    if (!(cov_scale >= 0.0f) || !std::isfinite(cov_scale)) return fail(MIPNERF_E_INVALID, "density_grid: cov_scale must be finite and >= 0");
+    if (c->cfg.unbounded) return fail(MIPNERF_E_UNSUPPORTED, "density_grid: the unbounded-scene model lives in a contracted space; its lattice is not implemented");
+    if (c->cfg.max_deg_point - c->cfg.min_deg_point != 16 || c->cfg.min_deg_point < 0 || c->cfg.max_deg_point > 31)
+        return fail(MIPNERF_E_UNSUPPORTED, "density_grid: the lattice encoder is generated for max_deg_point - min_deg_point == 16");
+    if ((uintptr_t)workspace & 15) return fail(MIPNERF_E_INVALID, "density_grid: the workspace must be 16-byte aligned");
+    const size_t row = grid_row_bytes(precision);
+    if (workspace_bytes < kGridViewBytes + row) return fail(MIPNERF_E_WORKSPACE, "density_grid: the workspace holds no lattice point (see mipnerf_density_grid_workspace_bytes)");
+    const int64_t n = (int64_t)dims[0] * dims[1] * dims[2];
+    int64_t chunk = (int64_t)((workspace_bytes - kGridViewBytes) / row);
+    if (chunk > n) chunk = n;
+    if (chunk > 256) chunk -= chunk % 256;                             // whole MLP tiles except in the last chunk
+    // workspace: zero view row | activated outputs [chunk, 4] | encoding rows [chunk, 96]
+    char* ws = (char*)workspace;
+    float* rgb_sigma = (float*)(ws + kGridViewBytes);
+    void* enc = ws + kGridViewBytes + (size_t)chunk * 16;
+    HIP_TRY(hipMemsetAsync(ws, 0, kGridViewBytes, S(stream)));
+    for (int64_t first = 0; first < n; first += chunk) {
+        const int64_t m = n - first < chunk ? n - first : chunk;
+        HIP_TRY(mip::launch_lattice_ipe(dims, lo, hi, first, m, cov_scale, c->cfg.min_deg_point, c->cfg.max_deg_point, enc,
+                                        precision == MIPNERF_PREC_BF16, S(stream)));
+        // num_samples = m: every point of the chunk reads view row 0
+        if (int rc = mipnerf_mlp_forward(c, m, (int32_t)m, enc, ws, precision, rgb_sigma, nullptr, stream)) return rc;
+        HIP_TRY(mip::launch_store_sigma(m, rgb_sigma, sigma + first, S(stream)));
+    }
+    return MIPNERF_OK;
+}
+
+// workspace of the extraction: totals [2] (padded to 256 bytes) | vbase [n] | block_v [nb] | block_f [nb] | mask [n]
+struct IsoWorkspace {
+    unsigned* totals; unsigned* vbase; unsigned* block_v; unsigned* block_f; unsigned char* mask;
+    size_t bytes;
+};
+static IsoWorkspace iso_workspace(void* base, int64_t n) {
+    const size_t nb = ((size_t)mip::iso_num_blocks(n) + 63) / 64 * 64;
+    const size_t np = ((size_t)n + 63) / 64 * 64;
+    char* p = (char*)base;
+    IsoWorkspace w;
+    w.totals = (unsigned*)p;
+    w.vbase = (unsigned*)(p + 256);
+    w.block_v = w.vbase + np;
+    w.block_f = w.block_v + nb;
+    w.mask = (unsigned char*)(w.block_f + nb);
+    w.bytes = 256 + 4 * (np + 2 * nb) + np;
+    return w;
+}
+
+size_t mipnerf_isosurface_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    if (nx < 2 || ny < 2 || nz < 2 || 7 * (int64_t)nx * ny * nz >= (1LL << 31)) return 0;
+    return iso_workspace(nullptr, (int64_t)nx * ny * nz).bytes;
+}
+
+int mipnerf_isosurface_count(const int32_t* dims, const float* grid, float threshold, void* workspace, size_t workspace_bytes,
+                             int64_t* num_vertices_host, int64_t* num_faces_host, void* stream) {
+    const float unit_lo[3] = {0.f, 0.f, 0.f}, unit_hi[3] = {1.f, 1.f, 1.f};
+    if (int rc = lattice_check("isosurface_count", dims, unit_lo, unit_hi)) return rc;
+    if (!grid || !workspace || !num_vertices_host || !num_faces_host) return fail(MIPNERF_E_INVALID, "isosurface_count: null argument");
+    if (std::isnan(threshold)) return fail(MIPNERF_E_INVALID, "isosurface_count: the threshold is NaN");
+    if ((uintptr_t)workspace & 15) return fail(MIPNERF_E_INVALID, "isosurface_count: the workspace must be 16-byte aligned");
+    const IsoWorkspace w = iso_workspace(workspace, (int64_t)dims[0] * dims[1] * dims[2]);
+    if (workspace_bytes < w.bytes) return fail(MIPNERF_E_WORKSPACE, "isosurface_count: workspace too small (%zu < %zu bytes)", workspace_bytes, w.bytes);
+    HIP_TRY(mip::launch_iso_count(dims, grid, threshold, w.mask, w.vbase, w.block_v, w.block_f, w.totals, S(stream)));
+    unsigned totals[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(totals, w.totals, sizeof(totals), hipMemcpyDeviceToHost, S(stream)));
+    HIP_TRY(hipStreamSynchronize(S(stream)));
+    *num_vertices_host = (int64_t)totals[0];
+    *num_faces_host = (int64_t)totals[1];
+    return MIPNERF_OK;
+}
+
+int mipnerf_isosurface_emit(const int32_t* dims, const float* lo, const float* hi, const float* grid, float threshold,
+                            const void* workspace, size_t workspace_bytes, float* vertices, float* normals, int32_t* faces,
+                            int64_t* vertex_edges, void* stream) {
+    if (int rc = lattice_check("isosurface_emit", dims, lo, hi)) return rc;
+    if (!grid || !workspace) return fail(MIPNERF_E_INVALID, "isosurface_emit: null argument");
+    if ((uintptr_t)workspace & 15) return fail(MIPNERF_E_INVALID, "isosurface_emit: the workspace must be 16-byte aligned");
+    const IsoWorkspace w = iso_workspace(const_cast<void*>(workspace), (int64_t)dims[0] * dims[1] * dims[2]);
+    if (workspace_bytes < w.bytes) return fail(MIPNERF_E_WORKSPACE, "isosurface_emit: workspace too small (%zu < %zu bytes)", workspace_bytes, w.bytes);
+    if (!vertices && !normals && !faces && !vertex_edges) return MIPNERF_OK;
+    static_assert(sizeof(long long) == sizeof(int64_t), "vertex_edges is int64");
+    HIP_TRY(mip::launch_iso_emit(dims, lo, hi, grid, threshold, w.mask, w.vbase, w.block_f, vertices, normals, faces,
+                                 (long long*)vertex_edges, S(stream)));
     return MIPNERF_OK;
 }
 

@@ -248,6 +248,19 @@ hipError_t launch_box_pyramid(int64_t n, int h, int w, int n_levels, const unsig
 // ---- kernels_downscale.hip ----------------------------------------------------------------------
 hipError_t launch_area_downscale(int64_t n, int H, int W, int C, int F, const unsigned char* src, float* out_rgb, hipStream_t st);
 
+// ---- kernels_mesh.hip: lattice encoding in front of the MLP kernels, marching tetrahedra behind them ---------------------
+// encoding rows [count, 6 * (max_deg - min_deg)] of the lattice points first ... first + count - 1 (flat index (k * ny + j) * nx + i)
+hipError_t launch_lattice_ipe(const int dims[3], const float lo[3], const float hi[3], int64_t first, int64_t count, float cov_scale,
+                              int min_deg, int max_deg, void* enc, bool bf16, hipStream_t st);
+hipError_t launch_store_sigma(int64_t count, const float* rgb_sigma, float* sigma, hipStream_t st);
+int64_t iso_num_blocks(int64_t num_points);      // entries of block_v / block_f
+// classify + scans: mask [n] bytes, vbase [n], block_v / block_f [iso_num_blocks(n)], totals [2] = (V, F)
+hipError_t launch_iso_count(const int dims[3], const float* f, float thr, unsigned char* mask, unsigned* vbase, unsigned* block_v,
+                            unsigned* block_f, unsigned* totals, hipStream_t st);
+hipError_t launch_iso_emit(const int dims[3], const float lo[3], const float hi[3], const float* f, float thr, const unsigned char* mask,
+                           const unsigned* vbase, const unsigned* block_f, float* vertices, float* normals, int* faces,
+                           long long* vertex_edges, hipStream_t st);
+
 // ---- selftest.hip -------------------------------------------------------------------------------
 // returns 0 if the MFMA fragment layouts and the LDS-DMA path behave as the kernels assume;
 // otherwise a bit mask (1: bf16 32x32x16 layout, 2: f32 32x32x2 layout, 4: global_load_lds)

@@ -508,3 +508,103 @@ def integrated_pos_enc_360(means_covs, min_deg=0, max_deg=1, contracted=True, pr
     L.check(L.lib().mipnerf_gauss_360(M, min_deg, max_deg, int(bool(contracted)), _ptr(means), _ptr(covs), _ptr(enc), precision,
                                       None, None, _stream()), "integrated_pos_enc_360")
     return enc
+
+
+# ---- geometry out of a trained field (csrc/kernels_mesh.hip) -------------------------------------------------------------
+def _lattice_args(name, dims, lo, hi):
+    import ctypes as C
+    dims = [int(d) for d in (dims if hasattr(dims, "__len__") else (dims,) * 3)]
+    lo = [float(v) for v in (lo if hasattr(lo, "__len__") else (lo,) * 3)]
+    hi = [float(v) for v in (hi if hasattr(hi, "__len__") else (hi,) * 3)]
+    if len(dims) != 3 or len(lo) != 3 or len(hi) != 3:
+        raise ValueError(f"{name}: dims, lo and hi have three entries, in (x, y, z) order")
+    return dims, (C.c_int32 * 3)(*dims), (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
+
+
+def _field_mlp(mlp_or_model, name):
+    """The MLP of a system / MipNerf / MLP; the unbounded-scene model is refused (its field lives in a contracted space)."""
+    m = getattr(mlp_or_model, "mip_nerf", mlp_or_model)
+    mlp = getattr(m, "mlp", m)
+    if getattr(m, "unbounded", False) or getattr(mlp, "_cfg_extra", {}).get("unbounded", 0):
+        raise NotImplementedError(f"{name}: unbounded=True models are not supported (meshing a contracted space is a different question)")
+    if not hasattr(mlp, "native"):
+        raise TypeError(f"{name}: expected a MipNeRFSystem, MipNerf or MLP, got {type(mlp_or_model).__name__}")
+    return mlp
+
+
+def density_grid(mlp_or_model, dims, lo, hi, cov_scale=1.0, precision=None, chunk=None):
+    """Activated density of the field on a lattice of dims = (nx, ny, nz) Gaussians over the box lo .. hi: `sigma` [nz, ny, nx] fp32.
+    Point (i, j, k) has the mean lo + float32(i) * h, h = (hi - lo) / float32(n - 1), and the diagonal covariance cov_scale * h * h / 12
+    (cov_scale = 0: a point query); the view branch runs on a zero view encoding.  `precision`: L.PREC_FP32 / L.PREC_BF16 or 'fp32' /
+    'bf16' (default: the model's).  `chunk`: lattice points per MLP launch (default 2^18); the result does not depend on it."""
+    mlp = _field_mlp(mlp_or_model, "density_grid")
+    dev = next(mlp.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError(f"density_grid: the MI355X-native path needs the model on a HIP device (it is on {dev}); there is no CPU fallback")
+    prec = mlp.precision if precision is None else {"fp32": L.PREC_FP32, "bf16": L.PREC_BF16}.get(precision, precision)
+    dims, cdims, clo, chi = _lattice_args("density_grid", dims, lo, hi)
+    n = dims[0] * dims[1] * dims[2]
+    chunk = min(max(n, 1), 1 << 18) if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("density_grid: chunk must be positive")
+    with torch.cuda.device(dev):
+        ctx = mlp.native(dev)
+        need = int(L.lib().mipnerf_density_grid_workspace_bytes(ctx.handle, chunk, prec))
+        if need == 0:
+            raise ValueError(f"density_grid: unknown precision {precision!r}")
+        ws = ctx.scratch("density_grid", need)
+        sigma = torch.empty(max(dims[2], 0), max(dims[1], 0), max(dims[0], 0), device=dev, dtype=torch.float32)
+        L.check(L.lib().mipnerf_density_grid(ctx.handle, cdims, clo, chi, float(cov_scale), prec, _ptr(sigma), _ptr(ws), need, _stream()),
+                "density_grid")
+    return sigma
+
+
+def field_at(mlp_or_model, points, variances, viewdirs, precision=None):
+    """The field at given Gaussians: points [M, 3], variances [M] (one isotropic variance per point) or [M, 3], unit view directions
+    [M, 3] -> rgb_sigma [M, 4] = (r, g, b, sigma) activated.  mipnerf_integrated_pos_enc + mipnerf_pos_enc + mipnerf_mlp_forward with one
+    sample per ray: the calls the renderer's per-stage path makes, no second path."""
+    mlp = _field_mlp(mlp_or_model, "field_at")
+    prec = mlp.precision if precision is None else {"fp32": L.PREC_FP32, "bf16": L.PREC_BF16}.get(precision, precision)
+    points = _f32c(points, "points").reshape(-1, 3)
+    M = points.shape[0]
+    if M == 0:
+        return torch.empty(0, 4, device=points.device, dtype=torch.float32)
+    var = _f32c(variances, "variances")
+    var = (var.reshape(M, 1).expand(M, 3) if var.numel() == M else var.reshape(M, 3)).contiguous()
+    e = mlp._cfg_extra
+    min_deg = e.get("min_deg_point", 0)
+    max_deg = e.get("max_deg_point", min_deg + mlp.arch["xyz_dim"] // 6)
+    with torch.no_grad():
+        enc = integrated_pos_enc((points, var), min_deg, max_deg, precision=prec).reshape(M, 1, -1)
+        venc = None
+        if e.get("use_viewdirs", 1):
+            venc = pos_enc(_f32c(viewdirs, "viewdirs").reshape(M, 3), 0, (mlp.arch["view_dim"] - 3) // 6, precision=prec)
+        return mlp(enc, venc, precision=prec, return_activated=True)[2].reshape(M, 4)
+
+
+def isosurface(grid, threshold, lo, hi, return_edges=False):
+    """Marching tetrahedra (Kuhn split) of any fp32 device lattice `grid` [nz, ny, nx] over the box lo .. hi ((x, y, z) order): inside is
+    grid > threshold.  Returns (vertices [V, 3] fp32, normals [V, 3] fp32, faces [F, 3] int32[, vertex_edges [V, 2] int64]) on the device;
+    the rules and the orders are those of include/mipnerf_hip.h (mipnerf_isosurface_count / _emit).  The vertex count has to reach the
+    host, so the call synchronises the stream and cannot be captured into a graph."""
+    import ctypes as C
+    g = _f32c(grid, "grid")
+    if g.dim() != 3:
+        raise ValueError(f"isosurface: expected a [nz, ny, nx] lattice, got {tuple(g.shape)}")
+    dims, cdims, clo, chi = _lattice_args("isosurface", (g.shape[2], g.shape[1], g.shape[0]), lo, hi)
+    dev = g.device
+    with torch.cuda.device(dev):
+        need = int(L.lib().mipnerf_isosurface_workspace_bytes(*dims))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        nv, nf = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().mipnerf_isosurface_count(cdims, _ptr(g), float(threshold), _ptr(ws), need, C.byref(nv), C.byref(nf), _stream()),
+                "isosurface_count")
+        V, F = int(nv.value), int(nf.value)
+        vertices = torch.empty(V, 3, device=dev, dtype=torch.float32)
+        normals = torch.empty(V, 3, device=dev, dtype=torch.float32)
+        faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
+        edges = torch.empty(V, 2, device=dev, dtype=torch.int64) if return_edges else None
+        if V:
+            L.check(L.lib().mipnerf_isosurface_emit(cdims, clo, chi, _ptr(g), float(threshold), _ptr(ws), need, _ptr(vertices), _ptr(normals),
+                                                    _ptr(faces) if F else None, _ptr(edges), _stream()), "isosurface_emit")
+    return (vertices, normals, faces, edges) if return_edges else (vertices, normals, faces)
