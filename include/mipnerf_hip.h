@@ -348,6 +348,46 @@ int mipnerf_isosurface_emit(const int32_t* dims_host, const float* lo_host, cons
                             const void* workspace, size_t workspace_bytes, float* vertices, float* normals, int32_t* faces,
                             int64_t* vertex_edges, void* stream);
 
+/* ---- empty-space skipping for whole frames: occupancy bits of any lattice, ray culling, compaction (ABI 6 grows; nothing above changes) ----
+ * The conventions are those of the lattice above: dims = (nx, ny, nz) points over lo .. hi in (x, y, z) order, h = (hi - lo) /
+ * float(n - 1) per axis in fp32.  There are (nx - 1) (ny - 1) (nz - 1) CELLS; cell (i, j, k) spans lo + i h .. lo + (i + 1) h.
+ *   - cell (i, j, k) is raw-occupied iff any of its 8 corner values grid[k + dz][j + dy][i + dx] is > threshold or is NaN;
+ *   - a cell is occupied iff any raw-occupied cell lies within Chebyshev distance `dilate` (>= 0) of it;
+ *   - storage is bit-packed along x: uint32 bits [nz - 1, ny - 1, ceil((nx - 1) / 32)]; cell i is bit i & 31 of word i >> 5; padding bits
+ *     are 0.  mipnerf_occupancy_words is that word count (0 for dims no lattice may have).
+ * mipnerf_occupancy_build: one lane per cell, a wave's ballot is two words; dilation is three separable passes on the packed words
+ * (`scratch`: as many words again, needed only when dilate > 0).  No atomics: two runs give the same bytes.  Does not allocate or
+ * synchronise (graph-capturable).
+ * mipnerf_ray_occupancy: live [num_rays] bytes (1 / 0).  Per ray the coarse level's deterministic fence posts t_0 .. t_N (those of
+ * mipnerf_sample_along_rays with t_rand = NULL: near + (far - near) * linspace(0, 1, N + 1)[i], or linear in disparity); frustum i has
+ * the end points p0 = o + t_i d and p1 = o + t_{i+1} d, the half-width rho = cone_scale * radii * t_{i+1}, per axis the bounding
+ * interval [min(p0, p1) - rho, max(p0, p1) + rho] and the cell range floor((x - lo) / h) of its two ends, inclusive at both ends.  The
+ * part of a range that falls outside the grid counts as occupied when outside_occupied != 0, otherwise it is clipped away.  A ray is
+ * live iff some frustum's cell range contains an occupied bit (a ray with a NaN coordinate is live).  Fine samples lie inside
+ * [t_0, t_N], so the coarse frusta cover them.  hi > lo on every axis, 1 <= num_samples <= MIPNERF_MAX_SAMPLES.  viewdirs and lossmult
+ * of `rays` are not read.  Does not allocate or synchronise.
+ * mipnerf_compact_rays: an exclusive scan of `live` (sums per 1024 rays, one single-workgroup scan, per-ray bases; no atomics), then
+ * the live rays gathered IN THEIR ORIGINAL ORDER into out_rays (a NULL field is skipped) and out_index[j] = the source ray of compact
+ * slot j.  The live count has to reach the host: the call makes one 8-byte read-back and SYNCHRONISES the stream -- it cannot be
+ * captured into a hipGraph.  workspace: mipnerf_compact_rays_workspace_bytes(num_rays), 16-byte aligned; live 4-byte aligned;
+ * num_rays < 2^31; num_rays = 0 returns count 0 without a launch.
+ * mipnerf_scatter_frame: writes every pixel of every level once (comp_rgb, distance, acc of `full`; weights / t_samples are not
+ * touched): pixel index[j], j < count, takes slot j of `compact`; a pixel with live = 0 takes what volumetric_rendering (mip.py:395-400)
+ * yields for all-zero weights: rgb = 1 with white_bkgd != 0 else 0, acc = 0, distance = near[pixel].  1 <= num_levels <= 4.  Does not
+ * allocate or synchronise. */
+int64_t mipnerf_occupancy_words(int32_t nx, int32_t ny, int32_t nz);
+int mipnerf_occupancy_build(const int32_t* dims_host, const float* grid, float threshold, int32_t dilate, uint32_t* bits,
+                            uint32_t* scratch, void* stream);
+int mipnerf_ray_occupancy(const int32_t* dims_host, const float* lo_host, const float* hi_host, const uint32_t* bits, int64_t num_rays,
+                          int32_t num_samples, const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale,
+                          uint8_t* live, void* stream);
+size_t mipnerf_compact_rays_workspace_bytes(int64_t num_rays);
+int mipnerf_compact_rays(int64_t num_rays, const uint8_t* live, const mipnerf_rays* rays, const mipnerf_rays_out* out_rays,
+                         int32_t* out_index, void* workspace, size_t workspace_bytes, int64_t* count_host, void* stream);
+int mipnerf_scatter_frame(int64_t num_rays, int64_t count, int32_t num_levels, const int32_t* index, const uint8_t* live,
+                          const float* near, int32_t white_bkgd, const mipnerf_level_out* compact, const mipnerf_level_out* full,
+                          void* stream);
+
 /* ---- training side ---------------------------------------------------------------------- */
 /* activations (mip_nerf.py:236-238): raw [M,4] = (raw_rgb, raw_density) -> rgb_sigma [M,4];
  * density_randn [M] (NULL = none): raw_density + density_noise * density_randn first (mip_nerf.py:232-233). */

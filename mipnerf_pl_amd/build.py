@@ -42,6 +42,7 @@ UNITS = [
     ("kernels_pyramid.hip", ["-ffp-contract=off"]),     # q_rgb * q_a + (1 - q_a) rounds three times, as on the host
     ("kernels_downscale.hip", ["-ffp-contract=off"]),   # float(q) / 255.f stays one rounded division
     ("kernels_mesh.hip", ["-ffp-contract=off"]),        # lattice means lo + float(i) * h and the shared IPE round as stated in the header
+    ("kernels_occupancy.hip", ["-ffp-contract=off"]),   # frustum end points o + t * d and floor((x - lo) / h) round as stated in the header
     ("selftest.hip", ["-ffp-contract=off"]),
     ("capi.hip", []),
 ]

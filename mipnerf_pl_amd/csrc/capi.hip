@@ -1039,6 +1039,90 @@ int mipnerf_isosurface_emit(const int32_t* dims, const float* lo, const float* h
     return MIPNERF_OK;
 }
 
+// ---- empty-space skipping for whole frames (kernels_occupancy.hip) -------------------------------------------------------
+int64_t mipnerf_occupancy_words(int32_t nx, int32_t ny, int32_t nz) {
+    if (nx < 2 || ny < 2 || nz < 2 || 7 * (int64_t)nx * ny * nz >= (1LL << 31)) return 0;
+    return (int64_t)(ny - 1) * (nz - 1) * ((nx - 1 + 31) / 32);
+}
+
+int mipnerf_occupancy_build(const int32_t* dims, const float* grid, float threshold, int32_t dilate, uint32_t* bits, uint32_t* scratch,
+                            void* stream) {
+    const float unit_lo[3] = {0.f, 0.f, 0.f}, unit_hi[3] = {1.f, 1.f, 1.f};
+    if (int rc = lattice_check("occupancy_build", dims, unit_lo, unit_hi)) return rc;
+    if (!grid || !bits) return fail(MIPNERF_E_INVALID, "occupancy_build: null argument");
+    if (std::isnan(threshold)) return fail(MIPNERF_E_INVALID, "occupancy_build: the threshold is NaN");
+    if (dilate < 0) return fail(MIPNERF_E_INVALID, "occupancy_build: dilate must be >= 0 (got %d)", dilate);
+    if (dilate > 0 && !scratch) return fail(MIPNERF_E_INVALID, "occupancy_build: dilate > 0 needs the scratch words");
+    if (dilate > 0 && scratch == bits) return fail(MIPNERF_E_INVALID, "occupancy_build: bits and scratch must not be the same buffer");
+    HIP_TRY(mip::launch_occupancy_build(dims, grid, threshold, dilate, bits, scratch, S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_ray_occupancy(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
+                          const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale, uint8_t* live,
+                          void* stream) {
+    if (int rc = lattice_check("ray_occupancy", dims, lo, hi)) return rc;
+    for (int a = 0; a < 3; ++a)
+        if (!(hi[a] > lo[a])) return fail(MIPNERF_E_INVALID, "ray_occupancy: the box needs hi > lo on every axis");
+    if (B < 0 || B >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "ray_occupancy: bad ray count");
+    if (N < 1 || N > MIPNERF_MAX_SAMPLES) return fail(MIPNERF_E_INVALID, "ray_occupancy: num_samples must be in [1, %d]", MIPNERF_MAX_SAMPLES);
+    if (!(cone_scale >= 0.0f) || !std::isfinite(cone_scale)) return fail(MIPNERF_E_INVALID, "ray_occupancy: cone_scale must be finite and >= 0");
+    if (B == 0) return MIPNERF_OK;
+    if (!bits || !rays || !rays->origins || !rays->directions || !rays->radii || !rays->near || !rays->far || !live)
+        return fail(MIPNERF_E_INVALID, "ray_occupancy: null argument");
+    HIP_TRY(mip::launch_ray_occupancy(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
+                                      disparity != 0, outside_occupied != 0, cone_scale, live, S(stream)));
+    return MIPNERF_OK;
+}
+
+// workspace of the compaction: the live count (8 bytes, padded to 256) | block_sum [compact_num_blocks(n)]
+size_t mipnerf_compact_rays_workspace_bytes(int64_t n) {
+    if (n < 0 || n >= (1LL << 31)) return 0;
+    return 256 + 4 * (((size_t)mip::compact_num_blocks(n) + 63) / 64 * 64);
+}
+
+int mipnerf_compact_rays(int64_t n, const uint8_t* live, const mipnerf_rays* rays, const mipnerf_rays_out* out_rays, int32_t* out_index,
+                         void* workspace, size_t workspace_bytes, int64_t* count_host, void* stream) {
+    if (n < 0 || n >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "compact_rays: bad ray count");
+    if (!count_host) return fail(MIPNERF_E_INVALID, "compact_rays: null argument");
+    *count_host = 0;
+    if (n == 0) return MIPNERF_OK;
+    if (!live || !rays || !out_rays || !out_index || !workspace) return fail(MIPNERF_E_INVALID, "compact_rays: null argument");
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)live & 3)) return fail(MIPNERF_E_INVALID, "compact_rays: the workspace must be 16-byte aligned, live 4-byte aligned");
+    const size_t need = mipnerf_compact_rays_workspace_bytes(n);
+    if (workspace_bytes < need) return fail(MIPNERF_E_WORKSPACE, "compact_rays: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    const float* in[7] = {rays->origins, rays->directions, rays->viewdirs, rays->radii, rays->lossmult, rays->near, rays->far};
+    float* out[7] = {out_rays->origins, out_rays->directions, out_rays->viewdirs, out_rays->radii, out_rays->lossmult, out_rays->near, out_rays->far};
+    for (int q = 0; q < 7; ++q)
+        if (out[q] && !in[q]) return fail(MIPNERF_E_INVALID, "compact_rays: an output field has no input");
+    unsigned long long* total = (unsigned long long*)workspace;
+    HIP_TRY(mip::launch_compact_rays(n, live, in, out, out_index, (unsigned*)((char*)workspace + 256), total, S(stream)));
+    unsigned long long host_total = 0;
+    HIP_TRY(hipMemcpyAsync(&host_total, total, sizeof(host_total), hipMemcpyDeviceToHost, S(stream)));
+    HIP_TRY(hipStreamSynchronize(S(stream)));
+    *count_host = (int64_t)host_total;
+    return MIPNERF_OK;
+}
+
+int mipnerf_scatter_frame(int64_t n, int64_t count, int32_t num_levels, const int32_t* index, const uint8_t* live, const float* nearp,
+                          int32_t white_bkgd, const mipnerf_level_out* compact, const mipnerf_level_out* full, void* stream) {
+    if (n < 0 || n >= (1LL << 31) || count < 0 || count > n) return fail(MIPNERF_E_INVALID, "scatter_frame: bad ray count");
+    if (num_levels < 1 || num_levels > mip::kMaxScatterLevels) return fail(MIPNERF_E_INVALID, "scatter_frame: num_levels must be in [1, %d]", mip::kMaxScatterLevels);
+    if (n == 0) return MIPNERF_OK;
+    if (!live || !nearp || !full || (count > 0 && (!index || !compact))) return fail(MIPNERF_E_INVALID, "scatter_frame: null argument");
+    const float* c_rgb[mip::kMaxScatterLevels]; const float* c_dist[mip::kMaxScatterLevels]; const float* c_acc[mip::kMaxScatterLevels];
+    float* f_rgb[mip::kMaxScatterLevels]; float* f_dist[mip::kMaxScatterLevels]; float* f_acc[mip::kMaxScatterLevels];
+    for (int l = 0; l < num_levels; ++l) {
+        f_rgb[l] = full[l].comp_rgb; f_dist[l] = full[l].distance; f_acc[l] = full[l].acc;
+        c_rgb[l] = count ? compact[l].comp_rgb : nullptr; c_dist[l] = count ? compact[l].distance : nullptr; c_acc[l] = count ? compact[l].acc : nullptr;
+        if (!f_rgb[l] || !f_dist[l] || !f_acc[l] || (count > 0 && (!c_rgb[l] || !c_dist[l] || !c_acc[l])))
+            return fail(MIPNERF_E_INVALID, "scatter_frame: level %d has a null comp_rgb, distance or acc", l);
+    }
+    HIP_TRY(mip::launch_scatter_frame(n, count, num_levels, index, live, nearp, white_bkgd, c_rgb, c_dist, c_acc, f_rgb, f_dist, f_acc,
+                                      S(stream)));
+    return MIPNERF_OK;
+}
+
 // ---- training-side entry points ------------------------------------------------------------------
 int mipnerf_activate(int64_t M, const float* raw, float rgb_padding, float density_bias, const float* density_randn,
                      float density_noise, float* rgb_sigma, void* stream) {

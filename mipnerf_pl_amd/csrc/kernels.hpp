@@ -261,6 +261,22 @@ hipError_t launch_iso_emit(const int dims[3], const float lo[3], const float hi[
                            const unsigned* vbase, const unsigned* block_f, float* vertices, float* normals, int* faces,
                            long long* vertex_edges, hipStream_t st);
 
+// ---- kernels_occupancy.hip: occupancy bits of a lattice, ray classification, compaction and scatter of a frame -----------
+// bits / scratch: (ny - 1) * (nz - 1) * ceil((nx - 1) / 32) words each; scratch is touched only when dilate > 0
+hipError_t launch_occupancy_build(const int dims[3], const float* f, float thr, int dilate, unsigned* bits, unsigned* scratch,
+                                  hipStream_t st);
+hipError_t launch_ray_occupancy(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
+                                const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
+                                int disparity, int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st);
+int64_t compact_num_blocks(int64_t n);           // entries of block_sum
+// in / out: the 7 ray fields in the order of mipnerf_rays (an out entry may be NULL: that field is not gathered)
+hipError_t launch_compact_rays(int64_t n, const unsigned char* live, const float* const in[7], float* const out[7], int* out_index,
+                               unsigned* block_sum, unsigned long long* total, hipStream_t st);
+constexpr int kMaxScatterLevels = 4;
+hipError_t launch_scatter_frame(int64_t n, int64_t count, int num_levels, const int* index, const unsigned char* live, const float* nearp,
+                                int white_bkgd, const float* const c_rgb[], const float* const c_dist[], const float* const c_acc[],
+                                float* const f_rgb[], float* const f_dist[], float* const f_acc[], hipStream_t st);
+
 // ---- selftest.hip -------------------------------------------------------------------------------
 // returns 0 if the MFMA fragment layouts and the LDS-DMA path behave as the kernels assume;
 // otherwise a bit mask (1: bf16 32x32x16 layout, 2: f32 32x32x2 layout, 4: global_load_lds)

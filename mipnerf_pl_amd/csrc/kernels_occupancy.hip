@@ -1,0 +1,413 @@
+// Empty-space skipping for whole frames (gfx950, wave64), compiled with -ffp-contract=off:
+//   k_occ_raw / k_occ_dilate_*   occupancy bits of any fp32 lattice [nz, ny, nx]: one lane per cell, the wave's __ballot is two packed
+//                                words; dilation as three separable passes on the packed words (shifts and ORs along x, word ORs along
+//                                y and z);
+//   k_ray_occupancy              one wavefront per ray: lanes take the coarse level's frusta lane, lane + 64, ..., test the cell range of
+//                                each frustum's bounding box with word masks, the wave reduces with a ballot;
+//   k_compact_* / k_scatter_frame  exclusive scan of the live bytes (sums per 1024 rays + one single-workgroup scan + per-ray bases, the
+//                                arrangement of kernels_mesh.hip), the live rays gathered in their order, and the way back: every pixel of
+//                                every level written once.
+// No atomics anywhere: two runs give the same bytes.  Every result leaves through ordinary vector stores.
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+#include "raymath.hpp"
+
+namespace mip {
+
+static inline unsigned occ_grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
+
+// cells (nx - 1, ny - 1, nz - 1), words per x row of cells
+struct OccGrid {
+    int cx, cy, cz;
+    int wx;           // ceil(cx / 32)
+};
+
+static OccGrid occ_grid(const int dims[3]) {
+    OccGrid g;
+    g.cx = dims[0] - 1; g.cy = dims[1] - 1; g.cz = dims[2] - 1;
+    g.wx = (g.cx + 31) / 32;
+    return g;
+}
+
+// ------------------------------------------------------------------------------------------
+// raw occupancy: cell (i, j, k) is occupied iff any of its 8 corner values is > thr or NaN
+// ------------------------------------------------------------------------------------------
+// One wave per 64 consecutive cells of an x row; 4 waves per workgroup.  Lanes past the row vote 0, which are the padding bits.
+__global__ void __launch_bounds__(256)
+k_occ_raw(OccGrid g, int nx, int ny, const float* __restrict__ f, float thr, unsigned* __restrict__ bits) {
+    const int lane = threadIdx.x & 63;
+    const int pairs = (g.wx + 1) >> 1;                                   // waves per row
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int64_t rows = (int64_t)g.cy * g.cz;
+    if (wave >= rows * pairs) return;                                    // wave-uniform
+    const int row = (int)(wave / pairs), wp = (int)(wave - (int64_t)row * pairs);
+    const int k = row / g.cy, j = row - k * g.cy;
+    const int i = wp * 64 + lane;
+    bool occ = false;
+    if (i < g.cx) {
+        const float* p = f + ((int64_t)k * ny + j) * nx + i;
+        const int64_t sy = nx, sz = (int64_t)nx * ny;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const float v = p[(c & 1) + ((c >> 1) & 1) * sy + ((c >> 2) & 1) * sz];
+            occ = occ || !(v <= thr);                                    // > thr or NaN
+        }
+    }
+    const unsigned long long m = __ballot(occ);
+    unsigned* out = bits + (int64_t)row * g.wx + 2 * wp;
+    if (lane == 0) out[0] = (unsigned)m;
+    if (lane == 1 && 2 * wp + 1 < g.wx) out[1] = (unsigned)(m >> 32);
+}
+
+// bit i of the row shifted towards higher cells by s >= 1: word w of (row << s)
+__device__ __forceinline__ unsigned occ_row_shl(const unsigned* __restrict__ row, int wx, int w, int s) {
+    const int q = s >> 5, r = s & 31;
+    const int a = w - q;
+    unsigned v = a >= 0 ? row[a] << r : 0u;
+    if (r && a - 1 >= 0) v |= row[a - 1] >> (32 - r);
+    return v;
+}
+__device__ __forceinline__ unsigned occ_row_shr(const unsigned* __restrict__ row, int wx, int w, int s) {
+    const int q = s >> 5, r = s & 31;
+    const int a = w + q;
+    unsigned v = a < wx ? row[a] >> r : 0u;
+    if (r && a + 1 < wx) v |= row[a + 1] << (32 - r);
+    return v;
+}
+
+// x pass: one thread per word; the padding bits of a row's last word stay 0
+__global__ void __launch_bounds__(256)
+k_occ_dilate_x(OccGrid g, int d, const unsigned* __restrict__ in, unsigned* __restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = (int64_t)g.cy * g.cz * g.wx;
+    if (idx >= total) return;
+    const int64_t rowi = idx / g.wx;
+    const int w = (int)(idx - rowi * g.wx);
+    const unsigned* row = in + rowi * g.wx;
+    unsigned v = row[w];
+    const int reach = d < g.cx ? d : g.cx;                               // a shift by the row's length or more brings nothing in
+    for (int s = 1; s <= reach; ++s) v |= occ_row_shl(row, g.wx, w, s) | occ_row_shr(row, g.wx, w, s);
+    const int last = g.cx - 32 * w;                                      // cells of this word
+    if (last < 32) v &= (1u << last) - 1u;
+    out[idx] = v;
+}
+
+// y (axis 1) and z (axis 2) passes: word ORs over the neighbours within d along the axis
+__global__ void __launch_bounds__(256)
+k_occ_dilate_axis(OccGrid g, int axis, int d, const unsigned* __restrict__ in, unsigned* __restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = (int64_t)g.cy * g.cz * g.wx;
+    if (idx >= total) return;
+    const int64_t rowi = idx / g.wx;
+    const int k = (int)(rowi / g.cy), j = (int)(rowi - (int64_t)k * g.cy);
+    const int pos = axis == 1 ? j : k, n = axis == 1 ? g.cy : g.cz;
+    const int64_t stride = axis == 1 ? (int64_t)g.wx : (int64_t)g.wx * g.cy;
+    const int a = pos - d > 0 ? pos - d : 0, b = pos + d < n - 1 ? pos + d : n - 1;
+    unsigned v = 0;
+    for (int q = a; q <= b; ++q) v |= in[idx + (int64_t)(q - pos) * stride];
+    out[idx] = v;
+}
+
+hipError_t launch_occupancy_build(const int dims[3], const float* f, float thr, int dilate, unsigned* bits, unsigned* scratch,
+                                  hipStream_t st) {
+    const OccGrid g = occ_grid(dims);
+    const int64_t waves = (int64_t)g.cy * g.cz * ((g.wx + 1) / 2);
+    const int64_t words = (int64_t)g.cy * g.cz * g.wx;
+    unsigned* raw = dilate > 0 ? scratch : bits;
+    hipLaunchKernelGGL(k_occ_raw, dim3(occ_grid_for(waves, 4)), dim3(256), 0, st, g, dims[0], dims[1], f, thr, raw);
+    if (dilate > 0) {
+        const dim3 grid(occ_grid_for(words, 256)), block(256);
+        hipLaunchKernelGGL(k_occ_dilate_x, grid, block, 0, st, g, dilate, scratch, bits);
+        hipLaunchKernelGGL(k_occ_dilate_axis, grid, block, 0, st, g, 1, dilate, bits, scratch);
+        hipLaunchKernelGGL(k_occ_dilate_axis, grid, block, 0, st, g, 2, dilate, scratch, bits);
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// ray classification
+// ------------------------------------------------------------------------------------------
+struct OccBox {
+    OccGrid g;
+    float lo[3], h[3];
+};
+
+// floor((x - lo) / h) as an int in [-1, cells]: everything below the grid is -1, everything past it (and NaN) is `cells`
+__device__ __forceinline__ int occ_cell(float x, float lo, float h, int cells) {
+    const float c = floorf((x - lo) / h);
+    if (c < 0.0f) return -1;
+    if (!(c < (float)cells)) return cells;
+    return (int)c;
+}
+
+// does the inclusive cell box [c0, c1] (inside the grid) hold an occupied bit?
+__device__ __forceinline__ bool occ_box_test(const OccGrid& g, const unsigned* __restrict__ bits, const int c0[3], const int c1[3]) {
+    const int w0 = c0[0] >> 5, w1 = c1[0] >> 5;
+    const unsigned first = ~0u << (c0[0] & 31);
+    const unsigned last = ~0u >> (31 - (c1[0] & 31));
+    for (int k = c0[2]; k <= c1[2]; ++k) {
+        for (int j = c0[1]; j <= c1[1]; ++j) {
+            const unsigned* row = bits + ((int64_t)k * g.cy + j) * g.wx;
+            for (int w = w0; w <= w1; ++w) {
+                unsigned m = ~0u;
+                if (w == w0) m &= first;
+                if (w == w1) m &= last;
+                if (row[w] & m) return true;
+            }
+        }
+    }
+    return false;
+}
+
+constexpr int kOccRaysPerBlock = 4;
+
+// K = the sample-count bucket of the per-ray kernels (frusta per lane)
+template <int K>
+__global__ void __launch_bounds__(64 * kOccRaysPerBlock)
+k_ray_occupancy(int64_t B, int N, OccBox box, const unsigned* __restrict__ bits, const float* __restrict__ origins,
+                const float* __restrict__ dirs, const float* __restrict__ radii, const float* __restrict__ nearp,
+                const float* __restrict__ farp, int disparity, int outside_occupied, float cone_scale,
+                unsigned char* __restrict__ live) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * kOccRaysPerBlock + (threadIdx.x >> 6);
+    if (b >= B) return;                                                  // wave-uniform
+    const float o[3] = {origins[b * 3], origins[b * 3 + 1], origins[b * 3 + 2]};
+    const float d[3] = {dirs[b * 3], dirs[b * 3 + 1], dirs[b * 3 + 2]};
+    const float nv = nearp[b], fv = farp[b];
+    const float rr = cone_scale * radii[b];
+    const int cells[3] = {box.g.cx, box.g.cy, box.g.cz};
+    bool any = false;
+    for (int kk = 0; kk < K; ++kk) {
+        const int i = lane + 64 * kk;
+        bool hit = false;
+        if (i < N) {
+            const float t0 = level0_t(nv, fv, N, i, disparity != 0), t1 = level0_t(nv, fv, N, i + 1, disparity != 0);
+            const float rho = rr * t1;
+            int c0[3], c1[3];
+            bool outside = false, empty = false;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float p0 = o[a] + t0 * d[a], p1 = o[a] + t1 * d[a];
+                const float xlo = fminf(p0, p1) - rho, xhi = fmaxf(p0, p1) + rho;
+                if (!(xlo <= xhi)) outside = true;                       // a NaN ray is never culled
+                c0[a] = occ_cell(xlo, box.lo[a], box.h[a], cells[a]);
+                c1[a] = occ_cell(xhi, box.lo[a], box.h[a], cells[a]);
+                if (c0[a] < 0 || c1[a] >= cells[a]) outside = true;
+                if (c0[a] < 0) c0[a] = 0;
+                if (c1[a] >= cells[a]) c1[a] = cells[a] - 1;
+                if (c0[a] > c1[a]) empty = true;
+            }
+            if (outside && outside_occupied) hit = true;
+            else if (!empty) hit = occ_box_test(box.g, bits, c0, c1);
+        }
+        if (__ballot(hit) != 0ull) { any = true; break; }                // wave-uniform
+    }
+    if (lane == 0) live[b] = any ? 1 : 0;
+}
+
+hipError_t launch_ray_occupancy(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
+                                const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
+                                int disparity, int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st) {
+    OccBox box;
+    box.g = occ_grid(dims);
+    for (int a = 0; a < 3; ++a) {
+        box.lo[a] = lo[a];
+        box.h[a] = (hi[a] - lo[a]) / (float)(dims[a] - 1);
+    }
+    const dim3 grid(occ_grid_for(B, kOccRaysPerBlock)), block(64 * kOccRaysPerBlock);
+    const int K = (N + 63) / 64;
+#define MIP_OCC(KK)                                                                                                              \
+    hipLaunchKernelGGL((k_ray_occupancy<KK>), grid, block, 0, st, B, N, box, bits, origins, dirs, radii, nearp, farp, disparity, \
+                       outside_occupied, cone_scale, live)
+    if (K <= 1) MIP_OCC(1);                   // the K buckets of the per-ray kernels (kernels_ray.hip)
+    else if (K <= 2) MIP_OCC(2);
+    else if (K <= 4) MIP_OCC(4);
+    else if (K <= 8) MIP_OCC(8);
+    else MIP_OCC(16);
+#undef MIP_OCC
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// compaction: exclusive scan of the live bytes, gather in order
+// ------------------------------------------------------------------------------------------
+constexpr int kCmpBlock = 256;
+constexpr int kCmpPer = 4;              // consecutive rays per thread: one 4-byte load of live bytes
+constexpr int kCmpTile = kCmpBlock * kCmpPer;
+constexpr int kCmpScanBlock = 1024;
+
+// workgroup-wide exclusive scan (WAVES * 64 threads; s_wave holds WAVES words): a becomes its exclusive prefix, total the sum.
+// Fixed order: the same inputs give the same outputs.
+template <int WAVES>
+__device__ __forceinline__ void cmp_block_scan(unsigned& a, unsigned* s_wave, unsigned& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned ia = a;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned oa = __shfl_up(ia, d, 64);
+        if (lane >= d) ia += oa;
+    }
+    __syncthreads();                      // s_wave may still be read by an earlier call
+    if (lane == 63) s_wave[wave] = ia;
+    __syncthreads();
+    unsigned base = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const unsigned x = s_wave[w];
+        if (w < wave) base += x;
+        total += x;
+    }
+    a = base + ia - a;
+}
+
+// the live flags of rays p0 .. p0 + 3 as bits 0 .. 3
+__device__ __forceinline__ unsigned cmp_flags(const unsigned char* __restrict__ live, int64_t p0, int64_t n) {
+    unsigned fl = 0;
+    if (p0 + kCmpPer <= n) {
+        const unsigned packed = *reinterpret_cast<const unsigned*>(live + p0);     // p0 is a multiple of 4, live 4-byte aligned
+#pragma unroll
+        for (int r = 0; r < kCmpPer; ++r) fl |= ((packed >> (8 * r)) & 0xffu) ? 1u << r : 0u;
+    } else {
+        for (int r = 0; p0 + r < n; ++r) fl |= live[p0 + r] ? 1u << r : 0u;
+    }
+    return fl;
+}
+
+__global__ void __launch_bounds__(kCmpBlock)
+k_compact_count(int64_t n, const unsigned char* __restrict__ live, unsigned* __restrict__ block_sum) {
+    __shared__ unsigned s_wave[kCmpBlock / 64];
+    const int64_t p0 = ((int64_t)blockIdx.x * kCmpBlock + threadIdx.x) * kCmpPer;
+    unsigned c = p0 < n ? __popc(cmp_flags(live, p0, n)) : 0u, total;
+    cmp_block_scan<kCmpBlock / 64>(c, s_wave, total);
+    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
+}
+
+// ONE workgroup turns the block sums into exclusive block bases in place, in index order; *total = the live count
+__global__ void __launch_bounds__(kCmpScanBlock)
+k_compact_scan_blocks(int nblocks, unsigned* __restrict__ block_sum, unsigned long long* __restrict__ total) {
+    __shared__ unsigned s_wave[kCmpScanBlock / 64];
+    unsigned run = 0;
+    for (int b0 = 0; b0 < nblocks; b0 += kCmpScanBlock * kCmpPer) {
+        const int b = b0 + threadIdx.x * kCmpPer;
+        unsigned v[kCmpPer], s = 0;
+#pragma unroll
+        for (int r = 0; r < kCmpPer; ++r) {
+            v[r] = b + r < nblocks ? block_sum[b + r] : 0u;
+            s += v[r];
+        }
+        unsigned t;
+        cmp_block_scan<kCmpScanBlock / 64>(s, s_wave, t);
+#pragma unroll
+        for (int r = 0; r < kCmpPer; ++r) {
+            if (b + r < nblocks) block_sum[b + r] = run + s;
+            s += v[r];
+        }
+        run += t;
+    }
+    if (threadIdx.x == 0) *total = (unsigned long long)run;
+}
+
+struct RaySoA {
+    const float* in[7];
+    float* out[7];
+};
+
+// per-ray bases, then the live rays and their source indices at their compact slots
+__global__ void __launch_bounds__(kCmpBlock)
+k_compact_gather(int64_t n, const unsigned char* __restrict__ live, const unsigned* __restrict__ block_base, RaySoA rays,
+                 int* __restrict__ out_index) {
+    __shared__ unsigned s_wave[kCmpBlock / 64];
+    const int64_t p0 = ((int64_t)blockIdx.x * kCmpBlock + threadIdx.x) * kCmpPer;
+    const unsigned fl = p0 < n ? cmp_flags(live, p0, n) : 0u;
+    unsigned c = __popc(fl), total;
+    cmp_block_scan<kCmpBlock / 64>(c, s_wave, total);
+    if (fl == 0) return;
+    int64_t slot = (int64_t)block_base[blockIdx.x] + c;
+#pragma unroll
+    for (int r = 0; r < kCmpPer; ++r) {
+        if (!((fl >> r) & 1u)) continue;
+        const int64_t p = p0 + r;
+        out_index[slot] = (int)p;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {                                    // origins, directions, viewdirs [n, 3]
+            if (rays.out[q] == nullptr) continue;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) rays.out[q][slot * 3 + a] = rays.in[q][p * 3 + a];
+        }
+#pragma unroll
+        for (int q = 3; q < 7; ++q)                                      // radii, lossmult, near, far [n, 1]
+            if (rays.out[q] != nullptr) rays.out[q][slot] = rays.in[q][p];
+        ++slot;
+    }
+}
+
+int64_t compact_num_blocks(int64_t n) { return (n + kCmpTile - 1) / kCmpTile; }
+
+hipError_t launch_compact_rays(int64_t n, const unsigned char* live, const float* const in[7], float* const out[7], int* out_index,
+                               unsigned* block_sum, unsigned long long* total, hipStream_t st) {
+    const int64_t nb = compact_num_blocks(n);
+    RaySoA rays;
+    for (int q = 0; q < 7; ++q) { rays.in[q] = in[q]; rays.out[q] = out[q]; }
+    hipLaunchKernelGGL(k_compact_count, dim3((unsigned)nb), dim3(kCmpBlock), 0, st, n, live, block_sum);
+    hipLaunchKernelGGL(k_compact_scan_blocks, dim3(1), dim3(kCmpScanBlock), 0, st, (int)nb, block_sum, total);
+    hipLaunchKernelGGL(k_compact_gather, dim3((unsigned)nb), dim3(kCmpBlock), 0, st, n, live, block_sum, rays, out_index);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// scatter: every pixel of every level is written once
+// ------------------------------------------------------------------------------------------
+struct ScatterLevels {
+    int n;
+    const float* c_rgb[kMaxScatterLevels];
+    const float* c_dist[kMaxScatterLevels];
+    const float* c_acc[kMaxScatterLevels];
+    float* f_rgb[kMaxScatterLevels];
+    float* f_dist[kMaxScatterLevels];
+    float* f_acc[kMaxScatterLevels];
+};
+
+// Thread p does two independent things: a dead pixel p takes the values of a ray with all-zero weights; compact slot p (p < count)
+// goes to its source pixel.  The two sets of pixels are disjoint and cover the frame.
+__global__ void __launch_bounds__(256)
+k_scatter_frame(int64_t n, int64_t count, const int* __restrict__ index, const unsigned char* __restrict__ live,
+                const float* __restrict__ nearp, float bkgd, ScatterLevels lv) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (!live[p]) {
+        const float nv = nearp[p];
+        for (int l = 0; l < lv.n; ++l) {
+            lv.f_rgb[l][p * 3] = bkgd; lv.f_rgb[l][p * 3 + 1] = bkgd; lv.f_rgb[l][p * 3 + 2] = bkgd;
+            lv.f_dist[l][p] = nv;
+            lv.f_acc[l][p] = 0.0f;
+        }
+    }
+    if (p < count) {
+        const int64_t dst = index[p];
+        for (int l = 0; l < lv.n; ++l) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) lv.f_rgb[l][dst * 3 + a] = lv.c_rgb[l][p * 3 + a];
+            lv.f_dist[l][dst] = lv.c_dist[l][p];
+            lv.f_acc[l][dst] = lv.c_acc[l][p];
+        }
+    }
+}
+
+hipError_t launch_scatter_frame(int64_t n, int64_t count, int num_levels, const int* index, const unsigned char* live, const float* nearp,
+                                int white_bkgd, const float* const c_rgb[], const float* const c_dist[], const float* const c_acc[],
+                                float* const f_rgb[], float* const f_dist[], float* const f_acc[], hipStream_t st) {
+    ScatterLevels lv;
+    lv.n = num_levels;
+    for (int l = 0; l < kMaxScatterLevels; ++l) {
+        const bool on = l < num_levels;
+        lv.c_rgb[l] = on ? c_rgb[l] : nullptr; lv.c_dist[l] = on ? c_dist[l] : nullptr; lv.c_acc[l] = on ? c_acc[l] : nullptr;
+        lv.f_rgb[l] = on ? f_rgb[l] : nullptr; lv.f_dist[l] = on ? f_dist[l] : nullptr; lv.f_acc[l] = on ? f_acc[l] : nullptr;
+    }
+    hipLaunchKernelGGL(k_scatter_frame, dim3(occ_grid_for(n, 256)), dim3(256), 0, st, n, count, index, live, nearp,
+                       white_bkgd ? 1.0f : 0.0f, lv);
+    return hipGetLastError();
+}
+
+}  // namespace mip

@@ -17,12 +17,7 @@ namespace mip {
 // ------------------------------------------------------------------------------------------
 // sample_along_rays, t part (models/mip.py:143-163)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float level0_t(float nearv, float farv, int n_samples, int i, bool disparity) {
-    const float lin = torch_linspace_at(0.0f, 1.0f, n_samples + 1, i);
-    if (disparity) return 1.0f / (1.0f / nearv * (1.0f - lin) + 1.0f / farv * lin);
-    return nearv + (farv - nearv) * lin;
-}
-
+// (level0_t, the deterministic fence post i of the coarse level, lives in raymath.hpp: kernels_occupancy.hip tests the same values)
 __global__ void __launch_bounds__(256)
 k_sample_along_rays(int64_t B, int N, const float* __restrict__ nearp, const float* __restrict__ farp,
                     const float* __restrict__ t_rand, int disparity, float* __restrict__ t_out) {

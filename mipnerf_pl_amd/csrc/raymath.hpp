@@ -118,6 +118,13 @@ MIP_HD float torch_linspace_at(float start, float end, int steps, int i) {
     return (i < steps / 2) ? fmaf(step, (float)i, start) : fmaf(-step, (float)(steps - 1 - i), end);
 }
 
+// sample_along_rays, t part (models/mip.py:143-163): the deterministic fence post i of the coarse level, i in [0, n_samples]
+MIP_HD float level0_t(float nearv, float farv, int n_samples, int i, bool disparity) {
+    const float lin = torch_linspace_at(0.0f, 1.0f, n_samples + 1, i);
+    if (disparity) return 1.0f / (1.0f / nearv * (1.0f - lin) + 1.0f / farv * lin);
+    return nearv + (farv - nearv) * lin;
+}
+
 MIP_HD float nan_to_num(float x) {
     if (x != x) return 0.0f;
     if (x > 3.4028234663852886e38f) return 3.4028234663852886e38f;

@@ -14,7 +14,7 @@ import argparse
 import torch
 
 from .evaluate import evaluate, summarize_results
-from .render_video import add_common_args, flag_given, is_scene360, load_system
+from .render_video import add_common_args, cli_occupancy, flag_given, is_scene360, load_system, refuse_unbounded_cull
 
 
 def build_parser():
@@ -29,6 +29,7 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     system = load_system(args)
+    refuse_unbounded_cull(args, system)
     hp = system.hparams
     exp_name = hp["exp_name"]
     if not args.summa_only:
@@ -44,8 +45,9 @@ def main(argv=None):
             white_bkgd = bool(hp["val.white_bkgd"])
         if scene360 and not flag_given(argv, "--base_size"):
             base_size = (dataset.w, dataset.h)
+        occupancy = cli_occupancy(args, system, (dataset[i][0] for i in range(len(dataset))))
         evaluate(system, dataset, args.out_dir, exp_name, scale=args.scale, save_image=args.save_image, chunk_size=args.chunk_size,
-                 white_bkgd=white_bkgd, use_graph=args.use_graph, base_size=base_size)
+                 white_bkgd=white_bkgd, use_graph=args.use_graph, base_size=base_size, occupancy=occupancy)
     summary = summarize_results(args.out_dir, [exp_name], args.scale)
     print("PSNR | SSIM | Average")
     print(summary)

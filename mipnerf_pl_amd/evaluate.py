@@ -28,11 +28,14 @@ DEFAULT_CHUNK = 12288        # eval.py / render_video.py --chunk_size
 class FrameEvaluator:
     """Everything one image size needs: the frame's `GraphedFrame` (or its eager form) and the device buffers of the image bytes."""
 
-    def __init__(self, model, height, width, chunk_size, white_bkgd, device, use_graph=True):
-        from .model import GraphedFrame
+    def __init__(self, model, height, width, chunk_size, white_bkgd, device, use_graph=True, occupancy=None):
+        from .model import CulledFrame, GraphedFrame
         self.h, self.w = int(height), int(width)
         n = self.h * self.w
-        self.frame = GraphedFrame(model, n, chunk_size, white_bkgd, device, capture=use_graph)
+        if occupancy is None:
+            self.frame = GraphedFrame(model, n, chunk_size, white_bkgd, device, capture=use_graph)
+        else:       # rays that touch no occupied cell are skipped; the live count varies per frame, so the chunks run eagerly
+            self.frame = CulledFrame(model, n, chunk_size, white_bkgd, device, occupancy)
         self.vis_ws = torch.empty(ops.visualize_workspace_floats(n), dtype=torch.float32, device=device)
         self.rgb_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
         self.dist_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
@@ -50,6 +53,49 @@ class FrameEvaluator:
         ops.visualize_map(dist, out=self.dist_u8, workspace=self.vis_ws)
         ops.visualize_map(acc, out=self.acc_u8, workspace=self.vis_ws)
         return self.rgb_u8, self.dist_u8, self.acc_u8
+
+
+def corner_ray_bound(frames):
+    """The largest absolute coordinate of the segment end points o + near d and o + far d over the four corner rays of every frame of
+    `frames` (Rays of [H, W, k] tensors).  The end points are affine in the pixel position, so the corners bound every pixel's."""
+    bound = 0.0
+    for rays in frames:
+        for y in (0, -1):
+            for x in (0, -1):
+                o, d = rays.origins[y, x], rays.directions[y, x]
+                for t in (rays.near[y, x], rays.far[y, x]):
+                    bound = max(bound, float((o + t * d).abs().max()))
+    return bound
+
+
+def cull_box(frames, grid):
+    """The half-width B of the occupancy box [-B, B]^3 of `grid` points per axis that holds every ray segment of `frames` plus one cell:
+    B = B0 + h with h = 2 B / (grid - 1) the box's own cell, i.e. B = B0 (grid - 1) / (grid - 3)."""
+    if grid < 4:
+        raise ValueError("the occupancy grid needs at least 4 points per axis")
+    return corner_ray_bound(frames) * (grid - 1) / (grid - 3)
+
+
+def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bound=None, verbose=True):
+    """`ops.field_occupancy` of the system's field on grid^3 points over [-bound, bound]^3 (default: `cull_box` of `frames`), printing the
+    occupied share of the grid once.  The unbounded-scene model is refused."""
+    if getattr(system.mip_nerf, "unbounded", False):
+        raise NotImplementedError("empty-space culling: unbounded=True models are not supported (their field lives in a contracted space)")
+    if bound is None:
+        if frames is None:
+            raise ValueError("scene_occupancy: give the frames to be rendered or a bound")
+        bound = cull_box(frames, grid)
+    occ = ops.field_occupancy(system, grid=grid, lo=-float(bound), hi=float(bound), threshold=threshold, dilate=dilate)
+    if verbose:
+        print("cull: occupied share of the {0}^3 grid over +-{1:.4f} (threshold {2:g}, dilate {3}): {4:.4f}".format(
+            grid, float(bound), threshold, dilate, occ.occupied_fraction()))
+    return occ
+
+
+def report_live_share(shares):
+    """The closing line of a culled run: the mean share of rays rendered per frame."""
+    if shares:
+        print("cull: mean live share per frame: {:.4f} ({} frames)".format(float(np.mean(shares)), len(shares)))
 
 
 def save_images(rgb_u8, dist_u8, acc_u8, path, idx):
@@ -84,9 +130,11 @@ def write_metrics(folder, psnrs, ssims):
 
 
 def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chunk_size=DEFAULT_CHUNK, white_bkgd=True, use_graph=True,
-             base_size=(800, 800)):
+             base_size=(800, 800), occupancy=None):
     """eval.py:main after the checkpoint is loaded: every image of `dataset` (a test split of `datasets.dataset_dict`) rendered by
-    `system.mip_nerf`, PSNR / SSIM recorded, the images written when `save_image`.  Returns (psnrs, ssims) as lists of floats."""
+    `system.mip_nerf`, PSNR / SSIM recorded, the images written when `save_image`.  Returns (psnrs, ssims) as lists of floats.
+    `occupancy` (an `ops.Occupancy`, e.g. `scene_occupancy`): rays that touch no occupied cell are not rendered (`model.CulledFrame`);
+    None is the full path."""
     if scale not in (1, 4):
         raise ValueError("scale must be 1 or 4 (eval.py --scale)")
     model = system.mip_nerf
@@ -95,15 +143,17 @@ def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chun
     for i in range(scale):
         os.makedirs(os.path.join(folder, str(2 ** i)), exist_ok=True)
     slots = image_slots(dataset.sizes, scale, base_size[0])
-    evaluators, psnrs, ssims = {}, [], []
+    evaluators, psnrs, ssims, shares = {}, [], [], []
     with torch.no_grad():
         for idx in range(len(dataset)):
             rays, gt = dataset[idx]
             h, w = int(gt.shape[0]), int(gt.shape[1])
             ev = evaluators.get((h, w))
             if ev is None:
-                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph)
+                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy)
             rgb, dist, acc = ev.render(rays)
+            if occupancy is not None:
+                shares.append(ev.frame.live_count / float(h * w))
             psnr, ssim = ops.eval_errors(rgb, gt[..., :3])
             psnrs.append(psnr.item())
             ssims.append(ssim.item())
@@ -112,6 +162,7 @@ def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chun
                 save_images(*ev.images(rgb, dist, acc), os.path.join(folder, sub), n)
     write_metrics(folder, psnrs, ssims)
     generate_video(folder)
+    report_live_share(shares)
     return psnrs, ssims
 
 

@@ -813,9 +813,13 @@ class GraphedFrame:
         self.acc = [torch.zeros(self.n, device=device) for _ in range(L_)]
         self.graph = None
 
-    def _run_chunks(self):
+    def _run_chunks(self, count: Optional[int] = None):
+        """`count` (default: all n): only the first `count` rays of the static buffers are rendered (CulledFrame's compacted rays)."""
         m, N = self.model, self.model.num_samples
-        bounds = [(lo, min(self.n, lo + self.chunk)) for lo in range(0, self.n, self.chunk)]
+        total = self.n if count is None else int(count)
+        bounds = [(lo, min(total, lo + self.chunk)) for lo in range(0, total, self.chunk)]
+        if not bounds:
+            return
         lanes = min(self.lanes, len(bounds))
         ctx = m.mlp.native(self.dev)
         need = int(L.lib().mipnerf_workspace_bytes(ctx.handle, min(self.n, self.chunk)))
@@ -879,4 +883,61 @@ class GraphedFrame:
                 self._run_chunks()
         else:
             self.graph.replay()
+        return self.rgb[0], self.rgb[-1], self.dist[-1]
+
+
+class CulledFrame:
+    """Whole-frame rendering that skips the rays a trained field's occupancy grid (`ops.field_occupancy`) proves empty.  The call contract
+    is `GraphedFrame`'s: `__call__(flat_rays) -> (coarse_rgb [n, 3], fine_rgb [n, 3], distance [n])`, `.acc[l]`, `.n`, `.chunk`,
+    `.white_bkgd`; `.live_count` is the number of rays the last call rendered.
+    Per frame: the rays are copied in, classified (`ops.ray_occupancy`: a ray is culled only if no coarse frustum of it touches an occupied
+    cell), compacted in their order (`ops.compact_rays`), rendered as ceil(live / chunk) chunk forwards of the existing path over the
+    compact buffers (`GraphedFrame._run_chunks`: its lanes and scratch), and scattered back (`ops.scatter_frame`): a culled pixel gets what
+    `volumetric_rendering` yields for all-zero weights (background colour, acc 0, distance near).  A live ray's arithmetic does not depend
+    on its neighbours, so its results are bit for bit those of `GraphedFrame`.
+    The chunk forwards run eagerly: the live count differs from frame to frame and has to reach the host (one 8-byte read-back and one
+    stream synchronisation per frame), so a frame cannot be one captured graph."""
+
+    def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, occupancy,
+                 lanes: Optional[int] = None, outside_occupied: bool = True, cone_scale: float = 1.0):
+        if getattr(model, "unbounded", False):
+            raise NotImplementedError("CulledFrame: unbounded=True models are not supported (their field lives in a contracted space)")
+        self.model, self.n, self.chunk, self.white_bkgd, self.dev = model, int(num_rays), int(chunk), bool(white_bkgd), device
+        self.occupancy, self.outside_occupied, self.cone_scale = occupancy, bool(outside_occupied), float(cone_scale)
+        # the compacted rays and their results live in an eager GraphedFrame: its chunk loop, lanes and scratch render the first live_count rays
+        self._compact = GraphedFrame(model, num_rays, chunk, white_bkgd, device, lanes=lanes, capture=False)
+        self.static_in = Rays(*[torch.zeros(self.n, k, device=device) for k in (3, 3, 3, 1, 1, 1, 1)])
+        L_ = model.num_levels
+        self.rgb = [torch.zeros(self.n, 3, device=device) for _ in range(L_)]
+        self.dist = [torch.zeros(self.n, device=device) for _ in range(L_)]
+        self.acc = [torch.zeros(self.n, device=device) for _ in range(L_)]
+        self.live = torch.zeros(self.n, dtype=torch.uint8, device=device)
+        self.index = torch.zeros(max(self.n, 1), dtype=torch.int32, device=device)
+        self._ws = torch.empty(max(int(L.lib().mipnerf_compact_rays_workspace_bytes(self.n)), 16), dtype=torch.uint8, device=device)
+        self.live_count = 0
+
+    def __call__(self, rays: Rays):
+        if rays.origins.shape[0] != self.n:
+            raise ValueError(f"CulledFrame built for {self.n} rays, got {rays.origins.shape[0]}")
+        if self.n == 0:
+            self.live_count = 0
+            return self.rgb[0], self.rgb[-1], self.dist[-1]
+        m, c = self.model, self._compact
+        with torch.cuda.device(self.dev), torch.no_grad():
+            m.mlp.native(self.dev)
+            for dst, src in zip(self.static_in, rays):
+                dst.copy_(src)
+            ops.ray_occupancy(self.occupancy, self.static_in, m.num_samples, disparity=m.disparity, outside_occupied=self.outside_occupied,
+                              cone_scale=self.cone_scale, out=self.live)
+            self.live_count = ops.compact_rays(self.live, self.static_in, c.static_in, self.index, workspace=self._ws)
+            # the ragged tail differs from frame to frame: keep the per-sample scratch of the full chunk and of this tail only (the
+            # synchronisation in compact_rays came after the join of the last frame's lanes, so nothing still reads the others)
+            tail = self.live_count % self.chunk
+            for scratch in getattr(c, "_scratch", []):
+                for b in [b for b in scratch if b not in (min(self.n, self.chunk), tail)]:
+                    del scratch[b]
+            c._run_chunks(self.live_count)
+            ops.scatter_frame(self.index, self.live_count, [(c.rgb[l], c.dist[l], c.acc[l]) for l in range(m.num_levels)],
+                              [(self.rgb[l], self.dist[l], self.acc[l]) for l in range(m.num_levels)], self.live, self.static_in.near,
+                              self.white_bkgd)
         return self.rgb[0], self.rgb[-1], self.dist[-1]

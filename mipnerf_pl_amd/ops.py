@@ -608,3 +608,139 @@ def isosurface(grid, threshold, lo, hi, return_edges=False):
             L.check(L.lib().mipnerf_isosurface_emit(cdims, clo, chi, _ptr(g), float(threshold), _ptr(ws), need, _ptr(vertices), _ptr(normals),
                                                     _ptr(faces) if F else None, _ptr(edges), _stream()), "isosurface_emit")
     return (vertices, normals, faces, edges) if return_edges else (vertices, normals, faces)
+
+
+# ---- empty-space skipping for whole frames (csrc/kernels_occupancy.hip) ----------------------------------------------------
+class Occupancy:
+    """Occupancy bits of a lattice (include/mipnerf_hip.h, mipnerf_occupancy_build): `bits` uint32 on the device
+    [nz - 1, ny - 1, ceil((nx - 1) / 32)], cell i of an x row is bit i & 31 of word i >> 5, padding bits are 0; `dims` =
+    (nx, ny, nz) lattice POINTS, `lo` / `hi` the box in (x, y, z) order, h = (hi - lo) / float(n - 1)."""
+
+    def __init__(self, bits, dims, lo, hi):
+        self.bits, self.dims, self.lo, self.hi = bits, tuple(int(d) for d in dims), tuple(float(v) for v in lo), tuple(float(v) for v in hi)
+
+    @property
+    def cells(self):
+        return tuple(d - 1 for d in self.dims)
+
+    def occupied_fraction(self) -> float:
+        """Share of the cells that are occupied (a host read-back of the words)."""
+        import numpy as np
+        words = self.bits.cpu().numpy()
+        count = int(np.unpackbits(words.view(np.uint8)).sum())
+        cx, cy, cz = self.cells
+        return count / float(cx * cy * cz)
+
+
+def occupancy_grid(lattice, threshold, lo, hi, dilate=1):
+    """Occupancy bits of any fp32 device lattice [nz, ny, nx] over the box lo .. hi ((x, y, z) order, the conventions of `isosurface`):
+    cell (i, j, k) is raw-occupied iff any of its 8 corner values is > threshold or is NaN; a cell is occupied iff a raw-occupied cell lies
+    within Chebyshev distance `dilate` (>= 0) of it.  Returns an `Occupancy`.  No atomics: two runs give the same bytes."""
+    g = _f32c(lattice, "lattice")
+    if g.dim() != 3:
+        raise ValueError(f"occupancy_grid: expected a [nz, ny, nx] lattice, got {tuple(g.shape)}")
+    dims, cdims, clo, chi = _lattice_args("occupancy_grid", (g.shape[2], g.shape[1], g.shape[0]), lo, hi)
+    dilate = int(dilate)
+    with torch.cuda.device(g.device):
+        words = int(L.lib().mipnerf_occupancy_words(*dims))
+        if words == 0:
+            raise ValueError(f"occupancy_grid: a lattice needs at least 2 points per axis and 7 nx ny nz < 2^31 (got {dims})")
+        shape = (dims[2] - 1, dims[1] - 1, (dims[0] - 1 + 31) // 32)
+        bits = torch.empty(shape, dtype=torch.uint32, device=g.device)
+        scratch = torch.empty(shape, dtype=torch.uint32, device=g.device) if dilate > 0 else None
+        L.check(L.lib().mipnerf_occupancy_build(cdims, _ptr(g), float(threshold), dilate, _ptr(bits), _ptr(scratch), _stream()),
+                "occupancy_build")
+    return Occupancy(bits, dims, [float(v) for v in clo], [float(v) for v in chi])
+
+
+def field_occupancy(model_or_system, grid=128, lo=None, hi=None, threshold=0.01, dilate=1, cov_scale=1.0, precision=None):
+    """`density_grid` of the field on grid^3 (or (nx, ny, nz)) points over lo .. hi, then `occupancy_grid` of it.  The threshold is a
+    density and scene dependent, like the mesh threshold.  unbounded=True models are refused (their field lives in a contracted space)."""
+    _field_mlp(model_or_system, "field_occupancy")
+    if lo is None or hi is None:
+        raise ValueError("field_occupancy: give the box lo .. hi the grid spans (the rays of the cameras to be rendered should stay inside it)")
+    sigma = density_grid(model_or_system, grid, lo, hi, cov_scale=cov_scale, precision=precision)
+    return occupancy_grid(sigma, threshold, lo, hi, dilate=dilate)
+
+
+def _rays_ptrs(rays, n, name):
+    """RaysPtrs of 7 flat fp32 device fields [n, k] plus the tensors that keep them alive"""
+    keep = []
+    for k, t in zip(type(rays)._fields, rays):
+        t = _f32c(t, k)
+        if t.shape[0] != n:
+            raise ValueError(f"{name}: {k} has {t.shape[0]} rays, expected {n}")
+        keep.append(t)
+    return L.RaysPtrs(*[t.data_ptr() for t in keep]), keep
+
+
+def ray_occupancy(occ, rays, num_samples, disparity=False, outside_occupied=True, cone_scale=1.0, out=None):
+    """live uint8 [n]: 1 where some coarse frustum of the ray touches an occupied cell of `occ`.  Frustum i of the coarse level's
+    deterministic fence posts t_0 .. t_N has the end points p0 = o + t_i d, p1 = o + t_{i+1} d, the half-width rho = cone_scale * radii *
+    t_{i+1}, per axis the bounding interval [min(p0, p1) - rho, max(p0, p1) + rho] and the cell range floor((x - lo) / h), inclusive at both
+    ends; the part of a range outside the grid counts as occupied when `outside_occupied`, otherwise it is clipped away.  `rays`: flat
+    [n, k] device rays."""
+    import ctypes as C
+    n = int(rays.origins.shape[0])
+    dev = occ.bits.device
+    live = torch.empty(n, dtype=torch.uint8, device=dev) if out is None else out
+    if live.dtype != torch.uint8 or live.numel() != n or not live.is_contiguous():
+        raise ValueError("ray_occupancy: out must be a contiguous uint8 tensor with one byte per ray")
+    if n == 0:
+        return live
+    _, cdims, clo, chi = _lattice_args("ray_occupancy", occ.dims, occ.lo, occ.hi)
+    with torch.cuda.device(dev):
+        rp, keep = _rays_ptrs(rays, n, "ray_occupancy")
+        L.check(L.lib().mipnerf_ray_occupancy(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(disparity)),
+                                              int(bool(outside_occupied)), float(cone_scale), _ptr(live), _stream()), "ray_occupancy")
+    return live
+
+
+def compact_rays(live, rays, out_rays, out_index, workspace=None):
+    """Gathers the rays with live != 0, in their original order, into the first `count` rows of `out_rays` (7 preallocated [n, k] fp32
+    fields) and writes the source ray of compact slot j to out_index[j] (int32 [n]).  Returns `count`.  The count has to reach the host:
+    one 8-byte read-back and one stream synchronisation per call, which is why the call cannot be captured into a graph."""
+    import ctypes as C
+    n = int(live.numel())
+    if live.dtype != torch.uint8 or not live.is_contiguous() or out_index.dtype != torch.int32 or out_index.numel() < n:
+        raise ValueError("compact_rays: live is uint8 [n], out_index int32 [n]")
+    if n == 0:
+        return 0
+    with torch.cuda.device(live.device):
+        need = int(L.lib().mipnerf_compact_rays_workspace_bytes(n))
+        ws = torch.empty(need, dtype=torch.uint8, device=live.device) if workspace is None else workspace
+        rp, keep = _rays_ptrs(rays, n, "compact_rays")
+        op, keep_out = _rays_ptrs(out_rays, n, "compact_rays")
+        for a, b in zip(out_rays, keep_out):
+            if a.data_ptr() != b.data_ptr():
+                raise ValueError("compact_rays: out_rays must be contiguous fp32 tensors")
+        count = C.c_int64(0)
+        L.check(L.lib().mipnerf_compact_rays(n, _ptr(live), C.byref(rp), C.byref(op), _ptr(out_index), _ptr(ws), ws.numel(),
+                                             C.byref(count), _stream()), "compact_rays")
+    return int(count.value)
+
+
+def scatter_frame(index, count, compact_outputs, full_outputs, live, near, white_bkgd):
+    """Writes every pixel of every level once.  `compact_outputs` / `full_outputs`: per level (rgb [m, 3], distance [m], acc [m]) with
+    m >= count and m = n.  Pixel index[j], j < count, takes compact slot j; a pixel with live = 0 takes what volumetric_rendering yields
+    for all-zero weights: rgb = 1 with `white_bkgd` else 0, acc = 0, distance = near."""
+    n = int(live.numel())
+    if n == 0:
+        return
+    nl = len(full_outputs)
+    if len(compact_outputs) != nl:
+        raise ValueError("scatter_frame: compact and full outputs have different level counts")
+    comp, full = (L.LevelOut * nl)(), (L.LevelOut * nl)()
+    keep = []
+    for l in range(nl):
+        for arr, outs, rows in ((comp, compact_outputs[l], int(count)), (full, full_outputs[l], n)):
+            rgb, dist, acc = outs
+            for t, width in ((rgb, 3), (dist, 1), (acc, 1)):
+                if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.numel() < rows * width:
+                    raise ValueError("scatter_frame: outputs are contiguous fp32 device tensors with at least `count` / n rows")
+            arr[l] = L.LevelOut(rgb.data_ptr(), dist.data_ptr(), acc.data_ptr(), None, None)
+            keep += [rgb, dist, acc]
+    near = _f32c(near, "near")
+    with torch.cuda.device(live.device):
+        L.check(L.lib().mipnerf_scatter_frame(n, int(count), nl, _ptr(index), _ptr(live), _ptr(near), int(bool(white_bkgd)), comp, full,
+                                              _stream()), "scatter_frame")

@@ -21,14 +21,15 @@ import os
 import numpy as np
 import torch
 
-from .evaluate import DEFAULT_CHUNK, FrameEvaluator, generate_video, save_images
+from .evaluate import DEFAULT_CHUNK, FrameEvaluator, generate_video, report_live_share, save_images, scene_occupancy
 
 CAMERA_ANGLE_X = 0.6911112070083618       # render_video.py --camera_angle_x default (Blender's lego)
 
 
 def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_angle_x=CAMERA_ANGLE_X, chunk_size=DEFAULT_CHUNK,
-                 white_bkgd=True, n_poses=120, use_graph=True):
-    """render_video.py:run_render after the checkpoint is loaded.  Returns the output folder."""
+                 white_bkgd=True, n_poses=120, use_graph=True, occupancy=None):
+    """render_video.py:run_render after the checkpoint is loaded.  Returns the output folder.  `occupancy` (an `ops.Occupancy`): rays
+    that touch no occupied cell are not rendered (`model.CulledFrame`); None is the full path."""
     from .datasets import RenderGen
     model = system.mip_nerf
     device = next(model.parameters()).device
@@ -38,21 +39,24 @@ def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_
     focal = .5 * base_size[0] / np.tan(.5 * camera_angle_x)
     dataset = RenderGen(focal, base_size, scale, device=device, n_poses=n_poses)
     nums = len(dataset) // scale
-    evaluators = {}
+    evaluators, shares = {}, []
     with torch.no_grad():
         for idx in range(len(dataset)):
             rays = dataset[idx]
             h, w = dataset.sizes[idx]
             ev = evaluators.get((h, w))
             if ev is None:
-                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph)
+                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy)
             images = ev.images(*ev.render(rays))
+            if occupancy is not None:
+                shares.append(ev.frame.live_count / float(h * w))
             save_images(*images, os.path.join(folder, str(int(base_size[0] / w))), idx % nums)
     generate_video(folder)
+    report_live_share(shares)
     return folder
 
 
-def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAULT_CHUNK, white_bkgd=False, use_graph=True):
+def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAULT_CHUNK, white_bkgd=False, use_graph=True, occupancy=None):
     """The interpolated path through the poses of `dataset` (a `datasets.RealData360` split), every frame as in `render_video`.
     Returns the output folder."""
     from .datasets import PathGen
@@ -62,11 +66,16 @@ def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAU
     os.makedirs(os.path.join(folder, "1"), exist_ok=True)
     path = PathGen(dataset, n_views, device=device)
     h, w = path.sizes[0]
-    ev = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph)
+    ev = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy)
+    shares = []
     with torch.no_grad():
         for idx in range(len(path)):
-            save_images(*ev.images(*ev.render(path[idx])), os.path.join(folder, "1"), idx)
+            images = ev.images(*ev.render(path[idx]))
+            if occupancy is not None:
+                shares.append(ev.frame.live_count / float(h * w))
+            save_images(*images, os.path.join(folder, "1"), idx)
     generate_video(folder)
+    report_live_share(shares)
     return folder
 
 
@@ -100,7 +109,29 @@ def add_common_args(p):
     p.add_argument("--precision", help="MLP precision (default: the checkpoint's)", choices=["fp32", "bf16"], default=None)
     p.add_argument("--no-graph", dest="use_graph", help="render each frame eagerly instead of replaying a captured hipGraph",
                    action="store_false")
+    p.add_argument("--cull", help="skip the rays that touch no occupied cell of the field's occupancy grid (bounded scenes only)", action="store_true")
+    p.add_argument("--cull_grid", help="--cull: lattice points per axis of the occupancy grid", type=int, default=128)
+    p.add_argument("--cull_threshold", help="--cull: a cell is occupied when the density at one of its corners exceeds this; scene dependent, like "
+                   "the mesh threshold: a foggy field needs a higher one", type=float, default=0.01)
+    p.add_argument("--cull_dilate", help="--cull: occupied cells grow by this many cells in every direction", type=int, default=1)
+    p.add_argument("--cull_bound", help="--cull: the grid spans [-B, B]^3 (default: the largest coordinate any ray of the cameras to be rendered "
+                   "reaches between near and far, plus one cell)", type=float, default=None)
     return p
+
+
+def refuse_unbounded_cull(args, system):
+    """--cull with a checkpoint of the unbounded-scene model: exit before anything is rendered."""
+    if args.cull and getattr(system.mip_nerf, "unbounded", False):
+        raise SystemExit("--cull: this checkpoint holds the unbounded-scene model (unbounded=True); its field lives in a contracted space and "
+                         "has no occupancy grid -- render it without --cull")
+
+
+def cli_occupancy(args, system, frames):
+    """The occupancy grid the --cull flags ask for (None without --cull); `frames`: an iterable of the Rays [H, W, k] to be rendered."""
+    if not args.cull:
+        return None
+    return scene_occupancy(system, frames if args.cull_bound is None else None, grid=args.cull_grid, threshold=args.cull_threshold,
+                           dilate=args.cull_dilate, bound=args.cull_bound)
 
 
 def build_parser():
@@ -131,7 +162,9 @@ def main(argv=None):
         if args.render_images_dir is None:
             raise SystemExit("only generate video, you must give the different scale image base dir (--render_images_dir)")
         return generate_video(args.render_images_dir)
-    system = load_system(args).to(torch.device("cuda")).eval()
+    system = load_system(args)
+    refuse_unbounded_cull(args, system)
+    system = system.to(torch.device("cuda")).eval()
     hp = system.hparams
     if (args.path or ("interp" if is_scene360(hp) else "spheric")) == "interp":
         from .datasets import RealData360
@@ -141,12 +174,23 @@ def main(argv=None):
         dataset = RealData360(args.data, split=args.split, white_bkgd=hp["val.white_bkgd"],
                               batch_type="all_images" if args.split == "train" else "single_image",
                               factor=args.factor if args.factor is not None else int(hp.get("factor", 4)), device=dev)
+        occupancy = None
+        if args.cull:
+            from .datasets import PathGen
+            path = PathGen(dataset, args.n_views, device=dev)
+            occupancy = cli_occupancy(args, system, (path[i] for i in range(len(path))))
         return render_path(system, dataset, args.out_dir, hp["exp_name"], n_views=args.n_views, chunk_size=args.chunk_size,
                            white_bkgd=args.white_bkgd if flag_given(argv, "--white_bkgd") else bool(hp["val.white_bkgd"]),
-                           use_graph=args.use_graph)
+                           use_graph=args.use_graph, occupancy=occupancy)
+    occupancy = None
+    if args.cull:
+        from .datasets import RenderGen
+        focal = .5 * args.base_size[0] / np.tan(.5 * args.camera_angle_x)
+        gen = RenderGen(focal, args.base_size, args.scale, device=next(system.parameters()).device, n_poses=args.n_poses)
+        occupancy = cli_occupancy(args, system, (gen[i] for i in range(len(gen))))
     return render_video(system, args.out_dir, system.hparams["exp_name"], args.scale, base_size=args.base_size,
                         camera_angle_x=args.camera_angle_x, chunk_size=args.chunk_size, white_bkgd=args.white_bkgd,
-                        n_poses=args.n_poses, use_graph=args.use_graph)
+                        n_poses=args.n_poses, use_graph=args.use_graph, occupancy=occupancy)
 
 
 if __name__ == "__main__":
