@@ -2,8 +2,15 @@
 
     python -m mipnerf_pl_amd.build [--force]
 
-Steps: (1) regenerate mlp_bf16_gen.hip / mlp_plan_gen.hpp from mlp_plan.py, (2) compile each
-.hip translation unit to an object (the ray-math units with -ffp-contract=off, see
+Steps: (1) run the four generators of csrc/ (what they share lives in csrc/gen_common.py), one kernel per architecture variant <i> of
+gen_mlp_bf16.VARIANTS (variant 0 of the first two without the suffix):
+    gen_mlp_bf16.py   mlp_bf16_gen[_v<i>].hip, mlp_plan_gen.hpp, mlp_variants_gen.hpp
+    gen_mlp_train.py  mlp_bf16_trainfwd_gen[_v<i>].hip or mlp_bf16_trainfwd_pre_gen_v<i>.hip, mlp_bf16_dgrad_gen[_v<i>].hip,
+                      _gen_train_tables[_v<i>].bin, mlp_train_variants_gen.hpp
+    gen_mlp_f32r.py   mlp_f32r_gen_v<i>.hip, _gen_f32r_tables_v<i>.bin, mlp_f32r_variants_gen.hpp
+    gen_pre_gemm.py   pre_gemm_gen_v<i>.hip, mlp_bf16_pre_gen_v<i>.hip, mlp_bf16_fused_gen_v<i>.hip, _gen_pre_tables_v<i>.bin,
+                      mlp_pre_variants_gen.hpp
+(2) compile each .hip translation unit to an object (the ray-math units with -ffp-contract=off, see
 raymath.hpp), (3) link the shared library next to the sources.  No torch headers are used:
 the library's only dependency is the HIP runtime.
 """
@@ -11,6 +18,7 @@ from __future__ import annotations
 
 import hashlib
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -46,6 +54,31 @@ UNITS = [
     ("selftest.hip", ["-ffp-contract=off"]),
     ("capi.hip", []),
 ]
+# the generated per-variant families: (unit stem, flags of its units, stem of its table blob, linker symbol of the blob); a unit is
+# <stem>_v<i>.hip, a blob <stem>[_v<i>].bin linked in as <symbol>[_v<i>].  The fused IPE must round like kernels_ray.hip.
+FAMILIES = [
+    ("mlp_bf16_gen", NO_IEEE + ["-ffp-contract=off"], None, None),
+    ("mlp_bf16_trainfwd_gen", NO_IEEE + ["-ffp-contract=off"], "_gen_train_tables", "mip_train_tables"),
+    ("mlp_bf16_trainfwd_pre_gen", NO_IEEE + ["-ffp-contract=off"], None, None),
+    ("mlp_bf16_dgrad_gen", NO_IEEE, None, None),
+    ("mlp_f32r_gen", NO_IEEE + ["-ffp-contract=off"], "_gen_f32r_tables", "mip_f32r_tables"),     # the register-resident fp32 kernels
+    ("pre_gemm_gen", NO_IEEE + ["-ffp-contract=off"], "_gen_pre_tables", "mip_pre_tables"),       # two- and one-kernel bf16 forms of wide encodings
+    ("mlp_bf16_pre_gen", NO_IEEE + ["-ffp-contract=off"], None, None),
+    ("mlp_bf16_fused_gen", NO_IEEE + ["-ffp-contract=off"], None, None),
+]
+
+
+def _family_files(col, ext):
+    """sorted (file name, family row, variant suffix) of the files <stem>[_v<i>].<ext> in csrc/, stem = column `col` of the family rows"""
+    out = []
+    for f in sorted(os.listdir(CSRC)):
+        for fam in FAMILIES:
+            m = fam[col] and re.fullmatch(re.escape(fam[col]) + r"((?:_v\d+)?)\.(?:" + ext + ")", f)
+            if m:
+                out.append((f, fam, m.group(1)))
+    return out
+
+
 # measurement tooling (in-process MFMA ceilings, CU -> CU hand-off probe): its own library, include/mipnerf_diag.h -- the drop-in
 # library above is the hot path only
 DIAG_LIB = os.path.join(CSRC, "libmipnerf_diag.so")
@@ -72,55 +105,33 @@ def _digest(paths, flags) -> str:
 
 
 def generate() -> None:
-    """Run the two generators.  Every architecture of gen_mlp_bf16.VARIANTS gets its own inference kernel (mlp_bf16_gen_v<i>.hip),
+    """Run the four generators.  Every architecture of gen_mlp_bf16.VARIANTS gets its own inference kernel (mlp_bf16_gen_v<i>.hip),
     its training kernels + table blob when mlp_train_plan covers it, and a row in the generated dispatch headers; files of
     variants that no longer exist are removed first, so adding / removing a shape is an edit of VARIANTS and a rebuild."""
-    import re
-    for f in os.listdir(CSRC):
-        if re.fullmatch(r"(mlp_bf16(_trainfwd|_trainfwd_pre|_dgrad)?_gen_v\d+\.(hip|o)|_gen_train_tables(_v\d+)?\.bin|mlp_f32r_gen_v\d+\.(hip|o)|_gen_f32r_tables_v\d+\.bin|"
-                        r"pre_gemm_gen_v\d+\.(hip|o)|mlp_bf16_pre_gen_v\d+\.(hip|o)|mlp_bf16_fused_gen_v\d+\.(hip|o)|_gen_pre_tables_v\d+\.bin)", f):
+    for f, _, sfx in _family_files(0, "hip|o") + _family_files(2, "bin"):
+        if sfx or f.endswith(".bin"):          # (the unsuffixed units of variant 0 are listed in UNITS)
             os.remove(os.path.join(CSRC, f))
-    subprocess.check_call([sys.executable, os.path.join(CSRC, "gen_mlp_bf16.py"), CSRC])
-    subprocess.check_call([sys.executable, os.path.join(CSRC, "gen_mlp_train.py"), CSRC])
-    subprocess.check_call([sys.executable, os.path.join(CSRC, "gen_mlp_f32r.py"), CSRC])
-    subprocess.check_call([sys.executable, os.path.join(CSRC, "gen_pre_gemm.py"), CSRC])
+    for gen in ("gen_mlp_bf16.py", "gen_mlp_train.py", "gen_mlp_f32r.py", "gen_pre_gemm.py"):
+        subprocess.check_call([sys.executable, os.path.join(CSRC, gen), CSRC])
 
 
 def variant_units():
     """(source, flags) of the generated per-variant kernels present after generate()."""
-    import re
-    out = []
-    for f in sorted(os.listdir(CSRC)):
-        # inference + training-forward kernels, the two- and one-kernel bf16 forms of wide encodings (gen_pre_gemm.py), the register-resident
-        # fp32 kernels (gen_mlp_f32r.py)
-        if re.fullmatch(r"(mlp_bf16_gen|mlp_bf16_trainfwd(_pre)?_gen|pre_gemm_gen|mlp_bf16_pre_gen|mlp_bf16_fused_gen|mlp_f32r_gen)_v\d+\.hip", f):
-            out.append((f, NO_IEEE + ["-ffp-contract=off"]))
-        elif re.fullmatch(r"mlp_bf16_dgrad_gen_v\d+\.hip", f):
-            out.append((f, NO_IEEE))
-    return out
+    return [(f, fam[1]) for f, fam, sfx in _family_files(0, "hip") if sfx]
 
 
 def tables_object() -> str:
-    """Link the binary training tables (written by gen_mlp_train.py, one blob per trainable variant) into the library: a
-    one-object file made with the assembler's .incbin, so mlp_train_plan.py stays the only definition of those tables."""
+    """Link the binary tables the generators write (one blob per variant and family that has one) into the library: a
+    one-object file made with the assembler's .incbin, so the plan modules stay the only definition of those tables."""
     src = os.path.join(CSRC, "_gen_train_tables.c")
     obj = os.path.join(CSRC, "train_tables.o")
+    blobs = _family_files(2, "bin")
     with open(src, "w") as f:
         f.write("/* generated by build.py */\n")
-        import re
-        for name in sorted(n for n in os.listdir(CSRC) if re.fullmatch(r"_gen_train_tables(_v\d+)?\.bin", n)):
-            sfx = name[len("_gen_train_tables"):-len(".bin")]
-            blob = os.path.join(CSRC, name)
-            f.write('__asm__(".section .rodata\\n.global mip_train_tables%s\\n.balign 16\\n'
-                    'mip_train_tables%s:\\n.incbin \\"%s\\"\\n.previous\\n");\n' % (sfx, sfx, blob))
-        for name in sorted(n for n in os.listdir(CSRC) if re.fullmatch(r"_gen_f32r_tables_v\d+\.bin", n)):
-            sfx = name[len("_gen_f32r_tables"):-len(".bin")]
-            f.write('__asm__(".section .rodata\\n.global mip_f32r_tables%s\\n.balign 16\\n'
-                    'mip_f32r_tables%s:\\n.incbin \\"%s\\"\\n.previous\\n");\n' % (sfx, sfx, os.path.join(CSRC, name)))
-        for name in sorted(n for n in os.listdir(CSRC) if re.fullmatch(r"_gen_pre_tables_v\d+\.bin", n)):
-            sfx = name[len("_gen_pre_tables"):-len(".bin")]
-            f.write('__asm__(".section .rodata\\n.global mip_pre_tables%s\\n.balign 16\\n'
-                    'mip_pre_tables%s:\\n.incbin \\"%s\\"\\n.previous\\n");\n' % (sfx, sfx, os.path.join(CSRC, name)))
+        for fam in FAMILIES:                       # family by family, as the dispatch headers declare them
+            for name, _, sfx in [b for b in blobs if b[1] is fam]:
+                f.write('__asm__(".section .rodata\\n.global %s%s\\n.balign 16\\n'
+                        '%s%s:\\n.incbin \\"%s\\"\\n.previous\\n");\n' % (fam[3], sfx, fam[3], sfx, os.path.join(CSRC, name)))
     subprocess.check_call(["gcc", "-c", "-fPIC", src, "-o", obj])
     return obj
 

@@ -19,19 +19,18 @@ be demoted to scratch), and the software pipeline is explicit:
 Usage: python gen_mlp_bf16.py [outdir]
 """
 import os
+import re
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gen_common as gc  # noqa: E402
+from gen_common import CHUNK_BYTES, HERE, NE, PREFETCH, WAVES  # noqa: E402
 from mipnerf_pl_amd.mlp_plan import Plan, Arch  # noqa: E402
 
-WAVES = 8             # wavefronts per workgroup (32 samples each); the 512-wide trunk: 4 (waves_of)
 GROUP = 4 * WAVES     # chunks per ring slot (wave w DMAs chunks 4w..4w+3 of a group)
 SLOTS = 2             # ring slots
-CHUNK_BYTES = 1024
-PREFETCH = 4          # A-fragment prefetch distance in chunks (registers A0..)
 # Every kernel gives static priority 1 to the second-dispatched half of the workgroup (the arbitration loser on every segment): 0.4722-0.4756 vs
 # 0.4762-0.4773 ms per launch in three alternating A/B pairs (+0.4 %, profiles/r02k_setprio_ab.log).
 # The trunk kernels of the two-kernel form read pre_x / pre_acc (read once, 1.5 KB per sample) with the non-temporal policy, so that they do not push
@@ -39,7 +38,6 @@ PREFETCH = 4          # A-fragment prefetch distance in chunks (registers A0..)
 # profiles/r04z_trunk_nt_loads_ab.txt).
 # Computing the NEXT tile's integrated positional encoding piecewise in the shadow of this tile's MFMAs measured -0.56 % cycles but +0.25 % time
 # (profiles/r03f_ipe_shadow_ab.txt): it is computed in a VALU-only phase at the start of every tile.
-NE = 3                # rotating registers for LDS-resident B operands (E0..E2)
 # one-kernel form of a wide encoding (Plan.fused): wave-private LDS ring of encoding k-steps (1 KiB each, global_load_lds from the fragment buffer
 # k_cast_ipe_360 writes) and how many k-steps ahead of its MFMAs a k-step's DMA is issued (its B-operand read happens two k-steps ahead)
 FUSED_RING = 8
@@ -194,7 +192,6 @@ def build_schedule(plan: Plan):
     return panels, slots
 
 
-import re  # noqa: E402
 _WRITES = re.compile(r"epilogue_half<[^>]*>\(\w+, ([XY]\[\d+\])\);\s*/\*op(\d+)\*/")
 
 
@@ -649,20 +646,8 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
     e("           const __bf16* __restrict__ enc, const __bf16* __restrict__ viewenc, float4* __restrict__ rgb_sigma,")
     e("           float4* __restrict__ raw_out, int64_t M, int num_samples, int ntiles, float density_bias,")
     e("           float rgb_padding, RayIn rin, const float* __restrict__ dnoise, float dnoise_scale) {")
-    e("    extern __shared__ __attribute__((aligned(16))) char smem[];")
-    e("    const int tid = threadIdx.x;")
-    e("    const int lane = tid & 63;")
-    e("    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);")
-    e("    const int hi = lane >> 5, n = lane & 31;")
-    e("    const unsigned lane16 = (unsigned)lane * 16u;")
-    e("    const char* ring_lane = smem + lane16;")
-    e("    const char* bias_lane = smem + kRingBytes + hi * 64;")
-    e("    char* encw = smem + kEncOff + wave * kEncWaveBytes;     // wave-private (uniform base)")
-    e("    const char* enc_lane = encw + lane16;")
-    e("    for (int i = tid; i < kBiasBytes / 16; i += blockDim.x)")
-    e("        reinterpret_cast<float4*>(smem + kRingBytes)[i] = reinterpret_cast<const float4*>(bias_tab)[i];")
-    e("    __syncthreads();")
-    e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // MI355X_MICROARCH.md, two waves per SIMD, item 4")
+    lines += gc.thread_prologue(("encw", "enc_lane", "kEncOff", "kEncWaveBytes"), priv_note="     // wave-private (uniform base)",
+                                setprio_note="MI355X_MICROARCH.md, two waves per SIMD, item 4", first_group=not (wide or fused))
     if wide:
         e("    if ((int)blockIdx.x < ntiles) {")
         for g in range(AHEAD):
@@ -674,8 +659,6 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
         e(f"        const char* encb = uniform_ptr(pre_x + ((int64_t)blockIdx.x * {WAVES} + wave) * {nk_enc * 1024});      // the first tile's first encoding k-steps")
         e("        PROLOGUE_ENC_DMAS")
         e("    }")
-    else:
-        e("    if ((int)blockIdx.x < ntiles) issue_group<DMA>(stream, smem, 0, 0, wave, lane16);")
     e("    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {")
     e("        const bool has_next = tile + (int)gridDim.x < ntiles;")
     e("        const int64_t s = (int64_t)tile * kTileSamples + wave * 32 + n;")
@@ -704,11 +687,6 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
         e(f"        const char* encb = uniform_ptr(pre_x + ((int64_t)tile * {WAVES} + wave) * {nk_enc * 1024});                     // this wave tile's fragment run")
         e(f"        const char* encb_next = uniform_ptr(has_next ? pre_x + ((int64_t)(tile + (int)gridDim.x) * {WAVES} + wave) * {nk_enc * 1024} : encb);")
     e("        float raw_density = 0.0f, raw_r = 0.0f, raw_g = 0.0f, raw_b = 0.0f;")
-
-    def lda(c):
-        slot = (c // GROUP) % SLOTS
-        off = slot * GROUP * CHUNK_BYTES + (c % GROUP) * CHUNK_BYTES
-        return f"A{c % PREFETCH} = LDA({off});"
 
     # ---- assign E registers to LDS-resident B operands and place their loads -----------------
     side = {c: [] for c in range(nreal)}
@@ -814,7 +792,7 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
     body_start = len(lines)
     e(f"        {group_begin(0)}")
     for c in range(PREFETCH):
-        e(f"        {lda(c)}")
+        e(f"        {gc.lda(c, GROUP, SLOTS)}")
     for stmt in prologue:
         e(f"        {stmt}")
     for stmt in bias_pieces(plan, panels[0]):
@@ -832,7 +810,7 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
             if lc % GROUP == 0:
                 g = lc // GROUP
                 e(f"        {group_begin(g)}")
-            e(f"        {lda(lc)}")
+            e(f"        {gc.lda(lc, GROUP, SLOTS)}")
         for stmt in side[c]:
             e(f"        {stmt}")
         e("        PIN();")
@@ -848,13 +826,7 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
         for i, ln in enumerate(lines):
             if "PROLOGUE_ENC_DMAS" in ln:
                 lines[i] = "\n".join("        " + st for st in enc_prologue)
-    e("        if (hi == 0 && s < M) {")
-    e("            // mip_nerf.py:232-233: raw_density += density_noise * randn (randomized training only), BEFORE the activation")
-    e("            const float noisy_density = dnoise ? raw_density + dnoise_scale * dnoise[s] : raw_density;")
-    e("            rgb_sigma[s] = make_float4(rgb_activation(raw_r, rgb_padding), rgb_activation(raw_g, rgb_padding),")
-    e("                                       rgb_activation(raw_b, rgb_padding), density_activation(noisy_density, density_bias));")
-    e("            if (raw_out) raw_out[s] = make_float4(raw_r, raw_g, raw_b, raw_density);")
-    e("        }")
+    lines += ["        " + ln for ln in gc.activation_store(training=False)]
     e("    }")
     if wide or fused:
         e('    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the refill runs around the stream: no LDS-DMA may land after the workgroup has released its LDS')
@@ -869,81 +841,35 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
     if pre or fused:
         e("// pre_x / pre_acc: the two outputs of launch_pre_gemm for the same M (16 KiB + 32 KiB per wave tile of 32 samples)")
         e("// (one-kernel form: pre_x = the encoding's fragment buffer -- whole 256-sample tiles, as k_cast_ipe_360 writes it --, pre_acc = nullptr)")
-        e(f"hipError_t launch_mlp_bf16{sfx}(const void* stream_w, const float* bias_tab, const void* pre_x, const void* pre_acc, const void* viewenc,")
-        e("                           float* rgb_sigma, float* raw_out, int64_t M, int num_samples, float density_bias,")
-        e("                           float rgb_padding, int grid_limit, const float* dnoise, float dnoise_scale, hipStream_t st) {")
-        e("    const int ntiles = (int)((M + kTileSamples - 1) / kTileSamples);")
-        e("    int grid = ntiles < grid_limit ? ntiles : grid_limit;")
-        e("    if (grid < 1) grid = 1;")
-        e("    static int attr_done[64] = {};")
-        e("    int dev = 0;")
-        e("    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;")
-        e("    if (!attr_done[dev]) {")
-        e("        hipError_t er = hipFuncSetAttribute((const void*)k_mlp_bf16<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-        e("        if (er != hipSuccess) return er;")
-        e("        attr_done[dev] = 1;")
-        e("    }")
-        e("    const RayIn rin = {nullptr, nullptr, nullptr, nullptr, 0, 0};")
-        e("    hipLaunchKernelGGL((k_mlp_bf16<true, false>), dim3(grid), dim3(%d), kLdsBytes, st, (const char*)stream_w, bias_tab," % (WAVES * 64))
-        e("                       (const char*)pre_x, (const char*)pre_acc, (const __bf16*)nullptr, (const __bf16*)viewenc, (float4*)rgb_sigma,")
-        e("                       (float4*)raw_out, M, num_samples, ntiles, density_bias, rgb_padding, rin, dnoise, dnoise_scale);")
-        e("    return hipGetLastError();")
-        e("}")
+        lines += gc.launcher(f"launch_mlp_bf16{sfx}", "bf16_pre", ["k_mlp_bf16<true, false>"], rayin="null", launch=[
+            "    hipLaunchKernelGGL((k_mlp_bf16<true, false>), dim3(grid), dim3(%d), kLdsBytes, st, (const char*)stream_w, bias_tab," % (WAVES * 64),
+            "                       (const char*)pre_x, (const char*)pre_acc, (const __bf16*)nullptr, (const __bf16*)viewenc, (float4*)rgb_sigma,",
+            "                       (float4*)raw_out, M, num_samples, ntiles, density_bias, rgb_padding, rin, dnoise, dnoise_scale);"])
         e("}  // namespace mip")
         return "\n".join(lines) + "\n"
-    e(f"hipError_t launch_mlp_bf16{sfx}(const void* stream_w, const float* bias_tab, const void* enc, const void* viewenc,")
-    e("                           float* rgb_sigma, float* raw_out, int64_t M, int num_samples, float density_bias,")
-    e("                           float rgb_padding, int grid_limit, bool dma, const RayInputs* rays, const float* dnoise,")
-    e("                           float dnoise_scale, hipStream_t st) {")
-    e("    const int ntiles = (int)((M + kTileSamples - 1) / kTileSamples);")
-    e(f"    grid_limit *= {WG_PER_CU};      // workgroups per CU (LDS: {lds_bytes} B each)")
-    e("    int grid = ntiles < grid_limit ? ntiles : grid_limit;")
-    e("    if (grid < 1) grid = 1;")
-    e("    static int attr_done[64] = {};")
-    e("    int dev = 0;")
-    e("    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;")
-    e("    if (!attr_done[dev]) {")
-    e("        hipError_t er = hipFuncSetAttribute((const void*)k_mlp_bf16<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-    e("        if (er != hipSuccess) return er;")
-    e("        er = hipFuncSetAttribute((const void*)k_mlp_bf16<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-    e("        if (er != hipSuccess) return er;")
-    e("        er = hipFuncSetAttribute((const void*)k_mlp_bf16<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-    e("        if (er != hipSuccess) return er;")
-    e("        attr_done[dev] = 1;")
-    e("    }")
-    e("    RayIn rin = {nullptr, nullptr, nullptr, nullptr, 0, 0};")
-    e("    if (rays) rin = RayIn{rays->t, rays->origins, rays->dirs, rays->radii, rays->min_deg, rays->disable_integration};")
-    e("#define MIP_LAUNCH(D, I) hipLaunchKernelGGL((k_mlp_bf16<D, I>), dim3(grid), dim3(%d), kLdsBytes, st, (const char*)stream_w, \\" % (WAVES * 64))
-    e("        bias_tab, (const __bf16*)enc, (const __bf16*)viewenc, (float4*)rgb_sigma, (float4*)raw_out, M, num_samples, ntiles, \\")
-    e("        density_bias, rgb_padding, rin, dnoise, dnoise_scale)")
-    e("    if (rays) MIP_LAUNCH(true, true);")
-    e("    else if (dma) MIP_LAUNCH(true, false);")
-    e("    else MIP_LAUNCH(false, false);")
-    e("#undef MIP_LAUNCH")
-    e("    return hipGetLastError();")
-    e("}")
+    lines += gc.launcher(f"launch_mlp_bf16{sfx}", "bf16", ["k_mlp_bf16<true, false>", "k_mlp_bf16<false, false>", "k_mlp_bf16<true, true>"],
+                         wg_per_cu=WG_PER_CU, lds_bytes=lds_bytes, rayin="rays", launch=[
+        "#define MIP_LAUNCH(D, I) hipLaunchKernelGGL((k_mlp_bf16<D, I>), dim3(grid), dim3(%d), kLdsBytes, st, (const char*)stream_w, \\" % (WAVES * 64),
+        "        bias_tab, (const __bf16*)enc, (const __bf16*)viewenc, (float4*)rgb_sigma, (float4*)raw_out, M, num_samples, ntiles, \\",
+        "        density_bias, rgb_padding, rin, dnoise, dnoise_scale)",
+        "    if (rays) MIP_LAUNCH(true, true);",
+        "    else if (dma) MIP_LAUNCH(true, false);",
+        "    else MIP_LAUNCH(false, false);",
+        "#undef MIP_LAUNCH"])
     e("}  // namespace mip")
     return "\n".join(lines) + "\n"
 
 
 def gen_variants_header(n):
     """Declarations + dispatch table of the per-variant inference launchers (capi.hip indexes it with PlanDesc::variant)."""
-    L = ["// AUTO-GENERATED by gen_mlp_bf16.py from VARIANTS -- do not edit by hand.", "#pragma once", '#include "kernels.hpp"',
-         "namespace mip {",
-         "typedef hipError_t (*LaunchBf16Fn)(const void* stream_w, const float* bias_tab, const void* enc, const void* viewenc,",
-         "                                   float* rgb_sigma, float* raw_out, int64_t M, int num_samples, float density_bias,",
-         "                                   float rgb_padding, int grid_limit, bool dma, const RayInputs* rays, const float* dnoise,",
-         "                                   float dnoise_scale, hipStream_t st);"]
-    for vi in range(1, n):
-        if not VARIANTS[vi].bf16_kernels:
-            continue
-        L.append(f"hipError_t launch_mlp_bf16_v{vi}(const void*, const float*, const void*, const void*, float*, float*, int64_t, int, float, float,")
-        L.append("                               int, bool, const RayInputs*, const float*, float, hipStream_t);")
-    names = ", ".join("nullptr /* fp32 only */" if not VARIANTS[vi].bf16_kernels else ("launch_mlp_bf16" if vi == 0 else f"launch_mlp_bf16_v{vi}")
-                      for vi in range(n))
-    L.append(f"static const LaunchBf16Fn kLaunchBf16[{n}] = {{{names}}};")
-    L.append("}  // namespace mip")
-    return "\n".join(L) + "\n"
+    bf16 = [vi for vi in range(n) if VARIANTS[vi].bf16_kernels]
+    body = gc.fn_typedef("LaunchBf16Fn", "bf16")
+    for vi in bf16:
+        if vi:      # (variant 0: declared in kernels.hpp)
+            body += gc.prototype(f"launch_mlp_bf16_v{vi}", "bf16")
+    entries = {vi: "launch_mlp_bf16" + (f"_v{vi}" if vi else "") if vi in bf16 else "nullptr /* fp32 only */" for vi in range(n)}
+    return gc.dispatch_header("// AUTO-GENERATED by gen_mlp_bf16.py from VARIANTS -- do not edit by hand.", body,
+                              [("LaunchBf16Fn", "kLaunchBf16", entries)], n)
 
 
 def main():

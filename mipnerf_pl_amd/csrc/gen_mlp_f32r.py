@@ -21,9 +21,9 @@ ring, 0.943 with the layer structure.
 import os
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
-
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gen_common as gc  # noqa: E402
+from gen_common import HERE  # noqa: E402
 from mipnerf_pl_amd.mlp_plan import DLAYOUT, NATURAL  # noqa: E402
 from mipnerf_pl_amd.mlp_f32r_plan import GROUP_CHUNKS, NSLOT, RING_SLOTS, F32RPlan, supported  # noqa: E402
 
@@ -380,7 +380,9 @@ class Gen:
         assert len(dens) == 1 and len(col) == 1
         doi, coi = dens[0][0], col[0][0]
         nrgb = col[0][1].thin[0].nrows
-        has_view = any(b.src == "view" for op in p.ops for b in op.blocks)
+        launcher = gc.launcher(f"launch_mlp_f32r_v{self.vi}", "f32r", ["k_mlp_f32r"], namespace=ns, range_check="nt64 > 0x7fffffff", attr_first=True, launch=[
+            f"    hipLaunchKernelGGL(k_mlp_f32r, dim3(grid), dim3({WAVES * 64}), kLdsBytes, st, (const char*)stream_w, aux, enc, viewenc, (float4*)rgb_sigma,",
+            "                       (float4*)raw_out, M, num_samples, ntiles, density_bias, rgb_padding, dnoise, dnoise_scale);"])
         src = f"""// AUTO-GENERATED by gen_mlp_f32r.py from mlp_f32r_plan.py -- do not edit by hand.
 // Register-resident fp32 MFMA MLP of Mip-NeRF (reference: models/mip_nerf.py:75-111 + activations 232-238), v_mfma_f32_32x32x2_f32.
 // architecture variant {self.vi}: depth {a.net_depth} width {a.net_width} cond {a.net_depth_condition}x{a.net_width_condition} xyz {a.xyz_dim} use_viewdirs={int(a.use_viewdirs)}
@@ -469,52 +471,24 @@ k_mlp_f32r(const char* __restrict__ stream_w, const float* __restrict__ aux, con
 }}
 }}  // namespace {ns}
 
-hipError_t launch_mlp_f32r_v{self.vi}(const void* stream_w, const float* aux, const float* enc, const float* viewenc, float* rgb_sigma, float* raw_out,
-                               int64_t M, int num_samples, float density_bias, float rgb_padding, int grid_limit, const float* dnoise,
-                               float dnoise_scale, hipStream_t st) {{
-    using namespace {ns};
-    static int attr_done[64] = {{}};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_done[dev]) {{
-        hipError_t er = hipFuncSetAttribute((const void*)k_mlp_f32r, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (er != hipSuccess) return er;
-        attr_done[dev] = 1;
-    }}
-    const int64_t nt64 = (M + kTileSamples - 1) / kTileSamples;
-    if (nt64 > 0x7fffffff) return hipErrorInvalidValue;
-    const int ntiles = (int)nt64;
-    int grid = ntiles < grid_limit ? ntiles : grid_limit;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_mlp_f32r, dim3(grid), dim3({WAVES * 64}), kLdsBytes, st, (const char*)stream_w, aux, enc, viewenc, (float4*)rgb_sigma,
-                       (float4*)raw_out, M, num_samples, ntiles, density_bias, rgb_padding, dnoise, dnoise_scale);
-    return hipGetLastError();
-}}
+{chr(10).join(launcher)}
 }}  // namespace mip
 """
         return src
 
 
 def variants_header(vis, n):
-    L = ["// AUTO-GENERATED by gen_mlp_f32r.py -- do not edit by hand.", "#pragma once", '#include "kernels.hpp"', "namespace mip {",
-         "typedef hipError_t (*LaunchF32RFn)(const void* stream_w, const float* aux, const float* enc, const float* viewenc, float* rgb_sigma,",
-         "                                   float* raw_out, int64_t M, int num_samples, float density_bias, float rgb_padding, int grid_limit,",
-         "                                   const float* dnoise, float dnoise_scale, hipStream_t st);"]
+    body = gc.fn_typedef("LaunchF32RFn", "f32r")
     for vi in vis:
-        L.append(f"hipError_t launch_mlp_f32r_v{vi}(const void*, const float*, const float*, const float*, float*, float*, int64_t, int, float, float, int,")
-        L.append("                               const float*, float, hipStream_t);")
-        L.append(f'extern "C" const unsigned char mip_f32r_tables_v{vi}[];')
-    names = ", ".join(f"launch_mlp_f32r_v{vi}" if vi in vis else "nullptr" for vi in range(n))
-    blobs = ", ".join(f"mip_f32r_tables_v{vi}" if vi in vis else "nullptr" for vi in range(n))
-    L.append(f"static const LaunchF32RFn kLaunchF32R[{n}] = {{{names}}};")
-    L.append(f"static const unsigned char* const kF32RTableBlobs[{n}] = {{{blobs}}};")
-    L.append("}  // namespace mip")
-    return "\n".join(L) + "\n"
+        body += gc.prototype(f"launch_mlp_f32r_v{vi}", "f32r")
+        body.append(f'extern "C" const unsigned char mip_f32r_tables_v{vi}[];')
+    return gc.dispatch_header("// AUTO-GENERATED by gen_mlp_f32r.py -- do not edit by hand.", body,
+                              [("LaunchF32RFn", "kLaunchF32R", {vi: f"launch_mlp_f32r_v{vi}" for vi in vis}),
+                               ("unsigned char* const", "kF32RTableBlobs", {vi: f"mip_f32r_tables_v{vi}" for vi in vis})], n)
 
 
 def main():
     outdir = sys.argv[1] if len(sys.argv) > 1 else HERE
-    sys.path.insert(0, HERE)
     from gen_mlp_bf16 import VARIANTS
     vis = []
     for vi, arch in enumerate(VARIANTS):

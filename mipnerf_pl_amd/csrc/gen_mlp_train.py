@@ -17,17 +17,11 @@ Usage: python gen_mlp_train.py [outdir]
 import os
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
-sys.path.insert(0, HERE)
-from mipnerf_pl_amd.mlp_plan import Plan  # noqa: E402
-from mipnerf_pl_amd.mlp_train_plan import GROUP, SLOTS, TrainPlan  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gen_common as gc  # noqa: E402
+from gen_common import CHUNK_BYTES, HERE, NE, PREFETCH, WAVES  # noqa: E402
 from gen_mlp_bf16 import KERNEL_PREAMBLE  # noqa: E402
-
-WAVES = 8
-CHUNK_BYTES = 1024
-PREFETCH = 4
-NE = 3
+from mipnerf_pl_amd.mlp_train_plan import GROUP, SLOTS, TrainPlan  # noqa: E402
 
 TRAIN_PREAMBLE = r"""
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -162,7 +156,7 @@ def count_stores(stmt: str) -> int:
     return stmt.count("store_tfrag<") + stmt.count("reinterpret_cast<u32x4*>(mask_wave")
 
 
-def emit_tile_body(e, prog, side, nchunks_total, prologue_lines, final_lines, lda):
+def emit_tile_body(e, prog, side, nchunks_total, prologue_lines, final_lines):
     """MFMA slots with A prefetch PREFETCH chunks ahead and ring-group boundaries where the load cursor
     enters a new group.  nchunks_total >= len(slots): trailing (padding) groups are still cycled through so
     that the ring phase is tile-invariant.  Every boundary drains the wave's vector memory operations (a counted
@@ -173,7 +167,7 @@ def emit_tile_body(e, prog, side, nchunks_total, prologue_lines, final_lines, ld
     def group_begin(g):
         e(f"        GROUP_BEGIN({g}, {(g + 1) % SLOTS});")
     for c in range(min(PREFETCH, nslots)):
-        e(f"        {lda(c)}")
+        e(f"        {gc.lda(c, GROUP, SLOTS)}")
     for ln in prologue_lines:
         e(f"        {ln}")
     e("        PIN();")
@@ -190,7 +184,7 @@ def emit_tile_body(e, prog, side, nchunks_total, prologue_lines, final_lines, ld
         if lc < nslots:
             if lc % GROUP == 0:
                 group_begin(lc // GROUP)
-            e(f"        {lda(lc)}")
+            e(f"        {gc.lda(lc, GROUP, SLOTS)}")
         for stmt in side[c]:
             e(f"        {stmt}")
         e("        PIN();")
@@ -343,26 +337,23 @@ def file_header(e, ns, consts):
     e("constexpr bool DMA = true;")
 
 
-SELECTORS = [
-    "bf16x8 P1, P2;   // selection matrices of the transposing MFMAs: P1[k][n] = (n == k), P2[k][n] = (n == 16 + k)",
-    "#pragma unroll",
-    "for (int j = 0; j < 8; ++j) {",
-    "    P1[j] = (__bf16)((n == hi * 8 + j) ? 1.0f : 0.0f);",
-    "    P2[j] = (__bf16)((n == 16 + hi * 8 + j) ? 1.0f : 0.0f);",
-    "}",
-]
-
-
 def gen_trainfwd(tp: TrainPlan, variant: int = 0) -> str:
-    if tp.pre_gemm:
-        return gen_trainfwd_pre(tp, variant)
-    sfx = f"_v{variant}" if variant else ""
+    """Forward-with-save.  tp.pre_gemm (TrainPlan.build(arch, pre_gemm=True); round 5): the TRUNK of the two-kernel bf16 form -- k_pre_gemm
+    (gen_pre_gemm.py, unchanged) has computed layer 0 and the encoding half of the skip layer; the kernel starts from the preloaded register
+    set X = bf16(relu(layer 0)) -- whose eight T-blocks and ReLU mask row it writes first (x1 > 0 <=> the pre-activation was positive) --,
+    runs layers 1 .. D-1, head, view layer and colour like the standard kernel (same panels, same epilogues, same T-block / mask stores),
+    and initialises the skip layer's accumulators from k_pre_gemm's fp32 partial sums.  The encoding's own T-blocks do not exist there: the
+    weight-gradient kernel reads the encoding fragments (WJob.b_src = 1)."""
+    pre = tp.pre_gemm
+    sfx = f"_pre_v{variant}" if pre else (f"_v{variant}" if variant else "")
+    kname = "k_mlp_bf16_trainfwd_pre" if pre else "k_mlp_bf16_trainfwd"
     plan = tp.fwd
     a = plan.arch
+    assert not pre or (plan.pre_gemm and a.net_width == 256)
     nchunks = len(plan.chunks)
     nreal = plan.n_real_chunks        # the stream is padded with zero chunks to whole ring groups (mlp_plan.RING_MULTIPLE)
     assert nchunks % GROUP == 0 and (nchunks // GROUP) % SLOTS == 0
-    nenc = a.xyz_dim // 16
+    nenc = 0 if pre else a.xyz_dim // 16       # (trunk: only the two view-encoding k-steps live in the wave-private area)
     enc_wave_bytes = 8192
     assert (nenc + 2) * 1024 <= enc_wave_bytes
     nbias_bytes = plan.n_tiles * 128
@@ -373,42 +364,38 @@ def gen_trainfwd(tp: TrainPlan, variant: int = 0) -> str:
     prog = build_fwd_prog(tp)
     # padding: the rest of the last ring group, plus at most one whole group of zeros (two view layers: 35 groups + 1; the folded 128-wide variant:
     # 10 groups + 8 chunks, padded to 12), each unentered group begun by an extra GROUP_BEGIN at the tile end (emit_tile_body)
-    assert len(prog.slots) == nreal and nchunks - nreal < SLOTS * GROUP
+    assert len(prog.slots) == nreal
+    if pre:
+        assert nchunks - nreal < GROUP or (nchunks - nreal == GROUP and nreal % GROUP == 0)
+    else:
+        assert nchunks - nreal < SLOTS * GROUP
     side_e, prologue_e = assign_lds_b(prog, nreal)
     side = place_sides(prog, nreal)
     for c in range(nreal):
         side[c] = side_e[c] + side[c]
-    check_hazards(prog, side)
+    check_hazards(prog, side, preloaded=pre)
     lines = []
     e = lines.append
     file_header(e, "trainfwd" + sfx, dict(kRingBytes=ring_bytes, kBiasBytes=nbias_bytes, kEncOff=enc_off,
                                     kEncWaveBytes=enc_wave_bytes, kLdsBytes=lds_bytes,
                                     kGroupBytes=GROUP * CHUNK_BYTES, kNumGroups=nchunks // GROUP,
                                     kTileSamples=WAVES * 32, kNH=tp.NH, kNMask=tp.NMASK))
-    e("template <bool IPE>")
-    e(f"__global__ void __launch_bounds__({WAVES * 64})")
-    e("k_mlp_bf16_trainfwd(const char* __restrict__ stream, const float* __restrict__ bias_tab,")
-    e("                    const __bf16* __restrict__ enc, const __bf16* __restrict__ viewenc, float4* __restrict__ rgb_sigma,")
-    e("                    float4* __restrict__ raw_out, char* __restrict__ HT, char* __restrict__ masks, int64_t M,")
-    e("                    int num_samples, int ntiles, float density_bias, float rgb_padding, RayIn rin,")
-    e("                    const float* __restrict__ dnoise, float dnoise_scale) {")
-    e("    extern __shared__ __attribute__((aligned(16))) char smem[];")
-    e("    const int tid = threadIdx.x;")
-    e("    const int lane = tid & 63;")
-    e("    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);")
-    e("    const int hi = lane >> 5, n = lane & 31;")
-    e("    const unsigned lane16 = (unsigned)lane * 16u;")
-    e("    const char* ring_lane = smem + lane16;")
-    e("    const char* bias_lane = smem + kRingBytes + hi * 64;")
-    e("    char* encw = smem + kEncOff + wave * kEncWaveBytes;")
-    e("    const char* enc_lane = encw + lane16;")
-    for ln in SELECTORS:
-        e("    " + ln)
-    e("    for (int i = tid; i < kBiasBytes / 16; i += blockDim.x)")
-    e("        reinterpret_cast<float4*>(smem + kRingBytes)[i] = reinterpret_cast<const float4*>(bias_tab)[i];")
-    e("    __syncthreads();")
-    e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // as the inference kernel (gen_mlp_bf16.py)")
-    e("    if ((int)blockIdx.x < ntiles) issue_group<DMA>(stream, smem, 0, 0, wave, lane16);")
+    if pre:
+        e(f"__global__ void __launch_bounds__({WAVES * 64})")
+        e("k_mlp_bf16_trainfwd_pre(const char* __restrict__ stream, const float* __restrict__ bias_tab, const char* __restrict__ pre_x,")
+        e("                        const char* __restrict__ pre_acc, const __bf16* __restrict__ viewenc, float4* __restrict__ rgb_sigma,")
+        e("                        float4* __restrict__ raw_out, char* __restrict__ HT, char* __restrict__ masks, int64_t M,")
+        e("                        int num_samples, int ntiles, float density_bias, float rgb_padding,")
+        e("                        const float* __restrict__ dnoise, float dnoise_scale) {")
+    else:
+        e("template <bool IPE>")
+        e(f"__global__ void __launch_bounds__({WAVES * 64})")
+        e("k_mlp_bf16_trainfwd(const char* __restrict__ stream, const float* __restrict__ bias_tab,")
+        e("                    const __bf16* __restrict__ enc, const __bf16* __restrict__ viewenc, float4* __restrict__ rgb_sigma,")
+        e("                    float4* __restrict__ raw_out, char* __restrict__ HT, char* __restrict__ masks, int64_t M,")
+        e("                    int num_samples, int ntiles, float density_bias, float rgb_padding, RayIn rin,")
+        e("                    const float* __restrict__ dnoise, float dnoise_scale) {")
+    lines += gc.thread_prologue(("encw", "enc_lane", "kEncOff", "kEncWaveBytes"), selectors=True)
     e("    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {")
     e("        const bool has_next = tile + (int)gridDim.x < ntiles;")
     e("        const int64_t wt = (int64_t)tile * 8 + wave;                 // wave tile (uniform)")
@@ -417,225 +404,78 @@ def gen_trainfwd(tp: TrainPlan, variant: int = 0) -> str:
     e("        const int64_t ray = sc / num_samples;")
     e("        char* ht_wave = HT + wt * (int64_t)(kNH * 2048);")
     e("        char* mask_wave = masks + wt * (int64_t)(kNMask * 1024);")
-    e("        if (IPE) {      // encoding computed here (registers -> LDS), see ipe_to_lds in gen_mlp_bf16.py")
-    e(f"            issue_encodings<DMA, {nenc}, {nenc}>(nullptr, viewenc + ray * 32 + hi * 8, encw, lane16);")
-    e(f"            ipe_to_lds<{nenc}>(rin, sc, num_samples, hi, encw + lane16);")
-    e("        } else {")
-    e(f"            issue_encodings<DMA, {nenc}, 0>(enc + sc * {a.xyz_dim} + hi * 8, viewenc + ray * 32 + hi * 8, encw, lane16);")
-    e("        }")
+    if pre:
+        e("        issue_encodings<DMA, 0, 0>(nullptr, viewenc + ray * 32 + hi * 8, encw, lane16);")
+    else:
+        e("        if (IPE) {      // encoding computed here (registers -> LDS), see ipe_to_lds in gen_mlp_bf16.py")
+        e(f"            issue_encodings<DMA, {nenc}, {nenc}>(nullptr, viewenc + ray * 32 + hi * 8, encw, lane16);")
+        e(f"            ipe_to_lds<{nenc}>(rin, sc, num_samples, hi, encw + lane16);")
+        e("        } else {")
+        e(f"            issue_encodings<DMA, {nenc}, 0>(enc + sc * {a.xyz_dim} + hi * 8, viewenc + ray * 32 + hi * 8, encw, lane16);")
+        e("        }")
     e("        bf16x8 X[16], Y[16], " + ", ".join(f"A{i}" for i in range(PREFETCH)) + ", E0, E1, E2;")
+    if pre:
+        e("        // what k_pre_gemm left for this wave tile: X = bf16(relu(layer 0)) as 16 lane-linear fragments, the skip layer's accumulator images")
+        e("        const char* prex_lane = pre_x + wt * 16384 + lane16;")
+        e("        const char* pre_lane = pre_acc + wt * 32768 + lane16;")
+        for k in range(16):
+            e(f"        X[{k}] = PRE_LD(reinterpret_cast<const bf16x8*>(prex_lane + {k * 1024}));")
     e("        f32x16 acc00, acc01, acc10, acc11;")
     e("        unsigned mq0 = 0, mq1 = 0, mq2 = 0, mq3 = 0;")
     e("        float raw_density = 0.0f, raw_r = 0.0f, raw_g = 0.0f, raw_b = 0.0f;")
 
-    def lda(c):
-        slot = (c // GROUP) % SLOTS
-        off = slot * GROUP * CHUNK_BYTES + (c % GROUP) * CHUNK_BYTES
-        return f"A{c % PREFETCH} = LDA({off});"
-    # tile prologue: transposed encodings (inputs of layer 0 / the skip layer / the view layer for wgrad)
+    # tile prologue: the transposed inputs the weight-gradient kernel needs -- the encodings (inputs of layer 0 / the skip layer), or the
+    # T-blocks and ReLU mask of x1 from the preloaded registers (trunk) --, then the T-block of the view features
     pro = []
-    e0 = tp.h_blocks["enc"][0]
     accs = ["acc10", "acc11"]
-    k = 0
-    for b in range(nenc // 2):
+
+    def tblock(k, b0, b1, blk):      # the k-th T-block of the prologue: the two accumulators alternate
         acc = accs[k % 2]
-        k += 1
-        pro.append(f"E0 = LDB({2 * b * 1024}); E1 = LDB({(2 * b + 1) * 1024});")
-        pro.append(f"TMFMA0({acc}, E0, P1); MFMA({acc}, E1, P2);")
-        pro.append(f"store_tfrag<0>({acc}, ht_wave + {(e0 + b) * 2048}, lane16); store_tfrag<8>({acc}, ht_wave + {(e0 + b) * 2048}, lane16);")
+        pro.append(f"TMFMA0({acc}, {b0}, P1); MFMA({acc}, {b1}, P2);")
+        pro.append(f"store_tfrag<0>({acc}, ht_wave + {blk * 2048}, lane16); store_tfrag<8>({acc}, ht_wave + {blk * 2048}, lane16);")
+    if pre:
+        x1 = tp.h_blocks["x1"][0]
+        nW = a.net_width // 32
+        for t in range(nW):
+            tblock(t, f"X[{2 * t}]", f"X[{2 * t + 1}]", x1 + t)
+            if t % 2 == 0:
+                pro.append(f"mq{t // 2} = tile_mask(X[{2 * t}], X[{2 * t + 1}]);")
+            else:
+                pro.append(f"mq{t // 2} |= tile_mask(X[{2 * t}], X[{2 * t + 1}]) << 8;")
+        vals = ", ".join(f"mq{q}" if q < (nW + 1) // 2 else "0u" for q in range(4))
+        pro.append(f"*reinterpret_cast<u32x4*>(mask_wave + 0 + lane16) = u32x4{{{vals}}};      // mask row 0 = layer 0")
+    else:
+        e0 = tp.h_blocks["enc"][0]
+        for b in range(nenc // 2):
+            pro.append(f"E0 = LDB({2 * b * 1024}); E1 = LDB({(2 * b + 1) * 1024});")
+            tblock(b, "E0", "E1", e0 + b)
     if "view" in tp.h_blocks:          # use_viewdirs=False has no view layer, hence no view-feature T-block
-        acc = accs[k % 2]
-        vb = tp.h_blocks["view"][0]
         pro.append(f"E0 = LDB({nenc * 1024}); E1 = LDB({(nenc + 1) * 1024});")
-        pro.append(f"TMFMA0({acc}, E0, P1); MFMA({acc}, E1, P2);")
-        pro.append(f"store_tfrag<0>({acc}, ht_wave + {vb * 2048}, lane16); store_tfrag<8>({acc}, ht_wave + {vb * 2048}, lane16);")
+        tblock(a.net_width // 32 if pre else nenc // 2, "E0", "E1", tp.h_blocks["view"][0])
     pro += prologue_e
     pro += prog.panels[0]["pre"]
-    final = list(prog.panels[-1]["post"])
-    final += [
-        "if (hi == 0 && s < M) {",
-        "    const float noisy_density = dnoise ? raw_density + dnoise_scale * dnoise[s] : raw_density;   // mip_nerf.py:232-233",
-        "    rgb_sigma[s] = make_float4(rgb_activation(raw_r, rgb_padding), rgb_activation(raw_g, rgb_padding),",
-        "                               rgb_activation(raw_b, rgb_padding), density_activation(noisy_density, density_bias));",
-        "    raw_out[s] = make_float4(raw_r, raw_g, raw_b, raw_density);",
-        "}",
-    ]
-    emit_tile_body(e, prog, side, nchunks, pro, final, lda)
+    final = list(prog.panels[-1]["post"]) + gc.activation_store(training=True)
+    emit_tile_body(e, prog, side, nchunks, pro, final)
     e("    }")
     e("}")
     e("}  // namespace trainfwd" + sfx)
     e("")
-    e(f"int mlp_trainfwd_lds_bytes{sfx}() {{ return trainfwd{sfx}::kLdsBytes; }}")
-    e(f"hipError_t launch_mlp_bf16_trainfwd{sfx}(const void* stream_w, const float* bias_tab, const void* enc, const void* viewenc,")
-    e("                                    float* rgb_sigma, float* raw_out, void* HT, void* masks, int64_t M, int num_samples,")
-    e("                                    float density_bias, float rgb_padding, int grid_limit, const RayInputs* rays,")
-    e("                                    const float* dnoise, float dnoise_scale, hipStream_t st) {")
-    e(f"    using namespace trainfwd{sfx};")
-    e("    const int ntiles = (int)((M + kTileSamples - 1) / kTileSamples);")
-    e("    int grid = ntiles < grid_limit ? ntiles : grid_limit;")
-    e("    if (grid < 1) grid = 1;")
-    e("    static int attr_done[64] = {};")
-    e("    int dev = 0;")
-    e("    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;")
-    e("    if (!attr_done[dev]) {")
-    e("        hipError_t er = hipFuncSetAttribute((const void*)k_mlp_bf16_trainfwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-    e("        if (er != hipSuccess) return er;")
-    e("        er = hipFuncSetAttribute((const void*)k_mlp_bf16_trainfwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-    e("        if (er != hipSuccess) return er;")
-    e("        attr_done[dev] = 1;")
-    e("    }")
-    e("    RayIn rin = {nullptr, nullptr, nullptr, nullptr, 0, 0};")
-    e("    if (rays) rin = RayIn{rays->t, rays->origins, rays->dirs, rays->radii, rays->min_deg, rays->disable_integration};")
-    e("#define MIP_LAUNCH(I) hipLaunchKernelGGL((k_mlp_bf16_trainfwd<I>), dim3(grid), dim3(%d), kLdsBytes, st, (const char*)stream_w, \\" % (WAVES * 64))
-    e("        bias_tab, (const __bf16*)enc, (const __bf16*)viewenc, (float4*)rgb_sigma, (float4*)raw_out, (char*)HT, (char*)masks, M, \\")
-    e("        num_samples, ntiles, density_bias, rgb_padding, rin, dnoise, dnoise_scale)")
-    e("    if (rays) MIP_LAUNCH(true); else MIP_LAUNCH(false);")
-    e("#undef MIP_LAUNCH")
-    e("    return hipGetLastError();")
-    e("}")
+    if pre:
+        lines += gc.launcher(f"launch_mlp_bf16_trainfwd{sfx}", "trainfwd_pre", [kname], namespace=f"trainfwd{sfx}", launch=[
+            f"    hipLaunchKernelGGL(k_mlp_bf16_trainfwd_pre, dim3(grid), dim3({WAVES * 64}), kLdsBytes, st, (const char*)stream_w, bias_tab,",
+            "                       (const char*)pre_x, (const char*)pre_acc, (const __bf16*)viewenc, (float4*)rgb_sigma, (float4*)raw_out, (char*)HT,",
+            "                       (char*)masks, M, num_samples, ntiles, density_bias, rgb_padding, dnoise, dnoise_scale);"])
+    else:
+        e(f"int mlp_trainfwd_lds_bytes{sfx}() {{ return trainfwd{sfx}::kLdsBytes; }}")
+        lines += gc.launcher(f"launch_mlp_bf16_trainfwd{sfx}", "trainfwd", [kname + "<false>", kname + "<true>"], namespace=f"trainfwd{sfx}",
+                             rayin="rays", launch=[
+            "#define MIP_LAUNCH(I) hipLaunchKernelGGL((k_mlp_bf16_trainfwd<I>), dim3(grid), dim3(%d), kLdsBytes, st, (const char*)stream_w, \\" % (WAVES * 64),
+            "        bias_tab, (const __bf16*)enc, (const __bf16*)viewenc, (float4*)rgb_sigma, (float4*)raw_out, (char*)HT, (char*)masks, M, \\",
+            "        num_samples, ntiles, density_bias, rgb_padding, rin, dnoise, dnoise_scale)",
+            "    if (rays) MIP_LAUNCH(true); else MIP_LAUNCH(false);",
+            "#undef MIP_LAUNCH"])
     e("}  // namespace mip")
     return "\n".join(lines) + "\n"
-
-
-def gen_trainfwd_pre(tp: TrainPlan, variant: int) -> str:
-    """TRUNK forward-with-save of the two-kernel bf16 form (TrainPlan.build(arch, pre_gemm=True); round 5): k_pre_gemm (gen_pre_gemm.py,
-    unchanged) has computed layer 0 and the encoding half of the skip layer; this kernel starts from the preloaded register set
-    X = bf16(relu(layer 0)) -- whose eight T-blocks and ReLU mask row it writes first (x1 > 0 <=> the pre-activation was positive) --,
-    runs layers 1 .. D-1, head, view layer and colour like k_mlp_bf16_trainfwd (same panels, same epilogues, same T-block / mask
-    stores), and initialises the skip layer's accumulators from k_pre_gemm's fp32 partial sums.  The encoding's own T-blocks do not
-    exist: the weight-gradient kernel reads the encoding fragments (WJob.b_src = 1)."""
-    sfx = f"_pre_v{variant}"
-    plan = tp.fwd
-    a = plan.arch
-    assert plan.pre_gemm and a.net_width == 256
-    nchunks = len(plan.chunks)
-    nreal = plan.n_real_chunks
-    assert nchunks % GROUP == 0 and (nchunks // GROUP) % SLOTS == 0
-    enc_wave_bytes = 8192            # only the two view-encoding k-steps live there
-    nbias_bytes = plan.n_tiles * 128
-    ring_bytes = SLOTS * GROUP * CHUNK_BYTES
-    enc_off = (ring_bytes + nbias_bytes + 1023) // 1024 * 1024
-    lds_bytes = enc_off + WAVES * enc_wave_bytes
-    assert lds_bytes <= 160 * 1024
-    prog = build_fwd_prog(tp)
-    assert len(prog.slots) == nreal and (nchunks - nreal < GROUP or (nchunks - nreal == GROUP and nreal % GROUP == 0))
-    side_e, prologue_e = assign_lds_b(prog, nreal)
-    side = place_sides(prog, nreal)
-    for c in range(nreal):
-        side[c] = side_e[c] + side[c]
-    check_hazards(prog, side, preloaded=True)
-    lines = []
-    e = lines.append
-    file_header(e, "trainfwd" + sfx, dict(kRingBytes=ring_bytes, kBiasBytes=nbias_bytes, kEncOff=enc_off,
-                                    kEncWaveBytes=enc_wave_bytes, kLdsBytes=lds_bytes,
-                                    kGroupBytes=GROUP * CHUNK_BYTES, kNumGroups=nchunks // GROUP,
-                                    kTileSamples=WAVES * 32, kNH=tp.NH, kNMask=tp.NMASK))
-    e(f"__global__ void __launch_bounds__({WAVES * 64})")
-    e("k_mlp_bf16_trainfwd_pre(const char* __restrict__ stream, const float* __restrict__ bias_tab, const char* __restrict__ pre_x,")
-    e("                        const char* __restrict__ pre_acc, const __bf16* __restrict__ viewenc, float4* __restrict__ rgb_sigma,")
-    e("                        float4* __restrict__ raw_out, char* __restrict__ HT, char* __restrict__ masks, int64_t M,")
-    e("                        int num_samples, int ntiles, float density_bias, float rgb_padding,")
-    e("                        const float* __restrict__ dnoise, float dnoise_scale) {")
-    e("    extern __shared__ __attribute__((aligned(16))) char smem[];")
-    e("    const int tid = threadIdx.x;")
-    e("    const int lane = tid & 63;")
-    e("    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);")
-    e("    const int hi = lane >> 5, n = lane & 31;")
-    e("    const unsigned lane16 = (unsigned)lane * 16u;")
-    e("    const char* ring_lane = smem + lane16;")
-    e("    const char* bias_lane = smem + kRingBytes + hi * 64;")
-    e("    char* encw = smem + kEncOff + wave * kEncWaveBytes;")
-    e("    const char* enc_lane = encw + lane16;")
-    for ln in SELECTORS:
-        e("    " + ln)
-    e("    for (int i = tid; i < kBiasBytes / 16; i += blockDim.x)")
-    e("        reinterpret_cast<float4*>(smem + kRingBytes)[i] = reinterpret_cast<const float4*>(bias_tab)[i];")
-    e("    __syncthreads();")
-    e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // as the inference kernel (gen_mlp_bf16.py)")
-    e("    if ((int)blockIdx.x < ntiles) issue_group<DMA>(stream, smem, 0, 0, wave, lane16);")
-    e("    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {")
-    e("        const bool has_next = tile + (int)gridDim.x < ntiles;")
-    e("        const int64_t wt = (int64_t)tile * 8 + wave;                 // wave tile (uniform)")
-    e("        const int64_t s = wt * 32 + n;")
-    e("        const int64_t sc = s < M ? s : M - 1;")
-    e("        const int64_t ray = sc / num_samples;")
-    e("        char* ht_wave = HT + wt * (int64_t)(kNH * 2048);")
-    e("        char* mask_wave = masks + wt * (int64_t)(kNMask * 1024);")
-    e("        issue_encodings<DMA, 0, 0>(nullptr, viewenc + ray * 32 + hi * 8, encw, lane16);")
-    e("        bf16x8 X[16], Y[16], " + ", ".join(f"A{i}" for i in range(PREFETCH)) + ", E0, E1, E2;")
-    e("        // what k_pre_gemm left for this wave tile: X = bf16(relu(layer 0)) as 16 lane-linear fragments, the skip layer's accumulator images")
-    e("        const char* prex_lane = pre_x + wt * 16384 + lane16;")
-    e("        const char* pre_lane = pre_acc + wt * 32768 + lane16;")
-    for k in range(16):
-        e(f"        X[{k}] = PRE_LD(reinterpret_cast<const bf16x8*>(prex_lane + {k * 1024}));")
-    e("        f32x16 acc00, acc01, acc10, acc11;")
-    e("        unsigned mq0 = 0, mq1 = 0, mq2 = 0, mq3 = 0;")
-    e("        float raw_density = 0.0f, raw_r = 0.0f, raw_g = 0.0f, raw_b = 0.0f;")
-
-    def lda(c):
-        slot = (c // GROUP) % SLOTS
-        off = slot * GROUP * CHUNK_BYTES + (c % GROUP) * CHUNK_BYTES
-        return f"A{c % PREFETCH} = LDA({off});"
-    # tile prologue: T-blocks and ReLU mask of x1 (from the preloaded registers), T-block of the view features
-    pro = []
-    accs = ["acc10", "acc11"]
-    x1 = tp.h_blocks["x1"][0]
-    nW = a.net_width // 32
-    for t in range(nW):
-        acc = accs[t % 2]
-        pro.append(f"TMFMA0({acc}, X[{2 * t}], P1); MFMA({acc}, X[{2 * t + 1}], P2);")
-        pro.append(f"store_tfrag<0>({acc}, ht_wave + {(x1 + t) * 2048}, lane16); store_tfrag<8>({acc}, ht_wave + {(x1 + t) * 2048}, lane16);")
-        if t % 2 == 0:
-            pro.append(f"mq{t // 2} = tile_mask(X[{2 * t}], X[{2 * t + 1}]);")
-        else:
-            pro.append(f"mq{t // 2} |= tile_mask(X[{2 * t}], X[{2 * t + 1}]) << 8;")
-    vals = ", ".join(f"mq{q}" if q < (nW + 1) // 2 else "0u" for q in range(4))
-    pro.append(f"*reinterpret_cast<u32x4*>(mask_wave + 0 + lane16) = u32x4{{{vals}}};      // mask row 0 = layer 0")
-    acc = accs[nW % 2]
-    vb = tp.h_blocks["view"][0]
-    pro.append("E0 = LDB(0); E1 = LDB(1024);")
-    pro.append(f"TMFMA0({acc}, E0, P1); MFMA({acc}, E1, P2);")
-    pro.append(f"store_tfrag<0>({acc}, ht_wave + {vb * 2048}, lane16); store_tfrag<8>({acc}, ht_wave + {vb * 2048}, lane16);")
-    pro += prologue_e
-    pro += prog.panels[0]["pre"]
-    final = list(prog.panels[-1]["post"])
-    final += [
-        "if (hi == 0 && s < M) {",
-        "    const float noisy_density = dnoise ? raw_density + dnoise_scale * dnoise[s] : raw_density;   // mip_nerf.py:232-233",
-        "    rgb_sigma[s] = make_float4(rgb_activation(raw_r, rgb_padding), rgb_activation(raw_g, rgb_padding),",
-        "                               rgb_activation(raw_b, rgb_padding), density_activation(noisy_density, density_bias));",
-        "    raw_out[s] = make_float4(raw_r, raw_g, raw_b, raw_density);",
-        "}",
-    ]
-    emit_tile_body(e, prog, side, nchunks, pro, final, lda)
-    e("    }")
-    e("}")
-    e("}  // namespace trainfwd" + sfx)
-    e("")
-    e(f"hipError_t launch_mlp_bf16_trainfwd{sfx}(const void* stream_w, const float* bias_tab, const void* pre_x, const void* pre_acc, const void* viewenc,")
-    e("                                    float* rgb_sigma, float* raw_out, void* HT, void* masks, int64_t M, int num_samples,")
-    e("                                    float density_bias, float rgb_padding, int grid_limit, const float* dnoise, float dnoise_scale,")
-    e("                                    hipStream_t st) {")
-    e(f"    using namespace trainfwd{sfx};")
-    e("    const int ntiles = (int)((M + kTileSamples - 1) / kTileSamples);")
-    e("    int grid = ntiles < grid_limit ? ntiles : grid_limit;")
-    e("    if (grid < 1) grid = 1;")
-    e("    static int attr_done[64] = {};")
-    e("    int dev = 0;")
-    e("    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;")
-    e("    if (!attr_done[dev]) {")
-    e("        hipError_t er = hipFuncSetAttribute((const void*)k_mlp_bf16_trainfwd_pre, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-    e("        if (er != hipSuccess) return er;")
-    e("        attr_done[dev] = 1;")
-    e("    }")
-    e(f"    hipLaunchKernelGGL(k_mlp_bf16_trainfwd_pre, dim3(grid), dim3({WAVES * 64}), kLdsBytes, st, (const char*)stream_w, bias_tab,")
-    e("                       (const char*)pre_x, (const char*)pre_acc, (const __bf16*)viewenc, (float4*)rgb_sigma, (float4*)raw_out, (char*)HT,")
-    e("                       (char*)masks, M, num_samples, ntiles, density_bias, rgb_padding, dnoise, dnoise_scale);")
-    e("    return hipGetLastError();")
-    e("}")
-    e("}  // namespace mip")
-    return "\n".join(lines) + "\n"
-
 
 
 # =================================================================================================================
@@ -712,19 +552,8 @@ def gen_dgrad(tp: TrainPlan, variant: int = 0) -> str:
     e(f"__global__ void __launch_bounds__({WAVES * 64})")
     e("k_mlp_bf16_dgrad(const char* __restrict__ stream, const float4* __restrict__ d_raw, const char* __restrict__ masks,")
     e("                 char* __restrict__ GT, int64_t M, int ntiles) {")
-    e("    extern __shared__ __attribute__((aligned(16))) char smem[];")
-    e("    const int tid = threadIdx.x;")
-    e("    const int lane = tid & 63;")
-    e("    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);")
-    e("    const int hi = lane >> 5, n = lane & 31;")
-    e("    const unsigned lane16 = (unsigned)lane * 16u;")
-    e("    const char* ring_lane = smem + lane16;")
-    e("    char* privw = smem + kPrivOff + wave * kPrivWaveBytes;          // wave-private (uniform base)")
-    e("    const char* priv_lane = privw + lane16;")
-    for ln in SELECTORS:
-        e("    " + ln)
-    e("    if (wave >= 4) __builtin_amdgcn_s_setprio(1);     // as the inference kernel (gen_mlp_bf16.py)")
-    e("    if ((int)blockIdx.x < ntiles) issue_group<DMA>(stream, smem, 0, 0, wave, lane16);")
+    lines += gc.thread_prologue(("privw", "priv_lane", "kPrivOff", "kPrivWaveBytes"), priv_note="          // wave-private (uniform base)",
+                                bias=False, selectors=True)
     e("    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {")
     e("        const bool has_next = tile + (int)gridDim.x < ntiles;")
     e("        const int64_t wt = (int64_t)tile * 8 + wave;")
@@ -739,11 +568,6 @@ def gen_dgrad(tp: TrainPlan, variant: int = 0) -> str:
     e("        bf16x8 X[16], Y[16], R, " + ", ".join(f"A{i}" for i in range(PREFETCH)) + ";")
     e("        f32x16 acc00, acc01, acc10, acc11;")
     e("        u32x4 MK0, MK1;")
-
-    def lda(c):
-        slot = (c // GROUP) % SLOTS
-        off = slot * GROUP * CHUNK_BYTES + (c % GROUP) * CHUNK_BYTES
-        return f"A{c % PREFETCH} = LDA({off});"
     rb = tp.g_blocks["raw"][0]
     pro = [
         "{",
@@ -758,30 +582,15 @@ def gen_dgrad(tp: TrainPlan, variant: int = 0) -> str:
     pro += prog.panels[0]["pre"]
     pro += [f"store_tfrag<0>(acc10, gt_wave + {rb * 2048}, lane16); store_tfrag<8>(acc10, gt_wave + {rb * 2048}, lane16);"]
     final = list(prog.panels[-1]["post"])
-    emit_tile_body(e, prog, side, nchunks, pro, final, lda)
+    emit_tile_body(e, prog, side, nchunks, pro, final)
     e("    }")
     e("}")
     e("}  // namespace dgrad" + sfx)
     e("")
     e(f"int mlp_dgrad_lds_bytes{sfx}() {{ return dgrad{sfx}::kLdsBytes; }}")
-    e(f"hipError_t launch_mlp_bf16_dgrad{sfx}(const void* stream_wT, const float* d_raw, const void* masks, void* GT, int64_t M,")
-    e("                                 int grid_limit, hipStream_t st) {")
-    e(f"    using namespace dgrad{sfx};")
-    e("    const int ntiles = (int)((M + kTileSamples - 1) / kTileSamples);")
-    e("    int grid = ntiles < grid_limit ? ntiles : grid_limit;")
-    e("    if (grid < 1) grid = 1;")
-    e("    static int attr_done[64] = {};")
-    e("    int dev = 0;")
-    e("    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;")
-    e("    if (!attr_done[dev]) {")
-    e("        hipError_t er = hipFuncSetAttribute((const void*)k_mlp_bf16_dgrad, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-    e("        if (er != hipSuccess) return er;")
-    e("        attr_done[dev] = 1;")
-    e("    }")
-    e(f"    hipLaunchKernelGGL(k_mlp_bf16_dgrad, dim3(grid), dim3({WAVES * 64}), kLdsBytes, st, (const char*)stream_wT,")
-    e("                       (const float4*)d_raw, (const char*)masks, (char*)GT, M, ntiles);")
-    e("    return hipGetLastError();")
-    e("}")
+    lines += gc.launcher(f"launch_mlp_bf16_dgrad{sfx}", "dgrad", ["k_mlp_bf16_dgrad"], namespace=f"dgrad{sfx}", launch=[
+        f"    hipLaunchKernelGGL(k_mlp_bf16_dgrad, dim3(grid), dim3({WAVES * 64}), kLdsBytes, st, (const char*)stream_wT,",
+        "                       (const float4*)d_raw, (const char*)masks, (char*)GT, M, ntiles);"])
     e("}  // namespace mip")
     return "\n".join(lines) + "\n"
 
@@ -816,41 +625,22 @@ def train_variants():
 def gen_train_variants_header(trainable, n, pre=()):
     """Declarations + dispatch tables of the per-variant training launchers and table blobs (nullptr: no bf16 training kernels).
     `pre`: the variants whose forward-with-save is the trunk of the two-kernel form (their row of kLaunchTrainFwd stays null)."""
-    L = ["// AUTO-GENERATED by gen_mlp_train.py from gen_mlp_bf16.VARIANTS -- do not edit by hand.", "#pragma once", '#include "kernels.hpp"']
+    name = lambda stem, vi: stem + (f"_v{vi}" if vi else "")
+    body = gc.fn_typedef("LaunchTrainFwdFn", "trainfwd") + gc.fn_typedef("LaunchTrainFwdPreFn", "trainfwd_pre") + gc.fn_typedef("LaunchDgradFn", "dgrad")
     for vi in trainable:
-        sfx = f"_v{vi}" if vi else ""
-        L.append(f'extern "C" const unsigned char mip_train_tables{sfx}[];')
-    L += ["namespace mip {",
-          "typedef hipError_t (*LaunchTrainFwdFn)(const void* stream_w, const float* bias_tab, const void* enc, const void* viewenc,",
-          "                                       float* rgb_sigma, float* raw_out, void* HT, void* masks, int64_t M, int num_samples,",
-          "                                       float density_bias, float rgb_padding, int grid_limit, const RayInputs* rays,",
-          "                                       const float* dnoise, float dnoise_scale, hipStream_t st);",
-          "typedef hipError_t (*LaunchTrainFwdPreFn)(const void* stream_w, const float* bias_tab, const void* pre_x, const void* pre_acc,",
-          "                                          const void* viewenc, float* rgb_sigma, float* raw_out, void* HT, void* masks, int64_t M,",
-          "                                          int num_samples, float density_bias, float rgb_padding, int grid_limit, const float* dnoise,",
-          "                                          float dnoise_scale, hipStream_t st);",
-          "typedef hipError_t (*LaunchDgradFn)(const void* stream_wT, const float* d_raw, const void* masks, void* GT, int64_t M,",
-          "                                    int grid_limit, hipStream_t st);"]
-    for vi in trainable:
-        if vi == 0:
+        if vi == 0:      # declared in kernels.hpp
             continue
         if vi in pre:
-            L.append(f"hipError_t launch_mlp_bf16_trainfwd_pre_v{vi}(const void*, const float*, const void*, const void*, const void*, float*, float*, void*, void*,")
-            L.append("                                            int64_t, int, float, float, int, const float*, float, hipStream_t);")
+            body += gc.prototype(f"launch_mlp_bf16_trainfwd_pre_v{vi}", "trainfwd_pre")
         else:
-            L.append(f"hipError_t launch_mlp_bf16_trainfwd_v{vi}(const void*, const float*, const void*, const void*, float*, float*, void*, void*,")
-            L.append("                                        int64_t, int, float, float, int, const RayInputs*, const float*, float, hipStream_t);")
-        L.append(f"hipError_t launch_mlp_bf16_dgrad_v{vi}(const void*, const float*, const void*, void*, int64_t, int, hipStream_t);")
-
-    def tab(fmt0, fmtv, which):
-        return ", ".join((fmt0 if vi == 0 else fmtv.format(vi)) if vi in which else "nullptr" for vi in range(n))
-    std = [vi for vi in trainable if vi not in pre]
-    L.append(f"static const LaunchTrainFwdFn kLaunchTrainFwd[{n}] = {{{tab('launch_mlp_bf16_trainfwd', 'launch_mlp_bf16_trainfwd_v{}', std)}}};")
-    L.append(f"static const LaunchTrainFwdPreFn kLaunchTrainFwdPre[{n}] = {{{tab('nullptr', 'launch_mlp_bf16_trainfwd_pre_v{}', list(pre))}}};")
-    L.append(f"static const LaunchDgradFn kLaunchDgrad[{n}] = {{{tab('launch_mlp_bf16_dgrad', 'launch_mlp_bf16_dgrad_v{}', trainable)}}};")
-    L.append(f"static const unsigned char* const kTrainTableBlobs[{n}] = {{{tab('mip_train_tables', 'mip_train_tables_v{}', trainable)}}};")
-    L.append("}  // namespace mip")
-    return "\n".join(L) + "\n"
+            body += gc.prototype(f"launch_mlp_bf16_trainfwd_v{vi}", "trainfwd")
+        body += gc.prototype(f"launch_mlp_bf16_dgrad_v{vi}", "dgrad")
+    rows = [("LaunchTrainFwdFn", "kLaunchTrainFwd", {vi: name("launch_mlp_bf16_trainfwd", vi) for vi in trainable if vi not in pre}),
+            ("LaunchTrainFwdPreFn", "kLaunchTrainFwdPre", {vi: f"launch_mlp_bf16_trainfwd_pre_v{vi}" for vi in pre}),
+            ("LaunchDgradFn", "kLaunchDgrad", {vi: name("launch_mlp_bf16_dgrad", vi) for vi in trainable}),
+            ("unsigned char* const", "kTrainTableBlobs", {vi: name("mip_train_tables", vi) for vi in trainable})]
+    return gc.dispatch_header("// AUTO-GENERATED by gen_mlp_train.py from gen_mlp_bf16.VARIANTS -- do not edit by hand.", body, rows, n,
+                              before_namespace=[f'extern "C" const unsigned char {name("mip_train_tables", vi)}[];' for vi in trainable])
 
 
 def main():

@@ -29,15 +29,12 @@ Usage: python gen_pre_gemm.py [outdir]
 import os
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
-sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gen_common as gc  # noqa: E402
 import gen_mlp_bf16 as gb  # noqa: E402
+from gen_common import CHUNK_BYTES as CHUNK, HERE, PREFETCH, WAVES  # noqa: E402
 from mipnerf_pl_amd.mlp_pre_plan import GROUP, RING_SLOTS, PrePlan, supported  # noqa: E402
 
-WAVES = 8
-CHUNK = 1024
-PREFETCH = 4                                              # A fragments in flight (registers A0..A3)
 # rotating B-operand registers EB0..: DEPTH - 1 k-steps in flight.  Must divide the 84 k-steps of a tile (12 or 14), so that the register of
 # k-step s is the same in every tile (the loads run ahead across the tile boundary)
 DEPTH = 12
@@ -60,20 +57,17 @@ def gen_gemm(p: PrePlan, vi: int) -> str:
     split = p.split
     depth = DEPTH_SPLIT if split else DEPTH
     nsteps = nk if split else 2 * nk     # k-steps per tile and wave
-    assert depth < nk and GROUP % nt == 0 and nsteps % depth == 0, "the B-register rotation must be tile-periodic"
+    assert depth < nk and GROUP % nt == 0 and nt % PREFETCH == 0 and nsteps % depth == 0, "the B-register rotation must be tile-periodic"
     tile_waves = 4 if split else WAVES   # wave tiles (32 samples) per workgroup tile
     nslots = nsteps * nt                 # MFMAs per wave and tile
 
-    def lda(c):
+    def a_load(c):
         """A fragment of wave-local slot c.  Split form: the stream is [k-step][matrix][tile]; the matrix (= the wave's half of the workgroup)
         is a wave-uniform 8-KiB offset folded into ring_lane"""
         if split:
             ks, t = divmod(c, nt)
-            gc = ks * 2 * nt + t
-        else:
-            gc = c
-        slot = (gc // GROUP) % RING_SLOTS
-        return f"A{c % PREFETCH} = LDA({slot * GROUP * CHUNK + (gc % GROUP) * CHUNK});"
+            c = ks * 2 * nt + t          # (same rotating register: nt is a multiple of PREFETCH)
+        return gc.lda(c, GROUP, RING_SLOTS)
 
     slots_per_group = GROUP // 2 if split else GROUP      # wave-local MFMA slots between two ring barriers
 
@@ -95,7 +89,7 @@ def gen_gemm(p: PrePlan, vi: int) -> str:
         lc = c + PREFETCH
         if lc % slots_per_group == 0:
             E("gb", (lc // slots_per_group) % ngroups)  # lc == nslots: group 0 of the NEXT tile (its first A loads follow below)
-        E("stmt", lda(lc % nslots))                     # past the end: the next tile's first fragments (harmless after the last tile)
+        E("stmt", a_load(lc % nslots))                  # past the end: the next tile's first fragments (harmless after the last tile)
         if t == nt - 1:
             # load the operand depth - 1 k-steps ahead (wrapping into the next pass / the next tile) into the register the PREVIOUS
             # k-step read, so the youngest MFMA that used it is 8 slots back
@@ -240,7 +234,7 @@ def gen_gemm(p: PrePlan, vi: int) -> str:
     e(f"    RING_BARRIER({vmk[0]});")
     e("    issue_group<DMA>(stream, smem, 2, 2, wave, lane16);")
     for c in range(PREFETCH):
-        e(f"    {lda(c)}")
+        e(f"    {a_load(c)}")
     e("    for (;;) {")
     e("        const int tnext = tile + nwg;")
     e("        const bool has_next = tnext < ntiles;")
@@ -282,57 +276,31 @@ def gen_gemm(p: PrePlan, vi: int) -> str:
     e(f"}}  // namespace pre_v{vi}")
     e("")
     e("// enc: bf16, fragment layout (frag != 0; ceil(M / 256) * 8 wave tiles) or row-major [M, xyz_dim]; pre_x / pre_acc: 16 KiB / 32 KiB per wave tile")
-    e(f"hipError_t launch_pre_gemm_v{vi}(const void* stream_w, const float* bias_tab, const void* enc, int frag, void* pre_x, void* pre_acc,")
-    e("                              int64_t M, int grid_limit, hipStream_t st) {")
-    e(f"    using namespace pre_v{vi};")
-    e("    const int64_t nt64 = (M + kTileSamples - 1) / kTileSamples;")
-    e("    if (nt64 < 1 || nt64 > 0x7fffffff) return hipErrorInvalidValue;")
-    e("    const int ntiles = (int)nt64;")
-    e("    int grid = ntiles < grid_limit ? ntiles : grid_limit;")
-    e("    if (grid < 1) grid = 1;")
-    e("    static int attr_done[64] = {};")
-    e("    int dev = 0;")
-    e("    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;")
-    e("    if (!attr_done[dev]) {")
-    e("        hipError_t er = hipFuncSetAttribute((const void*)k_pre_gemm<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-    e("        if (er != hipSuccess) return er;")
-    e("        er = hipFuncSetAttribute((const void*)k_pre_gemm<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);")
-    e("        if (er != hipSuccess) return er;")
-    e("        attr_done[dev] = 1;")
-    e("    }")
-    e(f"    if (frag) hipLaunchKernelGGL((k_pre_gemm<true>), dim3(grid), dim3({WAVES * 64}), kLdsBytes, st, (const char*)stream_w, bias_tab, (const char*)enc,")
-    e("                                 (char*)pre_x, (char*)pre_acc, M, ntiles, grid);")
-    e(f"    else hipLaunchKernelGGL((k_pre_gemm<false>), dim3(grid), dim3({WAVES * 64}), kLdsBytes, st, (const char*)stream_w, bias_tab, (const char*)enc,")
-    e("                            (char*)pre_x, (char*)pre_acc, M, ntiles, grid);")
-    e("    return hipGetLastError();")
-    e("}")
+    launch = "hipLaunchKernelGGL((k_pre_gemm<%s>), dim3(grid), dim3(%d), kLdsBytes, st, (const char*)stream_w, bias_tab, (const char*)enc,"
+    L += gc.launcher(f"launch_pre_gemm_v{vi}", "pre_gemm", ["k_pre_gemm<true>", "k_pre_gemm<false>"], namespace=f"pre_v{vi}",
+                     range_check="nt64 < 1 || nt64 > 0x7fffffff", launch=[
+        "    if (frag) " + launch % ("true", WAVES * 64),
+        "                                 (char*)pre_x, (char*)pre_acc, M, ntiles, grid);",
+        "    else " + launch % ("false", WAVES * 64),
+        "                            (char*)pre_x, (char*)pre_acc, M, ntiles, grid);"])
     e("}  // namespace mip")
     return "\n".join(L) + "\n"
 
 
 def variants_header(vis, n):
-    L = ["// AUTO-GENERATED by gen_pre_gemm.py -- do not edit by hand.", "#pragma once", '#include "kernels.hpp"', "namespace mip {",
-         "// two-kernel bf16 MLP of the variants whose encoding is too wide for k_mlp_bf16's wave-private LDS area (mlp_pre_plan.py)",
-         "typedef hipError_t (*LaunchPreGemmFn)(const void* stream_w, const float* bias_tab, const void* enc, int frag, void* pre_x, void* pre_acc,",
-         "                                      int64_t M, int grid_limit, hipStream_t st);",
-         "typedef hipError_t (*LaunchBf16PreFn)(const void* stream_w, const float* bias_tab, const void* pre_x, const void* pre_acc, const void* viewenc,",
-         "                                      float* rgb_sigma, float* raw_out, int64_t M, int num_samples, float density_bias, float rgb_padding,",
-         "                                      int grid_limit, const float* dnoise, float dnoise_scale, hipStream_t st);"]
+    body = ["// two-kernel bf16 MLP of the variants whose encoding is too wide for k_mlp_bf16's wave-private LDS area (mlp_pre_plan.py)"]
+    body += gc.fn_typedef("LaunchPreGemmFn", "pre_gemm") + gc.fn_typedef("LaunchBf16PreFn", "bf16_pre")
     for vi in vis:
-        L.append(f"hipError_t launch_pre_gemm_v{vi}(const void*, const float*, const void*, int, void*, void*, int64_t, int, hipStream_t);")
-        L.append(f"hipError_t launch_mlp_bf16_pre_v{vi}(const void*, const float*, const void*, const void*, const void*, float*, float*, int64_t, int, float,")
-        L.append("                                   float, int, const float*, float, hipStream_t);")
-        L.append(f"hipError_t launch_mlp_bf16_fused_v{vi}(const void*, const float*, const void*, const void*, const void*, float*, float*, int64_t, int, float,")
-        L.append("                                     float, int, const float*, float, hipStream_t);")
-        L.append(f'extern "C" const unsigned char mip_pre_tables_v{vi}[];')
-    f = lambda fmt: ", ".join(fmt.format(vi) if vi in vis else "nullptr" for vi in range(n))
-    L.append(f"static const LaunchPreGemmFn kLaunchPreGemm[{n}] = {{{f('launch_pre_gemm_v{}')}}};")
-    L.append(f"static const LaunchBf16PreFn kLaunchBf16Pre[{n}] = {{{f('launch_mlp_bf16_pre_v{}')}}};")
-    L.append("// one-kernel form (round 6): same launcher shape as the trunk's; pre_x = the encoding's fragment buffer, pre_acc = nullptr")
-    L.append(f"static const LaunchBf16PreFn kLaunchBf16Fused[{n}] = {{{f('launch_mlp_bf16_fused_v{}')}}};")
-    L.append(f"static const unsigned char* const kPreTableBlobs[{n}] = {{{f('mip_pre_tables_v{}')}}};")
-    L.append("}  // namespace mip")
-    return "\n".join(L) + "\n"
+        body += gc.prototype(f"launch_pre_gemm_v{vi}", "pre_gemm")
+        body += gc.prototype(f"launch_mlp_bf16_pre_v{vi}", "bf16_pre") + gc.prototype(f"launch_mlp_bf16_fused_v{vi}", "bf16_pre")
+        body.append(f'extern "C" const unsigned char mip_pre_tables_v{vi}[];')
+    f = lambda fmt: {vi: fmt.format(vi) for vi in vis}
+    return gc.dispatch_header("// AUTO-GENERATED by gen_pre_gemm.py -- do not edit by hand.", body, [
+        ("LaunchPreGemmFn", "kLaunchPreGemm", f("launch_pre_gemm_v{}")),
+        ("LaunchBf16PreFn", "kLaunchBf16Pre", f("launch_mlp_bf16_pre_v{}")),
+        "// one-kernel form (round 6): same launcher shape as the trunk's; pre_x = the encoding's fragment buffer, pre_acc = nullptr",
+        ("LaunchBf16PreFn", "kLaunchBf16Fused", f("launch_mlp_bf16_fused_v{}")),
+        ("unsigned char* const", "kPreTableBlobs", f("mip_pre_tables_v{}"))], n)
 
 
 def main():

@@ -448,3 +448,56 @@ def test_sample_count_limit_is_one_number_everywhere():
             n += 1
         assert src.count("(8); break;") == src.count("(16); break;"), f          # no dispatch without the 16-samples-per-lane bucket
     assert n == 7
+
+
+def _type_list(params):
+    """The types of a C++ parameter list: names and default arguments dropped, whitespace normalised."""
+    out = []
+    for p in params.split(","):
+        p = " ".join(p.split("=")[0].split())
+        m = re.fullmatch(r"(.*[\s*&])([A-Za-z_]\w*)", p)
+        if m and m.group(1).strip() != "const":          # "<type> <name>"; an unnamed "const float*" or "int" has no name to drop
+            p = m.group(1)
+        out.append(re.sub(r"\s*([*&])\s*", r"\1", p).strip())
+    return out
+
+
+def test_generated_launcher_signatures_have_one_source(tmp_path):
+    """Every launch_* the generators define has ONE parameter list (gen_common.SIGNATURES): the type list of its definition equals that of
+    its prototype in the generated dispatch header, of the function-pointer typedef of every table that holds it, and -- for the variant-0
+    launchers, which kernels.hpp declares by hand -- of the declaration there."""
+    import subprocess
+    import sys
+    csrc = os.path.join(REPO, "mipnerf_pl_amd", "csrc")
+    for gen in ("gen_mlp_bf16.py", "gen_mlp_train.py", "gen_mlp_f32r.py", "gen_pre_gemm.py"):
+        subprocess.run([sys.executable, os.path.join(csrc, gen), str(tmp_path)], check=True, stdout=subprocess.DEVNULL)
+    defs, protos, typedefs, tabled = {}, {}, {}, {}
+    for f in sorted(os.listdir(tmp_path)):
+        src = open(os.path.join(tmp_path, f), errors="replace").read() if f.endswith((".hip", ".hpp")) else ""
+        if f.endswith(".hip"):
+            for m in re.finditer(r"^hipError_t (launch_\w+)\(([^()]*)\) \{", src, re.M):
+                assert m.group(1) not in defs, m.group(1)
+                defs[m.group(1)] = _type_list(m.group(2))
+        elif f.endswith("_variants_gen.hpp"):
+            for m in re.finditer(r"^hipError_t (launch_\w+)\(([^()]*)\);", src, re.M):
+                assert m.group(1) not in protos, m.group(1)
+                protos[m.group(1)] = _type_list(m.group(2))
+            for m in re.finditer(r"^typedef hipError_t \(\*(\w+)\)\(([^()]*)\);", src, re.M):
+                typedefs[m.group(1)] = _type_list(m.group(2))
+            for m in re.finditer(r"^static const (\w+) k\w+\[\d+\] = \{([^}]*)\};", src, re.M):
+                for name in re.findall(r"\blaunch_\w+", m.group(2)):
+                    tabled.setdefault(name, []).append(m.group(1))
+    hand = {m.group(1): _type_list(m.group(2))
+            for m in re.finditer(r"^hipError_t (launch_\w+)\(([^()]*)\);", open(os.path.join(csrc, "kernels.hpp")).read(), re.M)}
+    nunits = sum(f.endswith(".hip") for f in os.listdir(tmp_path))
+    assert len(defs) == nunits >= 18 and len(typedefs) == 7          # one launcher per generated unit, one typedef per launcher kind
+    variant0 = sorted(n for n in defs if not re.search(r"_v\d+$", n))
+    assert variant0 == ["launch_mlp_bf16", "launch_mlp_bf16_dgrad", "launch_mlp_bf16_trainfwd"]
+    for name, types in defs.items():
+        assert len(types) >= 7 and all(types), (name, types)
+        declared = hand if name in variant0 else protos
+        assert declared.get(name) == types, (name, "declaration", declared.get(name), types)
+        assert tabled.get(name), f"{name} is in no dispatch table"
+        for t in tabled[name]:
+            assert typedefs[t] == types, (name, t, typedefs[t], types)
+    assert sorted(protos) == sorted(n for n in defs if n not in variant0)

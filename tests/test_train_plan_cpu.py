@@ -148,16 +148,21 @@ def test_variant_plan_emulates_and_is_embedded(vi, arch_kw, shape):
 
 def test_generator_schedule_passes_hazard_check(tmp_path):
     """gen_mlp_train.py replays both tile programs and asserts the register-set discipline (every B operand of op i
-    was written by op i-1, every transposed register by the op that stores it)."""
-    out = subprocess.run([sys.executable, os.path.join(REPO, "mipnerf_pl_amd", "csrc", "gen_mlp_train.py"), str(tmp_path)],
-                         capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-2000:]
-    for f in ("mlp_bf16_trainfwd_gen.hip", "mlp_bf16_dgrad_gen.hip", "mlp_bf16_trainfwd_gen_v1.hip", "mlp_bf16_dgrad_gen_v1.hip",
-              "mlp_bf16_trainfwd_gen_v2.hip", "mlp_bf16_dgrad_gen_v2.hip", "mlp_bf16_trainfwd_gen_v3.hip", "mlp_bf16_dgrad_gen_v3.hip",
-              "mlp_bf16_trainfwd_gen_v5.hip", "mlp_bf16_dgrad_gen_v5.hip"):
-        gen = open(os.path.join(tmp_path, f)).read()
-        committed = open(os.path.join(REPO, "mipnerf_pl_amd", "csrc", f)).read()
-        assert gen == committed, f"{f} is stale: re-run python -m mipnerf_pl_amd.build"
+    was written by op i-1, every transposed register by the op that stores it); so do the other generators for their kernels.
+    And every generated source or header present in csrc/ -- the tracked ones in a clean checkout, all of them in a built tree --
+    is byte for byte what the four generators write."""
+    csrc = os.path.join(REPO, "mipnerf_pl_amd", "csrc")
+    for gen in ("gen_mlp_bf16.py", "gen_mlp_train.py", "gen_mlp_f32r.py", "gen_pre_gemm.py"):
+        out = subprocess.run([sys.executable, os.path.join(csrc, gen), str(tmp_path)], capture_output=True, text=True)
+        assert out.returncode == 0, out.stderr[-2000:]
+    compared = 0
+    for f in sorted(os.listdir(tmp_path)):
+        if f.endswith((".hip", ".hpp")) and os.path.exists(os.path.join(csrc, f)):
+            gen = open(os.path.join(tmp_path, f), "rb").read()
+            committed = open(os.path.join(csrc, f), "rb").read()
+            assert gen == committed, f"{f} is stale: re-run python -m mipnerf_pl_amd.build"
+            compared += 1
+    assert compared >= 23, compared          # the 18 tracked .hip units and 5 headers at least
 
 
 @pytest.mark.parametrize("arch_kw", [dict(net_width=192, net_width_condition=64), dict(net_width=64, net_width_condition=64)])
