@@ -111,24 +111,121 @@ def maxdiff(a, b):
 import torch.nn.functional as F  # noqa: E402
 
 
-def mlp_torch(mlp, samples_enc, viewdirs_enc, dtype):
-    """models/mip_nerf.py:75-111 through torch ops (library GEMMs): plain-PyTorch fp32 reference of the MLP for the tests."""
-    def lin(layer, x):
-        return F.linear(x, layer.weight.to(dtype), layer.bias.to(dtype))
+def mlp_functional(p, samples_enc, viewdirs_enc, skip_index, pre=None):
+    """models/mip_nerf.py:75-111 through torch ops on a dict of state_dict-named tensors, in THEIR dtype (float64 leaves give the
+    float64 reference and its autograd gradients).  viewdirs_enc=None is MLP.forward(x, None) (:99-110): colour and density heads
+    both read the trunk, extra_layer / view_layers are unused.  `pre` (a list) receives every hidden layer's pre-activation, trunk
+    layers first, then the view layers."""
+    def lin(name, x):
+        return F.linear(x, p[name + ".weight"], p[name + ".bias"])
+
+    def hidden(name, x):
+        h = lin(name, x)
+        if pre is not None:
+            pre.append(h)
+        return torch.relu(h)
     num_samples = samples_enc.shape[1]
-    inputs = samples_enc.to(dtype)
+    inputs = samples_enc
     x = inputs
-    for i, layer in enumerate(mlp.layers):
-        x = torch.relu(lin(layer[0], x))
-        if i % mlp.skip_index == 0 and i > 0:
+    for i in range(sum(1 for k in p if k.startswith("layers.") and k.endswith(".weight"))):
+        x = hidden(f"layers.{i}.0", x)
+        if i % skip_index == 0 and i > 0:
             x = torch.cat([x, inputs], dim=-1)
-    raw_density = lin(mlp.density_layer, x)
-    bottleneck = lin(mlp.extra_layer, x)
-    vd = viewdirs_enc.to(dtype)[:, None, :].expand(-1, num_samples, -1)
-    x = torch.cat([bottleneck, vd], dim=-1)
-    for layer in mlp.view_layers:
-        x = torch.relu(lin(layer[0], x))
-    raw_rgb = lin(mlp.color_layer, x)
-    return torch.cat([raw_rgb, raw_density], dim=-1).float()
+    raw_density = lin("density_layer", x)
+    if viewdirs_enc is not None:
+        bottleneck = lin("extra_layer", x)
+        vd = viewdirs_enc[:, None, :].expand(-1, num_samples, -1)
+        x = torch.cat([bottleneck, vd], dim=-1)
+        for i in range(sum(1 for k in p if k.startswith("view_layers.") and k.endswith(".weight"))):
+            x = hidden(f"view_layers.{i}.0", x)
+    raw_rgb = lin("color_layer", x)
+    return torch.cat([raw_rgb, raw_density], dim=-1)
 
 
+def mlp_torch(mlp, samples_enc, viewdirs_enc, dtype):
+    """models/mip_nerf.py:75-111 through torch ops (library GEMMs): plain-PyTorch fp32 reference of the MLP for the tests
+    (viewdirs_enc=None: the use_viewdirs=False form)."""
+    p = {k: v.to(dtype) for k, v in mlp.named_parameters()}
+    vd = None if viewdirs_enc is None else viewdirs_enc.to(dtype)
+    return mlp_functional(p, samples_enc.to(dtype), vd, mlp.skip_index).float()
+
+
+# ---- float64 reference of the fp32 MLP backward at ragged sizes (test_gpu_f32_backward.py) ----------------------------------------
+# rows at the tile, K-block, split and slice boundaries of the fp32 backward's kernels: their d_raw is scaled by
+# F32_BOUNDARY_GAIN, so one of them dropped or counted twice moves every used gradient by far more than the bound
+F32_BOUNDARY_ROWS = (15, 16, 63, 64, 255, 256, 511, 512, 2047, 2048, 2079, 2080)
+F32_BOUNDARY_GAIN = 4.0
+F32_MASK_MARGIN = 32.0
+F32_MASK_ROUNDS = 20
+
+
+def f32_boundary_rows(M):
+    return sorted({0, M - 1} | {r for r in F32_BOUNDARY_ROWS if r < M})
+
+
+def mlp_grads(params, enc, venc, d_raw, skip_index, dtype, enc_grad=False, pre=None):
+    """raw and the autograd gradients of sum(raw * d_raw) of mlp_functional in `dtype`, on the CPU: (raw, {name: grad or None for
+    a parameter the architecture does not use}, d_enc or None)"""
+    p = {k: torch.from_numpy(v).to(dtype).requires_grad_(True) for k, v in params.items()}
+    e = torch.from_numpy(enc).to(dtype).requires_grad_(enc_grad)
+    v = None if venc is None else torch.from_numpy(venc).to(dtype)
+    raw = mlp_functional(p, e, v, skip_index, pre)
+    (raw * torch.from_numpy(d_raw).to(dtype)).sum().backward()
+    return raw.detach(), {k: None if t.grad is None else t.grad.detach() for k, t in p.items()}, e.grad
+
+
+def f32_backward_case(arch, B, N, seed, use_viewdirs=True):
+    """Seeded inputs of one MLP backward whose ReLU signs are the same in float64 and in fp32 (so that the gradient is the same
+    linear map of d_raw in both).  arch = oracle make_params keywords.  For every hidden layer delta = max |pre-activation(float64)
+    - pre-activation(torch fp32)| and tau = F32_MASK_MARGIN * delta; a sample with a float64 pre-activation inside +-tau gets a
+    fresh encoding row from the same generator (its index and d_raw stay), at most F32_MASK_ROUNDS times.  Reference only: no
+    kernel runs here."""
+    rng = np.random.default_rng(seed)
+    M = B * N
+    params = orc.make_params(seed, density_gain=10.0, **arch)
+    skip = arch.get("skip_index", 4)
+    enc = rng.uniform(-1.0, 1.0, (B, N, 96)).astype(np.float32)
+    venc = rng.uniform(-1.0, 1.0, (B, 27)).astype(np.float32)
+    d_raw = rng.standard_normal((B, N, 4)).astype(np.float32)
+    d_raw.reshape(M, 4)[f32_boundary_rows(M)] *= np.float32(F32_BOUNDARY_GAIN)
+    p64 = {k: torch.from_numpy(v).double() for k, v in params.items()}
+    p32 = {k: torch.from_numpy(v) for k, v in params.items()}
+    v32 = torch.from_numpy(venc) if use_viewdirs else None
+    v64 = v32.double() if use_viewdirs else None
+    # the first pass and the last one (the verdict) cover every sample; the passes in between only the redrawn rows, with delta the
+    # largest seen so far
+    enc2 = enc.reshape(M, 96)
+    delta = [0.0] * sum(1 for k in params if k.endswith("0.weight"))
+    rows, full, rounds = np.arange(M), True, 0
+    while True:
+        pre64, pre32 = [], []
+        with torch.no_grad():
+            e32 = torch.from_numpy(enc2[rows])[:, None, :]
+            mlp_functional(p64, e32.double(), None if v64 is None else v64[rows // N], skip, pre64)
+            mlp_functional(p32, e32, None if v32 is None else v32[rows // N], skip, pre32)
+        delta = [max(d, float((a - b.double()).abs().max())) for d, a, b in zip(delta, pre64, pre32)]
+        tau = [F32_MASK_MARGIN * d for d in delta]
+        close = torch.zeros(rows.size, dtype=torch.bool)
+        for a, t in zip(pre64, tau):
+            close |= (a.abs() <= t).any(-1).reshape(-1)
+        bad = rows[close.numpy()]
+        if bad.size == 0 and full:
+            break
+        if bad.size == 0:
+            rows, full = np.arange(M), True
+            continue
+        if rounds == F32_MASK_ROUNDS:
+            break
+        enc2[bad] = rng.uniform(-1.0, 1.0, (bad.size, 96)).astype(np.float32)
+        rows, full, rounds = bad, False, rounds + 1
+    assert bad.size == 0, f"{bad.size} samples still have a pre-activation inside +-tau after {F32_MASK_ROUNDS} rounds"
+    return dict(params=params, enc=enc, venc=venc, d_raw=d_raw, skip_index=skip, use_viewdirs=use_viewdirs, delta=delta, tau=tau,
+                rounds=rounds)
+
+
+def rel_err(x, ref):
+    """max |x - ref| / max |ref| in float64"""
+    x = x.detach().double().cpu() if torch.is_tensor(x) else torch.from_numpy(np.asarray(x)).double()
+    ref = ref.detach().double().cpu()
+    assert x.shape == ref.shape, (x.shape, ref.shape)
+    return float((x - ref).abs().max() / ref.abs().max())
