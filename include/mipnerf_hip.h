@@ -543,7 +543,7 @@ int mipnerf_set_option(mipnerf_ctx* ctx, int option, int value);
  * (option 2); synchronises on the recorded events. */
 int mipnerf_mlp_launch_stats(mipnerf_ctx* ctx, double* total_ms, int64_t* launches);
 /* Host-only exports of the static plan tables (no GPU needed), used by the CPU tests to
- * prove the C++ plan expansion equals mipnerf_pl_amd/mlp_plan.py.  which: 0 = bf16 stream
+ * prove that the tables the library expands from its embedded chunk records (mlp_plan.blob) equal mipnerf_pl_amd/mlp_plan.py.  which: 0 = bf16 stream
  * pack table, 1 = bias table, 2 = fp32 stream pack table (flat parameter indices, -1 = 0) of Plan.build(),
  * 3 = dgrad (W^T) stream pack table, 4 = wgrad partial -> parameter index table, 5 = wgrad job table,
  * 6 = pack table and 7 = bias table of the stream the bf16 forward kernels read (Plan.build(fold_view=True): the bottleneck

@@ -4,7 +4,7 @@
 
 Steps: (1) run the four generators of csrc/ (what they share lives in csrc/gen_common.py), one kernel per architecture variant <i> of
 gen_mlp_bf16.VARIANTS (variant 0 of the first two without the suffix):
-    gen_mlp_bf16.py   mlp_bf16_gen[_v<i>].hip, mlp_plan_gen.hpp, mlp_variants_gen.hpp
+    gen_mlp_bf16.py   mlp_bf16_gen[_v<i>].hip, _gen_plan_tables[_v<i>].bin, mlp_plan_gen.hpp, mlp_variants_gen.hpp
     gen_mlp_train.py  mlp_bf16_trainfwd_gen[_v<i>].hip or mlp_bf16_trainfwd_pre_gen_v<i>.hip, mlp_bf16_dgrad_gen[_v<i>].hip,
                       _gen_train_tables[_v<i>].bin, mlp_train_variants_gen.hpp
     gen_mlp_f32r.py   mlp_f32r_gen_v<i>.hip, _gen_f32r_tables_v<i>.bin, mlp_f32r_variants_gen.hpp
@@ -57,7 +57,7 @@ UNITS = [
 # the generated per-variant families: (unit stem, flags of its units, stem of its table blob, linker symbol of the blob); a unit is
 # <stem>_v<i>.hip, a blob <stem>[_v<i>].bin linked in as <symbol>[_v<i>].  The fused IPE must round like kernels_ray.hip.
 FAMILIES = [
-    ("mlp_bf16_gen", NO_IEEE + ["-ffp-contract=off"], None, None),
+    ("mlp_bf16_gen", NO_IEEE + ["-ffp-contract=off"], "_gen_plan_tables", "mip_plan_tables"),
     ("mlp_bf16_trainfwd_gen", NO_IEEE + ["-ffp-contract=off"], "_gen_train_tables", "mip_train_tables"),
     ("mlp_bf16_trainfwd_pre_gen", NO_IEEE + ["-ffp-contract=off"], None, None),
     ("mlp_bf16_dgrad_gen", NO_IEEE, None, None),

@@ -46,156 +46,104 @@ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 using mip::plan::PlanDesc;
 
-// ---- plan expansion (mirror of mlp_plan.Plan.pack_table / bias_table / pack_table_f32) ----------
-struct Tables {
-    std::vector<int32_t> pack_bf16;   // [kNumChunks*512] flat parameter index or -1
-    std::vector<int32_t> bias;        // [kNumTiles*32]
-    std::vector<int32_t> pack_f32;    // [kNumChunks*512]
-    std::vector<int> tensor_off;      // flat offset of each parameter tensor
-    int total_params = 0;
-    mip::F32Net net;
+// ---- plan tables: binary blob produced by mlp_plan.blob() (the only definition of the weight-stream layout), linked in by
+// train_tables.c.  Every 512-entry chunk of a pack table travels as one record (tensor, row0, ld, nrows, col[16]) ----------
+constexpr int kDescInts = 20, kLayerInts = 12;
+struct PlanTables {
+    const int32_t* pack = nullptr;       // [num_chunks] records of the plain plan's bf16 stream (debug table 0)
+    const int32_t* bias = nullptr;       // [num_tiles * 32] flat parameter index or -1 (the fp32 kernel's bias table)
+    const int32_t* fwd_pack = nullptr;   // [fwd_num_chunks] records of the bf16 forward kernels' stream
+    const int32_t* fwd_bias = nullptr;   // [fwd_num_tiles * 32]
+    const int32_t* pack_f32 = nullptr;   // [n_f32_chunks] records of the fp32 stream
+    const int32_t* layers = nullptr;     // [num_ops] rows x_in0, kb0, x_in1, kb1, x_out, ntiles, first_tile, relu, kind, chunk0, stage_view, enc_mask
+    int n_f32_chunks = 0;
 };
 
-int kmap(int kind, int ksl, int hi, int j) {
-    if (kind == 0) return ksl * 16 + hi * 8 + j;
-    const int t = ksl >> 1, u = ksl & 1;
-    return 32 * t + 8 * (2 * u + (j >> 2)) + 4 * hi + (j & 3);
+int total_params(const PlanDesc& P) {
+    int n = 0;
+    for (int i = 0; i < P.num_param_tensors; ++i) n += P.param_numel[i];
+    return n;
 }
 
-void build_tables(Tables& T, const PlanDesc& P) {
-    using namespace mip::plan;
-    const OpDesc* kOps = P.ops;
-    const int kNumOps = P.num_ops, kNetWidth = P.net_width, kXyzDim = P.xyz_dim;
-    T.tensor_off.resize(P.num_param_tensors);
-    int off = 0;
-    for (int i = 0; i < P.num_param_tensors; ++i) { T.tensor_off[i] = off; off += P.param_numel[i]; }
-    T.total_params = off;
-    T.pack_bf16.assign((size_t)P.num_chunks * 512, -1);      // includes the zero padding chunks at the end of the stream
-    T.pack_f32.assign((size_t)P.num_chunks * 512, -1);
-    T.bias.assign((size_t)P.num_tiles * 32, -1);
-    size_t ci = 0;
-    auto fill_chunk = [&](const OpDesc& op, int ti, int ks) {
-        const TileDesc& tile = op.tiles[ti];
-        int ksl = ks, si = 0;
-        while (ksl >= op.segs[si].nk) { ksl -= op.segs[si].nk; ++si; }
-        const SegDesc& seg = op.segs[si];
-        for (int hi = 0; hi < 2; ++hi)
-            for (int j = 0; j < 8; ++j) {
-                const int c = kmap(seg.kind, ksl, hi, j);
-                if (c >= seg.ncols) continue;
-                for (int m = 0; m < tile.nrows; ++m)
-                    T.pack_bf16[ci * 512 + (size_t)(hi * 32 + m) * 8 + j] =
-                        T.tensor_off[tile.wt] + (tile.row0 + m) * tile.ld + seg.col0 + c;
-            }
-        ++ci;
-    };
-    for (int oi = 0; oi < kNumOps; ++oi) {
-        const OpDesc& op = kOps[oi];
-        int nk = 0;
-        for (int s = 0; s < op.nsegs; ++s) nk += op.segs[s].nk;
-        for (int t = 0; t < op.ntiles; t += 2) {
-            const bool pair = t + 1 < op.ntiles;
-            for (int ks = 0; ks < nk; ++ks) {
-                fill_chunk(op, t, ks);
-                if (pair) fill_chunk(op, t + 1, ks);
-            }
-        }
-        for (int t = 0; t < op.ntiles; ++t)
-            for (int hi = 0; hi < 2; ++hi)
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (row < op.tiles[t].nrows)
-                        T.bias[(size_t)(op.first_tile + t) * 32 + hi * 16 + r] =
-                            T.tensor_off[op.tiles[t].bt] + op.tiles[t].row0 + row;
-                }
-    }
-    // fp32 stream: [op][tile][kb], natural column order; LDS layout of kernels_mlp_f32.hip: [buffer B | buffer A | encoding]
-    mip::F32Net& net = T.net;
-    memset(&net, 0, sizeof net);
-    net.nlayers = kNumOps;
-    net.width = kNetWidth;
-    net.xyz_dim = kXyzDim;
-    // Wide encodings (the 672 off-axis features of the unbounded-scene model): a 64-sample tile with the encoding resident does not
-    // fit the CU's LDS.  Instead of halving the tile (half the reuse of every weight chunk), the two layers that read the encoding
-    // stream that B operand from global memory (it stays in L1 / L2: 64 rows x 64 B per k block), and the encoding columns shrink to
-    // the view features + the VALU heads' partials.
-    const int ecols_full = kXyzDim > 32 ? kXyzDim : 32;
-    const bool stream_enc = mip::mlp_f32_tile_samples(2 * kNetWidth + ecols_full + 4) < 64 && mip::mlp_f32_tile_samples(2 * kNetWidth + 64 + 4) == 64;
-    const int ecols = stream_enc ? 64 : ecols_full;
-    net.pad = stream_enc ? 1 : 0;
-    net.enc_col = 2 * kNetWidth;
-    net.dens_col = 2 * kNetWidth + ecols;
-    net.num_rgb = P.num_rgb;
-    net.ldx = 2 * kNetWidth + ecols + 4;
-    size_t cf = 0;
-    int cur_col = -1;                  // LDS column of the buffer that holds the current activation (mlp_plan.f32_layers)
-    for (int oi = 0; oi < kNumOps; ++oi) {
-        const OpDesc& op = kOps[oi];
-        std::vector<int> colmap;
-        for (int s = 0; s < op.nsegs; ++s)
-            for (int c = 0; c < op.segs[s].nk * 16; ++c)
-                colmap.push_back(c < op.segs[s].ncols ? op.segs[s].col0 + c : -1);
-        const int kb = (int)colmap.size() / 16;
-        mip::F32Layer& L = net.layers[oi];
-        const int out_col = cur_col == kNetWidth ? 0 : kNetWidth;    // write the buffer that is not being read
-        const int prev_out = cur_col;
-        auto seg_col = [&](const SegDesc& sg) { return sg.kind == 0 ? net.enc_col : prev_out; };   // natural = encoding / view
-        L.x_in0 = seg_col(op.segs[0]);
-        L.kb0 = op.segs[0].nk;
-        L.x_in1 = op.nsegs > 1 ? seg_col(op.segs[1]) : 0;
-        L.kb1 = op.nsegs > 1 ? op.segs[1].nk : 0;
-        L.x_out = out_col;
-        L.ntiles = op.ntiles;
-        L.first_tile = op.first_tile;
-        L.relu = op.relu;
-        L.kind = op.kind;
-        L.chunk0 = (int)cf;
-        L.stage_view = (op.kind == 1 && P.use_viewdirs) ? 1 : 0;
-        // bit 0 / 1: K segment 0 / 1 is the sample encoding and is streamed from global memory (see above)
-        L.pad = (stream_enc && op.segs[0].kind == 0 && op.segs[0].ncols == kXyzDim ? 1 : 0) |
-                (stream_enc && op.nsegs > 1 && op.segs[1].kind == 0 && op.segs[1].ncols == kXyzDim ? 2 : 0);
-        if (op.kind == 0 || (op.kind == 1 && op.ntiles > 1)) cur_col = out_col;     // a density-only head moves nothing
-        for (int t = 0; t < op.ntiles; ++t)
-            for (int k = 0; k < kb; ++k) {
-                const TileDesc& tile = op.tiles[t];
-                for (int hi = 0; hi < 2; ++hi)
-                    for (int j = 0; j < 8; ++j) {
-                        const int col = colmap[k * 16 + hi * 8 + j];
-                        if (col < 0) continue;
-                        for (int m = 0; m < tile.nrows; ++m)
-                            T.pack_f32[cf * 512 + (size_t)(hi * 32 + m) * 8 + j] =
-                                T.tensor_off[tile.wt] + (tile.row0 + m) * tile.ld + col;
-                    }
-                ++cf;
-            }
-    }
+bool plan_tables(PlanTables& T, const PlanDesc& P) {
+    const int32_t* h = reinterpret_cast<const int32_t*>(mip::kPlanTableBlobs[P.variant]);
+    if (h[0] != 0x504C4E31 || h[1] != P.num_chunks || h[2] != P.num_tiles || h[3] != P.fwd_num_chunks || h[4] != P.fwd_num_tiles ||
+        h[5] < 0 || h[5] > P.num_chunks || h[6] != P.num_ops || h[6] > mip::kF32MaxLayers || h[7] != total_params(P) || h[8] != P.fold)
+        return false;
+    if (!P.fold && (h[3] != h[1] || h[4] != h[2])) return false;
+    T.pack = h + 16;
+    T.bias = T.pack + (size_t)h[1] * kDescInts;
+    const int32_t* p = T.bias + (size_t)h[2] * 32;
+    T.fwd_pack = P.fold ? p : T.pack;
+    T.fwd_bias = P.fold ? p + (size_t)h[3] * kDescInts : T.bias;
+    if (P.fold) p = T.fwd_bias + (size_t)h[4] * 32;
+    T.pack_f32 = p;
+    T.n_f32_chunks = h[5];
+    T.layers = T.pack_f32 + (size_t)h[5] * kDescInts;
+    return T.layers + (size_t)h[6] * kLayerInts == h + h[9];
 }
 
-// The plan of the bf16 forward kernels (inference and training forward-with-save share its stream): the folded ops of the generated
-// header, with the derived tensors (mlp_plan.Plan.derived_shapes) appended to the parameter tensors so that build_tables / encode index
-// them as tensors num_param_tensors and num_param_tensors + 1 (computed by the pack kernel: FoldDesc)
-PlanDesc fwd_desc(const PlanDesc& P) {
-    PlanDesc F = P;
-    F.ops = P.fwd_ops;
-    F.num_ops = P.fwd_num_ops;
-    F.num_chunks = P.fwd_num_chunks;
-    F.num_real_chunks = P.fwd_num_real_chunks;
-    F.num_tiles = P.fwd_num_tiles;
+// flat offset of each parameter tensor, then of the derived tensors of the folded plan (mlp_plan.Plan.derived_shapes: tensors
+// num_param_tensors and num_param_tensors + 1, computed by the pack kernel: FoldDesc)
+std::vector<int> tensor_offsets(const PlanDesc& P) {
+    std::vector<int> off(P.num_param_tensors);
+    int o = 0;
+    for (int i = 0; i < P.num_param_tensors; ++i) { off[i] = o; o += P.param_numel[i]; }
     if (P.fold) {
-        F.param_numel[F.num_param_tensors++] = P.net_width_cond * (P.net_width + P.view_dim);
-        F.param_numel[F.num_param_tensors++] = P.net_width_cond;
+        off.push_back(o);
+        off.push_back(o + P.net_width_cond * (P.net_width + P.view_dim));
     }
-    return F;
+    return off;
+}
+
+// chunk records -> index table of `table_chunks` chunks (the rest stays -1): entry (hi * 32 + m, j) of a chunk is element
+// (row0 + m) * ld + col[hi * 8 + j] of `tensor`, written as a flat parameter index (toff) or as (tensor << 20) | element for k_pack
+std::vector<int32_t> expand(const int32_t* desc, int n, int table_chunks, const std::vector<int>* toff) {
+    std::vector<int32_t> out((size_t)table_chunks * 512, -1);
+    for (int ci = 0; ci < n; ++ci) {
+        const int32_t* d = desc + (size_t)ci * kDescInts;
+        const int32_t base = toff ? (*toff)[d[0]] : d[0] << 20;
+        for (int hi = 0; hi < 2; ++hi)
+            for (int m = 0; m < d[3]; ++m)
+                for (int j = 0; j < 8; ++j)
+                    if (d[4 + hi * 8 + j] >= 0) out[(size_t)ci * 512 + (hi * 32 + m) * 8 + j] = base + (d[1] + m) * d[2] + d[4 + hi * 8 + j];
+    }
+    return out;
+}
+
+// LDS layout of kernels_mlp_f32.hip: [buffer B | buffer A | encoding]; the layer rows come from mlp_plan.Plan.f32_layers.
+// Wide encodings (the 672 off-axis features of the unbounded-scene model): a 64-sample tile with the encoding resident does not
+// fit the CU's LDS.  Instead of halving the tile (half the reuse of every weight chunk), the two layers that read the encoding
+// stream that B operand from global memory (it stays in L1 / L2: 64 rows x 64 B per k block), and the encoding columns shrink to
+// the view features + the VALU heads' partials.
+mip::F32Net f32net(const PlanDesc& P, const int32_t* layers) {
+    mip::F32Net net;
+    memset(&net, 0, sizeof net);
+    const int W = P.net_width, ecols_full = P.xyz_dim > 32 ? P.xyz_dim : 32;
+    const bool stream_enc = mip::mlp_f32_tile_samples(2 * W + ecols_full + 4) < 64 && mip::mlp_f32_tile_samples(2 * W + 64 + 4) == 64;
+    const int ecols = stream_enc ? 64 : ecols_full;
+    net.nlayers = P.num_ops;
+    net.width = W;
+    net.xyz_dim = P.xyz_dim;
+    net.pad = stream_enc ? 1 : 0;
+    net.enc_col = 2 * W;
+    net.dens_col = 2 * W + ecols;
+    net.num_rgb = P.num_rgb;
+    net.ldx = 2 * W + ecols + 4;
+    for (int i = 0; i < P.num_ops; ++i) {
+        const int32_t* r = layers + i * kLayerInts;
+        // pad: bit 0 / 1 = K segment 0 / 1 is the sample encoding and is streamed from global memory
+        net.layers[i] = mip::F32Layer{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10], stream_enc ? r[11] : 0};
+    }
+    return net;
 }
 
 bool max_deg_span_is_16(const mipnerf_config& cfg) { return cfg.max_deg_point - cfg.min_deg_point == 16 && cfg.min_deg_point >= 0 && cfg.max_deg_point <= 31; }
 
-int off_total(const Tables& T) { return T.total_params; }
-
 // flat index -> (tensor << 20 | offset) as consumed by k_pack
-std::vector<int32_t> encode(const std::vector<int32_t>& flat, const std::vector<int>& toff) {
-    std::vector<int32_t> out(flat.size());
-    for (size_t i = 0; i < flat.size(); ++i) {
+std::vector<int32_t> encode(const int32_t* flat, size_t n, const std::vector<int>& toff) {
+    std::vector<int32_t> out(n);
+    for (size_t i = 0; i < n; ++i) {
         const int32_t f = flat[i];
         if (f < 0) { out[i] = -1; continue; }
         int t = (int)toff.size() - 1;
@@ -274,27 +222,24 @@ bool pre_tables(PreTables& T, int variant, int nparams) {
 struct mipnerf_ctx {
     mipnerf_config cfg;
     const PlanDesc* P = nullptr;     // the generated architecture variant this context runs (mlp_plan_gen.hpp kPlans)
-    Tables tab;                      // the plan's tables (fp32 kernel)
-    Tables ftab;                     // the bf16 forward kernels' tables (fwd_desc: the bottleneck folded into view layer 0)
-    int32_t* d_pack_bf16 = nullptr;
-    int32_t* d_pack_f32 = nullptr;
-    int32_t* d_bias_idx = nullptr;
-    int32_t* d_fwd_bias_idx = nullptr;
+    std::vector<int> tensor_off;     // flat offset of each parameter tensor (tensor_offsets)
+    mip::F32Net net;                 // the LDS-resident fp32 kernel's layers (f32net)
+    // every packed stream of the context: mipnerf_set_params gathers `n` parameters through the device index table `idx` into `out`
+    // (add_stream fills the list, mipnerf_destroy frees both buffers; the launchers read `out` through the typed pointers below)
+    struct PackedStream { int32_t* idx; void* out; int64_t n; bool bf16; };
+    std::vector<PackedStream> streams;
     void* d_stream_bf16 = nullptr;   // fwd_num_chunks * 1 KiB (inference + training forward)
     float* d_stream_f32 = nullptr;   // num_chunks * 2 KiB
     float* d_bias = nullptr;         // num_tiles * 32 floats (fp32 kernel)
     float* d_fwd_bias = nullptr;     // fwd_num_tiles * 32 floats (bf16 forward kernels)
     // register-resident fp32 kernel (variants up to 256 wide): its own weight stream (1-KiB chunks) and aux table
     F32RTables f32r;
-    int32_t* d_pack_f32r = nullptr;
-    int32_t* d_aux_idx_f32r = nullptr;
     float* d_stream_f32r = nullptr;
     float* d_aux_f32r = nullptr;
     int f32_resident = 1;            // option 5: 1 = k_mlp_f32r where generated (inference), 0 = the LDS-resident k_mlp_f32
     // two-kernel bf16 inference of the variants whose encoding does not fit k_mlp_bf16's wave-private LDS area (gen_pre_gemm.py):
     // k_pre_gemm's weight stream + accumulator images, the trunk kernel's stream + bias table, and scratch for the per-stage entry point
     PreTables pre;
-    int32_t* d_pre_idx[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // index tables: gemm pack, gemm bias, trunk pack, trunk bias, one-kernel pack, one-kernel bias
     void* d_fused_stream = nullptr;  // one-kernel form (round 6): its weight stream and bias table
     float* d_fused_bias = nullptr;
     int fused_pre = 1;               // option 6: 1 = mipnerf_forward runs the one-kernel form where generated, 0 = k_pre_gemm + trunk (same bits)
@@ -309,8 +254,6 @@ struct mipnerf_ctx {
     bool pre_scratch_used = false;
     // training (bf16): W^T stream of the dgrad kernel, wgrad job tables
     TrainTables tt;
-    int32_t* d_pack_dgrad = nullptr;
-    int32_t* d_pack_extraT = nullptr;   // index table of W_extra^T (the transpose as a gather, so it joins the one pack launch)
     void* d_stream_dgrad = nullptr;
     mip::WgradJob* d_jobs = nullptr;
     int32_t* d_otab = nullptr;
@@ -388,13 +331,25 @@ constexpr int kF32WgradSplits = 256;
 
 // the fp32 kernel evaluates the two thin heads (density, colour) on the VALU straight from the fp32 master parameters
 mip::F32Net f32net_with_heads(const mipnerf_ctx* c) {
-    mip::F32Net net = c->tab.net;
+    mip::F32Net net = c->net;
     const int D = c->P->net_depth, Dc = c->P->net_depth_cond;
     net.dens_w = c->pp.p[2 * D];
     net.dens_b = c->pp.p[2 * D + 1];
     net.col_w = c->pp.p[2 * D + 4 + 2 * Dc];
     net.col_b = c->pp.p[2 * D + 5 + 2 * Dc];
     return net;
+}
+
+// one packed stream of the context: upload its index table, allocate its output (2 bytes per entry in bf16, else 4) and list it
+template <typename T>
+hipError_t add_stream(mipnerf_ctx* c, const std::vector<int32_t>& idx, bool bf16, T** out) {
+    mipnerf_ctx::PackedStream s{nullptr, nullptr, (int64_t)idx.size(), bf16};
+    hipError_t er = hipMalloc(&s.idx, idx.size() * 4);
+    if (er == hipSuccess) er = hipMalloc(&s.out, idx.size() * (bf16 ? 2 : 4));
+    if (er == hipSuccess) er = hipMemcpy(s.idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice);
+    c->streams.push_back(s);          // also after a failure: mipnerf_destroy frees what was allocated
+    *out = static_cast<T*>(s.out);
+    return er;
 }
 
 #define NEED_BF16_TRAIN(what)                                                                                               \
@@ -482,76 +437,50 @@ int mipnerf_create(const mipnerf_config* cfg, mipnerf_ctx** out) {
     mipnerf_ctx* c = new mipnerf_ctx();
     c->cfg = *cfg;
     c->P = P;
-    build_tables(c->tab, *P);
-    build_tables(c->ftab, fwd_desc(*P));
-    const std::vector<int32_t> e_bf16 = encode(c->ftab.pack_bf16, c->ftab.tensor_off);
-    const std::vector<int32_t> e_fbias = encode(c->ftab.bias, c->ftab.tensor_off);
-    const std::vector<int32_t> e_f32 = encode(c->tab.pack_f32, c->tab.tensor_off);
-    const std::vector<int32_t> e_bias = encode(c->tab.bias, c->tab.tensor_off);
-    const size_t nst = (size_t)P->num_chunks * 512, nst_fwd = (size_t)P->fwd_num_chunks * 512;
+    c->tensor_off = tensor_offsets(*P);
+    PlanTables pl;
+    if (!plan_tables(pl, *P)) {
+        mipnerf_destroy(c);
+        return fail(MIPNERF_E_INVALID, "mipnerf_create: embedded plan tables are inconsistent with the compiled plan");
+    }
+    c->net = f32net(*P, pl.layers);
     hipError_t er = hipSuccess;
     auto chk = [&](hipError_t e) { if (er == hipSuccess) er = e; };
-    chk(hipMalloc(&c->d_pack_bf16, nst_fwd * 4));
-    chk(hipMalloc(&c->d_pack_f32, nst * 4));
-    chk(hipMalloc(&c->d_bias_idx, e_bias.size() * 4));
-    chk(hipMalloc(&c->d_fwd_bias_idx, e_fbias.size() * 4));
-    chk(hipMalloc(&c->d_stream_bf16, nst_fwd * 2));
-    chk(hipMalloc(&c->d_stream_f32, nst * 4));
-    chk(hipMalloc(&c->d_bias, e_bias.size() * 4));
-    chk(hipMalloc(&c->d_fwd_bias, e_fbias.size() * 4));
-    if (er == hipSuccess) {
-        chk(hipMemcpy(c->d_pack_bf16, e_bf16.data(), nst_fwd * 4, hipMemcpyHostToDevice));
-        chk(hipMemcpy(c->d_pack_f32, e_f32.data(), nst * 4, hipMemcpyHostToDevice));
-        chk(hipMemcpy(c->d_bias_idx, e_bias.data(), e_bias.size() * 4, hipMemcpyHostToDevice));
-        chk(hipMemcpy(c->d_fwd_bias_idx, e_fbias.data(), e_fbias.size() * 4, hipMemcpyHostToDevice));
-    }
+    auto add = [&](const std::vector<int32_t>& idx, bool bf16, auto** out) { if (er == hipSuccess) er = add_stream(c, idx, bf16, out); };
+    auto flat = [&](const int32_t* idx, size_t n) { return encode(idx, n, c->tensor_off); };
+    add(expand(pl.fwd_pack, P->fwd_num_chunks, P->fwd_num_chunks, nullptr), true, &c->d_stream_bf16);
+    add(expand(pl.pack_f32, pl.n_f32_chunks, P->num_chunks, nullptr), false, &c->d_stream_f32);      // sized like the plain bf16 stream
+    add(flat(pl.bias, (size_t)P->num_tiles * 32), false, &c->d_bias);
+    add(flat(pl.fwd_bias, (size_t)P->fwd_num_tiles * 32), false, &c->d_fwd_bias);
     if (er != hipSuccess) {
         mipnerf_destroy(c);
         return fail(MIPNERF_E_HIP, "mipnerf_create: %s", hipGetErrorString(er));
     }
     if (mip::kLaunchF32R[P->variant]) {
-        if (!f32r_tables(c->f32r, P->variant, off_total(c->tab))) {
+        if (!f32r_tables(c->f32r, P->variant, total_params(*P))) {
             mipnerf_destroy(c);
             return fail(MIPNERF_E_INVALID, "mipnerf_create: embedded tables of the register-resident fp32 kernel are inconsistent with the compiled plan");
         }
-        const size_t np = (size_t)c->f32r.n_chunks * 256, na = (size_t)c->f32r.n_aux;
-        const std::vector<int32_t> e_p = encode(std::vector<int32_t>(c->f32r.pack, c->f32r.pack + np), c->tab.tensor_off);
-        const std::vector<int32_t> e_a = encode(std::vector<int32_t>(c->f32r.aux, c->f32r.aux + na), c->tab.tensor_off);
-        chk(hipMalloc(&c->d_pack_f32r, np * 4));
-        chk(hipMalloc(&c->d_aux_idx_f32r, na * 4));
-        chk(hipMalloc(&c->d_stream_f32r, np * 4));
-        chk(hipMalloc(&c->d_aux_f32r, na * 4));
-        if (er == hipSuccess) {
-            chk(hipMemcpy(c->d_pack_f32r, e_p.data(), np * 4, hipMemcpyHostToDevice));
-            chk(hipMemcpy(c->d_aux_idx_f32r, e_a.data(), na * 4, hipMemcpyHostToDevice));
-        }
+        add(flat(c->f32r.pack, (size_t)c->f32r.n_chunks * 256), false, &c->d_stream_f32r);
+        add(flat(c->f32r.aux, (size_t)c->f32r.n_aux), false, &c->d_aux_f32r);
         if (er != hipSuccess) {
             mipnerf_destroy(c);
             return fail(MIPNERF_E_HIP, "mipnerf_create (fp32 register-resident tables): %s", hipGetErrorString(er));
         }
     }
     if (has_bf16_pre(P)) {
-        if (!pre_tables(c->pre, P->variant, off_total(c->tab))) {
+        if (!pre_tables(c->pre, P->variant, total_params(*P))) {
             mipnerf_destroy(c);
             return fail(MIPNERF_E_INVALID, "mipnerf_create: embedded tables of the two-kernel bf16 form are inconsistent with the compiled plan");
         }
         const PreTables& pt = c->pre;
-        const int32_t* src[6] = {pt.gemm_pack, pt.gemm_bias, pt.trunk_pack, pt.trunk_bias, pt.fused_pack, pt.fused_bias};
-        const size_t cnt[6] = {(size_t)pt.n_gemm_chunks * 512, (size_t)pt.n_gemm_bias, (size_t)pt.n_trunk_chunks * 512, (size_t)pt.n_trunk_tiles * 32,
-                               (size_t)pt.n_fused_chunks * 512, (size_t)pt.n_fused_tiles * 32};
-        for (int i = 0; i < 6; ++i) {
-            if (cnt[i] == 0) continue;
-            const std::vector<int32_t> enc_i = encode(std::vector<int32_t>(src[i], src[i] + cnt[i]), c->tab.tensor_off);
-            chk(hipMalloc(&c->d_pre_idx[i], cnt[i] * 4));
-            if (er == hipSuccess) chk(hipMemcpy(c->d_pre_idx[i], enc_i.data(), cnt[i] * 4, hipMemcpyHostToDevice));
-        }
-        chk(hipMalloc(&c->d_pre_gemm_stream, cnt[0] * 2));
-        chk(hipMalloc(&c->d_pre_gemm_bias, cnt[1] * 4));
-        chk(hipMalloc(&c->d_pre_trunk_stream, cnt[2] * 2));
-        chk(hipMalloc(&c->d_pre_trunk_bias, cnt[3] * 4));
-        if (cnt[4]) {
-            chk(hipMalloc(&c->d_fused_stream, cnt[4] * 2));
-            chk(hipMalloc(&c->d_fused_bias, cnt[5] * 4));
+        add(flat(pt.gemm_pack, (size_t)pt.n_gemm_chunks * 512), true, &c->d_pre_gemm_stream);
+        add(flat(pt.gemm_bias, (size_t)pt.n_gemm_bias), false, &c->d_pre_gemm_bias);
+        add(flat(pt.trunk_pack, (size_t)pt.n_trunk_chunks * 512), true, &c->d_pre_trunk_stream);
+        add(flat(pt.trunk_bias, (size_t)pt.n_trunk_tiles * 32), false, &c->d_pre_trunk_bias);
+        if (pt.n_fused_chunks) {
+            add(flat(pt.fused_pack, (size_t)pt.n_fused_chunks * 512), true, &c->d_fused_stream);
+            add(flat(pt.fused_bias, (size_t)pt.n_fused_tiles * 32), false, &c->d_fused_bias);
         }
         if (er != hipSuccess) {
             mipnerf_destroy(c);
@@ -563,29 +492,23 @@ int mipnerf_create(const mipnerf_config* cfg, mipnerf_ctx** out) {
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
         c->grid_limit = cus;
     // ---- training tables (one blob per variant with generated bf16 training kernels) ----
-    if (has_bf16_train_any(P) && (!train_tables(c->tt, P->variant) || c->tt.nparams != off_total(c->tab))) {
+    if (has_bf16_train_any(P) && (!train_tables(c->tt, P->variant) || c->tt.nparams != total_params(*P))) {
         mipnerf_destroy(c);
         return fail(MIPNERF_E_INVALID, "mipnerf_create: embedded training tables are inconsistent with the compiled plan");
     }
     if (has_bf16_train_any(P)) {
         const TrainTables& tt = c->tt;
-        const std::vector<int32_t> flat(tt.bpack, tt.bpack + (size_t)tt.n_bchunks * 512);
-        const std::vector<int32_t> e_dg = encode(flat, c->tab.tensor_off);
-        chk(hipMalloc(&c->d_pack_dgrad, e_dg.size() * 4));
-        chk(hipMalloc(&c->d_stream_dgrad, e_dg.size() * 2));
+        add(flat(tt.bpack, (size_t)tt.n_bchunks * 512), true, &c->d_stream_dgrad);
         chk(hipMalloc(&c->d_jobs, (size_t)tt.njobs * sizeof(mip::WgradJob)));
         chk(hipMalloc(&c->d_otab, (size_t)tt.njobs * tt.job_floats * 4));
         chk(hipMalloc(&c->d_jobslots, (size_t)tt.njobs * sizeof(int2)));
         chk(hipMalloc(&c->d_scratch, (size_t)(tt.n_scratch > 0 ? tt.n_scratch : 1) * 4));
-        chk(hipMalloc(&c->d_extra_wT, (size_t)P->net_width * P->net_width * 4));
         const int Wn = P->net_width, t_extra = 2 * P->net_depth + 2;
         std::vector<int32_t> e_xt((size_t)Wn * Wn);
         for (int i = 0; i < Wn; ++i)
             for (int j = 0; j < Wn; ++j) e_xt[(size_t)i * Wn + j] = (int32_t)((t_extra << 20) | (j * Wn + i));     // out[i][j] = W[j][i]
-        chk(hipMalloc(&c->d_pack_extraT, e_xt.size() * 4));
+        add(e_xt, false, &c->d_extra_wT);      // W_extra^T: the transpose as a gather, so it joins the one pack launch
         if (er == hipSuccess) {
-            chk(hipMemcpy(c->d_pack_extraT, e_xt.data(), e_xt.size() * 4, hipMemcpyHostToDevice));
-            chk(hipMemcpy(c->d_pack_dgrad, e_dg.data(), e_dg.size() * 4, hipMemcpyHostToDevice));
             chk(hipMemcpy(c->d_jobs, tt.jobs, (size_t)tt.njobs * sizeof(mip::WgradJob), hipMemcpyHostToDevice));
             chk(hipMemcpy(c->d_otab, tt.otab, (size_t)tt.njobs * tt.job_floats * 4, hipMemcpyHostToDevice));
         }
@@ -598,22 +521,18 @@ int mipnerf_create(const mipnerf_config* cfg, mipnerf_ctx** out) {
         const int rc = mipnerf_set_wgrad_splits(c, nullptr);
         if (rc) { mipnerf_destroy(c); return rc; }
     }
+    if ((int)c->streams.size() > mip::kMaxPackSegments) {
+        mipnerf_destroy(c);
+        return fail(MIPNERF_E_INVALID, "mipnerf_create: more than %d packed streams", mip::kMaxPackSegments);
+    }
     *out = c;
     return MIPNERF_OK;
 }
 
 int mipnerf_destroy(mipnerf_ctx* c) {
     if (!c) return MIPNERF_OK;
-    (void)hipFree(c->d_pack_bf16); (void)hipFree(c->d_pack_f32); (void)hipFree(c->d_bias_idx);
-    (void)hipFree(c->d_stream_bf16); (void)hipFree(c->d_stream_f32); (void)hipFree(c->d_bias);
-    (void)hipFree(c->d_fwd_bias_idx); (void)hipFree(c->d_fwd_bias);
-    (void)hipFree(c->d_pack_dgrad); (void)hipFree(c->d_stream_dgrad); (void)hipFree(c->d_jobs); (void)hipFree(c->d_otab);
-    (void)hipFree(c->d_wgtab); (void)hipFree(c->d_jobslots); (void)hipFree(c->d_scratch); (void)hipFree(c->d_extra_wT);
-    (void)hipFree(c->d_pack_extraT);
-    (void)hipFree(c->d_pack_f32r); (void)hipFree(c->d_aux_idx_f32r); (void)hipFree(c->d_stream_f32r); (void)hipFree(c->d_aux_f32r);
-    for (int i = 0; i < 6; ++i) (void)hipFree(c->d_pre_idx[i]);
-    (void)hipFree(c->d_fused_stream); (void)hipFree(c->d_fused_bias);
-    (void)hipFree(c->d_pre_gemm_stream); (void)hipFree(c->d_pre_gemm_bias); (void)hipFree(c->d_pre_trunk_stream); (void)hipFree(c->d_pre_trunk_bias);
+    for (const mipnerf_ctx::PackedStream& s : c->streams) { (void)hipFree(s.idx); (void)hipFree(s.out); }
+    (void)hipFree(c->d_jobs); (void)hipFree(c->d_otab); (void)hipFree(c->d_wgtab); (void)hipFree(c->d_jobslots); (void)hipFree(c->d_scratch);
     (void)hipFree(c->d_pre_scratch);
     if (c->pre_scratch_event) (void)hipEventDestroy(c->pre_scratch_event);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -646,7 +565,6 @@ int mipnerf_set_params(mipnerf_ctx* c, const float* const* params_host, void* st
         if (!params_host[i]) return fail(MIPNERF_E_INVALID, "parameter tensor %d is null", i);
         pp.p[i] = params_host[i];
     }
-    const int64_t nst = (int64_t)P.num_chunks * 512;
     // every stream of the context in ONE launch: bf16 stream, fp32 stream, bias tables, and for the trainable variants the
     // transposed (dgrad) stream and W_extra^T (a gather through an index table like the others).  The bf16 forward stream and its
     // bias table read the folded view layer, which the pack kernel computes from the parameters where it meets it (FoldDesc)
@@ -657,36 +575,11 @@ int mipnerf_set_params(mipnerf_ctx* c, const float* const* params_host, void* st
         const int D = P.net_depth;
         sg.fold = mip::FoldDesc{P.num_param_tensors, P.net_width, P.net_width + P.view_dim, 2 * D + 4, 2 * D + 5, 2 * D + 2, 2 * D + 3};
     }
-    bool sg_overflow = false;
-    auto add = [&](const int32_t* table, int64_t n, void* out, bool bf16) {
-        if (sg.n >= mip::kMaxPackSegments) { sg_overflow = true; return; }       // checked BEFORE the arrays are written
-        sg.table[sg.n] = table; sg.out[sg.n] = out; sg.bf16[sg.n] = bf16 ? 1 : 0;
-        sg.start[sg.n + 1] = sg.start[sg.n] + n;
+    for (const mipnerf_ctx::PackedStream& s : c->streams) {      // (mipnerf_create keeps the list within kMaxPackSegments)
+        sg.table[sg.n] = s.idx; sg.out[sg.n] = s.out; sg.bf16[sg.n] = s.bf16 ? 1 : 0;
+        sg.start[sg.n + 1] = sg.start[sg.n] + s.n;
         ++sg.n;
-    };
-    add(c->d_pack_bf16, (int64_t)P.fwd_num_chunks * 512, c->d_stream_bf16, true);
-    add(c->d_pack_f32, nst, c->d_stream_f32, false);
-    add(c->d_bias_idx, (int64_t)P.num_tiles * 32, c->d_bias, false);
-    add(c->d_fwd_bias_idx, (int64_t)P.fwd_num_tiles * 32, c->d_fwd_bias, false);
-    if (has_bf16_train_any(&P)) {
-        add(c->d_pack_dgrad, (int64_t)c->tt.n_bchunks * 512, c->d_stream_dgrad, true);
-        add(c->d_pack_extraT, (int64_t)P.net_width * P.net_width, c->d_extra_wT, false);
     }
-    if (c->d_stream_f32r) {
-        add(c->d_pack_f32r, (int64_t)c->f32r.n_chunks * 256, c->d_stream_f32r, false);
-        add(c->d_aux_idx_f32r, (int64_t)c->f32r.n_aux, c->d_aux_f32r, false);
-    }
-    if (c->d_pre_gemm_stream) {
-        add(c->d_pre_idx[0], (int64_t)c->pre.n_gemm_chunks * 512, c->d_pre_gemm_stream, true);
-        add(c->d_pre_idx[1], (int64_t)c->pre.n_gemm_bias, c->d_pre_gemm_bias, false);
-        add(c->d_pre_idx[2], (int64_t)c->pre.n_trunk_chunks * 512, c->d_pre_trunk_stream, true);
-        add(c->d_pre_idx[3], (int64_t)c->pre.n_trunk_tiles * 32, c->d_pre_trunk_bias, false);
-        if (c->d_fused_stream) {
-            add(c->d_pre_idx[4], (int64_t)c->pre.n_fused_chunks * 512, c->d_fused_stream, true);
-            add(c->d_pre_idx[5], (int64_t)c->pre.n_fused_tiles * 32, c->d_fused_bias, false);
-        }
-    }
-    if (sg_overflow) return fail(MIPNERF_E_INVALID, "set_params: more than %d pack segments", mip::kMaxPackSegments);
     HIP_TRY(mip::launch_pack_multi(sg, pp, S(stream)));
     c->pp = pp;
     c->params_set = true;
@@ -1285,7 +1178,7 @@ static int wgrad_tiles(mipnerf_ctx* c, int64_t n_wt, const void* act, const void
             // partial feeds them: zero unless accumulating
             const int D = P.net_depth;
             for (int t = 2 * D + 2; t < 2 * D + 6; ++t)
-                HIP_TRY(hipMemsetAsync(grad_flat + c->tab.tensor_off[t], 0, (size_t)P.param_numel[t] * 4, S(stream)));
+                HIP_TRY(hipMemsetAsync(grad_flat + c->tensor_off[t], 0, (size_t)P.param_numel[t] * 4, S(stream)));
         }
         HIP_TRY(mip::launch_wgrad_reduce(partials, c->d_otab, c->d_jobslots, c->tt.njobs, grad_flat, c->d_scratch,
                                          c->tt.nparams, post, accumulate != 0, S(stream)));
@@ -1442,7 +1335,7 @@ static int mlp_backward_f32_impl(mipnerf_ctx* c, int64_t M, int32_t N, const flo
     const unsigned long long* bits0 = reinterpret_cast<const unsigned long long*>(save + (size_t)PL.num_ops * M * W);
     auto slot_bits = [&](int L) { return bits0 + (size_t)L * mip::f32_bits_slot_words(M, W); };
     auto P = [&](int t) { return c->pp.p[t]; };                       // fp32 master parameter t (state_dict order)
-    auto G = [&](int t) { return grad_flat + c->tab.tensor_off[t]; }; // its gradient
+    auto G = [&](int t) { return grad_flat + c->tensor_off[t]; }; // its gradient
     const int Dc = PL.net_depth_cond;        // view layers (mip_nerf.py:62-69): the first reads [bottleneck | view encoding], the others Wc -> Wc
     const int tDensW = 2 * D, tDensB = 2 * D + 1, tExW = 2 * D + 2, tExB = 2 * D + 3, tVW = 2 * D + 4, tVB = 2 * D + 5,
               tCW = 2 * D + 4 + 2 * Dc, tCB = 2 * D + 5 + 2 * Dc;
@@ -1871,53 +1764,45 @@ int mipnerf_selftest(void* stream) {
     return bad == 0 ? MIPNERF_OK : (0x100 | bad);
 }
 
-// Host-only debug export of the plan tables (flat parameter indices), used by the CPU tests to prove the
-// C++ expansion equals mlp_plan.py.  which: 0 bf16 pack, 1 bias, 2 fp32 pack (Plan.build), 6 / 7 the bf16 pack / bias table of the
-// forward kernels (Plan.build(fold_view=True)).  Returns element count.
+// Host-only debug export of the plan tables (flat parameter indices), used by the CPU tests to prove that what the library expands
+// from its embedded tables equals mlp_plan.py.  which: 0 bf16 pack, 1 bias, 2 fp32 pack (Plan.build), 6 / 7 the bf16 pack / bias table of
+// the forward kernels (Plan.build(fold_view=True)).  Returns element count.
 int64_t mipnerf_debug_table_variant(int variant, int which, int32_t* out_host, int64_t cap) {
     if (variant < 0 || variant >= mip::plan::kNumVariants || which < 0 || which > 7) return -1;
+    const PlanDesc& P = mip::plan::kPlans[variant];
+    std::vector<int32_t> v;
     if (which >= 3 && which <= 5) {     // training tables of the variant (3 dgrad pack, 4 wgrad partial -> parameter, 5 jobs)
         TrainTables tt;
         if (!train_tables(tt, variant)) return -1;
         const int32_t* src = which == 3 ? tt.bpack : (which == 4 ? tt.otab : tt.jobs);
-        const int64_t n = which == 3 ? (int64_t)tt.n_bchunks * 512 : (which == 4 ? (int64_t)tt.njobs * tt.job_floats : tt.njobs * 20);
-        if (out_host && cap >= n) memcpy(out_host, src, (size_t)n * 4);
-        return n;
+        v.assign(src, src + (which == 3 ? (size_t)tt.n_bchunks * 512 : (which == 4 ? (size_t)tt.njobs * tt.job_floats : (size_t)tt.njobs * 20)));
+    } else {
+        PlanTables T;
+        if (!plan_tables(T, P)) return -1;
+        const std::vector<int> toff = tensor_offsets(P);
+        if (which == 0) v = expand(T.pack, P.num_chunks, P.num_chunks, &toff);      // includes the zero padding chunks at the end of the stream
+        else if (which == 6) v = expand(T.fwd_pack, P.fwd_num_chunks, P.fwd_num_chunks, &toff);
+        else if (which == 2) v = expand(T.pack_f32, T.n_f32_chunks, P.num_chunks, &toff);
+        else if (which == 1) v.assign(T.bias, T.bias + (size_t)P.num_tiles * 32);
+        else v.assign(T.fwd_bias, T.fwd_bias + (size_t)P.fwd_num_tiles * 32);
     }
-    Tables T;
-    build_tables(T, which >= 6 ? fwd_desc(mip::plan::kPlans[variant]) : mip::plan::kPlans[variant]);
-    const std::vector<int32_t>& v = (which == 0 || which == 6) ? T.pack_bf16 : ((which == 1 || which == 7) ? T.bias : T.pack_f32);
     if (out_host && cap >= (int64_t)v.size()) memcpy(out_host, v.data(), v.size() * 4);
     return (int64_t)v.size();
 }
 
-int64_t mipnerf_debug_table(int which, int32_t* out_host, int64_t cap) {
-    if (which >= 6) return mipnerf_debug_table_variant(0, which, out_host, cap);
-    if (which >= 3 && which <= 5) {
-        TrainTables tt;
-        if (!train_tables(tt)) return -1;
-        const int32_t* src = which == 3 ? tt.bpack : (which == 4 ? tt.otab : tt.jobs);
-        const int64_t n = which == 3 ? (int64_t)tt.n_bchunks * 512 : (which == 4 ? (int64_t)tt.njobs * tt.job_floats : tt.njobs * 20);
-        if (out_host && cap >= n) memcpy(out_host, src, (size_t)n * 4);
-        return n;
-    }
-    Tables T;
-    build_tables(T, mip::plan::kPlans[0]);
-    const std::vector<int32_t>& v = which == 0 ? T.pack_bf16 : (which == 1 ? T.bias : T.pack_f32);
-    if (out_host && cap >= (int64_t)v.size()) memcpy(out_host, v.data(), v.size() * 4);
-    return (int64_t)v.size();
-}
+int64_t mipnerf_debug_table(int which, int32_t* out_host, int64_t cap) { return mipnerf_debug_table_variant(0, which, out_host, cap); }
 
 // Host-only: fp32 layer descriptors (x_in0, kb0, x_in1, kb1, x_out, ntiles, first_tile, relu, kind, chunk0, stage_view, ldx) x nlayers
 int64_t mipnerf_debug_f32net(int32_t* out_host, int64_t cap) {
-    Tables T;
-    build_tables(T, mip::plan::kPlans[0]);
-    const int n = T.net.nlayers;
+    PlanTables T;
+    if (!plan_tables(T, mip::plan::kPlans[0])) return -1;
+    const mip::F32Net net = f32net(mip::plan::kPlans[0], T.layers);
+    const int n = net.nlayers;
     if (out_host && cap >= (int64_t)n * 12)
         for (int i = 0; i < n; ++i) {
-            const mip::F32Layer& L = T.net.layers[i];
+            const mip::F32Layer& L = net.layers[i];
             const int32_t row[12] = {L.x_in0, L.kb0, L.x_in1, L.kb1, L.x_out, L.ntiles, L.first_tile, L.relu, L.kind, L.chunk0,
-                                     L.stage_view, T.net.ldx};
+                                     L.stage_view, net.ldx};
             memcpy(out_host + i * 12, row, sizeof row);
         }
     return n;

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Generate mlp_bf16_gen.hip (the register-resident bf16 MFMA MLP kernel) and
-mlp_plan_gen.hpp (plan descriptors for the host-side packer) from mlp_plan.Plan.
+mlp_plan_gen.hpp (the scalar description of every variant) from mlp_plan.Plan, and _gen_plan_tables[_v<i>].bin, the variant's
+pack / bias tables and fp32 layer rows (mlp_plan.blob) that the library links in and reads.
 
 The kernel is straight-line code: every chunk of the weight stream has a compile-time LDS
 ring offset, every activation register a literal index (runtime-indexed vector arrays would
@@ -27,7 +28,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gen_common as gc  # noqa: E402
 from gen_common import CHUNK_BYTES, HERE, NE, PREFETCH, WAVES  # noqa: E402
-from mipnerf_pl_amd.mlp_plan import Plan, Arch  # noqa: E402
+from mipnerf_pl_amd.mlp_plan import Plan, Arch, blob  # noqa: E402
 
 GROUP = 4 * WAVES     # chunks per ring slot (wave w DMAs chunks 4w..4w+3 of a group)
 SLOTS = 2             # ring slots
@@ -71,63 +72,26 @@ VARIANTS = [
 ]
 
 
-def _ops_table(plan: Plan, name: str):
-    L = [f"static const OpDesc {name}[{len(plan.ops)}] = {{"]
-    f32 = plan.f32_layers()
-    for op, fl in zip(plan.ops, f32):
-        segs = ", ".join(f"{{{s.kind}, {s.nk}, {s.col0}, {s.ncols}}}" for s in op.segs)
-        if len(op.segs) == 1:
-            segs += ", {0, 0, 0, 0}"
-        tiles = ", ".join(f"{{{t.wt}, {t.bt}, {t.row0}, {t.nrows}, {t.ld}}}" for t in op.tiles)
-        assert len(op.tiles) <= 17
-        kind = 1 if op.name == "head" else (2 if op.out == "rgb" else 0)
-        L.append(f"  /* {op.name} */ {{{len(op.segs)}, {{{segs}}}, {len(op.tiles)}, {{{tiles}}}, {op.first_tile}, {fl['x_in']}, {int(op.relu)}, {kind}}},")
-    L.append("};")
-    return L
-
-
 def gen_plan_header(plans, fplans) -> str:
-    """plans: Plan.build per variant (the fp32 kernel's tables, debug tables 0 / 1 / 2); fplans: the plans the bf16 forward kernels were
-    generated from (Plan.build(fold_view=True)), whose stream and bias table the context packs."""
-    plan = plans[0]
-    a = plan.arch
+    """The scalar description of every variant (mipnerf_create matches a configuration against it).  plans: Plan.build per variant
+    (the fp32 kernels' tables, debug tables 0 / 1 / 2); fplans: the plans the bf16 forward kernels were generated from
+    (Plan.build(fold_view=True)), whose stream and bias table the context packs.  The tables themselves travel as mlp_plan.blob()."""
     L = []
     L.append("// AUTO-GENERATED by gen_mlp_bf16.py from mlp_plan.py -- do not edit.")
     L.append("#pragma once")
     L.append("#include <stdint.h>")
     L.append("namespace mip { namespace plan {")
-    L.append("// ---- variant 0 (the shipped architecture; the bf16 training kernels exist for it only) ----")
-    L.append(f"constexpr int kNetDepth = {a.net_depth}, kNetWidth = {a.net_width}, kNetDepthCond = {a.net_depth_condition},")
-    L.append(f"              kNetWidthCond = {a.net_width_condition}, kSkipIndex = {a.skip_index}, kNumRgb = {a.num_rgb},")
-    L.append(f"              kNumDensity = {a.num_density}, kXyzDim = {a.xyz_dim}, kViewDim = {a.view_dim};")
-    shapes = a.param_shapes()
-    L.append(f"constexpr int kNumParamTensors = {len(shapes)};")
-    L.append("constexpr int kParamNumel[kNumParamTensors] = {" +
-             ", ".join(str(int(np.prod(s))) for _, s in shapes) + "};")
-    L.append(f"constexpr int kNumChunks = {len(plan.chunks)}, kNumTiles = {plan.n_tiles}, kNumOps = {len(plan.ops)};")
-    L.append(f"constexpr int kGroupChunks = {GROUP}, kRingSlots = {SLOTS}, kNumGroups = {len(plan.chunks) // GROUP};")
-    L.append("struct SegDesc { int kind, nk, col0, ncols; };            // kind 0 natural, 1 dlayout")
-    L.append("struct TileDesc { int wt, bt, row0, nrows, ld; };")
-    L.append("// kind 0 hidden, 1 head (last tile = density), 2 colour")
-    L.append("struct OpDesc { int nsegs; SegDesc segs[2]; int ntiles; TileDesc tiles[17]; int first_tile; int xcol_in; int relu; int kind; };")
     L.append("// ---- every architecture the library was generated for (gen_mlp_bf16.VARIANTS) ----")
     L.append("struct PlanDesc {")
     L.append("    int net_depth, net_width, net_depth_cond, net_width_cond, skip_index, num_rgb, num_density, xyz_dim, view_dim, use_viewdirs;")
     L.append("    int feat_per_deg;   // encoding features per frequency: 6 (axis-aligned IPE) or 42 (off-axis IPE of the unbounded-scene model)")
     L.append("    int num_param_tensors; int param_numel[32];")
     L.append("    int num_chunks, num_real_chunks, num_tiles, num_ops;")
-    L.append("    const OpDesc* ops;")
     L.append("    int variant;        // index of the generated bf16 inference kernel (launch_mlp_bf16 / launch_mlp_bf16_v<variant>)")
     L.append("    // the bf16 forward kernels' plan (Plan.build(fold_view=True)): the bottleneck folded into view layer 0, whose tiles read the")
-    L.append("    // derived tensors num_param_tensors (weight, Wc x (W + view_dim)) and num_param_tensors + 1 (bias); fold = 0: fwd_ops == ops")
+    L.append("    // derived tensors num_param_tensors (weight, Wc x (W + view_dim)) and num_param_tensors + 1 (bias); fold = 0: the plan above")
     L.append("    int fold, fwd_num_chunks, fwd_num_real_chunks, fwd_num_tiles, fwd_num_ops;")
-    L.append("    const OpDesc* fwd_ops;")
     L.append("};")
-    for vi, pl in enumerate(plans):
-        L += _ops_table(pl, "kOps" if vi == 0 else f"kOps_v{vi}")
-    for vi, pl in enumerate(fplans):
-        if pl.fold_view:
-            L += _ops_table(pl, "kFwdOps" if vi == 0 else f"kFwdOps_v{vi}")
     L.append(f"constexpr int kNumVariants = {len(plans)};")
     L.append("static const PlanDesc kPlans[kNumVariants] = {")
     for vi, (pl, fp) in enumerate(zip(plans, fplans)):
@@ -135,12 +99,10 @@ def gen_plan_header(plans, fplans) -> str:
         shp = b.param_shapes()
         assert len(shp) + 2 <= 32
         numel = ", ".join(str(int(np.prod(x))) for _, x in shp)
-        ops = 'kOps' if vi == 0 else f'kOps_v{vi}'
-        fops = ('kFwdOps' if vi == 0 else f'kFwdOps_v{vi}') if fp.fold_view else ops
         L.append(f"  {{{b.net_depth}, {b.net_width}, {b.net_depth_condition}, {b.net_width_condition}, {b.skip_index}, {b.num_rgb}, "
                  f"{b.num_density}, {b.xyz_dim}, {b.view_dim}, {int(b.use_viewdirs)}, {b.feat_per_deg}, {len(shp)}, {{{numel}}}, {len(pl.chunks)}, "
-                 f"{pl.n_real_chunks}, {pl.n_tiles}, {len(pl.ops)}, {ops}, {vi}, "
-                 f"{int(fp.fold_view)}, {len(fp.chunks)}, {fp.n_real_chunks}, {fp.n_tiles}, {len(fp.ops)}, {fops}}},")
+                 f"{pl.n_real_chunks}, {pl.n_tiles}, {len(pl.ops)}, {vi}, "
+                 f"{int(fp.fold_view)}, {len(fp.chunks)}, {fp.n_real_chunks}, {fp.n_tiles}, {len(fp.ops)}}},")
     L.append("};")
     L.append("}}  // namespace mip::plan")
     return "\n".join(L) + "\n"
@@ -861,7 +823,9 @@ def gen_kernel(plan: Plan, variant: int = 0) -> str:
 
 
 def gen_variants_header(n):
-    """Declarations + dispatch table of the per-variant inference launchers (capi.hip indexes it with PlanDesc::variant)."""
+    """Declarations + dispatch tables of the per-variant inference launchers and plan-table blobs (capi.hip indexes them with
+    PlanDesc::variant)."""
+    tables = {vi: "mip_plan_tables" + (f"_v{vi}" if vi else "") for vi in range(n)}
     bf16 = [vi for vi in range(n) if VARIANTS[vi].bf16_kernels]
     body = gc.fn_typedef("LaunchBf16Fn", "bf16")
     for vi in bf16:
@@ -869,7 +833,8 @@ def gen_variants_header(n):
             body += gc.prototype(f"launch_mlp_bf16_v{vi}", "bf16")
     entries = {vi: "launch_mlp_bf16" + (f"_v{vi}" if vi else "") if vi in bf16 else "nullptr /* fp32 only */" for vi in range(n)}
     return gc.dispatch_header("// AUTO-GENERATED by gen_mlp_bf16.py from VARIANTS -- do not edit by hand.", body,
-                              [("LaunchBf16Fn", "kLaunchBf16", entries)], n)
+                              [("LaunchBf16Fn", "kLaunchBf16", entries), ("unsigned char* const", "kPlanTableBlobs", tables)], n,
+                              before_namespace=[f'extern "C" const unsigned char {t}[];' for t in tables.values()])
 
 
 def main():
@@ -883,6 +848,8 @@ def main():
     with open(os.path.join(outdir, "mlp_variants_gen.hpp"), "w") as f:
         f.write(gen_variants_header(len(plans)))
     for vi, plan in enumerate(fplans):
+        with open(os.path.join(outdir, "_gen_plan_tables.bin" if vi == 0 else f"_gen_plan_tables_v{vi}.bin"), "wb") as f:
+            f.write(blob(plans[vi], plan))
         if not plan.arch.bf16_kernels:
             print(f"variant {vi}: plan tables only (fp32 kernels), {plan.n_real_chunks} chunks, {plan.n_tiles} tiles")
             continue

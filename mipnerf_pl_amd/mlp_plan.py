@@ -33,6 +33,9 @@ density and everything derived from it unchanged bit for bit.  The fp32 kernels 
 fp32 kernel (kernels_mlp_f32.hip) keeps activations in LDS in natural feature order and
 uses v_mfma_f32_32x32x2_f32; its packing is the same chunk idea with the natural k map and
 8 fp32 per lane (2 KiB chunks), in [layer][tile][kblock] order (`f32_layers`).
+
+The library has no copy of any of this: `blob` writes the three pack tables as one short record per chunk, with the bias tables and
+the fp32 layer rows, the build links that file in, and capi.hip expands the records.
 """
 from __future__ import annotations
 
@@ -344,13 +347,15 @@ class Plan:
     # ---- fp32 kernel layout (natural k order, activations in LDS) -----------------------
     def f32_layers(self):
         """Per layer of the LDS-resident fp32 kernel (kernels_mlp_f32.hip): K segments (x_in0, kb0), (x_in1, kb1), the
-        output column x_out, tiles, relu, kind.  LDS row layout per sample: cols [0,W) activation buffer B, [W,2W) buffer A
+        output column x_out, tiles, relu, kind, chunk0 (the layer's first chunk of the fp32 stream), enc_mask (bit s: K segment s is
+        the sample encoding).  LDS row layout per sample: cols [0,W) activation buffer B, [W,2W) buffer A
         (layers alternate: layer i writes A when i is even), [2W, 2W+max(xyz,32)) the encoding, later the padded view
         features; `runs` = (x_col0, w_col0, ncols) per segment in k order."""
         a = self.arch
         W = a.net_width
         enc_col = 2 * W
         layers = []
+        chunk0 = 0
         cur = None                      # LDS column of the buffer holding the current activation
         for oi, op in enumerate(self.ops):
             out_col = 0 if cur == W else W
@@ -363,7 +368,9 @@ class Plan:
             layers.append(dict(name=op.name, x_in0=segs[0][0], kb0=segs[0][1], x_in1=segs[1][0], kb1=segs[1][1],
                                x_out=out_col, kb=ktot // KSTEP, tiles=op.tiles, relu=op.relu, runs=cols,
                                first_tile=op.first_tile, x_in=segs[0][0], kind=kind,
-                               stage_view=int(kind == 1 and a.use_viewdirs)))
+                               stage_view=int(kind == 1 and a.use_viewdirs), chunk0=chunk0,
+                               enc_mask=sum(1 << i for i, s in enumerate(op.segs) if s.regset == "enc")))
+            chunk0 += len(op.tiles) * (ktot // KSTEP)
             if kind == 0 or (kind == 1 and len(op.tiles) > 1):
                 cur = out_col           # a head that is only the density row leaves the trunk output where it is
         return layers
@@ -374,11 +381,7 @@ class Plan:
         offs, _ = self.param_offsets()
         rows = []
         for L in self.f32_layers():
-            # natural column list of this layer input (padded per run to 16)
-            colmap = []
-            for (_, wcol0, n) in L["runs"]:
-                pad = _ceil(n, KSTEP) * KSTEP
-                colmap += [wcol0 + c if c < n else -1 for c in range(pad)]
+            colmap = self._f32_colmap(L)
             for tile in L["tiles"]:
                 for kb in range(L["kb"]):
                     tab = np.full((64, 8), -1, dtype=np.int32)
@@ -391,6 +394,57 @@ class Plan:
                             tab[hi * 32 + m, j] = offs[tile.wt] + (tile.row0 + m) * tile.ld + col
                     rows.append(tab)
         return np.stack(rows)
+
+    @staticmethod
+    def _f32_colmap(L):
+        """natural column list of a layer's input (every run padded to whole k blocks with -1)"""
+        colmap = []
+        for (_, wcol0, n) in L["runs"]:
+            colmap += [wcol0 + c if c < n else -1 for c in range(_ceil(n, KSTEP) * KSTEP)]
+        return colmap
+
+    # ---- the tables as the library carries them (blob below) ---------------------------------
+    def chunk_descs(self) -> np.ndarray:
+        """int32 [n_chunks, 20]: one record (tensor, row0, ld, nrows, col[16]) per chunk of pack_table():
+        pack_table()[ci, hi * 32 + m, j] = offset of tensor + (row0 + m) * ld + col[hi * 8 + j] for m < nrows, and -1 where
+        col < 0 or m >= nrows.  The k map, the segments, the pairing and the padding chunks (nrows = 0) are all in col and the order."""
+        d = np.zeros((len(self.chunks), 20), np.int32)
+        d[:, 4:] = -1
+        for ci, (oi, ti, ks) in enumerate(self.chunks):
+            if oi < 0:
+                continue
+            tile = self.ops[oi].tiles[ti]
+            seg, ksl = self.seg_of(self.ops[oi], ks)
+            cols = [self.kmap(seg.kind, ksl, hi, j) for hi in range(2) for j in range(8)]
+            d[ci] = [tile.wt, tile.row0, tile.ld, tile.nrows] + [seg.col0 + c if c < seg.ncols else -1 for c in cols]
+        return d
+
+    def chunk_descs_f32(self) -> np.ndarray:
+        """The same records for pack_table_f32(): [layer][tile][kb] order, natural columns."""
+        return np.array([[tile.wt, tile.row0, tile.ld, tile.nrows] + colmap[kb * KSTEP:(kb + 1) * KSTEP]
+                         for L in self.f32_layers() for colmap in [self._f32_colmap(L)]
+                         for tile in L["tiles"] for kb in range(L["kb"])], np.int32)
+
+
+BLOB_MAGIC = 0x504C4E31      # 'PLN1'
+DESC_INTS, LAYER_INTS = 20, 12
+
+
+def blob(plain: Plan, fwd: Plan) -> bytes:
+    """Binary tables of one architecture variant linked into libmipnerf_hip.so (gen_mlp_bf16.py writes it, capi.hip reads it and derives
+    nothing): header (16 int32: magic, chunks / tiles of `plain`, chunks / tiles of `fwd`, fp32 chunks, layers, parameter count, fold,
+    total int32 count), then the chunk records and the bias table of `plain` (Plan.build(arch): the fp32 kernels, debug tables 0 / 1),
+    those of `fwd` (the bf16 forward kernels' plan) unless it is the same plan (fold = 0), the fp32 stream's chunk records, and one row
+    per fp32 layer: x_in0, kb0, x_in1, kb1, x_out, ntiles, first_tile, relu, kind, chunk0, stage_view, enc_mask."""
+    assert fwd.arch == plain.arch and not plain.fold_view
+    layers = np.array([[L["x_in0"], L["kb0"], L["x_in1"], L["kb1"], L["x_out"], len(L["tiles"]), L["first_tile"], int(L["relu"]), L["kind"],
+                        L["chunk0"], L["stage_view"], L["enc_mask"]] for L in plain.f32_layers()], np.int32)
+    f32 = plain.chunk_descs_f32()
+    parts = [plain.chunk_descs(), plain.bias_table()] + ([fwd.chunk_descs(), fwd.bias_table()] if fwd.fold_view else []) + [f32, layers]
+    h = np.zeros(16, np.int32)
+    h[:10] = [BLOB_MAGIC, len(plain.chunks), plain.n_tiles, len(fwd.chunks), fwd.n_tiles, len(f32), len(layers), plain.param_offsets()[1],
+              int(fwd.fold_view), 16 + sum(p.size for p in parts)]
+    return b"".join(x.astype(np.int32).tobytes() for x in [h] + parts)
 
 
 def fold_params(arch: Arch, flat_params: np.ndarray) -> np.ndarray:

@@ -162,6 +162,72 @@ def test_architecture_variants_exported(lib):
             np.testing.assert_array_equal(got, want)
 
 
+def _read_plan_blob(b, plain, fwd):
+    """capi.hip's plan_tables restated: the sections of mlp_plan.blob() as arrays, or None where the library refuses the blob.  The
+    counts the library takes from the generated PlanDesc come from the two plans here."""
+    w = np.frombuffer(b, np.int32)
+    h = w[:16]
+    fold = int(fwd.fold_view)
+    if (h[0] != 0x504C4E31 or h[1] != len(plain.chunks) or h[2] != plain.n_tiles or h[3] != len(fwd.chunks) or h[4] != fwd.n_tiles or
+            not 0 <= h[5] <= len(plain.chunks) or h[6] != len(plain.ops) or h[6] > 16 or h[7] != plain.param_offsets()[1] or h[8] != fold):
+        return None
+    if not fold and (h[3] != h[1] or h[4] != h[2]):
+        return None
+    sizes = [h[1] * 20, h[2] * 32] + ([h[3] * 20, h[4] * 32] if fold else []) + [h[5] * 20, h[6] * 12]
+    if 16 + sum(sizes) != h[9]:
+        return None
+    parts = np.split(w[16:h[9]], np.cumsum(sizes)[:-1])
+    names = ["pack", "bias"] + (["fwd_pack", "fwd_bias"] if fold else []) + ["pack_f32", "layers"]
+    T = dict(zip(names, parts))
+    if not fold:
+        T["fwd_pack"], T["fwd_bias"] = T["pack"], T["bias"]
+    return T
+
+
+def _expand_chunk_records(desc, offs):
+    """idx[hi * 32 + m][j] = offs[tensor] + (row0 + m) * ld + col[hi * 8 + j] for m < nrows, -1 where col < 0 or m >= nrows"""
+    d = desc.reshape(-1, 20)
+    tensor, row0, ld, nrows = (d[:, i, None, None, None] for i in range(4))
+    col = d[:, 4:].reshape(-1, 2, 1, 8)
+    m = np.arange(32).reshape(1, 1, 32, 1)
+    idx = np.asarray(offs)[tensor] + (row0 + m) * ld + col
+    return np.where((col >= 0) & (m < nrows), idx, -1).reshape(-1, 64, 8)
+
+
+def _blob_archs():
+    from mipnerf_pl_amd.mlp_plan import Arch
+    return _variants() + [Arch(net_width=192, net_width_condition=64), Arch(net_width=64, net_width_condition=64)]
+
+
+@pytest.mark.parametrize("ai", range(9))
+def test_plan_blob_expands_to_the_python_tables(ai):
+    """The chunk records, bias tables and counts of mlp_plan.blob() (what the library links in and expands) give back pack_table(),
+    pack_table_f32() and both bias_table()s: every shape of VARIANTS and the two narrow ad-hoc shapes, with the forward plan plain and
+    folded (1-row density tiles, the 3-row colour tile, the 27-column view segment, all-padding chunks, the skip concat, no view
+    directions).  A blob with any one header count altered is refused by the reader's consistency checks."""
+    from mipnerf_pl_amd import mlp_plan
+    arch = _blob_archs()[ai]
+    plain = Plan.build(arch)
+    want = dict(pack=plain.pack_table(), pack_f32=plain.pack_table_f32(), bias=plain.bias_table().ravel())
+    assert (want["pack"][plain.n_real_chunks:] == -1).all()
+    for fold in (False, True):
+        fwd = Plan.build(arch, fold_view=fold)
+        blob = mlp_plan.blob(plain, fwd)
+        T = _read_plan_blob(blob, plain, fwd)
+        assert T is not None
+        offs = fwd.param_offsets()[0]                 # the real tensors, then the derived ones of a folded plan
+        np.testing.assert_array_equal(_expand_chunk_records(T["pack"], offs), want["pack"])
+        np.testing.assert_array_equal(_expand_chunk_records(T["pack_f32"], offs), want["pack_f32"])
+        np.testing.assert_array_equal(T["bias"], want["bias"])
+        np.testing.assert_array_equal(_expand_chunk_records(T["fwd_pack"], offs), fwd.pack_table())
+        np.testing.assert_array_equal(T["fwd_bias"], fwd.bias_table().ravel())
+        assert fwd.fold_view == (fold and arch.use_viewdirs) and (fwd.fold_view or T["fwd_pack"] is T["pack"])
+        for i in range(1, 10):
+            bad = np.frombuffer(blob, np.int32).copy()
+            bad[i] += 1
+            assert _read_plan_blob(bad.tobytes(), plain, fwd) is None, f"header word {i} altered and the blob still accepted"
+
+
 def test_variant_dataflow_emulation_matches_oracle():
     """Register dataflow of the generated bf16 kernels for the non-default shapes (half-width trunk; no view directions:
     density-only head, colour head on the trunk output), emulated in fp32, against the oracle MLP."""
