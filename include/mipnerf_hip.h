@@ -318,7 +318,7 @@ int mipnerf_area_downscale(int32_t num_images, int32_t height, int32_t width, in
  * colour is dropped), a strided store of the density.  The chunk is what the workspace holds: any size from
  * mipnerf_density_grid_workspace_bytes(ctx, chunk_points >= 1, precision) on is accepted (16-byte aligned), results do not depend on
  * it; a chunk past 256 points is cut to whole 256-point tiles.  Both precisions and every MLP shape of the bounded model;
- * cfg.unbounded = 1: MIPNERF_E_UNSUPPORTED (a lattice in the contracted space is a different question).  Does not allocate or
+ * cfg.unbounded = 1: MIPNERF_E_UNSUPPORTED (that model's lattice has to name its space: mipnerf_density_grid_360 below).  Does not allocate or
  * synchronise (graph-capturable). */
 size_t mipnerf_density_grid_workspace_bytes(const mipnerf_ctx* ctx, int64_t chunk_points, int precision);
 int mipnerf_density_grid(mipnerf_ctx* ctx, const int32_t* dims_host, const float* lo_host, const float* hi_host, float cov_scale,
@@ -347,6 +347,47 @@ int mipnerf_isosurface_count(const int32_t* dims_host, const float* grid, float 
 int mipnerf_isosurface_emit(const int32_t* dims_host, const float* lo_host, const float* hi_host, const float* grid, float threshold,
                             const void* workspace, size_t workspace_bytes, float* vertices, float* normals, int32_t* faces,
                             int64_t* vertex_edges, void* stream);
+
+/* ---- lattice of the unbounded-scene model (cfg.unbounded = 1; ABI 6 grows; nothing above changes) ----
+ * The MLP of that model reads the off-axis encoding of CONTRACTED Gaussians, so a lattice has to say in which space it lies.  dims, lo,
+ * hi, the flat index, h and cov_scale are those of the lattice above.
+ *   MIPNERF_SPACE_WORLD       the lattice lies in world coordinates: the Gaussian (lo + float(i) * h, diag(cov_scale * h * h / 12)) per
+ *                             axis in fp32 is contracted -- mean' = contract(mean), cov' = J cov J^T, the generic triple product of
+ *                             csrc/raymath360.hpp contract_gaussian, the sequence mipnerf_gauss_360 runs with contracted = 1 -- and then
+ *                             encoded.  For the central object of a capture.
+ *   MIPNERF_SPACE_CONTRACTED  the lattice is uniform in the contracted coordinates z (the whole scene lies in |z| < 2; the usual box is
+ *                             [-2, 2]^3): the Gaussian (z, diag(cov_scale * h * h / 12)) is encoded as it stands (contracted = 0).  With
+ *                             c = 2.f - 1.f / far_radius in fp32 (far_radius finite and > 1, world units) a point is OUTSIDE when its
+ *                             fp32 (zx * zx + zy * zy) + zz * zz exceeds c * c, and its density is then exactly 0.f.  far_radius is not
+ *                             read in world space.
+ * Un-contraction z -> x with contract(x) = z, in fp32: n = sqrt((zx * zx + zy * zy) + zz * zz); n <= 1: x = z; otherwise
+ * r = min(1.f / (2.f - min(n, c)), far_radius) and x = z * (r / n).  |z| is capped at c and the difference is exact for n in [1, 2]; the
+ * outer minimum keeps the promise that no result lies beyond far_radius where c is rounded up (far_radius no power of two) or to 2
+ * (far_radius >= 2^24).  A normal g of the contracted lattice is a density-gradient direction; its world direction is J^T g with the
+ * symmetric Jacobian J of the contraction at x, evaluated as normalize((2 r - 1) (g - (u . g) u) + (u . g) u), u = z / n; n <= 1: g
+ * unchanged; (0, 0, 0), or a result that is not finite, gives (0, 0, 0).
+ * mipnerf_density_grid_360: sigma [nz, ny, nx] fp32 of the lattice, walked in chunks as mipnerf_density_grid does: encoding rows from the
+ * lattice index (fp32 rows, or bf16 fragments of whole 256-point tiles), the MLP path of mipnerf_mlp_forward on a zero view encoding (bf16:
+ * the one-kernel form where the variant has one and option 6 is on, else the two-kernel form with its scratch inside the workspace), the
+ * density store (with the outside rule in the contracted space).  The chunk is the largest the workspace holds by
+ * mipnerf_density_grid_360_workspace_bytes(ctx, chunk_points >= 1, precision) (256-byte aligned); a chunk past 256 points is cut to whole
+ * 256-point tiles; results do not depend on it.  MIPNERF_E_UNSUPPORTED: a bounded context, or a variant without a kernel at `precision`
+ * (the workspace size is then 0).  MIPNERF_E_INVALID before any launch: bad dims, an unknown space, far_radius not finite or <= 1,
+ * cov_scale negative or not finite.  Does not allocate or synchronise (graph-capturable).
+ * mipnerf_lattice_ipe_360: the encoder alone (no context): rows [count, 42 * (max_deg - min_deg)] of the lattice points first ..
+ * first + count - 1 in fp32, bf16 or MIPNERF_OUT_BF16_FRAGMENTS (the buffer then holds ceil(count / 256) * 256 rows; points past the end
+ * repeat the last one); max_deg - min_deg a multiple of 8; enc 32-byte aligned.  Bit-identical to mipnerf_gauss_360 on the same Gaussians.
+ * mipnerf_uncontract_vertices: z [V, 3] -> x_out [V, 3] (may be NULL) and, when normals_z [V, 3] is given, normals_out [V, 3] by the rules
+ * above.  V = 0 returns without a launch.  Does not allocate or synchronise. */
+enum { MIPNERF_SPACE_WORLD = 0, MIPNERF_SPACE_CONTRACTED = 1 };
+size_t mipnerf_density_grid_360_workspace_bytes(const mipnerf_ctx* ctx, int64_t chunk_points, int precision);
+int mipnerf_density_grid_360(mipnerf_ctx* ctx, const int32_t* dims_host, const float* lo_host, const float* hi_host, float cov_scale,
+                             int space, float far_radius, int precision, float* sigma, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int mipnerf_lattice_ipe_360(const int32_t* dims_host, const float* lo_host, const float* hi_host, int64_t first, int64_t count,
+                            float cov_scale, int space, int32_t min_deg, int32_t max_deg, void* enc, int out_dtype, void* stream);
+int mipnerf_uncontract_vertices(int64_t num_vertices, float far_radius, const float* z, const float* normals_z, float* x_out,
+                                float* normals_out, void* stream);
 
 /* ---- empty-space skipping for whole frames: occupancy bits of any lattice, ray culling, compaction (ABI 6 grows; nothing above changes) ----
  * The conventions are those of the lattice above: dims = (nx, ny, nz) points over lo .. hi in (x, y, z) order, h = (hi - lo) /

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("MIPNERF_LIB", os.path.join(HERE, "csrc", "libmipnerf_
 OK, E_INVALID, E_UNSUPPORTED, E_HIP, E_WORKSPACE = 0, 1, 2, 3, 4
 PREC_FP32, PREC_BF16 = 0, 1
 OUT_BF16_FRAGMENTS = 2      # out_dtype of mipnerf_cast_ipe_360 only (include/mipnerf_hip.h)
+SPACE_WORLD, SPACE_CONTRACTED = 0, 1   # lattice spaces of the unbounded-scene model (include/mipnerf_hip.h)
+SPACES = {"world": SPACE_WORLD, "contracted": SPACE_CONTRACTED}
 FLAG_WHITE_BKGD, FLAG_DISPARITY = 1, 2
 NUM_PARAM_TENSORS = 24
 MAX_SAMPLES = 1024
@@ -84,6 +86,10 @@ SIGNATURES = {
     "mipnerf_area_downscale": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
     "mipnerf_density_grid_workspace_bytes": (_SZ, [_P, _I64, C.c_int]),
     "mipnerf_density_grid": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _F, C.c_int, _P, _P, _SZ, _P]),
+    "mipnerf_density_grid_360_workspace_bytes": (_SZ, [_P, _I64, C.c_int]),
+    "mipnerf_density_grid_360": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _F, C.c_int, _F, C.c_int, _P, _P, _SZ, _P]),
+    "mipnerf_lattice_ipe_360": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _I64, _I64, _F, C.c_int, _I32, _I32, _P, C.c_int, _P]),
+    "mipnerf_uncontract_vertices": (C.c_int, [_I64, _F, _P, _P, _P, _P, _P]),
     "mipnerf_isosurface_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "mipnerf_isosurface_count": (C.c_int, [C.POINTER(_I32), _P, _F, _P, _SZ, C.POINTER(_I64), C.POINTER(_I64), _P]),
     "mipnerf_isosurface_emit": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _F, _P, _SZ, _P, _P, _P, _P, _P]),

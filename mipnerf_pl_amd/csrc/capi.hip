@@ -875,6 +875,115 @@ int mipnerf_density_grid(mipnerf_ctx* c, const int32_t* dims, const float* lo, c
     return MIPNERF_OK;
 }
 
+// ---- the same for the unbounded-scene model (kernels_360.hip) ---------------------------------------------------------------
+// bf16 runs the one-kernel form on fragments where the variant has one (and option 6 has not switched it off); the two-kernel form
+// needs its 1.5 KiB per point of scratch between the kernels
+static inline bool grid360_one_kernel(const mipnerf_ctx* c) {
+    return c->fused_pre && c->d_fused_stream && mip::kLaunchBf16Fused[c->P->variant] != nullptr;
+}
+// workspace: zero view row | encoding (fp32 rows, or bf16 fragments of whole 256-point tiles) | pre_x | pre_acc | activated outputs [chunk, 4];
+// strictly increasing in the chunk, so the chunk a workspace holds is well defined
+static size_t grid360_bytes(const mipnerf_ctx* c, int64_t chunk, int precision) {
+    size_t b = kGridViewBytes + (size_t)chunk * 16;
+    if (precision == MIPNERF_PREC_BF16) {
+        b += pre_frag_bytes(c, (size_t)chunk);
+        if (!grid360_one_kernel(c)) b += pre_x_bytes(chunk) + pre_acc_bytes(chunk);
+    } else {
+        b += (size_t)chunk * c->P->xyz_dim * 4;
+    }
+    return b;
+}
+static int grid360_check(const char* who, const mipnerf_ctx* c, int precision) {
+    if (!c->cfg.unbounded) return fail(MIPNERF_E_UNSUPPORTED, "%s: a bounded model; its lattice is mipnerf_density_grid", who);
+    if (!max_deg_span_is_16(c->cfg) || c->P->xyz_dim != 42 * 16)
+        return fail(MIPNERF_E_UNSUPPORTED, "%s: the lattice encoder is generated for max_deg_point - min_deg_point == 16", who);
+    if (precision == MIPNERF_PREC_BF16 && !has_bf16_pre(c->P))
+        return fail(MIPNERF_E_UNSUPPORTED, "%s: this architecture variant has no bf16 kernel for the 672-wide encoding", who);
+    return MIPNERF_OK;
+}
+static int lattice360_args(const char* who, const int32_t* dims, const float* lo, const float* hi, float cov_scale, int space, float far_radius,
+                           int precision) {
+    if (int rc = lattice_check(who, dims, lo, hi)) return rc;
+    if (space != MIPNERF_SPACE_WORLD && space != MIPNERF_SPACE_CONTRACTED) return fail(MIPNERF_E_INVALID, "%s: unknown space %d", who, space);
+    if (!(std::isfinite(far_radius) && far_radius > 1.0f)) return fail(MIPNERF_E_INVALID, "%s: far_radius must be finite and > 1", who);
+    if (!(cov_scale >= 0.0f) || !std::isfinite(cov_scale)) return fail(MIPNERF_E_INVALID, "%s: cov_scale must be finite and >= 0", who);
+    if (precision != MIPNERF_PREC_FP32 && precision != MIPNERF_PREC_BF16) return fail(MIPNERF_E_INVALID, "%s: unknown precision %d", who, precision);
+    return MIPNERF_OK;
+}
+
+size_t mipnerf_density_grid_360_workspace_bytes(const mipnerf_ctx* c, int64_t chunk_points, int precision) {
+    if (!c || chunk_points < 1 || (precision != MIPNERF_PREC_FP32 && precision != MIPNERF_PREC_BF16)) return 0;
+    if (!c->cfg.unbounded || c->P->xyz_dim != 42 * 16 || (precision == MIPNERF_PREC_BF16 && !has_bf16_pre(c->P))) return 0;
+    return grid360_bytes(c, chunk_points, precision);
+}
+
+int mipnerf_density_grid_360(mipnerf_ctx* c, const int32_t* dims, const float* lo, const float* hi, float cov_scale, int space,
+                             float far_radius, int precision, float* sigma, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = lattice360_args("density_grid_360", dims, lo, hi, cov_scale, space, far_radius, precision)) return rc;
+    if (!c || !sigma || !workspace) return fail(MIPNERF_E_INVALID, "density_grid_360: null argument");
+    if (int rc = grid360_check("density_grid_360", c, precision)) return rc;
+    if (!c->params_set) return fail(MIPNERF_E_INVALID, "density_grid_360: mipnerf_set_params has not been called");
+    if ((uintptr_t)workspace & 255) return fail(MIPNERF_E_INVALID, "density_grid_360: the workspace must be 256-byte aligned");
+    const int64_t n = (int64_t)dims[0] * dims[1] * dims[2];
+    if (workspace_bytes < grid360_bytes(c, 1, precision))
+        return fail(MIPNERF_E_WORKSPACE, "density_grid_360: the workspace holds no lattice point (see mipnerf_density_grid_360_workspace_bytes)");
+    int64_t chunk = 1, up = n;                                         // the largest chunk the workspace holds
+    while (chunk < up) {
+        const int64_t mid = chunk + (up - chunk + 1) / 2;
+        if (grid360_bytes(c, mid, precision) <= workspace_bytes) chunk = mid; else up = mid - 1;
+    }
+    if (chunk > 256 && chunk < n) chunk -= chunk % 256;                // whole MLP tiles except in the last chunk
+    const bool bf16 = precision == MIPNERF_PREC_BF16;
+    char* ws = (char*)workspace;
+    char* enc = ws + kGridViewBytes;
+    char* pre_x = enc + (bf16 ? pre_frag_bytes(c, (size_t)chunk) : (size_t)chunk * c->P->xyz_dim * 4);
+    char* pre_acc = pre_x + (bf16 && !grid360_one_kernel(c) ? pre_x_bytes(chunk) : 0);
+    float* rgb_sigma = (float*)(pre_acc + (bf16 && !grid360_one_kernel(c) ? pre_acc_bytes(chunk) : 0));
+    const float cap = 2.0f - 1.0f / far_radius;
+    HIP_TRY(hipMemsetAsync(ws, 0, kGridViewBytes, S(stream)));
+    for (int64_t first = 0; first < n; first += chunk) {
+        const int64_t m = n - first < chunk ? n - first : chunk;
+        HIP_TRY(mip::launch_lattice_ipe_360(dims, lo, hi, first, m, cov_scale, space == MIPNERF_SPACE_WORLD, c->cfg.min_deg_point,
+                                            c->cfg.max_deg_point, enc, bf16, bf16, S(stream)));
+        // num_samples = m: every point of the chunk reads view row 0
+        if (bf16) {
+            HIP_TRY(launch_bf16_pre(c, enc, 1, ws, rgb_sigma, nullptr, m, (int)m, pre_x, pre_acc, nullptr, S(stream)));
+        } else if (int rc = mipnerf_mlp_forward(c, m, (int32_t)m, enc, ws, precision, rgb_sigma, nullptr, stream)) {
+            return rc;
+        }
+        if (space == MIPNERF_SPACE_CONTRACTED) {
+            HIP_TRY(mip::launch_store_sigma_360(dims, lo, hi, first, m, cap * cap, rgb_sigma, sigma, S(stream)));
+        } else {
+            HIP_TRY(mip::launch_store_sigma(m, rgb_sigma, sigma + first, S(stream)));
+        }
+    }
+    return MIPNERF_OK;
+}
+
+int mipnerf_lattice_ipe_360(const int32_t* dims, const float* lo, const float* hi, int64_t first, int64_t count, float cov_scale, int space,
+                            int32_t min_deg, int32_t max_deg, void* enc, int out_dtype, void* stream) {
+    if (int rc = lattice360_args("lattice_ipe_360", dims, lo, hi, cov_scale, space, 2.0f, MIPNERF_PREC_FP32)) return rc;
+    const bool frag = out_dtype == MIPNERF_OUT_BF16_FRAGMENTS;
+    if (out_dtype != MIPNERF_PREC_FP32 && out_dtype != MIPNERF_PREC_BF16 && !frag) return fail(MIPNERF_E_INVALID, "lattice_ipe_360: unknown out_dtype %d", out_dtype);
+    if (min_deg < 0 || max_deg <= min_deg || max_deg > 31 || (21 * (max_deg - min_deg)) % 8)
+        return fail(MIPNERF_E_INVALID, "lattice_ipe_360: need 0 <= min_deg < max_deg <= 31 and max_deg - min_deg a multiple of 8");
+    if (first < 0 || count < 1 || first + count > (int64_t)dims[0] * dims[1] * dims[2]) return fail(MIPNERF_E_INVALID, "lattice_ipe_360: points outside the lattice");
+    if (!enc || ((uintptr_t)enc & 31)) return fail(MIPNERF_E_INVALID, "lattice_ipe_360: enc must be a 32-byte aligned device pointer");
+    HIP_TRY(mip::launch_lattice_ipe_360(dims, lo, hi, first, count, cov_scale, space == MIPNERF_SPACE_WORLD, min_deg, max_deg, enc,
+                                        out_dtype != MIPNERF_PREC_FP32, frag, S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_uncontract_vertices(int64_t V, float far_radius, const float* z, const float* normals_z, float* x_out, float* normals_out,
+                                void* stream) {
+    if (V < 0 || !(std::isfinite(far_radius) && far_radius > 1.0f)) return fail(MIPNERF_E_INVALID, "uncontract_vertices: far_radius must be finite and > 1, num_vertices >= 0");
+    if ((normals_z == nullptr) != (normals_out == nullptr)) return fail(MIPNERF_E_INVALID, "uncontract_vertices: normals in and out go together");
+    if (V == 0) return MIPNERF_OK;
+    if (!z || (!x_out && !normals_out)) return fail(MIPNERF_E_INVALID, "uncontract_vertices: null argument");
+    HIP_TRY(mip::launch_uncontract(V, far_radius, z, normals_z, x_out, normals_out, S(stream)));
+    return MIPNERF_OK;
+}
+
 // workspace of the extraction: totals [2] (padded to 256 bytes) | vbase [n] | block_v [nb] | block_f [nb] | mask [n]
 struct IsoWorkspace {
     unsigned* totals; unsigned* vbase; unsigned* block_v; unsigned* block_f; unsigned char* mask;

@@ -63,6 +63,15 @@ hipError_t launch_cast_ipe_360(int64_t B, int N, int min_deg, int max_deg, int c
 
 hipError_t launch_gauss_360(int64_t M, int min_deg, int max_deg, int contracted, const float* means, const float* covs, void* enc,
                             bool bf16, float* means_out, float* covs_out, hipStream_t st);
+// lattice of the unbounded-scene model: encoding rows [count, 42 * (max_deg - min_deg)] of the lattice points first ... first + count - 1
+// (contracted != 0: the lattice lies in world space and each Gaussian is contracted first); frag: bf16 fragments, whole 256-point tiles.
+// store_sigma_360: sigma[first + s] = the density of chunk row s, or 0 where the point's squared norm exceeds c2.
+hipError_t launch_lattice_ipe_360(const int dims[3], const float lo[3], const float hi[3], int64_t first, int64_t count, float cov_scale,
+                                  int contracted, int min_deg, int max_deg, void* enc, bool bf16, bool frag, hipStream_t st);
+hipError_t launch_store_sigma_360(const int dims[3], const float lo[3], const float hi[3], int64_t first, int64_t count, float c2,
+                                  const float* rgb_sigma, float* sigma, hipStream_t st);
+// z -> x with contract(x) = z, nothing beyond far_radius; normals_z / normals may both be NULL, x may be NULL
+hipError_t launch_uncontract(int64_t V, float far_radius, const float* z, const float* normals_z, float* x, float* normals, hipStream_t st);
 
 // ---- kernels_train.hip ------------------------------------------------------------------------
 // dnoise (nullable): standard-normal draws [M]; the density pre-activation becomes raw + dnoise_scale * dnoise (mip_nerf.py:232-233)

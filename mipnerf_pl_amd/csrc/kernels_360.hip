@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "lattice.hpp"
 #include "raymath360.hpp"
 
 namespace mip {
@@ -99,28 +100,17 @@ constexpr int kFragSamples = 64;
 // An odd row length (PAD = 8) makes the 64 rows start in 64 different banks -- measured, no difference: 7.78-7.81 vs 7.79-7.82 ms per unbounded
 // bf16 forward; the kernel is bound by its 5.1 TB/s of stores, the conflicts hide behind them.
 constexpr int kIpe360RowPad = 7;
+// The part of the tile kernels behind the Gaussians: sg[m], m < 64, holds the Gaussian of sample s0 + m of M (samples past the end repeat the
+// last one).  Projections through LDS, then the vector stores.  Shared by the ray-side and the lattice-side kernel: same expressions, same bits.
+constexpr int kIpe360Row = kBasis360N + kIpe360RowPad;      // (>= 7 columns of wrap-around; see kIpe360RowPad above)
 template <typename OutT, bool FRAG>
-__global__ void __launch_bounds__(256)
-k_cast_ipe_360_tile(int64_t B, int N, int min_deg, int L, int contracted, const float* __restrict__ t, const float* __restrict__ origins,
-                    const float* __restrict__ dirs, const float* __restrict__ radii, OutT* __restrict__ enc) {
+__device__ __forceinline__ void ipe360_tile_store(const GaussFull (&sg)[kFragSamples], float (&sy)[kFragSamples][kIpe360Row],
+                                                  float (&sv)[kFragSamples][kIpe360Row], int tid, int64_t s0, int64_t M, int min_deg, int L,
+                                                  OutT* __restrict__ enc) {
     typedef OutT vec8 __attribute__((ext_vector_type(8)));
     // projections of a sample: its 21 directions followed by the first 7 again, so that the eight consecutive features of a vector
     // (directions j0 .. j0 + 7, wrapping into the next degree) are eight consecutive LDS words -- one address per vector, literal offsets
-    constexpr int kRow = kBasis360N + kIpe360RowPad;      // (>= 7 columns of wrap-around; see kIpe360RowPad above)
-    __shared__ GaussFull sg[kFragSamples];
-    __shared__ float sy[kFragSamples][kRow], sv[kFragSamples][kRow];
-    const int tid = threadIdx.x;
-    const int64_t s0 = (int64_t)blockIdx.x * kFragSamples, M = B * (int64_t)N;
-    if ((tid >> 6) == (int)(blockIdx.x & 3)) {
-        const int m = tid & 63;
-        const int64_t s = s0 + m, sc = s < M ? s : M - 1;
-        const int64_t b = sc / N;
-        const int i = (int)(sc - b * N);
-        const float d[3] = {dirs[b * 3], dirs[b * 3 + 1], dirs[b * 3 + 2]};
-        const float o[3] = {origins[b * 3], origins[b * 3 + 1], origins[b * 3 + 2]};
-        sg[m] = conical_frustum_to_gaussian_full(t[b * (N + 1) + i], t[b * (N + 1) + i + 1], d, o, radii[b], contracted != 0);
-    }
-    __syncthreads();
+    constexpr int kRow = kIpe360Row;
     for (int idx = tid; idx < kFragSamples * kRow; idx += 256) {
         const int m = idx / kRow, jj = idx - m * kRow;
         float y, var;
@@ -156,6 +146,100 @@ k_cast_ipe_360_tile(int64_t B, int N, int min_deg, int L, int contracted, const 
             row[q] = fs;
             row[q + nq] = fc;
         }
+    }
+}
+
+template <typename OutT, bool FRAG>
+__global__ void __launch_bounds__(256)
+k_cast_ipe_360_tile(int64_t B, int N, int min_deg, int L, int contracted, const float* __restrict__ t, const float* __restrict__ origins,
+                    const float* __restrict__ dirs, const float* __restrict__ radii, OutT* __restrict__ enc) {
+    __shared__ GaussFull sg[kFragSamples];
+    __shared__ float sy[kFragSamples][kIpe360Row], sv[kFragSamples][kIpe360Row];
+    const int tid = threadIdx.x;
+    const int64_t s0 = (int64_t)blockIdx.x * kFragSamples, M = B * (int64_t)N;
+    if ((tid >> 6) == (int)(blockIdx.x & 3)) {
+        const int m = tid & 63;
+        const int64_t s = s0 + m, sc = s < M ? s : M - 1;
+        const int64_t b = sc / N;
+        const int i = (int)(sc - b * N);
+        const float d[3] = {dirs[b * 3], dirs[b * 3 + 1], dirs[b * 3 + 2]};
+        const float o[3] = {origins[b * 3], origins[b * 3 + 1], origins[b * 3 + 2]};
+        sg[m] = conical_frustum_to_gaussian_full(t[b * (N + 1) + i], t[b * (N + 1) + i + 1], d, o, radii[b], contracted != 0);
+    }
+    __syncthreads();
+    ipe360_tile_store<OutT, FRAG>(sg, sy, sv, tid, s0, M, min_deg, L, enc);
+}
+
+// ---- lattice of the unbounded-scene model (include/mipnerf_hip.h): the encoding rows of lattice points first .. first + count - 1 straight
+// from the lattice index, the arrangement of k_cast_ipe_360_tile with the Gaussian (lo + float(i) h, diag(cov_scale h h / 12)) in the place
+// of the conical frustum's.  contracted != 0 (the "world" space): the generic contract_gaussian, what k_gauss_360 runs on the same numbers;
+// contracted = 0 (the "contracted" space): the Gaussian is encoded as it stands.  Row s of `enc` is lattice point first + s; FRAG: whole
+// 256-point tiles, points past the end repeat the last one.  Store-bound: 1344 B per point in bf16, 2688 B in fp32.
+__device__ __forceinline__ void lattice_mean_360(const Lattice& g, int p, float mean[3]) {
+    int idx[3];
+    lattice_ijk(g, p, idx[0], idx[1], idx[2]);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) mean[a] = g.lo[a] + (float)idx[a] * lattice_step(g, a);
+}
+__device__ __forceinline__ void lattice_point_360(const Lattice& g, int p, float mean[3], float var[3], float cov_scale) {
+    lattice_mean_360(g, p, mean);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float h = lattice_step(g, a);
+        var[a] = cov_scale * h * h / 12.0f;      // variance of a uniform box of side h
+    }
+}
+
+template <typename OutT, bool FRAG>
+__global__ void __launch_bounds__(256)
+k_lattice_ipe_360_tile(Lattice g, int64_t first, int64_t count, float cov_scale, int contracted, int min_deg, int L, OutT* __restrict__ enc) {
+    __shared__ GaussFull sg[kFragSamples];
+    __shared__ float sy[kFragSamples][kIpe360Row], sv[kFragSamples][kIpe360Row];
+    const int tid = threadIdx.x;
+    const int64_t s0 = (int64_t)blockIdx.x * kFragSamples;
+    if ((tid >> 6) == (int)(blockIdx.x & 3)) {
+        const int m = tid & 63;
+        const int64_t s = s0 + m, sc = s < count ? s : count - 1;
+        GaussFull gs;
+        float var[3];
+        lattice_point_360(g, (int)(first + sc), gs.mean, var, cov_scale);
+        gs.cov[0] = var[0]; gs.cov[1] = 0.0f; gs.cov[2] = 0.0f; gs.cov[3] = var[1]; gs.cov[4] = 0.0f; gs.cov[5] = var[2];
+        if (contracted) contract_gaussian(gs);
+        sg[m] = gs;
+    }
+    __syncthreads();
+    ipe360_tile_store<OutT, FRAG>(sg, sy, sv, tid, s0, count, min_deg, L, enc);
+}
+
+// k_store_sigma of kernels_mesh.hip with the outside rule of the contracted space: the point is formed again from its index, and
+// where its fp32 (zx zx + zy zy) + zz zz exceeds c2 = c * c the density is exactly 0.
+__global__ void __launch_bounds__(256)
+k_store_sigma_360(Lattice g, int64_t first, int64_t count, float c2, const float4* __restrict__ rgb_sigma, float* __restrict__ sigma) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= count) return;
+    float z[3];
+    lattice_mean_360(g, (int)(first + s), z);
+    const float n2 = (z[0] * z[0] + z[1] * z[1]) + z[2] * z[2];
+    sigma[first + s] = n2 > c2 ? 0.0f : rgb_sigma[s].w;
+}
+
+// un-contraction of vertices and (normals_z != nullptr) normals: raymath360.hpp uncontract_point / uncontract_normal, one thread per vertex
+__global__ void __launch_bounds__(256)
+k_uncontract(int64_t V, float far_radius, const float* __restrict__ z, const float* __restrict__ normals_z, float* __restrict__ x,
+             float* __restrict__ normals) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const float zv[3] = {z[v * 3], z[v * 3 + 1], z[v * 3 + 2]};
+    if (x) {
+        float xv[3];
+        uncontract_point(zv, far_radius, xv);
+        x[v * 3] = xv[0]; x[v * 3 + 1] = xv[1]; x[v * 3 + 2] = xv[2];
+    }
+    if (normals_z) {
+        const float gv[3] = {normals_z[v * 3], normals_z[v * 3 + 1], normals_z[v * 3 + 2]};
+        float nv[3];
+        uncontract_normal(zv, far_radius, gv, nv);
+        normals[v * 3] = nv[0]; normals[v * 3 + 1] = nv[1]; normals[v * 3 + 2] = nv[2];
     }
 }
 
@@ -281,6 +365,33 @@ hipError_t launch_cast_ipe_360(int64_t B, int N, int min_deg, int max_deg, int c
     else
         hipLaunchKernelGGL((k_cast_ipe_360<float>), grid, block, 0, st, B, N, min_deg, L, contracted, t, origins, dirs, radii,
                            (float*)enc, means, covs, 0);
+    return hipGetLastError();
+}
+
+// frag: bf16 only -- the buffer covers ceil(count / 256) * 256 rows (whole tiles of the MLP kernels, as launch_cast_ipe_360); needs (21 * L) % 8 == 0
+hipError_t launch_lattice_ipe_360(const int dims[3], const float lo[3], const float hi[3], int64_t first, int64_t count, float cov_scale,
+                                  int contracted, int min_deg, int max_deg, void* enc, bool bf16, bool frag, hipStream_t st) {
+    const int L = max_deg - min_deg;
+    if ((kBasis360N * L) % 8 != 0 || (frag && !bf16) || count < 1) return hipErrorInvalidValue;
+    const Lattice g = make_lattice(dims, lo, hi);
+    const int64_t wgs = frag ? ((count + 255) / 256) * (256 / kFragSamples) : (count + kFragSamples - 1) / kFragSamples;
+    const dim3 grid((unsigned)wgs), block(256);
+    if (frag) hipLaunchKernelGGL((k_lattice_ipe_360_tile<__bf16, true>), grid, block, 0, st, g, first, count, cov_scale, contracted, min_deg, L, (__bf16*)enc);
+    else if (bf16) hipLaunchKernelGGL((k_lattice_ipe_360_tile<__bf16, false>), grid, block, 0, st, g, first, count, cov_scale, contracted, min_deg, L, (__bf16*)enc);
+    else hipLaunchKernelGGL((k_lattice_ipe_360_tile<float, false>), grid, block, 0, st, g, first, count, cov_scale, contracted, min_deg, L, (float*)enc);
+    return hipGetLastError();
+}
+
+// sigma: the whole lattice [nz, ny, nx]; rgb_sigma: the chunk's rows
+hipError_t launch_store_sigma_360(const int dims[3], const float lo[3], const float hi[3], int64_t first, int64_t count, float c2,
+                                  const float* rgb_sigma, float* sigma, hipStream_t st) {
+    hipLaunchKernelGGL(k_store_sigma_360, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, make_lattice(dims, lo, hi), first, count, c2,
+                       (const float4*)rgb_sigma, sigma);
+    return hipGetLastError();
+}
+
+hipError_t launch_uncontract(int64_t V, float far_radius, const float* z, const float* normals_z, float* x, float* normals, hipStream_t st) {
+    hipLaunchKernelGGL(k_uncontract, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, V, far_radius, z, normals_z, x, normals);
     return hipGetLastError();
 }
 

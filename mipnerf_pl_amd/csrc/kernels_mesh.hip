@@ -11,31 +11,12 @@
 
 #include "ipe.hpp"
 #include "kernels.hpp"
+#include "lattice.hpp"
 #include "raymath.hpp"
 
 namespace mip {
 
 static inline unsigned mesh_grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
-// ------------------------------------------------------------------------------------------
-// lattice geometry: point (i, j, k) has the mean lo + float(i) * h per axis, h = (hi - lo) / float(n - 1)  (include/mipnerf_hip.h)
-// ------------------------------------------------------------------------------------------
-struct Lattice {
-    int nx, ny, nz;
-    float lo[3], hi[3];
-};
-
-__device__ __forceinline__ float lattice_step(const Lattice& g, int a) {
-    const int n = a == 0 ? g.nx : (a == 1 ? g.ny : g.nz);
-    return (g.hi[a] - g.lo[a]) / (float)(n - 1);
-}
-
-__device__ __forceinline__ void lattice_ijk(const Lattice& g, int p, int& i, int& j, int& k) {
-    const int row = p / g.nx;
-    i = p - row * g.nx;
-    k = row / g.ny;
-    j = row - k * g.ny;
-}
 
 // Two threads per lattice point, as k_integrated_pos_enc: no means or covariances go through memory.
 template <typename OutT, int L>

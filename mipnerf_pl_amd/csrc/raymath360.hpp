@@ -125,6 +125,47 @@ MIP_HD void contract_gaussian(GaussFull& g) {
     for (int a = 0; a < 3; ++a) g.mean[a] *= c.mean_scale;
 }
 
+// The way back from the contracted space (include/mipnerf_hip.h, "lattice of the unbounded-scene model"): z -> x with contract(x) = z.
+// c = 2 - 1 / far_radius caps |z|.  With n = |z| > 1: r = |x| = min(1 / (2 - min(n, c)), far_radius) -- the difference is exact in fp32 for
+// n in [1, 2]; the second minimum holds the promise "nothing beyond far_radius" where c has been rounded up (far_radius no power of two) or
+// to 2 (far_radius >= 2^24) -- and x = z * (r / n); n <= 1: x = z.
+MIP_HD float uncontract_radius(float n, float far_radius) {
+    const float c = 2.0f - 1.0f / far_radius;
+    const float r = 1.0f / (2.0f - (n < c ? n : c));
+    return r < far_radius ? r : far_radius;
+}
+MIP_HD void uncontract_point(const float z[3], float far_radius, float x[3]) {
+    const float n = sqrtf((z[0] * z[0] + z[1] * z[1]) + z[2] * z[2]);
+    const float s = n > 1.0f ? uncontract_radius(n, far_radius) / n : 1.0f;
+    x[0] = n > 1.0f ? z[0] * s : z[0]; x[1] = n > 1.0f ? z[1] * s : z[1]; x[2] = n > 1.0f ? z[2] * s : z[2];
+}
+
+// A normal g of the contracted space is a density-gradient direction; the world gradient is J^T g with the symmetric J of
+// contract_jacobian at x = uncontract_point(z): J = (1 / r^2) ((2 r - 1) (I - u u^T) + u u^T), u = z / |z|.  The common factor drops out of
+// the direction: normalize((2 r - 1) (g - (u . g) u) + (u . g) u), every term of the size of g.  |z| <= 1: g as it stands.
+// (0, 0, 0), and a result that is not finite, give (0, 0, 0).
+MIP_HD void uncontract_normal(const float z[3], float far_radius, const float g[3], float out[3]) {
+    const float n = sqrtf((z[0] * z[0] + z[1] * z[1]) + z[2] * z[2]);
+    float w[3] = {g[0], g[1], g[2]};
+    if (n > 1.0f) {
+        const float r = uncontract_radius(n, far_radius);
+        const float u[3] = {z[0] / n, z[1] / n, z[2] / n};
+        const float ug = (u[0] * g[0] + u[1] * g[1]) + u[2] * g[2];
+        const float a = 2.0f * r - 1.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float radial = ug * u[k];
+            w[k] = a * (g[k] - radial) + radial;
+        }
+        const float len = sqrtf((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] /= len;
+    }
+    const float chk = (w[0] + w[1]) + w[2];
+    const bool ok = chk - chk == 0.0f;          // false for inf and NaN (0 / 0 when g = 0 outside the unit ball)
+    out[0] = ok ? w[0] : 0.0f; out[1] = ok ? w[1] : 0.0f; out[2] = ok ? w[2] : 0.0f;
+}
+
 // projection on basis direction j: y = p . mean, var = p^T cov p
 MIP_HD void project_360(const GaussFull& g, int j, float& y, float& var) {
     const float px = kBasis360[j][0], py = kBasis360[j][1], pz = kBasis360[j][2];

@@ -4,7 +4,9 @@
 (`ops.density_grid`: an anti-aliased volume at any resolution), its isosurface by marching tetrahedra (`ops.isosurface`), and the MLP's
 colour at every vertex seen against the surface normal (`ops.field_at`, bytes by `ops.image_to_u8`).  `write_ply` / `read_ply`: binary
 little-endian PLY with float positions and normals, uchar colours and int faces -- what viewers, slicers and physics tools load.
-The unbounded-scene model is refused: its field lives in a contracted space."""
+The unbounded-scene model's field lives in a contracted space, so its mesh has to name the lattice's space: `space="world"` (a box in
+world coordinates, for the central object of a capture) or `space="contracted"` (the whole scene: the surface is cut in contracted
+coordinates and un-contracted, `ops.uncontract`); without a `space` that model is refused."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -24,6 +26,7 @@ class Mesh(NamedTuple):
     colors: Optional[torch.Tensor]         # [V, 3] uint8, or None
     sigma: torch.Tensor                    # [nz, ny, nx] float32, the density volume the surface was cut from
     rgb: Optional[torch.Tensor] = None     # [V, 3] float32, the colours before quantisation
+    vertices_contracted: Optional[torch.Tensor] = None     # [V, 3] float32, space="contracted" only: the vertices where the surface was cut
 
 
 def _triple(v, cast):
@@ -37,20 +40,39 @@ def lattice_variance(dims, lo, hi, cov_scale):
     return np.float32(cov_scale) * h * h / np.float32(12)
 
 
-def extract_mesh(system_or_model, grid=256, lo=(-1.5,) * 3, hi=(1.5,) * 3, threshold=DEFAULT_THRESHOLD, cov_scale=1.0, color=True,
-                 precision=None):
+CONTRACTED_BOUND = 2.0        # the contracted space is the ball |z| < 2
+
+
+def default_box(space):
+    """(lo, hi) of a mesh whose box is not given: [-1.5, 1.5]^3, or all of the contracted space [-2, 2]^3"""
+    b = CONTRACTED_BOUND if space == "contracted" else 1.5
+    return (-b,) * 3, (b,) * 3
+
+
+def extract_mesh(system_or_model, grid=256, lo=None, hi=None, threshold=DEFAULT_THRESHOLD, cov_scale=1.0, color=True,
+                 precision=None, space=None, far_radius=64.0):
     """Density volume -> isosurface at `threshold` -> vertex colours.  `grid`: points per axis, or (nx, ny, nz); lo / hi: the box,
-    (x, y, z).  Colours are the MLP's activated rgb at each vertex as a Gaussian of the lattice's variance, seen along -normal."""
-    dims, lo, hi = _triple(grid, int), _triple(lo, float), _triple(hi, float)
+    (x, y, z) (default: `default_box(space)`).  Colours are the MLP's activated rgb at each vertex as a Gaussian of the lattice's variance,
+    seen along -normal.  `space` (unbounded=True models, which need it): 'world' -- the lattice lies in world coordinates --, or
+    'contracted': the surface is cut in the contracted coordinates, coloured at the contracted vertices seen along minus the WORLD normal,
+    and then positions and normals are un-contracted (`ops.uncontract`; no vertex beyond `far_radius`); `vertices_contracted` keeps the
+    cut.  Where the surface reaches the box or the far sphere it is cut open, not capped."""
+    box = default_box(space)
+    dims, lo, hi = _triple(grid, int), _triple(box[0] if lo is None else lo, float), _triple(box[1] if hi is None else hi, float)
     with torch.no_grad():
-        sigma = ops.density_grid(system_or_model, dims, lo, hi, cov_scale=cov_scale, precision=precision)
+        sigma = ops.density_grid(system_or_model, dims, lo, hi, cov_scale=cov_scale, precision=precision, space=space, far_radius=far_radius)
         vertices, normals, faces = ops.isosurface(sigma, threshold, lo, hi)
+        cut = None
+        if space == "contracted":
+            cut = vertices
+            vertices, normals = ops.uncontract(cut, normals, far_radius=far_radius)
         rgb = colors = None
         if color:
             var = torch.from_numpy(lattice_variance(dims, lo, hi, cov_scale)).to(vertices.device)
-            rgb = ops.field_at(system_or_model, vertices, var.expand(vertices.shape[0], 3), -normals, precision=precision)[:, :3].contiguous()
+            at = vertices if cut is None else cut
+            rgb = ops.field_at(system_or_model, at, var.expand(at.shape[0], 3), -normals, precision=precision, space=space)[:, :3].contiguous()
             colors = ops.image_to_u8(rgb) if rgb.numel() else torch.empty(0, 3, dtype=torch.uint8, device=rgb.device)
-    return Mesh(vertices, normals, faces, colors, sigma, rgb)
+    return Mesh(vertices, normals, faces, colors, sigma, rgb, cut)
 
 
 def _ply_header(num_vertices, num_faces, with_color):

@@ -521,23 +521,33 @@ def _lattice_args(name, dims, lo, hi):
     return dims, (C.c_int32 * 3)(*dims), (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
 
 
-def _field_mlp(mlp_or_model, name):
-    """The MLP of a system / MipNerf / MLP; the unbounded-scene model is refused (its field lives in a contracted space)."""
+def _field_mlp(mlp_or_model, name, space=None):
+    """The MLP of a system / MipNerf / MLP.  `space` None: the bounded model; the unbounded-scene model is refused (its field lives in a
+    contracted space, so its lattice has to name one).  `space` 'world' / 'contracted': the unbounded-scene model, and nothing else."""
     m = getattr(mlp_or_model, "mip_nerf", mlp_or_model)
     mlp = getattr(m, "mlp", m)
-    if getattr(m, "unbounded", False) or getattr(mlp, "_cfg_extra", {}).get("unbounded", 0):
-        raise NotImplementedError(f"{name}: unbounded=True models are not supported (meshing a contracted space is a different question)")
+    unbounded = bool(getattr(m, "unbounded", False) or getattr(mlp, "_cfg_extra", {}).get("unbounded", 0))
+    if space is not None and space not in L.SPACES:
+        raise ValueError(f"{name}: space must be None, 'world' or 'contracted', got {space!r}")
+    if unbounded and space is None:
+        raise NotImplementedError(f"{name}: unbounded=True models are not supported (meshing a contracted space is a different question) "
+                                  "unless the lattice names its space: space='world' or space='contracted'")
+    if space is not None and not unbounded:
+        raise ValueError(f"{name}: space={space!r} belongs to unbounded=True models; a bounded model's lattice lies in world space as it is")
     if not hasattr(mlp, "native"):
         raise TypeError(f"{name}: expected a MipNeRFSystem, MipNerf or MLP, got {type(mlp_or_model).__name__}")
     return mlp
 
 
-def density_grid(mlp_or_model, dims, lo, hi, cov_scale=1.0, precision=None, chunk=None):
+def density_grid(mlp_or_model, dims, lo, hi, cov_scale=1.0, precision=None, chunk=None, space=None, far_radius=64.0):
     """Activated density of the field on a lattice of dims = (nx, ny, nz) Gaussians over the box lo .. hi: `sigma` [nz, ny, nx] fp32.
     Point (i, j, k) has the mean lo + float32(i) * h, h = (hi - lo) / float32(n - 1), and the diagonal covariance cov_scale * h * h / 12
     (cov_scale = 0: a point query); the view branch runs on a zero view encoding.  `precision`: L.PREC_FP32 / L.PREC_BF16 or 'fp32' /
-    'bf16' (default: the model's).  `chunk`: lattice points per MLP launch (default 2^18); the result does not depend on it."""
-    mlp = _field_mlp(mlp_or_model, "density_grid")
+    'bf16' (default: the model's).  `chunk`: lattice points per MLP launch (default 2^18); the result does not depend on it.
+    `space` (unbounded=True models only, which need it): 'world' -- the lattice lies in world coordinates and each Gaussian is contracted
+    before it is encoded -- or 'contracted' -- the lattice is uniform in the contracted coordinates (the whole scene lies in |z| < 2) and
+    points beyond |z| = 2 - 1 / far_radius get the density 0; the rules are those of include/mipnerf_hip.h (mipnerf_density_grid_360)."""
+    mlp = _field_mlp(mlp_or_model, "density_grid", space)
     dev = next(mlp.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError(f"density_grid: the MI355X-native path needs the model on a HIP device (it is on {dev}); there is no CPU fallback")
@@ -549,21 +559,66 @@ def density_grid(mlp_or_model, dims, lo, hi, cov_scale=1.0, precision=None, chun
         raise ValueError("density_grid: chunk must be positive")
     with torch.cuda.device(dev):
         ctx = mlp.native(dev)
-        need = int(L.lib().mipnerf_density_grid_workspace_bytes(ctx.handle, chunk, prec))
+        sizer = L.lib().mipnerf_density_grid_workspace_bytes if space is None else L.lib().mipnerf_density_grid_360_workspace_bytes
+        need = int(sizer(ctx.handle, chunk, prec))
         if need == 0:
+            if space is not None and prec in (L.PREC_FP32, L.PREC_BF16):
+                raise NotImplementedError("density_grid: this unbounded model's architecture has no lattice kernel at the requested precision")
             raise ValueError(f"density_grid: unknown precision {precision!r}")
         ws = ctx.scratch("density_grid", need)
         sigma = torch.empty(max(dims[2], 0), max(dims[1], 0), max(dims[0], 0), device=dev, dtype=torch.float32)
-        L.check(L.lib().mipnerf_density_grid(ctx.handle, cdims, clo, chi, float(cov_scale), prec, _ptr(sigma), _ptr(ws), need, _stream()),
-                "density_grid")
+        if space is None:
+            L.check(L.lib().mipnerf_density_grid(ctx.handle, cdims, clo, chi, float(cov_scale), prec, _ptr(sigma), _ptr(ws), need, _stream()),
+                    "density_grid")
+        else:
+            L.check(L.lib().mipnerf_density_grid_360(ctx.handle, cdims, clo, chi, float(cov_scale), L.SPACES[space], float(far_radius), prec,
+                                                     _ptr(sigma), _ptr(ws), need, _stream()), "density_grid")
     return sigma
 
 
-def field_at(mlp_or_model, points, variances, viewdirs, precision=None):
+def lattice_ipe_360(dims, lo, hi, cov_scale=1.0, space="contracted", min_deg=0, max_deg=16, precision=L.PREC_FP32, fragments=False,
+                    first=0, count=None, device="cuda"):
+    """The lattice encoder of the unbounded-scene model alone (mipnerf_lattice_ipe_360): rows [count, 42 * (max_deg - min_deg)] of the
+    lattice points first .. first + count - 1, fp32 or bf16; fragments=True (bf16): the MFMA B-operand fragment layout, an opaque
+    [ceil(count / 256) * 256, features] buffer.  The bits of `integrated_pos_enc_360` on the Gaussians the header states."""
+    if space not in L.SPACES:
+        raise ValueError(f"lattice_ipe_360: space must be 'world' or 'contracted', got {space!r}")
+    dims, cdims, clo, chi = _lattice_args("lattice_ipe_360", dims, lo, hi)
+    count = dims[0] * dims[1] * dims[2] - first if count is None else int(count)
+    if fragments and precision != L.PREC_BF16:
+        raise ValueError("lattice_ipe_360(fragments=True) is a bf16 layout")
+    rows = (count + 255) // 256 * 256 if fragments else count
+    enc = torch.empty(max(rows, 0), 42 * (max_deg - min_deg), device=device, dtype=_torch_dtype(precision))
+    with torch.cuda.device(enc.device):
+        L.check(L.lib().mipnerf_lattice_ipe_360(cdims, clo, chi, int(first), count, float(cov_scale), L.SPACES[space], min_deg, max_deg,
+                                                _ptr(enc), L.OUT_BF16_FRAGMENTS if fragments else precision, _stream()), "lattice_ipe_360")
+    return enc
+
+
+def uncontract(points, normals=None, far_radius=64.0):
+    """The way back from the contracted space: points z [..., 3] -> x with contract(x) = z, |z| capped at 2 - 1 / far_radius so that no
+    result lies beyond far_radius.  With `normals` (density-gradient directions of the contracted space at those points) returns
+    (x, world normals): J^T g normalised, (0, 0, 0) staying (0, 0, 0).  The rules are those of include/mipnerf_hip.h."""
+    z = _f32c(points, "points")
+    g = None if normals is None else _f32c(normals, "normals")
+    if g is not None and g.shape != z.shape:
+        raise ValueError("uncontract: one normal per point")
+    V = z.numel() // 3
+    x = torch.empty_like(z)
+    nw = None if g is None else torch.empty_like(g)
+    with torch.cuda.device(z.device):
+        L.check(L.lib().mipnerf_uncontract_vertices(V, float(far_radius), _ptr(z), _ptr(g), _ptr(x), _ptr(nw), _stream()), "uncontract")
+    return x if g is None else (x, nw)
+
+
+def field_at(mlp_or_model, points, variances, viewdirs, precision=None, space=None):
     """The field at given Gaussians: points [M, 3], variances [M] (one isotropic variance per point) or [M, 3], unit view directions
     [M, 3] -> rgb_sigma [M, 4] = (r, g, b, sigma) activated.  mipnerf_integrated_pos_enc + mipnerf_pos_enc + mipnerf_mlp_forward with one
-    sample per ray: the calls the renderer's per-stage path makes, no second path."""
-    mlp = _field_mlp(mlp_or_model, "field_at")
+    sample per ray: the calls the renderer's per-stage path makes, no second path.
+    `space` (unbounded=True models only, which need it): the points and variances are given in that lattice space -- 'world': each
+    Gaussian is contracted, then encoded; 'contracted': encoded as given (mipnerf_gauss_360 either way).  The view directions are always
+    world directions."""
+    mlp = _field_mlp(mlp_or_model, "field_at", space)
     prec = mlp.precision if precision is None else {"fp32": L.PREC_FP32, "bf16": L.PREC_BF16}.get(precision, precision)
     points = _f32c(points, "points").reshape(-1, 3)
     M = points.shape[0]
@@ -573,9 +628,13 @@ def field_at(mlp_or_model, points, variances, viewdirs, precision=None):
     var = (var.reshape(M, 1).expand(M, 3) if var.numel() == M else var.reshape(M, 3)).contiguous()
     e = mlp._cfg_extra
     min_deg = e.get("min_deg_point", 0)
-    max_deg = e.get("max_deg_point", min_deg + mlp.arch["xyz_dim"] // 6)
+    max_deg = e.get("max_deg_point", min_deg + mlp.arch["xyz_dim"] // (6 if space is None else 42))
     with torch.no_grad():
-        enc = integrated_pos_enc((points, var), min_deg, max_deg, precision=prec).reshape(M, 1, -1)
+        if space is None:
+            enc = integrated_pos_enc((points, var), min_deg, max_deg, precision=prec).reshape(M, 1, -1)
+        else:
+            enc = integrated_pos_enc_360((points, torch.diag_embed(var)), min_deg, max_deg, contracted=space == "world",
+                                         precision=prec).reshape(M, 1, -1)
         venc = None
         if e.get("use_viewdirs", 1):
             venc = pos_enc(_f32c(viewdirs, "viewdirs").reshape(M, 3), 0, (mlp.arch["view_dim"] - 3) // 6, precision=prec)
