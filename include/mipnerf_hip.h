@@ -407,6 +407,19 @@ int mipnerf_uncontract_vertices(int64_t num_vertices, float far_radius, const fl
  * live iff some frustum's cell range contains an occupied bit (a ray with a NaN coordinate is live).  Fine samples lie inside
  * [t_0, t_N], so the coarse frusta cover them.  hi > lo on every axis, 1 <= num_samples <= MIPNERF_MAX_SAMPLES.  viewdirs and lossmult
  * of `rays` are not read.  Does not allocate or synchronise.
+ * mipnerf_ray_span: the occupied span of every ray.  "Frustum i hits" is exactly the per-frustum test of mipnerf_ray_occupancy above (the
+ * same fence posts, p0, p1, rho, cell ranges, clipping and outside_occupied), and live [num_rays] is byte for byte what
+ * mipnerf_ray_occupancy writes for the same arguments.  first = the smallest hitting frustum index, last = the largest; near' = t_first
+ * and far' = t_{last + 1}: near_out and far_out are the fence posts themselves, the same fp32 function of (near, far, N, i) that
+ * mipnerf_sample_along_rays evaluates with t_rand = NULL, bit for bit.  A dead ray gets first = N, last = -1, near' = near and
+ * far' = far.  first, last (int32 [num_rays]) and near_out, far_out (fp32 [num_rays]) may each be NULL and are then skipped.  One
+ * wavefront per ray: the 64-frustum buckets are tested forward up to the first one with a hit and then backward from the last one down
+ * to it; no bucket is tested twice and a dead ray costs what it costs mipnerf_ray_occupancy.  What a renderer drops when it samples
+ * [near', far'] instead of [near, far] lies in frusta that hit nothing: only in cells whose 8 lattice corners are at or below the
+ * threshold, after dilation -- the statement culling makes about dead rays -- but the samples of a tightened ray sit elsewhere, so its
+ * results are NOT those of the untightened ray.  The frusta cover [near, far] for any N, so the span found with one num_samples is valid
+ * for a renderer that uses another.  Arguments, validation and the zero-ray return as mipnerf_ray_occupancy.  Does not allocate or
+ * synchronise.
  * mipnerf_compact_rays: an exclusive scan of `live` (sums per 1024 rays, one single-workgroup scan, per-ray bases; no atomics), then
  * the live rays gathered IN THEIR ORIGINAL ORDER into out_rays (a NULL field is skipped) and out_index[j] = the source ray of compact
  * slot j.  The live count has to reach the host: the call makes one 8-byte read-back and SYNCHRONISES the stream -- it cannot be
@@ -422,6 +435,9 @@ int mipnerf_occupancy_build(const int32_t* dims_host, const float* grid, float t
 int mipnerf_ray_occupancy(const int32_t* dims_host, const float* lo_host, const float* hi_host, const uint32_t* bits, int64_t num_rays,
                           int32_t num_samples, const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale,
                           uint8_t* live, void* stream);
+int mipnerf_ray_span(const int32_t* dims_host, const float* lo_host, const float* hi_host, const uint32_t* bits, int64_t num_rays,
+                     int32_t num_samples, const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale,
+                     uint8_t* live, int32_t* first, int32_t* last, float* near_out, float* far_out, void* stream);
 size_t mipnerf_compact_rays_workspace_bytes(int64_t num_rays);
 int mipnerf_compact_rays(int64_t num_rays, const uint8_t* live, const mipnerf_rays* rays, const mipnerf_rays_out* out_rays,
                          int32_t* out_index, void* workspace, size_t workspace_bytes, int64_t* count_host, void* stream);

@@ -1077,6 +1077,24 @@ int mipnerf_ray_occupancy(const int32_t* dims, const float* lo, const float* hi,
     return MIPNERF_OK;
 }
 
+int mipnerf_ray_span(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
+                     const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale, uint8_t* live,
+                     int32_t* first, int32_t* last, float* near_out, float* far_out, void* stream) {
+    if (int rc = lattice_check("ray_span", dims, lo, hi)) return rc;
+    for (int a = 0; a < 3; ++a)
+        if (!(hi[a] > lo[a])) return fail(MIPNERF_E_INVALID, "ray_span: the box needs hi > lo on every axis");
+    if (B < 0 || B >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "ray_span: bad ray count");
+    if (N < 1 || N > MIPNERF_MAX_SAMPLES) return fail(MIPNERF_E_INVALID, "ray_span: num_samples must be in [1, %d]", MIPNERF_MAX_SAMPLES);
+    if (!(cone_scale >= 0.0f) || !std::isfinite(cone_scale)) return fail(MIPNERF_E_INVALID, "ray_span: cone_scale must be finite and >= 0");
+    if (B == 0) return MIPNERF_OK;
+    if (!bits || !rays || !rays->origins || !rays->directions || !rays->radii || !rays->near || !rays->far || !live)
+        return fail(MIPNERF_E_INVALID, "ray_span: null argument");
+    static_assert(sizeof(int) == sizeof(int32_t), "first / last are int32");
+    HIP_TRY(mip::launch_ray_span(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
+                                 disparity != 0, outside_occupied != 0, cone_scale, live, first, last, near_out, far_out, S(stream)));
+    return MIPNERF_OK;
+}
+
 // workspace of the compaction: the live count (8 bytes, padded to 256) | block_sum [compact_num_blocks(n)]
 size_t mipnerf_compact_rays_workspace_bytes(int64_t n) {
     if (n < 0 || n >= (1LL << 31)) return 0;

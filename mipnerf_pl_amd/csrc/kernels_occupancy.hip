@@ -4,6 +4,8 @@
 //                                y and z);
 //   k_ray_occupancy              one wavefront per ray: lanes take the coarse level's frusta lane, lane + 64, ..., test the cell range of
 //                                each frustum's bounding box with word masks, the wave reduces with a ballot;
+//   k_ray_span                   the same wave and the same per-frustum test: the smallest and the largest hitting frustum of a ray
+//                                (lowest / highest set bit of a bucket's ballot) and their outer fence posts near', far';
 //   k_compact_* / k_scatter_frame  exclusive scan of the live bytes (sums per 1024 rays + one single-workgroup scan + per-ray bases, the
 //                                arrangement of kernels_mesh.hip), the live rays gathered in their order, and the way back: every pixel of
 //                                every level written once.
@@ -162,6 +164,48 @@ __device__ __forceinline__ bool occ_box_test(const OccGrid& g, const unsigned* _
 
 constexpr int kOccRaysPerBlock = 4;
 
+// the ray of one wavefront: what every frustum test of it reads
+struct OccRay {
+    float o[3], d[3];
+    float nv, fv, rr;     // near, far, cone_scale * radius
+};
+
+__device__ __forceinline__ OccRay occ_load_ray(int64_t b, const float* __restrict__ origins, const float* __restrict__ dirs,
+                                               const float* __restrict__ radii, const float* __restrict__ nearp,
+                                               const float* __restrict__ farp, float cone_scale) {
+    OccRay r;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { r.o[a] = origins[b * 3 + a]; r.d[a] = dirs[b * 3 + a]; }
+    r.nv = nearp[b]; r.fv = farp[b];
+    r.rr = cone_scale * radii[b];
+    return r;
+}
+
+// does coarse frustum i (i < N) of the ray touch an occupied cell?  The one statement of the predicate: both ray kernels call it.
+__device__ __forceinline__ bool occ_frustum_hit(const OccBox& box, const unsigned* __restrict__ bits, const OccRay& r, int N, int i,
+                                                int disparity, int outside_occupied) {
+    const int cells[3] = {box.g.cx, box.g.cy, box.g.cz};
+    const float t0 = level0_t(r.nv, r.fv, N, i, disparity != 0), t1 = level0_t(r.nv, r.fv, N, i + 1, disparity != 0);
+    const float rho = r.rr * t1;
+    int c0[3], c1[3];
+    bool outside = false, empty = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float p0 = r.o[a] + t0 * r.d[a], p1 = r.o[a] + t1 * r.d[a];
+        const float xlo = fminf(p0, p1) - rho, xhi = fmaxf(p0, p1) + rho;
+        if (!(xlo <= xhi)) outside = true;                               // a NaN ray is never culled
+        c0[a] = occ_cell(xlo, box.lo[a], box.h[a], cells[a]);
+        c1[a] = occ_cell(xhi, box.lo[a], box.h[a], cells[a]);
+        if (c0[a] < 0 || c1[a] >= cells[a]) outside = true;
+        if (c0[a] < 0) c0[a] = 0;
+        if (c1[a] >= cells[a]) c1[a] = cells[a] - 1;
+        if (c0[a] > c1[a]) empty = true;
+    }
+    if (outside && outside_occupied) return true;
+    if (empty) return false;
+    return occ_box_test(box.g, bits, c0, c1);
+}
+
 // K = the sample-count bucket of the per-ray kernels (frusta per lane)
 template <int K>
 __global__ void __launch_bounds__(64 * kOccRaysPerBlock)
@@ -172,49 +216,73 @@ k_ray_occupancy(int64_t B, int N, OccBox box, const unsigned* __restrict__ bits,
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * kOccRaysPerBlock + (threadIdx.x >> 6);
     if (b >= B) return;                                                  // wave-uniform
-    const float o[3] = {origins[b * 3], origins[b * 3 + 1], origins[b * 3 + 2]};
-    const float d[3] = {dirs[b * 3], dirs[b * 3 + 1], dirs[b * 3 + 2]};
-    const float nv = nearp[b], fv = farp[b];
-    const float rr = cone_scale * radii[b];
-    const int cells[3] = {box.g.cx, box.g.cy, box.g.cz};
+    const OccRay r = occ_load_ray(b, origins, dirs, radii, nearp, farp, cone_scale);
     bool any = false;
     for (int kk = 0; kk < K; ++kk) {
         const int i = lane + 64 * kk;
-        bool hit = false;
-        if (i < N) {
-            const float t0 = level0_t(nv, fv, N, i, disparity != 0), t1 = level0_t(nv, fv, N, i + 1, disparity != 0);
-            const float rho = rr * t1;
-            int c0[3], c1[3];
-            bool outside = false, empty = false;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float p0 = o[a] + t0 * d[a], p1 = o[a] + t1 * d[a];
-                const float xlo = fminf(p0, p1) - rho, xhi = fmaxf(p0, p1) + rho;
-                if (!(xlo <= xhi)) outside = true;                       // a NaN ray is never culled
-                c0[a] = occ_cell(xlo, box.lo[a], box.h[a], cells[a]);
-                c1[a] = occ_cell(xhi, box.lo[a], box.h[a], cells[a]);
-                if (c0[a] < 0 || c1[a] >= cells[a]) outside = true;
-                if (c0[a] < 0) c0[a] = 0;
-                if (c1[a] >= cells[a]) c1[a] = cells[a] - 1;
-                if (c0[a] > c1[a]) empty = true;
-            }
-            if (outside && outside_occupied) hit = true;
-            else if (!empty) hit = occ_box_test(box.g, bits, c0, c1);
-        }
+        const bool hit = i < N && occ_frustum_hit(box, bits, r, N, i, disparity, outside_occupied);
         if (__ballot(hit) != 0ull) { any = true; break; }                // wave-uniform
     }
     if (lane == 0) live[b] = any ? 1 : 0;
 }
 
-hipError_t launch_ray_occupancy(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                                const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                                int disparity, int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st) {
+// The occupied span of a ray: the smallest and the largest hitting frustum and their outer fence posts.  The buckets are walked forward to
+// the first one whose ballot is non-zero (a dead ray costs what it costs k_ray_occupancy), then backward from the last bucket that holds a
+// frustum down to that one, whose ballot is kept: no bucket is tested twice.  Every branch on a ballot is wave-uniform.
+template <int K>
+__global__ void __launch_bounds__(64 * kOccRaysPerBlock)
+k_ray_span(int64_t B, int N, OccBox box, const unsigned* __restrict__ bits, const float* __restrict__ origins,
+           const float* __restrict__ dirs, const float* __restrict__ radii, const float* __restrict__ nearp,
+           const float* __restrict__ farp, int disparity, int outside_occupied, float cone_scale, unsigned char* __restrict__ live,
+           int* __restrict__ first, int* __restrict__ last, float* __restrict__ near_out, float* __restrict__ far_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * kOccRaysPerBlock + (threadIdx.x >> 6);
+    if (b >= B) return;                                                  // wave-uniform
+    const OccRay r = occ_load_ray(b, origins, dirs, radii, nearp, farp, cone_scale);
+    int fb = -1;                                                         // the first bucket with a hit and its ballot
+    unsigned long long fm = 0ull;
+    for (int kk = 0; kk < K; ++kk) {
+        const int i = lane + 64 * kk;
+        const bool hit = i < N && occ_frustum_hit(box, bits, r, N, i, disparity, outside_occupied);
+        const unsigned long long m = __ballot(hit);
+        if (m != 0ull) { fb = kk; fm = m; break; }                       // wave-uniform
+    }
+    int fi = N, li = -1;
+    if (fb >= 0) {                                                       // wave-uniform
+        fi = 64 * fb + __builtin_ctzll(fm);
+        int lb = fb;
+        unsigned long long lm = fm;
+        for (int kk = (N - 1) >> 6; kk > fb; --kk) {                     // (N - 1) >> 6 <= K - 1: the buckets past it hold no frustum
+            const int i = lane + 64 * kk;
+            const bool hit = i < N && occ_frustum_hit(box, bits, r, N, i, disparity, outside_occupied);
+            const unsigned long long m = __ballot(hit);
+            if (m != 0ull) { lb = kk; lm = m; break; }                   // wave-uniform
+        }
+        li = 64 * lb + 63 - __builtin_clzll(lm);
+    }
+    if (lane == 0) {
+        live[b] = fb >= 0 ? 1 : 0;
+        if (first != nullptr) first[b] = fi;
+        if (last != nullptr) last[b] = li;
+        if (near_out != nullptr) near_out[b] = fb >= 0 ? level0_t(r.nv, r.fv, N, fi, disparity != 0) : r.nv;
+        if (far_out != nullptr) far_out[b] = fb >= 0 ? level0_t(r.nv, r.fv, N, li + 1, disparity != 0) : r.fv;
+    }
+}
+
+static OccBox occ_box(const int dims[3], const float lo[3], const float hi[3]) {
     OccBox box;
     box.g = occ_grid(dims);
     for (int a = 0; a < 3; ++a) {
         box.lo[a] = lo[a];
         box.h[a] = (hi[a] - lo[a]) / (float)(dims[a] - 1);
     }
+    return box;
+}
+
+hipError_t launch_ray_occupancy(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
+                                const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
+                                int disparity, int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st) {
+    const OccBox box = occ_box(dims, lo, hi);
     const dim3 grid(occ_grid_for(B, kOccRaysPerBlock)), block(64 * kOccRaysPerBlock);
     const int K = (N + 63) / 64;
 #define MIP_OCC(KK)                                                                                                              \
@@ -226,6 +294,25 @@ hipError_t launch_ray_occupancy(const int dims[3], const float lo[3], const floa
     else if (K <= 8) MIP_OCC(8);
     else MIP_OCC(16);
 #undef MIP_OCC
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_span(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
+                           const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
+                           int disparity, int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last,
+                           float* near_out, float* far_out, hipStream_t st) {
+    const OccBox box = occ_box(dims, lo, hi);
+    const dim3 grid(occ_grid_for(B, kOccRaysPerBlock)), block(64 * kOccRaysPerBlock);
+    const int K = (N + 63) / 64;
+#define MIP_SPAN(KK)                                                                                                        \
+    hipLaunchKernelGGL((k_ray_span<KK>), grid, block, 0, st, B, N, box, bits, origins, dirs, radii, nearp, farp, disparity, \
+                       outside_occupied, cone_scale, live, first, last, near_out, far_out)
+    if (K <= 1) MIP_SPAN(1);
+    else if (K <= 2) MIP_SPAN(2);
+    else if (K <= 4) MIP_SPAN(4);
+    else if (K <= 8) MIP_SPAN(8);
+    else MIP_SPAN(16);
+#undef MIP_SPAN
     return hipGetLastError();
 }
 

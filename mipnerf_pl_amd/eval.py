@@ -14,7 +14,8 @@ import argparse
 import torch
 
 from .evaluate import evaluate, summarize_results
-from .render_video import add_common_args, cli_occupancy, flag_given, is_scene360, load_system, refuse_unbounded_cull
+from .render_video import (add_common_args, cli_occupancy, cli_span_samples, flag_given, is_scene360, load_system, refuse_tighten_without_cull,
+                           refuse_unbounded_cull)
 
 
 def build_parser():
@@ -28,6 +29,7 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    refuse_tighten_without_cull(args)
     system = load_system(args)
     refuse_unbounded_cull(args, system)
     hp = system.hparams
@@ -47,7 +49,8 @@ def main(argv=None):
             base_size = (dataset.w, dataset.h)
         occupancy = cli_occupancy(args, system, (dataset[i][0] for i in range(len(dataset))))
         evaluate(system, dataset, args.out_dir, exp_name, scale=args.scale, save_image=args.save_image, chunk_size=args.chunk_size,
-                 white_bkgd=white_bkgd, use_graph=args.use_graph, base_size=base_size, occupancy=occupancy)
+                 white_bkgd=white_bkgd, use_graph=args.use_graph, base_size=base_size, occupancy=occupancy, tighten=args.cull_tighten,
+                 span_samples=cli_span_samples(args, system) if args.cull else None)
     summary = summarize_results(args.out_dir, [exp_name], args.scale)
     print("PSNR | SSIM | Average")
     print(summary)

@@ -28,14 +28,16 @@ DEFAULT_CHUNK = 12288        # eval.py / render_video.py --chunk_size
 class FrameEvaluator:
     """Everything one image size needs: the frame's `GraphedFrame` (or its eager form) and the device buffers of the image bytes."""
 
-    def __init__(self, model, height, width, chunk_size, white_bkgd, device, use_graph=True, occupancy=None):
+    def __init__(self, model, height, width, chunk_size, white_bkgd, device, use_graph=True, occupancy=None, tighten=False, span_samples=None):
         from .model import CulledFrame, GraphedFrame
         self.h, self.w = int(height), int(width)
         n = self.h * self.w
         if occupancy is None:
+            if tighten:
+                raise ValueError("FrameEvaluator: tighten=True needs an occupancy grid")
             self.frame = GraphedFrame(model, n, chunk_size, white_bkgd, device, capture=use_graph)
         else:       # rays that touch no occupied cell are skipped; the live count varies per frame, so the chunks run eagerly
-            self.frame = CulledFrame(model, n, chunk_size, white_bkgd, device, occupancy)
+            self.frame = CulledFrame(model, n, chunk_size, white_bkgd, device, occupancy, tighten=tighten, span_samples=span_samples)
         self.vis_ws = torch.empty(ops.visualize_workspace_floats(n), dtype=torch.float32, device=device)
         self.rgb_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
         self.dist_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
@@ -92,10 +94,16 @@ def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bou
     return occ
 
 
-def report_live_share(shares):
-    """The closing line of a culled run: the mean share of rays rendered per frame."""
+def report_live_share(shares, spans=None):
+    """The closing line of a culled run: the mean share of rays rendered per frame and, for a tightened run (`spans`), the mean share
+    of [near, far] between the live rays' first and last occupied coarse frustum (`CulledFrame.span_share`; frames without a live ray do
+    not count)."""
     if shares:
-        print("cull: mean live share per frame: {:.4f} ({} frames)".format(float(np.mean(shares)), len(shares)))
+        line = "cull: mean live share per frame: {:.4f} ({} frames)".format(float(np.mean(shares)), len(shares))
+        spans = [v for v in (spans or []) if v == v]
+        if spans:
+            line += "; mean span share of the live rays: {:.4f}".format(float(np.mean(spans)))
+        print(line)
 
 
 def save_images(rgb_u8, dist_u8, acc_u8, path, idx):
@@ -130,11 +138,12 @@ def write_metrics(folder, psnrs, ssims):
 
 
 def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chunk_size=DEFAULT_CHUNK, white_bkgd=True, use_graph=True,
-             base_size=(800, 800), occupancy=None):
+             base_size=(800, 800), occupancy=None, tighten=False, span_samples=None):
     """eval.py:main after the checkpoint is loaded: every image of `dataset` (a test split of `datasets.dataset_dict`) rendered by
     `system.mip_nerf`, PSNR / SSIM recorded, the images written when `save_image`.  Returns (psnrs, ssims) as lists of floats.
     `occupancy` (an `ops.Occupancy`, e.g. `scene_occupancy`): rays that touch no occupied cell are not rendered (`model.CulledFrame`);
-    None is the full path."""
+    None is the full path.  `tighten` / `span_samples` are `CulledFrame`'s (live rays rendered on their occupied span -- not the untightened
+    frame --; the frusta count of the classification)."""
     if scale not in (1, 4):
         raise ValueError("scale must be 1 or 4 (eval.py --scale)")
     model = system.mip_nerf
@@ -143,17 +152,20 @@ def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chun
     for i in range(scale):
         os.makedirs(os.path.join(folder, str(2 ** i)), exist_ok=True)
     slots = image_slots(dataset.sizes, scale, base_size[0])
-    evaluators, psnrs, ssims, shares = {}, [], [], []
+    evaluators, psnrs, ssims, shares, spans = {}, [], [], [], []
     with torch.no_grad():
         for idx in range(len(dataset)):
             rays, gt = dataset[idx]
             h, w = int(gt.shape[0]), int(gt.shape[1])
             ev = evaluators.get((h, w))
             if ev is None:
-                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy)
+                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten,
+                                                         span_samples=span_samples)
             rgb, dist, acc = ev.render(rays)
             if occupancy is not None:
                 shares.append(ev.frame.live_count / float(h * w))
+                if tighten:         # the spans are there already; an untightened run launches and reads back nothing more
+                    spans.append(ev.frame.span_share)
             psnr, ssim = ops.eval_errors(rgb, gt[..., :3])
             psnrs.append(psnr.item())
             ssims.append(ssim.item())
@@ -162,7 +174,7 @@ def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chun
                 save_images(*ev.images(rgb, dist, acc), os.path.join(folder, sub), n)
     write_metrics(folder, psnrs, ssims)
     generate_video(folder)
-    report_live_share(shares)
+    report_live_share(shares, spans)
     return psnrs, ssims
 
 

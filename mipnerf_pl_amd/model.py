@@ -896,10 +896,23 @@ class CulledFrame:
     `volumetric_rendering` yields for all-zero weights (background colour, acc 0, distance near).  A live ray's arithmetic does not depend
     on its neighbours, so its results are bit for bit those of `GraphedFrame`.
     The chunk forwards run eagerly: the live count differs from frame to frame and has to reach the host (one 8-byte read-back and one
-    stream synchronisation per frame), so a frame cannot be one captured graph."""
+    stream synchronisation per frame), so a frame cannot be one captured graph.
+    `span_samples` (default: `model.num_samples`) is the number of coarse frusta the classification uses, with and without `tighten`.
+    `tighten=True` (opt-in; the default launches exactly what it launched before): the frame is classified by `ops.ray_span` instead, and
+    the live rays are rendered on their occupied span: first = the smallest hitting frustum index, last = the largest; near' = t_first and
+    far' = t_{last + 1}, the fence posts themselves (a dead ray gets first = N, last = -1, near' = near and far' = far).  `ops.compact_rays`
+    gathers a `Rays` whose near / far fields are the near' / far' arrays, `ops.scatter_frame` keeps the original near (a culled pixel's
+    distance = near), and the frame is bit for bit what the renderer yields on the same rays with near / far replaced by near' / far'.  A
+    tightened frame is NOT the untightened frame: the same number of samples sits in a shorter interval.  What is guaranteed is what
+    culling guarantees about dead rays: the dropped parts of a ray lie only in cells whose 8 lattice corners are at or below the threshold,
+    after dilation.  `span_samples` may differ from the count the model renders with (a checkpoint rendered with fewer samples keeps the
+    classification of its own count): the frusta cover [near, far] for any N, and whatever lies outside [near', far'] lies in frusta that
+    hit nothing, whatever count the renderer then uses.  `.span_share` (computed on demand, a host read-back): the mean of
+    (last - first + 1) / span_samples over the live rays of the last call (NaN when none was live)."""
 
     def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, occupancy,
-                 lanes: Optional[int] = None, outside_occupied: bool = True, cone_scale: float = 1.0):
+                 lanes: Optional[int] = None, outside_occupied: bool = True, cone_scale: float = 1.0, tighten: bool = False,
+                 span_samples: Optional[int] = None):
         if getattr(model, "unbounded", False):
             raise NotImplementedError("CulledFrame: unbounded=True models are not supported (their field lives in a contracted space)")
         self.model, self.n, self.chunk, self.white_bkgd, self.dev = model, int(num_rays), int(chunk), bool(white_bkgd), device
@@ -915,6 +928,33 @@ class CulledFrame:
         self.index = torch.zeros(max(self.n, 1), dtype=torch.int32, device=device)
         self._ws = torch.empty(max(int(L.lib().mipnerf_compact_rays_workspace_bytes(self.n)), 16), dtype=torch.uint8, device=device)
         self.live_count = 0
+        self.tighten = bool(tighten)
+        self._span_samples = None if span_samples is None else int(span_samples)
+        if not 1 <= self.span_samples <= L.MAX_SAMPLES:
+            raise ValueError(f"CulledFrame: span_samples must be in [1, {L.MAX_SAMPLES}] (got {self.span_samples})")
+        if self.tighten:
+            self.first = torch.zeros(self.n, dtype=torch.int32, device=device)
+            self.last = torch.zeros(self.n, dtype=torch.int32, device=device)
+            self.near_span = torch.zeros(self.n, 1, device=device)
+            self.far_span = torch.zeros(self.n, 1, device=device)
+
+    @property
+    def span_samples(self) -> int:
+        return int(self.model.num_samples) if self._span_samples is None else self._span_samples
+
+    @property
+    def span_share(self) -> float:
+        """mean of (last - first + 1) / span_samples over the live rays of the last call; without `tighten` the span is computed here"""
+        if self.n == 0 or self.live_count == 0:
+            return float("nan")
+        if self.tighten:
+            first, last = self.first, self.last
+        else:
+            with torch.cuda.device(self.dev):
+                _, first, last, _, _ = ops.ray_span(self.occupancy, self.static_in, self.span_samples, disparity=self.model.disparity,
+                                                    outside_occupied=self.outside_occupied, cone_scale=self.cone_scale)
+        live = last >= first
+        return float((last[live] - first[live] + 1).double().mean().item() / self.span_samples)
 
     def __call__(self, rays: Rays):
         if rays.origins.shape[0] != self.n:
@@ -927,9 +967,15 @@ class CulledFrame:
             m.mlp.native(self.dev)
             for dst, src in zip(self.static_in, rays):
                 dst.copy_(src)
-            ops.ray_occupancy(self.occupancy, self.static_in, m.num_samples, disparity=m.disparity, outside_occupied=self.outside_occupied,
-                              cone_scale=self.cone_scale, out=self.live)
-            self.live_count = ops.compact_rays(self.live, self.static_in, c.static_in, self.index, workspace=self._ws)
+            src = self.static_in
+            if self.tighten:
+                ops.ray_span(self.occupancy, src, self.span_samples, disparity=m.disparity, outside_occupied=self.outside_occupied,
+                             cone_scale=self.cone_scale, out=(self.live, self.first, self.last, self.near_span, self.far_span))
+                src = src._replace(near=self.near_span, far=self.far_span)      # the gather reads near' / far'; the scatter below the original near
+            else:
+                ops.ray_occupancy(self.occupancy, src, self.span_samples, disparity=m.disparity, outside_occupied=self.outside_occupied,
+                                  cone_scale=self.cone_scale, out=self.live)
+            self.live_count = ops.compact_rays(self.live, src, c.static_in, self.index, workspace=self._ws)
             # the ragged tail differs from frame to frame: keep the per-sample scratch of the full chunk and of this tail only (the
             # synchronisation in compact_rays came after the join of the last frame's lanes, so nothing still reads the others)
             tail = self.live_count % self.chunk

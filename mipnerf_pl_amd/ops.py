@@ -755,6 +755,36 @@ def ray_occupancy(occ, rays, num_samples, disparity=False, outside_occupied=True
     return live
 
 
+def ray_span(occ, rays, num_samples, disparity=False, outside_occupied=True, cone_scale=1.0, out=None):
+    """(live uint8 [n], first int32 [n], last int32 [n], near' fp32 [n, 1], far' fp32 [n, 1]): the occupied span of every ray.  "Frustum i
+    hits" is exactly the per-frustum test of `ray_occupancy`, and `live` is byte for byte what `ray_occupancy` returns for the same
+    arguments.  first = the smallest hitting frustum index, last = the largest; near' = t_first and far' = t_{last + 1} are the coarse
+    level's deterministic fence posts themselves, bit for bit those of the sampler.  A dead ray gets first = N, last = -1, near' = near and
+    far' = far.  `out`: a tuple of five preallocated tensors of those types (an entry of first / last / near' / far' may be None: it is
+    skipped and returned as None).  The frusta cover [near, far] for any N, so the span found with one `num_samples` is valid for a renderer
+    that uses another.  A ray rendered on [near', far'] is NOT the ray rendered on [near, far]: its samples sit elsewhere; what it leaves
+    out lies only in cells whose 8 lattice corners are at or below the threshold, after dilation."""
+    import ctypes as C
+    n = int(rays.origins.shape[0])
+    dev = occ.bits.device
+    if out is None:
+        out = (torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, 1, device=dev), torch.empty(n, 1, device=dev))
+    if len(out) != 5 or out[0] is None:
+        raise ValueError("ray_span: out is (live, first, last, near, far); only the last four may be None")
+    for t, dt in zip(out, (torch.uint8, torch.int32, torch.int32, torch.float32, torch.float32)):
+        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != dev):
+            raise ValueError("ray_span: out holds contiguous device tensors with one element per ray: uint8, int32, int32, fp32, fp32")
+    if n == 0:
+        return tuple(out)
+    _, cdims, clo, chi = _lattice_args("ray_span", occ.dims, occ.lo, occ.hi)
+    with torch.cuda.device(dev):
+        rp, keep = _rays_ptrs(rays, n, "ray_span")
+        L.check(L.lib().mipnerf_ray_span(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(disparity)),
+                                         int(bool(outside_occupied)), float(cone_scale), *[_ptr(t) for t in out], _stream()), "ray_span")
+    return tuple(out)
+
+
 def compact_rays(live, rays, out_rays, out_index, workspace=None):
     """Gathers the rays with live != 0, in their original order, into the first `count` rows of `out_rays` (7 preallocated [n, k] fp32
     fields) and writes the source ray of compact slot j to out_index[j] (int32 [n]).  Returns `count`.  The count has to reach the host:

@@ -27,9 +27,10 @@ CAMERA_ANGLE_X = 0.6911112070083618       # render_video.py --camera_angle_x def
 
 
 def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_angle_x=CAMERA_ANGLE_X, chunk_size=DEFAULT_CHUNK,
-                 white_bkgd=True, n_poses=120, use_graph=True, occupancy=None):
+                 white_bkgd=True, n_poses=120, use_graph=True, occupancy=None, tighten=False, span_samples=None):
     """render_video.py:run_render after the checkpoint is loaded.  Returns the output folder.  `occupancy` (an `ops.Occupancy`): rays
-    that touch no occupied cell are not rendered (`model.CulledFrame`); None is the full path."""
+    that touch no occupied cell are not rendered (`model.CulledFrame`); None is the full path.  `tighten` / `span_samples` are
+    `CulledFrame`'s (live rays rendered on their occupied span; the frusta count of the classification) and need an `occupancy`."""
     from .datasets import RenderGen
     model = system.mip_nerf
     device = next(model.parameters()).device
@@ -39,24 +40,28 @@ def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_
     focal = .5 * base_size[0] / np.tan(.5 * camera_angle_x)
     dataset = RenderGen(focal, base_size, scale, device=device, n_poses=n_poses)
     nums = len(dataset) // scale
-    evaluators, shares = {}, []
+    evaluators, shares, spans = {}, [], []
     with torch.no_grad():
         for idx in range(len(dataset)):
             rays = dataset[idx]
             h, w = dataset.sizes[idx]
             ev = evaluators.get((h, w))
             if ev is None:
-                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy)
+                ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten,
+                                                         span_samples=span_samples)
             images = ev.images(*ev.render(rays))
             if occupancy is not None:
                 shares.append(ev.frame.live_count / float(h * w))
+                if tighten:
+                    spans.append(ev.frame.span_share)
             save_images(*images, os.path.join(folder, str(int(base_size[0] / w))), idx % nums)
     generate_video(folder)
-    report_live_share(shares)
+    report_live_share(shares, spans)
     return folder
 
 
-def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAULT_CHUNK, white_bkgd=False, use_graph=True, occupancy=None):
+def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAULT_CHUNK, white_bkgd=False, use_graph=True, occupancy=None,
+                tighten=False, span_samples=None):
     """The interpolated path through the poses of `dataset` (a `datasets.RealData360` split), every frame as in `render_video`.
     Returns the output folder."""
     from .datasets import PathGen
@@ -66,16 +71,18 @@ def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAU
     os.makedirs(os.path.join(folder, "1"), exist_ok=True)
     path = PathGen(dataset, n_views, device=device)
     h, w = path.sizes[0]
-    ev = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy)
-    shares = []
+    ev = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten, span_samples=span_samples)
+    shares, spans = [], []
     with torch.no_grad():
         for idx in range(len(path)):
             images = ev.images(*ev.render(path[idx]))
             if occupancy is not None:
                 shares.append(ev.frame.live_count / float(h * w))
+                if tighten:
+                    spans.append(ev.frame.span_share)
             save_images(*images, os.path.join(folder, "1"), idx)
     generate_video(folder)
-    report_live_share(shares)
+    report_live_share(shares, spans)
     return folder
 
 
@@ -116,7 +123,28 @@ def add_common_args(p):
     p.add_argument("--cull_dilate", help="--cull: occupied cells grow by this many cells in every direction", type=int, default=1)
     p.add_argument("--cull_bound", help="--cull: the grid spans [-B, B]^3 (default: the largest coordinate any ray of the cameras to be rendered "
                    "reaches between near and far, plus one cell)", type=float, default=None)
+    p.add_argument("--cull_tighten", help="--cull: render every live ray on [near', far'], the fence posts around the coarse frusta of it that "
+                   "touch an occupied cell, instead of [near, far]: the same samples in a shorter interval.  Not the untightened frame: the "
+                   "samples sit elsewhere; the dropped parts of a ray lie only in cells the grid proves empty", action="store_true")
+    p.add_argument("--cull_span_samples", help="--cull: coarse frusta per ray the classification uses (default: the checkpoint's num_samples)",
+                   type=int, default=None)
+    p.add_argument("--render_samples", help="samples per ray and level to render with (default: the checkpoint's num_samples; the parameters do "
+                   "not depend on it); independent of --cull", type=int, default=None)
     return p
+
+
+def refuse_tighten_without_cull(args):
+    """--cull_tighten is a way of culling: without --cull it exits with a message before anything is loaded."""
+    if getattr(args, "cull_tighten", False) and not args.cull:
+        raise SystemExit("--cull_tighten tightens the rays that --cull keeps: give --cull as well")
+
+
+def cli_span_samples(args, system):
+    """The frusta count of the classification: --cull_span_samples, else the CHECKPOINT's num_samples -- with --render_samples the
+    renderer's count changes and the classification does not coarsen."""
+    if args.cull_span_samples is not None:
+        return int(args.cull_span_samples)
+    return int(getattr(system, "checkpoint_num_samples", system.hparams["nerf.num_samples"]))
 
 
 def refuse_unbounded_cull(args, system):
@@ -153,11 +181,25 @@ def load_system(args):
     """MipNeRFSystem.load_from_checkpoint(--ckpt), with --precision when given (on the host; the caller moves it)."""
     from .system import MipNeRFSystem
     kw = {"precision": args.precision} if args.precision else {}
-    return MipNeRFSystem.load_from_checkpoint(args.ckpt, **kw)
+    n = getattr(args, "render_samples", None)
+    if n is None:
+        system = MipNeRFSystem.load_from_checkpoint(args.ckpt, **kw)
+        system.checkpoint_num_samples = int(system.hparams["nerf.num_samples"])
+        return system
+    # the parameters do not depend on num_samples: the checkpoint's own count is read from its hyper-parameters, then the system is built
+    # with the other one (Lightning merges extra keywords into the stored hyper-parameters; the stand-in takes them as `hparams`)
+    from . import system as system_module
+    stored = torch.load(args.ckpt, map_location="cpu", weights_only=False).get("hyper_parameters", {})
+    override = {"nerf.num_samples": int(n)}
+    kw.update(override if system_module._HAVE_PL else {"hparams": override})
+    system = MipNeRFSystem.load_from_checkpoint(args.ckpt, **kw)
+    system.checkpoint_num_samples = int(stored.get("nerf.num_samples", n))
+    return system
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    refuse_tighten_without_cull(args)
     if args.gen_video_only:
         if args.render_images_dir is None:
             raise SystemExit("only generate video, you must give the different scale image base dir (--render_images_dir)")
@@ -181,7 +223,8 @@ def main(argv=None):
             occupancy = cli_occupancy(args, system, (path[i] for i in range(len(path))))
         return render_path(system, dataset, args.out_dir, hp["exp_name"], n_views=args.n_views, chunk_size=args.chunk_size,
                            white_bkgd=args.white_bkgd if flag_given(argv, "--white_bkgd") else bool(hp["val.white_bkgd"]),
-                           use_graph=args.use_graph, occupancy=occupancy)
+                           use_graph=args.use_graph, occupancy=occupancy, tighten=args.cull_tighten,
+                           span_samples=cli_span_samples(args, system) if args.cull else None)
     occupancy = None
     if args.cull:
         from .datasets import RenderGen
@@ -190,7 +233,8 @@ def main(argv=None):
         occupancy = cli_occupancy(args, system, (gen[i] for i in range(len(gen))))
     return render_video(system, args.out_dir, system.hparams["exp_name"], args.scale, base_size=args.base_size,
                         camera_angle_x=args.camera_angle_x, chunk_size=args.chunk_size, white_bkgd=args.white_bkgd,
-                        n_poses=args.n_poses, use_graph=args.use_graph, occupancy=occupancy)
+                        n_poses=args.n_poses, use_graph=args.use_graph, occupancy=occupancy, tighten=args.cull_tighten,
+                        span_samples=cli_span_samples(args, system) if args.cull else None)
 
 
 if __name__ == "__main__":
