@@ -420,6 +420,28 @@ int mipnerf_uncontract_vertices(int64_t num_vertices, float far_radius, const fl
  * results are NOT those of the untightened ray.  The frusta cover [near, far] for any N, so the span found with one num_samples is valid
  * for a renderer that uses another.  Arguments, validation and the zero-ray return as mipnerf_ray_occupancy.  Does not allocate or
  * synchronise.
+ * mipnerf_ray_occupancy_360 / mipnerf_ray_span_360: the same two calls for the unbounded-scene model and a bit grid laid out in CONTRACTED
+ * coordinates (the bits of a lattice of mipnerf_density_grid_360 with MIPNERF_SPACE_CONTRACTED; the whole scene lies in |z| < 2, so the box
+ * is usually [-2, 2]^3).  There is no disparity argument: the fence posts are those of mipnerf_sample_along_rays_360 with t_rand = NULL,
+ * t_i = 1 / (fi s_i + (1 - s_i) ni) with ni = 1 / near, fi = 1 / far, s_i = linspace(0, 1, N + 1)[i], bit for bit (one device function
+ * serves the sampler and these kernels), and near_out / far_out are those values.  Frustum i (t0 = t_i, t1 = t_{i+1}, rho = cone_scale *
+ * radii * t1, p0 = o + t0 d, p1 = o + t1 d) is bounded per axis by an interval [lo_a, hi_a] of contracted coordinates that contains
+ * contract(x) for every x = o + t d + delta with t in [t0, t1], delta perpendicular to d and |delta| <= cone_scale * radii * t.  The rule
+ * uses that contract keeps directions -- contract(x) = f(|x|) x / |x| with f(r) = r for r <= 1 and 2 - 1 / r otherwise -- and that
+ * |x / |x| - p / |p|| <= |x - p| / sqrt(|x| |p|).  With tc = clamp(-(o.d) / (d.d), t0, t1), rc = |o + tc d|, rmin = rc - rho and
+ * rmax = max(|p0|, |p1|) + rho:
+ *   - rmin >= 1 (the frustum lies wholly outside the unit ball): u0 = p0 / |p0|, u1 = p1 / |p1|, sag = 1 - sqrt(max(0, (1 + u0.u1) / 2))
+ *     (the sagitta of the great-circle arc between them), e = sag + rho / rmin, ulo_a = max(min(u0_a, u1_a) - e, -1), uhi_a =
+ *     min(max(u0_a, u1_a) + e, 1), flo = 2 - 1 / rmin, fhi = 2 - 1 / rmax, lo_a = ulo_a < 0 ? ulo_a fhi : ulo_a flo, hi_a = uhi_a > 0 ?
+ *     uhi_a fhi : uhi_a flo;
+ *   - otherwise: the world interval of the bounded rule, xlo_a = min(p0_a, p1_a) - rho, xhi_a = max(p0_a, p1_a) + rho, slo = rmax > 1 ?
+ *     (2 - 1 / rmax) / rmax : 1, lo_a = xlo_a < 0 ? xlo_a : xlo_a slo, hi_a = xhi_a > 0 ? xhi_a : xhi_a slo, both clamped to [-F, F] with
+ *     F = rmax > 1 ? 2 - 1 / rmax : rmax.
+ * The cell range of [lo_a, hi_a], the clipping, outside_occupied (which keeps its meaning for a box smaller than [-2, 2]^3), the ballot
+ * walk and the results of a dead ray are those of the bounded calls; a value that is not finite anywhere makes the frustum "outside", so
+ * such a ray is never culled when outside_occupied != 0.  Density is 0 beyond |z| = 2 - 1 / far_radius on the lattice, so far_radius must
+ * be no smaller than the largest |o + far d| of the rays to be classified.  Arguments (without `disparity`), validation and the zero-ray
+ * return as the bounded calls.  Neither call allocates or synchronises.
  * mipnerf_compact_rays: an exclusive scan of `live` (sums per 1024 rays, one single-workgroup scan, per-ray bases; no atomics), then
  * the live rays gathered IN THEIR ORIGINAL ORDER into out_rays (a NULL field is skipped) and out_index[j] = the source ray of compact
  * slot j.  The live count has to reach the host: the call makes one 8-byte read-back and SYNCHRONISES the stream -- it cannot be
@@ -438,6 +460,12 @@ int mipnerf_ray_occupancy(const int32_t* dims_host, const float* lo_host, const 
 int mipnerf_ray_span(const int32_t* dims_host, const float* lo_host, const float* hi_host, const uint32_t* bits, int64_t num_rays,
                      int32_t num_samples, const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale,
                      uint8_t* live, int32_t* first, int32_t* last, float* near_out, float* far_out, void* stream);
+int mipnerf_ray_occupancy_360(const int32_t* dims_host, const float* lo_host, const float* hi_host, const uint32_t* bits, int64_t num_rays,
+                              int32_t num_samples, const mipnerf_rays* rays, int32_t outside_occupied, float cone_scale, uint8_t* live,
+                              void* stream);
+int mipnerf_ray_span_360(const int32_t* dims_host, const float* lo_host, const float* hi_host, const uint32_t* bits, int64_t num_rays,
+                         int32_t num_samples, const mipnerf_rays* rays, int32_t outside_occupied, float cone_scale, uint8_t* live,
+                         int32_t* first, int32_t* last, float* near_out, float* far_out, void* stream);
 size_t mipnerf_compact_rays_workspace_bytes(int64_t num_rays);
 int mipnerf_compact_rays(int64_t num_rays, const uint8_t* live, const mipnerf_rays* rays, const mipnerf_rays_out* out_rays,
                          int32_t* out_index, void* workspace, size_t workspace_bytes, int64_t* count_host, void* stream);

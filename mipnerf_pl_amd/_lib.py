@@ -99,6 +99,9 @@ SIGNATURES = {
                                         _P, _P]),
     "mipnerf_ray_span": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _I64, _I32, C.POINTER(RaysPtrs), _I32, _I32, _F,
                                    _P, _P, _P, _P, _P, _P]),
+    "mipnerf_ray_occupancy_360": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _I64, _I32, C.POINTER(RaysPtrs), _I32, _F, _P, _P]),
+    "mipnerf_ray_span_360": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _I64, _I32, C.POINTER(RaysPtrs), _I32, _F,
+                                       _P, _P, _P, _P, _P, _P]),
     "mipnerf_compact_rays_workspace_bytes": (_SZ, [_I64]),
     "mipnerf_compact_rays": (C.c_int, [_I64, _P, C.POINTER(RaysPtrs), C.POINTER(RaysPtrs), _P, _P, _SZ, C.POINTER(_I64), _P]),
     "mipnerf_scatter_frame": (C.c_int, [_I64, _I64, _I32, _P, _P, _P, _I32, C.POINTER(LevelOut), C.POINTER(LevelOut), _P]),

@@ -1060,18 +1060,25 @@ int mipnerf_occupancy_build(const int32_t* dims, const float* grid, float thresh
     return MIPNERF_OK;
 }
 
+// what the four ray calls check before anything is launched; > 0: a return code, 0: launch, -1: zero rays, nothing to do
+static int ray_occupancy_check(const char* name, const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B,
+                               int32_t N, const mipnerf_rays* rays, float cone_scale, const uint8_t* live) {
+    if (int rc = lattice_check(name, dims, lo, hi)) return rc;
+    for (int a = 0; a < 3; ++a)
+        if (!(hi[a] > lo[a])) return fail(MIPNERF_E_INVALID, "%s: the box needs hi > lo on every axis", name);
+    if (B < 0 || B >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "%s: bad ray count", name);
+    if (N < 1 || N > MIPNERF_MAX_SAMPLES) return fail(MIPNERF_E_INVALID, "%s: num_samples must be in [1, %d]", name, MIPNERF_MAX_SAMPLES);
+    if (!(cone_scale >= 0.0f) || !std::isfinite(cone_scale)) return fail(MIPNERF_E_INVALID, "%s: cone_scale must be finite and >= 0", name);
+    if (B == 0) return -1;
+    if (!bits || !rays || !rays->origins || !rays->directions || !rays->radii || !rays->near || !rays->far || !live)
+        return fail(MIPNERF_E_INVALID, "%s: null argument", name);
+    return 0;
+}
+
 int mipnerf_ray_occupancy(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
                           const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale, uint8_t* live,
                           void* stream) {
-    if (int rc = lattice_check("ray_occupancy", dims, lo, hi)) return rc;
-    for (int a = 0; a < 3; ++a)
-        if (!(hi[a] > lo[a])) return fail(MIPNERF_E_INVALID, "ray_occupancy: the box needs hi > lo on every axis");
-    if (B < 0 || B >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "ray_occupancy: bad ray count");
-    if (N < 1 || N > MIPNERF_MAX_SAMPLES) return fail(MIPNERF_E_INVALID, "ray_occupancy: num_samples must be in [1, %d]", MIPNERF_MAX_SAMPLES);
-    if (!(cone_scale >= 0.0f) || !std::isfinite(cone_scale)) return fail(MIPNERF_E_INVALID, "ray_occupancy: cone_scale must be finite and >= 0");
-    if (B == 0) return MIPNERF_OK;
-    if (!bits || !rays || !rays->origins || !rays->directions || !rays->radii || !rays->near || !rays->far || !live)
-        return fail(MIPNERF_E_INVALID, "ray_occupancy: null argument");
+    if (int rc = ray_occupancy_check("ray_occupancy", dims, lo, hi, bits, B, N, rays, cone_scale, live)) return rc < 0 ? MIPNERF_OK : rc;
     HIP_TRY(mip::launch_ray_occupancy(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
                                       disparity != 0, outside_occupied != 0, cone_scale, live, S(stream)));
     return MIPNERF_OK;
@@ -1080,18 +1087,27 @@ int mipnerf_ray_occupancy(const int32_t* dims, const float* lo, const float* hi,
 int mipnerf_ray_span(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
                      const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale, uint8_t* live,
                      int32_t* first, int32_t* last, float* near_out, float* far_out, void* stream) {
-    if (int rc = lattice_check("ray_span", dims, lo, hi)) return rc;
-    for (int a = 0; a < 3; ++a)
-        if (!(hi[a] > lo[a])) return fail(MIPNERF_E_INVALID, "ray_span: the box needs hi > lo on every axis");
-    if (B < 0 || B >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "ray_span: bad ray count");
-    if (N < 1 || N > MIPNERF_MAX_SAMPLES) return fail(MIPNERF_E_INVALID, "ray_span: num_samples must be in [1, %d]", MIPNERF_MAX_SAMPLES);
-    if (!(cone_scale >= 0.0f) || !std::isfinite(cone_scale)) return fail(MIPNERF_E_INVALID, "ray_span: cone_scale must be finite and >= 0");
-    if (B == 0) return MIPNERF_OK;
-    if (!bits || !rays || !rays->origins || !rays->directions || !rays->radii || !rays->near || !rays->far || !live)
-        return fail(MIPNERF_E_INVALID, "ray_span: null argument");
+    if (int rc = ray_occupancy_check("ray_span", dims, lo, hi, bits, B, N, rays, cone_scale, live)) return rc < 0 ? MIPNERF_OK : rc;
     static_assert(sizeof(int) == sizeof(int32_t), "first / last are int32");
     HIP_TRY(mip::launch_ray_span(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
                                  disparity != 0, outside_occupied != 0, cone_scale, live, first, last, near_out, far_out, S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_ray_occupancy_360(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
+                              const mipnerf_rays* rays, int32_t outside_occupied, float cone_scale, uint8_t* live, void* stream) {
+    if (int rc = ray_occupancy_check("ray_occupancy_360", dims, lo, hi, bits, B, N, rays, cone_scale, live)) return rc < 0 ? MIPNERF_OK : rc;
+    HIP_TRY(mip::launch_ray_occupancy_360(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
+                                          outside_occupied != 0, cone_scale, live, S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_ray_span_360(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
+                         const mipnerf_rays* rays, int32_t outside_occupied, float cone_scale, uint8_t* live, int32_t* first,
+                         int32_t* last, float* near_out, float* far_out, void* stream) {
+    if (int rc = ray_occupancy_check("ray_span_360", dims, lo, hi, bits, B, N, rays, cone_scale, live)) return rc < 0 ? MIPNERF_OK : rc;
+    HIP_TRY(mip::launch_ray_span_360(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
+                                     outside_occupied != 0, cone_scale, live, first, last, near_out, far_out, S(stream)));
     return MIPNERF_OK;
 }
 

@@ -282,6 +282,14 @@ hipError_t launch_ray_span(const int dims[3], const float lo[3], const float hi[
                            const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
                            int disparity, int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last,
                            float* near_out, float* far_out, hipStream_t st);
+// the same two calls for a grid laid out in contracted coordinates (the unbounded-scene model: inverse-depth fence posts, no disparity flag)
+hipError_t launch_ray_occupancy_360(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
+                                    const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
+                                    int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st);
+hipError_t launch_ray_span_360(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
+                               const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
+                               int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last, float* near_out,
+                               float* far_out, hipStream_t st);
 int64_t compact_num_blocks(int64_t n);           // entries of block_sum
 // in / out: the 7 ray fields in the order of mipnerf_rays (an out entry may be NULL: that field is not gathered)
 hipError_t launch_compact_rays(int64_t n, const unsigned char* live, const float* const in[7], float* const out[7], int* out_index,

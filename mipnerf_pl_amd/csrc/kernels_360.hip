@@ -21,10 +21,7 @@ k_sample_along_rays_360(int64_t B, int N, const float* __restrict__ nearp, const
     const int64_t b = gid / (N + 1);
     const int i = (int)(gid - b * (N + 1));
     const float ni = 1.0f / nearp[b], fi = 1.0f / farp[b];
-    auto post = [&](int k) {
-        const float s = torch_linspace_at(0.0f, 1.0f, N + 1, k);
-        return fi * s + (1.0f - s) * ni;
-    };
+    auto post = [&](int k) { return level0_t_inv_360(ni, fi, N, k); };      // raymath360.hpp: shared with the 360 classifiers
     float ti = post(i);
     if (t_rand) {
         const float lo = i == 0 ? ti : 0.5f * (ti + post(i - 1));

@@ -6,6 +6,9 @@
 //                                each frustum's bounding box with word masks, the wave reduces with a ballot;
 //   k_ray_span                   the same wave and the same per-frustum test: the smallest and the largest hitting frustum of a ray
 //                                (lowest / highest set bit of a bucket's ballot) and their outer fence posts near', far';
+//   k_ray_occupancy_360 / k_ray_span_360  the same two bodies for the unbounded-scene model and a grid laid out in contracted
+//                                coordinates: inverse-depth fence posts, each frustum's image under contract() bounded by the closed
+//                                form of raymath360.hpp (contracted_frustum_box);
 //   k_compact_* / k_scatter_frame  exclusive scan of the live bytes (sums per 1024 rays + one single-workgroup scan + per-ray bases, the
 //                                arrangement of kernels_mesh.hip), the live rays gathered in their order, and the way back: every pixel of
 //                                every level written once.
@@ -13,7 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
-#include "raymath.hpp"
+#include "raymath360.hpp"
 
 namespace mip {
 
@@ -181,21 +184,46 @@ __device__ __forceinline__ OccRay occ_load_ray(int64_t b, const float* __restric
     return r;
 }
 
+// The per-frustum rules: which fence posts a ray's coarse level has and which per-axis interval, in the coordinates the grid is laid out
+// in, holds frustum [t0, t1].  The cell test and both kernel bodies below are written once over a rule.
+//   OccWorldRule   the bounded model: a grid in world coordinates, the frustum's own bounding box;
+//   Occ360Rule     the unbounded-scene model: a grid in contracted coordinates, inverse-depth fence posts (those of k_sample_along_rays_360)
+//                  and the box of raymath360.hpp contracted_frustum_box around the frustum's image under contract().
+struct OccWorldRule {
+    int disparity;
+    __device__ __forceinline__ float post(const OccRay& r, int N, int i) const { return level0_t(r.nv, r.fv, N, i, disparity != 0); }
+    __device__ __forceinline__ void bounds(const OccRay& r, float t0, float t1, float lo[3], float hi[3]) const {
+        const float rho = r.rr * t1;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float p0 = r.o[a] + t0 * r.d[a], p1 = r.o[a] + t1 * r.d[a];
+            lo[a] = fminf(p0, p1) - rho;
+            hi[a] = fmaxf(p0, p1) + rho;
+        }
+    }
+};
+struct Occ360Rule {
+    __device__ __forceinline__ float post(const OccRay& r, int N, int i) const { return level0_t_360(r.nv, r.fv, N, i); }
+    __device__ __forceinline__ void bounds(const OccRay& r, float t0, float t1, float lo[3], float hi[3]) const {
+        contracted_frustum_box(t0, t1, r.o, r.d, r.rr, lo, hi);
+    }
+};
+
 // does coarse frustum i (i < N) of the ray touch an occupied cell?  The one statement of the predicate: both ray kernels call it.
+template <class Rule>
 __device__ __forceinline__ bool occ_frustum_hit(const OccBox& box, const unsigned* __restrict__ bits, const OccRay& r, int N, int i,
-                                                int disparity, int outside_occupied) {
+                                                const Rule& rule, int outside_occupied) {
     const int cells[3] = {box.g.cx, box.g.cy, box.g.cz};
-    const float t0 = level0_t(r.nv, r.fv, N, i, disparity != 0), t1 = level0_t(r.nv, r.fv, N, i + 1, disparity != 0);
-    const float rho = r.rr * t1;
+    const float t0 = rule.post(r, N, i), t1 = rule.post(r, N, i + 1);
+    float xlo[3], xhi[3];
+    rule.bounds(r, t0, t1, xlo, xhi);
     int c0[3], c1[3];
     bool outside = false, empty = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float p0 = r.o[a] + t0 * r.d[a], p1 = r.o[a] + t1 * r.d[a];
-        const float xlo = fminf(p0, p1) - rho, xhi = fmaxf(p0, p1) + rho;
-        if (!(xlo <= xhi)) outside = true;                               // a NaN ray is never culled
-        c0[a] = occ_cell(xlo, box.lo[a], box.h[a], cells[a]);
-        c1[a] = occ_cell(xhi, box.lo[a], box.h[a], cells[a]);
+        if (!(xlo[a] <= xhi[a])) outside = true;                         // a NaN ray is never culled
+        c0[a] = occ_cell(xlo[a], box.lo[a], box.h[a], cells[a]);
+        c1[a] = occ_cell(xhi[a], box.lo[a], box.h[a], cells[a]);
         if (c0[a] < 0 || c1[a] >= cells[a]) outside = true;
         if (c0[a] < 0) c0[a] = 0;
         if (c1[a] >= cells[a]) c1[a] = cells[a] - 1;
@@ -206,44 +234,52 @@ __device__ __forceinline__ bool occ_frustum_hit(const OccBox& box, const unsigne
     return occ_box_test(box.g, bits, c0, c1);
 }
 
+// the arguments the ray kernels share
+struct OccRayArgs {
+    int64_t B;
+    int N;
+    OccBox box;
+    const unsigned* bits;
+    const float *origins, *dirs, *radii, *nearp, *farp;
+    int outside_occupied;
+    float cone_scale;
+    unsigned char* live;
+    int *first, *last;              // k_ray_span only; each may be null
+    float *near_out, *far_out;
+};
+
 // K = the sample-count bucket of the per-ray kernels (frusta per lane)
-template <int K>
-__global__ void __launch_bounds__(64 * kOccRaysPerBlock)
-k_ray_occupancy(int64_t B, int N, OccBox box, const unsigned* __restrict__ bits, const float* __restrict__ origins,
-                const float* __restrict__ dirs, const float* __restrict__ radii, const float* __restrict__ nearp,
-                const float* __restrict__ farp, int disparity, int outside_occupied, float cone_scale,
-                unsigned char* __restrict__ live) {
+template <int K, class Rule>
+__device__ __forceinline__ void ray_occupancy_body(const OccRayArgs& g, const Rule& rule) {
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * kOccRaysPerBlock + (threadIdx.x >> 6);
-    if (b >= B) return;                                                  // wave-uniform
-    const OccRay r = occ_load_ray(b, origins, dirs, radii, nearp, farp, cone_scale);
+    if (b >= g.B) return;                                                // wave-uniform
+    const int N = g.N;
+    const OccRay r = occ_load_ray(b, g.origins, g.dirs, g.radii, g.nearp, g.farp, g.cone_scale);
     bool any = false;
     for (int kk = 0; kk < K; ++kk) {
         const int i = lane + 64 * kk;
-        const bool hit = i < N && occ_frustum_hit(box, bits, r, N, i, disparity, outside_occupied);
+        const bool hit = i < N && occ_frustum_hit(g.box, g.bits, r, N, i, rule, g.outside_occupied);
         if (__ballot(hit) != 0ull) { any = true; break; }                // wave-uniform
     }
-    if (lane == 0) live[b] = any ? 1 : 0;
+    if (lane == 0) g.live[b] = any ? 1 : 0;
 }
 
 // The occupied span of a ray: the smallest and the largest hitting frustum and their outer fence posts.  The buckets are walked forward to
 // the first one whose ballot is non-zero (a dead ray costs what it costs k_ray_occupancy), then backward from the last bucket that holds a
 // frustum down to that one, whose ballot is kept: no bucket is tested twice.  Every branch on a ballot is wave-uniform.
-template <int K>
-__global__ void __launch_bounds__(64 * kOccRaysPerBlock)
-k_ray_span(int64_t B, int N, OccBox box, const unsigned* __restrict__ bits, const float* __restrict__ origins,
-           const float* __restrict__ dirs, const float* __restrict__ radii, const float* __restrict__ nearp,
-           const float* __restrict__ farp, int disparity, int outside_occupied, float cone_scale, unsigned char* __restrict__ live,
-           int* __restrict__ first, int* __restrict__ last, float* __restrict__ near_out, float* __restrict__ far_out) {
+template <int K, class Rule>
+__device__ __forceinline__ void ray_span_body(const OccRayArgs& g, const Rule& rule) {
     const int lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * kOccRaysPerBlock + (threadIdx.x >> 6);
-    if (b >= B) return;                                                  // wave-uniform
-    const OccRay r = occ_load_ray(b, origins, dirs, radii, nearp, farp, cone_scale);
+    if (b >= g.B) return;                                                // wave-uniform
+    const int N = g.N;
+    const OccRay r = occ_load_ray(b, g.origins, g.dirs, g.radii, g.nearp, g.farp, g.cone_scale);
     int fb = -1;                                                         // the first bucket with a hit and its ballot
     unsigned long long fm = 0ull;
     for (int kk = 0; kk < K; ++kk) {
         const int i = lane + 64 * kk;
-        const bool hit = i < N && occ_frustum_hit(box, bits, r, N, i, disparity, outside_occupied);
+        const bool hit = i < N && occ_frustum_hit(g.box, g.bits, r, N, i, rule, g.outside_occupied);
         const unsigned long long m = __ballot(hit);
         if (m != 0ull) { fb = kk; fm = m; break; }                       // wave-uniform
     }
@@ -254,19 +290,36 @@ k_ray_span(int64_t B, int N, OccBox box, const unsigned* __restrict__ bits, cons
         unsigned long long lm = fm;
         for (int kk = (N - 1) >> 6; kk > fb; --kk) {                     // (N - 1) >> 6 <= K - 1: the buckets past it hold no frustum
             const int i = lane + 64 * kk;
-            const bool hit = i < N && occ_frustum_hit(box, bits, r, N, i, disparity, outside_occupied);
+            const bool hit = i < N && occ_frustum_hit(g.box, g.bits, r, N, i, rule, g.outside_occupied);
             const unsigned long long m = __ballot(hit);
             if (m != 0ull) { lb = kk; lm = m; break; }                   // wave-uniform
         }
         li = 64 * lb + 63 - __builtin_clzll(lm);
     }
     if (lane == 0) {
-        live[b] = fb >= 0 ? 1 : 0;
-        if (first != nullptr) first[b] = fi;
-        if (last != nullptr) last[b] = li;
-        if (near_out != nullptr) near_out[b] = fb >= 0 ? level0_t(r.nv, r.fv, N, fi, disparity != 0) : r.nv;
-        if (far_out != nullptr) far_out[b] = fb >= 0 ? level0_t(r.nv, r.fv, N, li + 1, disparity != 0) : r.fv;
+        g.live[b] = fb >= 0 ? 1 : 0;
+        if (g.first != nullptr) g.first[b] = fi;
+        if (g.last != nullptr) g.last[b] = li;
+        if (g.near_out != nullptr) g.near_out[b] = fb >= 0 ? rule.post(r, N, fi) : r.nv;
+        if (g.far_out != nullptr) g.far_out[b] = fb >= 0 ? rule.post(r, N, li + 1) : r.fv;
     }
+}
+
+template <int K>
+__global__ void __launch_bounds__(64 * kOccRaysPerBlock) k_ray_occupancy(OccRayArgs g, int disparity) {
+    ray_occupancy_body<K>(g, OccWorldRule{disparity});
+}
+template <int K>
+__global__ void __launch_bounds__(64 * kOccRaysPerBlock) k_ray_span(OccRayArgs g, int disparity) {
+    ray_span_body<K>(g, OccWorldRule{disparity});
+}
+template <int K>
+__global__ void __launch_bounds__(64 * kOccRaysPerBlock) k_ray_occupancy_360(OccRayArgs g) {
+    ray_occupancy_body<K>(g, Occ360Rule{});
+}
+template <int K>
+__global__ void __launch_bounds__(64 * kOccRaysPerBlock) k_ray_span_360(OccRayArgs g) {
+    ray_span_body<K>(g, Occ360Rule{});
 }
 
 static OccBox occ_box(const int dims[3], const float lo[3], const float hi[3]) {
@@ -279,21 +332,38 @@ static OccBox occ_box(const int dims[3], const float lo[3], const float hi[3]) {
     return box;
 }
 
+static OccRayArgs occ_ray_args(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
+                               const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
+                               int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last, float* near_out,
+                               float* far_out) {
+    OccRayArgs g;
+    g.B = B; g.N = N;
+    g.box = occ_box(dims, lo, hi);
+    g.bits = bits;
+    g.origins = origins; g.dirs = dirs; g.radii = radii; g.nearp = nearp; g.farp = farp;
+    g.outside_occupied = outside_occupied; g.cone_scale = cone_scale;
+    g.live = live; g.first = first; g.last = last; g.near_out = near_out; g.far_out = far_out;
+    return g;
+}
+
+// the K buckets of the per-ray kernels (kernels_ray.hip)
+#define MIP_OCC_BUCKETS(KERNEL, N, ...)                                                                      \
+    do {                                                                                                     \
+        const dim3 grid(occ_grid_for(g.B, kOccRaysPerBlock)), block(64 * kOccRaysPerBlock);                  \
+        const int K = ((N) + 63) / 64;                                                                       \
+        if (K <= 1) hipLaunchKernelGGL((KERNEL<1>), grid, block, 0, st, __VA_ARGS__);                        \
+        else if (K <= 2) hipLaunchKernelGGL((KERNEL<2>), grid, block, 0, st, __VA_ARGS__);                   \
+        else if (K <= 4) hipLaunchKernelGGL((KERNEL<4>), grid, block, 0, st, __VA_ARGS__);                   \
+        else if (K <= 8) hipLaunchKernelGGL((KERNEL<8>), grid, block, 0, st, __VA_ARGS__);                   \
+        else hipLaunchKernelGGL((KERNEL<16>), grid, block, 0, st, __VA_ARGS__);                              \
+    } while (0)
+
 hipError_t launch_ray_occupancy(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
                                 const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
                                 int disparity, int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st) {
-    const OccBox box = occ_box(dims, lo, hi);
-    const dim3 grid(occ_grid_for(B, kOccRaysPerBlock)), block(64 * kOccRaysPerBlock);
-    const int K = (N + 63) / 64;
-#define MIP_OCC(KK)                                                                                                              \
-    hipLaunchKernelGGL((k_ray_occupancy<KK>), grid, block, 0, st, B, N, box, bits, origins, dirs, radii, nearp, farp, disparity, \
-                       outside_occupied, cone_scale, live)
-    if (K <= 1) MIP_OCC(1);                   // the K buckets of the per-ray kernels (kernels_ray.hip)
-    else if (K <= 2) MIP_OCC(2);
-    else if (K <= 4) MIP_OCC(4);
-    else if (K <= 8) MIP_OCC(8);
-    else MIP_OCC(16);
-#undef MIP_OCC
+    const OccRayArgs g = occ_ray_args(dims, lo, hi, bits, B, N, origins, dirs, radii, nearp, farp, outside_occupied, cone_scale, live,
+                                      nullptr, nullptr, nullptr, nullptr);
+    MIP_OCC_BUCKETS(k_ray_occupancy, N, g, disparity);
     return hipGetLastError();
 }
 
@@ -301,20 +371,32 @@ hipError_t launch_ray_span(const int dims[3], const float lo[3], const float hi[
                            const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
                            int disparity, int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last,
                            float* near_out, float* far_out, hipStream_t st) {
-    const OccBox box = occ_box(dims, lo, hi);
-    const dim3 grid(occ_grid_for(B, kOccRaysPerBlock)), block(64 * kOccRaysPerBlock);
-    const int K = (N + 63) / 64;
-#define MIP_SPAN(KK)                                                                                                        \
-    hipLaunchKernelGGL((k_ray_span<KK>), grid, block, 0, st, B, N, box, bits, origins, dirs, radii, nearp, farp, disparity, \
-                       outside_occupied, cone_scale, live, first, last, near_out, far_out)
-    if (K <= 1) MIP_SPAN(1);
-    else if (K <= 2) MIP_SPAN(2);
-    else if (K <= 4) MIP_SPAN(4);
-    else if (K <= 8) MIP_SPAN(8);
-    else MIP_SPAN(16);
-#undef MIP_SPAN
+    const OccRayArgs g = occ_ray_args(dims, lo, hi, bits, B, N, origins, dirs, radii, nearp, farp, outside_occupied, cone_scale, live,
+                                      first, last, near_out, far_out);
+    MIP_OCC_BUCKETS(k_ray_span, N, g, disparity);
     return hipGetLastError();
 }
+
+// the same two for a grid in contracted coordinates (Occ360Rule)
+hipError_t launch_ray_occupancy_360(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
+                                    const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
+                                    int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st) {
+    const OccRayArgs g = occ_ray_args(dims, lo, hi, bits, B, N, origins, dirs, radii, nearp, farp, outside_occupied, cone_scale, live,
+                                      nullptr, nullptr, nullptr, nullptr);
+    MIP_OCC_BUCKETS(k_ray_occupancy_360, N, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_ray_span_360(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
+                               const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
+                               int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last, float* near_out,
+                               float* far_out, hipStream_t st) {
+    const OccRayArgs g = occ_ray_args(dims, lo, hi, bits, B, N, origins, dirs, radii, nearp, farp, outside_occupied, cone_scale, live,
+                                      first, last, near_out, far_out);
+    MIP_OCC_BUCKETS(k_ray_span_360, N, g);
+    return hipGetLastError();
+}
+#undef MIP_OCC_BUCKETS
 
 // ------------------------------------------------------------------------------------------
 // compaction: exclusive scan of the live bytes, gather in order

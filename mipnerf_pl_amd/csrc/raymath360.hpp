@@ -184,4 +184,75 @@ MIP_HD float ipe360_feature(float y, float var, int half, int l, int min_deg) {
     return exp_accurate(-0.5f * vs) * sin_accurate(half ? (ys + kHalfPiF) : ys);
 }
 
+// ---- the ray side of empty-space skipping in the contracted space (include/mipnerf_hip.h, mipnerf_ray_occupancy_360) ----
+// Inverse-depth fence post k of the coarse level, k in [0, n_samples]: ni = 1 / near, fi = 1 / far.  The ONE statement of the expression:
+// k_sample_along_rays_360 and the 360 classifiers call it, so their fence posts are the same bits.
+MIP_HD float level0_t_inv_360(float ni, float fi, int n_samples, int k) {
+    const float s = torch_linspace_at(0.0f, 1.0f, n_samples + 1, k);
+    return fi * s + (1.0f - s) * ni;
+}
+MIP_HD float level0_t_360(float nearv, float farv, int n_samples, int k) {
+    return 1.0f / level0_t_inv_360(1.0f / nearv, 1.0f / farv, n_samples, k);
+}
+
+// Per-axis interval [lo_a, hi_a] of the contracted space that holds contract(x) for every x = o + t d + delta with t in [t0, t1], delta
+// perpendicular to d and |delta| <= rr t (rr = cone_scale * radius); rho = rr t1 bounds |delta|.  contract keeps directions --
+// contract(x) = f(|x|) x / |x| with f(r) = r inside the unit ball and 2 - 1 / r outside -- so radius and direction are bounded apart:
+//   tc = clamp(-(o.d) / (d.d), t0, t1), rc = |o + tc d|: the axis point nearest the centre; rmin = rc - rho, rmax = max(|p0|, |p1|) + rho
+//   rmin >= 1 (the frustum lies wholly outside the unit ball): with u0 = p0 / |p0|, u1 = p1 / |p1| every axis direction lies within the
+//     sagitta sag = 1 - sqrt(max(0, (1 + u0.u1) / 2)) of the chord u0 u1, and |x / |x| - p / |p|| <= |x - p| / sqrt(|x| |p|) <= rho / rmin
+//     for the off-axis part: e = sag + rho / rmin, [ulo_a, uhi_a] = [max(min(u0_a, u1_a) - e, -1), min(max(u0_a, u1_a) + e, 1)], and with
+//     flo = 2 - 1 / rmin, fhi = 2 - 1 / rmax: lo_a = ulo_a < 0 ? ulo_a fhi : ulo_a flo, hi_a = uhi_a > 0 ? uhi_a fhi : uhi_a flo;
+//   otherwise the world interval of the bounded rule, [xlo_a, xhi_a] = [min(p0_a, p1_a) - rho, max(p0_a, p1_a) + rho], shrunk towards 0 by
+//     the smallest scale contract applies in it, slo = rmax > 1 ? (2 - 1 / rmax) / rmax : 1: lo_a = xlo_a < 0 ? xlo_a : xlo_a slo,
+//     hi_a = xhi_a > 0 ? xhi_a : xhi_a slo, both clamped to [-F, F], F = rmax > 1 ? 2 - 1 / rmax : rmax.
+// A value that is not finite anywhere gives NaN bounds on every axis: the caller's cell rule then calls the frustum "outside".
+MIP_HD void contracted_frustum_box(float t0, float t1, const float o[3], const float d[3], float rr, float lo[3], float hi[3]) {
+    const float rho = rr * t1;
+    float p0[3], p1[3], pc[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { p0[a] = o[a] + t0 * d[a]; p1[a] = o[a] + t1 * d[a]; }
+    const float od = (o[0] * d[0] + o[1] * d[1]) + o[2] * d[2];
+    const float dd = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+    const float tc = fminf(fmaxf(-od / dd, t0), t1);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) pc[a] = o[a] + tc * d[a];
+    const float rc = sqrtf((pc[0] * pc[0] + pc[1] * pc[1]) + pc[2] * pc[2]);
+    const float n0 = sqrtf((p0[0] * p0[0] + p0[1] * p0[1]) + p0[2] * p0[2]);
+    const float n1 = sqrtf((p1[0] * p1[0] + p1[1] * p1[1]) + p1[2] * p1[2]);
+    const float rmin = rc - rho;
+    const float rmax = fmaxf(n0, n1) + rho;
+    const float chk = (n0 + n1) + (rc + rho);
+    if (!(chk - chk == 0.0f)) {                  // inf or NaN (fminf / fmaxf would drop a NaN operand)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = chk - chk;
+        return;
+    }
+    if (rmin >= 1.0f) {
+        float u0[3], u1[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { u0[a] = p0[a] / n0; u1[a] = p1[a] / n1; }
+        const float c = (u0[0] * u1[0] + u0[1] * u1[1]) + u0[2] * u1[2];
+        const float sag = 1.0f - sqrtf(fmaxf(0.0f, (1.0f + c) / 2.0f));
+        const float e = sag + rho / rmin;
+        const float flo = 2.0f - 1.0f / rmin, fhi = 2.0f - 1.0f / rmax;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float ulo = fmaxf(fminf(u0[a], u1[a]) - e, -1.0f), uhi = fminf(fmaxf(u0[a], u1[a]) + e, 1.0f);
+            lo[a] = ulo < 0.0f ? ulo * fhi : ulo * flo;
+            hi[a] = uhi > 0.0f ? uhi * fhi : uhi * flo;
+        }
+        return;
+    }
+    const float slo = rmax > 1.0f ? (2.0f - 1.0f / rmax) / rmax : 1.0f;
+    const float F = rmax > 1.0f ? 2.0f - 1.0f / rmax : rmax;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float xlo = fminf(p0[a], p1[a]) - rho, xhi = fmaxf(p0[a], p1[a]) + rho;
+        const float l = xlo < 0.0f ? xlo : xlo * slo, h = xhi > 0.0f ? xhi : xhi * slo;
+        lo[a] = fminf(fmaxf(l, -F), F);
+        hi[a] = fminf(fmaxf(h, -F), F);
+    }
+}
+
 }  // namespace mip

@@ -78,19 +78,61 @@ def cull_box(frames, grid):
     return corner_ray_bound(frames) * (grid - 1) / (grid - 3)
 
 
-def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bound=None, verbose=True):
+def corner_ray_radius(frames):
+    """The largest distance from the centre of the segment end points o + near d and o + far d over the four corner rays of every frame of
+    `frames` (Rays of [H, W, k] tensors).  The norm of an end point is convex in the pixel position, so the corners bound every pixel's, and
+    convex in t, so the two ends bound the whole segment."""
+    radius = 0.0
+    for rays in frames:
+        for y in (0, -1):
+            for x in (0, -1):
+                o, d = rays.origins[y, x], rays.directions[y, x]
+                for t in (rays.near[y, x], rays.far[y, x]):
+                    radius = max(radius, float((o + t * d).double().norm()))
+    return radius
+
+
+def cull_far_radius(frames, grid):
+    """The far radius R of a contracted-space occupancy grid of `grid` points per axis for `frames`: `corner_ray_radius` times
+    (grid - 1) / (grid - 3), the allowance `cull_box` makes.  The lattice's density is 0 beyond |z| = 2 - 1 / R, so nothing a ray reaches
+    may lie beyond it."""
+    if grid < 4:
+        raise ValueError("the occupancy grid needs at least 4 points per axis")
+    return max(corner_ray_radius(frames) * (grid - 1) / (grid - 3), 1.0 + 1e-3)
+
+
+def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bound=None, verbose=True, space=None, far_radius=None):
     """`ops.field_occupancy` of the system's field on grid^3 points over [-bound, bound]^3 (default: `cull_box` of `frames`), printing the
-    occupied share of the grid once.  The unbounded-scene model is refused."""
-    if getattr(system.mip_nerf, "unbounded", False):
-        raise NotImplementedError("empty-space culling: unbounded=True models are not supported (their field lives in a contracted space)")
-    if bound is None:
+    occupied share of the grid once.  The unbounded-scene model is refused unless `space='contracted'`: the grid then spans
+    [-bound, bound]^3 of the contracted space (default 2, all of it) with the density 0 beyond |z| = 2 - 1 / far_radius (default:
+    `cull_far_radius` of `frames`), and a bounded model is refused."""
+    unbounded = bool(getattr(system.mip_nerf, "unbounded", False))
+    if space is None:
+        if unbounded:
+            raise NotImplementedError("empty-space culling: unbounded=True models are not supported (their field lives in a contracted space) "
+                                      "unless the grid lies there too: space='contracted'")
+        if bound is None:
+            if frames is None:
+                raise ValueError("scene_occupancy: give the frames to be rendered or a bound")
+            bound = cull_box(frames, grid)
+        occ = ops.field_occupancy(system, grid=grid, lo=-float(bound), hi=float(bound), threshold=threshold, dilate=dilate)
+        if verbose:
+            print("cull: occupied share of the {0}^3 grid over +-{1:.4f} (threshold {2:g}, dilate {3}): {4:.4f}".format(
+                grid, float(bound), threshold, dilate, occ.occupied_fraction()))
+        return occ
+    if space != "contracted":
+        raise ValueError(f"scene_occupancy: space must be None or 'contracted' (a world box cannot hold an unbounded ray), got {space!r}")
+    if not unbounded:
+        raise ValueError("scene_occupancy: space='contracted' belongs to unbounded=True models; a bounded model's grid lies in world space")
+    if far_radius is None:
         if frames is None:
-            raise ValueError("scene_occupancy: give the frames to be rendered or a bound")
-        bound = cull_box(frames, grid)
-    occ = ops.field_occupancy(system, grid=grid, lo=-float(bound), hi=float(bound), threshold=threshold, dilate=dilate)
+            raise ValueError("scene_occupancy: give the frames to be rendered or a far_radius")
+        far_radius = cull_far_radius(frames, grid)
+    bound = 2.0 if bound is None else float(bound)
+    occ = ops.field_occupancy(system, grid=grid, lo=-bound, hi=bound, threshold=threshold, dilate=dilate, space=space, far_radius=float(far_radius))
     if verbose:
-        print("cull: occupied share of the {0}^3 grid over +-{1:.4f} (threshold {2:g}, dilate {3}): {4:.4f}".format(
-            grid, float(bound), threshold, dilate, occ.occupied_fraction()))
+        print("cull: occupied share of the {0}^3 grid over +-{1:.4f} of the contracted space, far radius {2:.4f} (threshold {3:g}, dilate {4}): "
+              "{5:.4f}".format(grid, bound, float(far_radius), threshold, dilate, occ.occupied_fraction()))
     return occ
 
 
@@ -141,8 +183,8 @@ def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chun
              base_size=(800, 800), occupancy=None, tighten=False, span_samples=None):
     """eval.py:main after the checkpoint is loaded: every image of `dataset` (a test split of `datasets.dataset_dict`) rendered by
     `system.mip_nerf`, PSNR / SSIM recorded, the images written when `save_image`.  Returns (psnrs, ssims) as lists of floats.
-    `occupancy` (an `ops.Occupancy`, e.g. `scene_occupancy`): rays that touch no occupied cell are not rendered (`model.CulledFrame`);
-    None is the full path.  `tighten` / `span_samples` are `CulledFrame`'s (live rays rendered on their occupied span -- not the untightened
+    `occupancy` (an `ops.Occupancy`, e.g. `scene_occupancy`; for the unbounded-scene model one with `space='contracted'`): rays that touch
+    no occupied cell are not rendered (`model.CulledFrame`); None is the full path.  `tighten` / `span_samples` are `CulledFrame`'s (live rays rendered on their occupied span -- not the untightened
     frame --; the frusta count of the classification)."""
     if scale not in (1, 4):
         raise ValueError("scale must be 1 or 4 (eval.py --scale)")

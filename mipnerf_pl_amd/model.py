@@ -908,13 +908,20 @@ class CulledFrame:
     after dilation.  `span_samples` may differ from the count the model renders with (a checkpoint rendered with fewer samples keeps the
     classification of its own count): the frusta cover [near, far] for any N, and whatever lies outside [near', far'] lies in frusta that
     hit nothing, whatever count the renderer then uses.  `.span_share` (computed on demand, a host read-back): the mean of
-    (last - first + 1) / span_samples over the live rays of the last call (NaN when none was live)."""
+    (last - first + 1) / span_samples over the live rays of the last call (NaN when none was live).
+    An unbounded=True model is accepted exactly when `occupancy.space == 'contracted'` (`ops.field_occupancy(..., space='contracted')`; a
+    bounded model with such a grid is refused, and the reverse): the classification walks the inverse-depth fence posts of the model's
+    coarse level, and a tightened ray is sampled in inverse depth on [near', far']."""
 
     def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, occupancy,
                  lanes: Optional[int] = None, outside_occupied: bool = True, cone_scale: float = 1.0, tighten: bool = False,
                  span_samples: Optional[int] = None):
-        if getattr(model, "unbounded", False):
-            raise NotImplementedError("CulledFrame: unbounded=True models are not supported (their field lives in a contracted space)")
+        unbounded, contracted = bool(getattr(model, "unbounded", False)), getattr(occupancy, "space", None) == "contracted"
+        if unbounded and not contracted:
+            raise NotImplementedError("CulledFrame: unbounded=True models are not supported (their field lives in a contracted space) unless "
+                                      "the occupancy grid lies there too: ops.field_occupancy(..., space='contracted')")
+        if contracted and not unbounded:
+            raise ValueError("CulledFrame: the occupancy grid lies in the contracted space of unbounded=True models; this model is bounded")
         self.model, self.n, self.chunk, self.white_bkgd, self.dev = model, int(num_rays), int(chunk), bool(white_bkgd), device
         self.occupancy, self.outside_occupied, self.cone_scale = occupancy, bool(outside_occupied), float(cone_scale)
         # the compacted rays and their results live in an eager GraphedFrame: its chunk loop, lanes and scratch render the first live_count rays

@@ -673,10 +673,15 @@ def isosurface(grid, threshold, lo, hi, return_edges=False):
 class Occupancy:
     """Occupancy bits of a lattice (include/mipnerf_hip.h, mipnerf_occupancy_build): `bits` uint32 on the device
     [nz - 1, ny - 1, ceil((nx - 1) / 32)], cell i of an x row is bit i & 31 of word i >> 5, padding bits are 0; `dims` =
-    (nx, ny, nz) lattice POINTS, `lo` / `hi` the box in (x, y, z) order, h = (hi - lo) / float(n - 1)."""
+    (nx, ny, nz) lattice POINTS, `lo` / `hi` the box in (x, y, z) order, h = (hi - lo) / float(n - 1).  `space`: None -- the box lies in
+    world coordinates (the bounded model) -- or 'contracted' -- in the contracted coordinates of the unbounded-scene model;
+    `ray_occupancy` / `ray_span` / `model.CulledFrame` dispatch on it."""
 
-    def __init__(self, bits, dims, lo, hi):
+    def __init__(self, bits, dims, lo, hi, space=None):
+        if space not in (None, "contracted"):
+            raise ValueError(f"Occupancy: space must be None or 'contracted', got {space!r}")
         self.bits, self.dims, self.lo, self.hi = bits, tuple(int(d) for d in dims), tuple(float(v) for v in lo), tuple(float(v) for v in hi)
+        self.space = space
 
     @property
     def cells(self):
@@ -712,14 +717,30 @@ def occupancy_grid(lattice, threshold, lo, hi, dilate=1):
     return Occupancy(bits, dims, [float(v) for v in clo], [float(v) for v in chi])
 
 
-def field_occupancy(model_or_system, grid=128, lo=None, hi=None, threshold=0.01, dilate=1, cov_scale=1.0, precision=None):
+def field_occupancy(model_or_system, grid=128, lo=None, hi=None, threshold=0.01, dilate=1, cov_scale=1.0, precision=None, space=None,
+                    far_radius=64.0):
     """`density_grid` of the field on grid^3 (or (nx, ny, nz)) points over lo .. hi, then `occupancy_grid` of it.  The threshold is a
-    density and scene dependent, like the mesh threshold.  unbounded=True models are refused (their field lives in a contracted space)."""
-    _field_mlp(model_or_system, "field_occupancy")
-    if lo is None or hi is None:
-        raise ValueError("field_occupancy: give the box lo .. hi the grid spans (the rays of the cameras to be rendered should stay inside it)")
-    sigma = density_grid(model_or_system, grid, lo, hi, cov_scale=cov_scale, precision=precision)
-    return occupancy_grid(sigma, threshold, lo, hi, dilate=dilate)
+    density and scene dependent, like the mesh threshold.  unbounded=True models are refused (their field lives in a contracted space)
+    unless `space='contracted'` names it: the lattice is then `density_grid(space='contracted', far_radius=far_radius)` over lo .. hi
+    (default [-2, 2]^3, the whole contracted space) and the result is tagged `space='contracted'`.  The density is 0 beyond
+    |z| = 2 - 1 / far_radius, so `far_radius` must be no smaller than the largest |o + far d| of the rays to be classified.
+    `space='world'` is refused: a world box cannot hold an unbounded ray."""
+    if space == "world":
+        raise ValueError("field_occupancy: space='world' is not supported: a world box cannot hold an unbounded ray (its far end lies anywhere); "
+                         "use space='contracted'")
+    _field_mlp(model_or_system, "field_occupancy", space)
+    if space is None:
+        if lo is None or hi is None:
+            raise ValueError("field_occupancy: give the box lo .. hi the grid spans (the rays of the cameras to be rendered should stay inside it)")
+        sigma = density_grid(model_or_system, grid, lo, hi, cov_scale=cov_scale, precision=precision)
+        return occupancy_grid(sigma, threshold, lo, hi, dilate=dilate)
+    if not (far_radius > 1.0 and far_radius < float("inf")):
+        raise ValueError(f"field_occupancy: far_radius must be finite and > 1 (got {far_radius})")
+    lo, hi = -2.0 if lo is None else lo, 2.0 if hi is None else hi
+    sigma = density_grid(model_or_system, grid, lo, hi, cov_scale=cov_scale, precision=precision, space=space, far_radius=far_radius)
+    occ = occupancy_grid(sigma, threshold, lo, hi, dilate=dilate)
+    occ.space = space
+    return occ
 
 
 def _rays_ptrs(rays, n, name):
@@ -733,13 +754,26 @@ def _rays_ptrs(rays, n, name):
     return L.RaysPtrs(*[t.data_ptr() for t in keep]), keep
 
 
+def _contracted_grid(occ, disparity, name):
+    """whether `occ` lies in the contracted space of the unbounded-scene model (whose rays are sampled in inverse depth: no disparity flag)"""
+    contracted = getattr(occ, "space", None) == "contracted"
+    if contracted and disparity:
+        raise ValueError(f"{name}: disparity=True does not apply to a grid in the contracted space (the unbounded-scene model samples in "
+                         "inverse depth)")
+    return contracted
+
+
 def ray_occupancy(occ, rays, num_samples, disparity=False, outside_occupied=True, cone_scale=1.0, out=None):
     """live uint8 [n]: 1 where some coarse frustum of the ray touches an occupied cell of `occ`.  Frustum i of the coarse level's
     deterministic fence posts t_0 .. t_N has the end points p0 = o + t_i d, p1 = o + t_{i+1} d, the half-width rho = cone_scale * radii *
     t_{i+1}, per axis the bounding interval [min(p0, p1) - rho, max(p0, p1) + rho] and the cell range floor((x - lo) / h), inclusive at both
     ends; the part of a range outside the grid counts as occupied when `outside_occupied`, otherwise it is clipped away.  `rays`: flat
-    [n, k] device rays."""
+    [n, k] device rays.
+    A grid with `occ.space == 'contracted'` (the unbounded-scene model): the fence posts are the inverse-depth ones of `sample_t_360` and
+    each frustum's image under `contract` is bounded by the closed form of include/mipnerf_hip.h (mipnerf_ray_occupancy_360);
+    `disparity=True` is refused."""
     import ctypes as C
+    contracted = _contracted_grid(occ, disparity, "ray_occupancy")
     n = int(rays.origins.shape[0])
     dev = occ.bits.device
     live = torch.empty(n, dtype=torch.uint8, device=dev) if out is None else out
@@ -750,8 +784,12 @@ def ray_occupancy(occ, rays, num_samples, disparity=False, outside_occupied=True
     _, cdims, clo, chi = _lattice_args("ray_occupancy", occ.dims, occ.lo, occ.hi)
     with torch.cuda.device(dev):
         rp, keep = _rays_ptrs(rays, n, "ray_occupancy")
-        L.check(L.lib().mipnerf_ray_occupancy(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(disparity)),
-                                              int(bool(outside_occupied)), float(cone_scale), _ptr(live), _stream()), "ray_occupancy")
+        if contracted:
+            L.check(L.lib().mipnerf_ray_occupancy_360(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp),
+                                                      int(bool(outside_occupied)), float(cone_scale), _ptr(live), _stream()), "ray_occupancy_360")
+        else:
+            L.check(L.lib().mipnerf_ray_occupancy(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(disparity)),
+                                                  int(bool(outside_occupied)), float(cone_scale), _ptr(live), _stream()), "ray_occupancy")
     return live
 
 
@@ -763,8 +801,11 @@ def ray_span(occ, rays, num_samples, disparity=False, outside_occupied=True, con
     far' = far.  `out`: a tuple of five preallocated tensors of those types (an entry of first / last / near' / far' may be None: it is
     skipped and returned as None).  The frusta cover [near, far] for any N, so the span found with one `num_samples` is valid for a renderer
     that uses another.  A ray rendered on [near', far'] is NOT the ray rendered on [near, far]: its samples sit elsewhere; what it leaves
-    out lies only in cells whose 8 lattice corners are at or below the threshold, after dilation."""
+    out lies only in cells whose 8 lattice corners are at or below the threshold, after dilation.
+    A grid with `occ.space == 'contracted'`: the rules of `ray_occupancy` for such a grid (mipnerf_ray_span_360); near' / far' are the fence
+    posts of `sample_t_360`, bit for bit, and `disparity=True` is refused."""
     import ctypes as C
+    contracted = _contracted_grid(occ, disparity, "ray_span")
     n = int(rays.origins.shape[0])
     dev = occ.bits.device
     if out is None:
@@ -780,8 +821,12 @@ def ray_span(occ, rays, num_samples, disparity=False, outside_occupied=True, con
     _, cdims, clo, chi = _lattice_args("ray_span", occ.dims, occ.lo, occ.hi)
     with torch.cuda.device(dev):
         rp, keep = _rays_ptrs(rays, n, "ray_span")
-        L.check(L.lib().mipnerf_ray_span(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(disparity)),
-                                         int(bool(outside_occupied)), float(cone_scale), *[_ptr(t) for t in out], _stream()), "ray_span")
+        if contracted:
+            L.check(L.lib().mipnerf_ray_span_360(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(outside_occupied)),
+                                                 float(cone_scale), *[_ptr(t) for t in out], _stream()), "ray_span_360")
+        else:
+            L.check(L.lib().mipnerf_ray_span(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(disparity)),
+                                             int(bool(outside_occupied)), float(cone_scale), *[_ptr(t) for t in out], _stream()), "ray_span")
     return tuple(out)
 
 

@@ -116,7 +116,13 @@ def add_common_args(p):
     p.add_argument("--precision", help="MLP precision (default: the checkpoint's)", choices=["fp32", "bf16"], default=None)
     p.add_argument("--no-graph", dest="use_graph", help="render each frame eagerly instead of replaying a captured hipGraph",
                    action="store_false")
-    p.add_argument("--cull", help="skip the rays that touch no occupied cell of the field's occupancy grid (bounded scenes only)", action="store_true")
+    p.add_argument("--cull", help="skip the rays that touch no occupied cell of the field's occupancy grid (a checkpoint of the unbounded-scene "
+                   "model needs --cull_space contracted as well)", action="store_true")
+    p.add_argument("--cull_space", help="--cull with a checkpoint of the unbounded-scene model: the space the occupancy grid is laid out in; "
+                   "its box is then [-B, B]^3 of the contracted space with --cull_bound B (default 2: all of it)", choices=["contracted"], default=None)
+    p.add_argument("--cull_far_radius", help="--cull_space contracted: the grid's density is 0 beyond this distance from the centre (default: the "
+                   "largest distance any corner ray of the cameras to be rendered reaches between near and far, times (grid - 1) / (grid - 3))",
+                   type=float, default=None)
     p.add_argument("--cull_grid", help="--cull: lattice points per axis of the occupancy grid", type=int, default=128)
     p.add_argument("--cull_threshold", help="--cull: a cell is occupied when the density at one of its corners exceeds this; scene dependent, like "
                    "the mesh threshold: a foggy field needs a higher one", type=float, default=0.01)
@@ -137,6 +143,10 @@ def refuse_tighten_without_cull(args):
     """--cull_tighten is a way of culling: without --cull it exits with a message before anything is loaded."""
     if getattr(args, "cull_tighten", False) and not args.cull:
         raise SystemExit("--cull_tighten tightens the rays that --cull keeps: give --cull as well")
+    if (getattr(args, "cull_space", None) is not None or getattr(args, "cull_far_radius", None) is not None) and not args.cull:
+        raise SystemExit("--cull_space / --cull_far_radius describe the grid of --cull: give --cull as well")
+    if getattr(args, "cull_far_radius", None) is not None and getattr(args, "cull_space", None) is None:
+        raise SystemExit("--cull_far_radius belongs to --cull_space contracted")
 
 
 def cli_span_samples(args, system):
@@ -148,18 +158,27 @@ def cli_span_samples(args, system):
 
 
 def refuse_unbounded_cull(args, system):
-    """--cull with a checkpoint of the unbounded-scene model: exit before anything is rendered."""
-    if args.cull and getattr(system.mip_nerf, "unbounded", False):
-        raise SystemExit("--cull: this checkpoint holds the unbounded-scene model (unbounded=True); its field lives in a contracted space and "
-                         "has no occupancy grid -- render it without --cull")
+    """--cull and the checkpoint's model must agree on the space: the unbounded-scene model needs --cull_space contracted, a bounded one
+    must not have it.  Exits before anything is rendered."""
+    unbounded, space = bool(getattr(system.mip_nerf, "unbounded", False)), getattr(args, "cull_space", None)
+    if args.cull and unbounded and space is None:
+        raise SystemExit("--cull: this checkpoint holds the unbounded-scene model (unbounded=True); its field lives in a contracted space -- "
+                         "give --cull_space contracted (and optionally --cull_far_radius R) for an occupancy grid laid out there, or render it "
+                         "without --cull")
+    if args.cull and space is not None and not unbounded:
+        raise SystemExit(f"--cull_space {space}: this checkpoint holds a bounded model; its occupancy grid lies in world space -- drop --cull_space")
 
 
 def cli_occupancy(args, system, frames):
     """The occupancy grid the --cull flags ask for (None without --cull); `frames`: an iterable of the Rays [H, W, k] to be rendered."""
     if not args.cull:
         return None
-    return scene_occupancy(system, frames if args.cull_bound is None else None, grid=args.cull_grid, threshold=args.cull_threshold,
-                           dilate=args.cull_dilate, bound=args.cull_bound)
+    space = getattr(args, "cull_space", None)
+    if space is None:
+        return scene_occupancy(system, frames if args.cull_bound is None else None, grid=args.cull_grid, threshold=args.cull_threshold,
+                               dilate=args.cull_dilate, bound=args.cull_bound)
+    return scene_occupancy(system, frames if args.cull_far_radius is None else None, grid=args.cull_grid, threshold=args.cull_threshold,
+                           dilate=args.cull_dilate, bound=args.cull_bound, space=space, far_radius=args.cull_far_radius)
 
 
 def build_parser():
