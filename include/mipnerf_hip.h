@@ -116,14 +116,29 @@ typedef struct mipnerf_rays_out {
 } mipnerf_rays_out;
 
 /* One camera for mipnerf_generate_rays: 32 floats =
- * c2w[3][4] | pix2cam[3][3] | width, height, near, far, lossmult, mode, focal | 4 pad.
- * mode 0: Blender pinhole formula with `focal` (datasets.py:226-228); mode 1: pix2cam matrix (datasets.py:125-131). */
+ * c2w[3][4] | pix2cam[3][3] | width, height, near, far, lossmult, mode, focal | distortion[4]   (floats 28..31; 0 for modes 0 and 1).
+ * mode 0: Blender pinhole formula with `focal` (datasets.py:226-228); mode 1: pix2cam matrix (datasets.py:125-131).
+ * Modes 2 and 3 are distorted COLMAP cameras (csrc/camera_models.hpp).  c = pix2cam @ (x + .5, y + .5, 1) as in mode 1, and pix2cam
+ * must be K^-1 with rows 1 and 2 negated (last row (0, 0, -1)), so that (xd, yd) = (c0, -c1) is the normalised DISTORTED image point;
+ * it is undistorted by 8 Newton steps started there (a fixed count, no data-dependent exit; a step with |determinant| < 1e-9 is a zero
+ * step; a non-finite result falls back to (xd, yd)).
+ * mode 2: radial-tangential, distortion = k1, k2, p1, p2 (COLMAP SIMPLE_RADIAL, RADIAL, OPENCV):
+ *     r2 = x^2 + y^2;  xd = x (1 + k1 r2 + k2 r2^2) + 2 p1 x y + p2 (r2 + 2 x^2);  yd likewise with p1 and p2 swapped.
+ *     camera direction (xu, -yu, -1).  All-zero coefficients give the bits of mode 1.
+ * mode 3: equidistant fisheye, distortion = k1, k2, k3, k4 (COLMAP OPENCV_FISHEYE): theta_d = |(xd, yd)| =
+ *     theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8); camera direction (sin theta xd / theta_d, -sin theta yd / theta_d,
+ *     -cos theta).  This direction is of UNIT length (modes 0-2: third component -1), so t, near and far of a mode-3 camera are distances
+ *     along the ray; it is the only form that survives a 90 degree half-angle.
+ * Radii of every mode: |d(y, x) - d(y + 1, x)| * 2/sqrt(12), the neighbour undistorted by its own solve. */
 #define MIPNERF_CAMERA_FLOATS 32
 
 typedef struct mipnerf_ctx mipnerf_ctx;
 
 const char* mipnerf_last_error(void);
 int mipnerf_abi_version(void);
+/* Number of camera modes mipnerf_generate_rays knows (4: modes 0..3 above).  A library without this symbol knows modes 0 and 1 only
+ * and would render a distorted record as a pinhole: check before building a mode-2 or mode-3 record. */
+int mipnerf_num_camera_modes(void);
 
 /* ---- context: configuration + packed weights ------------------------------------------ */
 /* MipNerf.__init__ (mip_nerf.py:117-170).  Fails with MIPNERF_E_UNSUPPORTED when the MLP
@@ -219,13 +234,15 @@ int mipnerf_sorted_piecewise_constant_pdf(int64_t num_rays, int32_t num_bins, co
 /* ---- device-side ray generation (Blender._generate_rays datasets.py:214-263, Multicam._generate_rays :116-168):
  * ray i = pixel pix_idx[i] (row-major y*W + x; NULL = pixel i) of camera cam_idx[i] (NULL = camera 0) of the
  * `cameras` table [ncam][MIPNERF_CAMERA_FLOATS] (device memory).  Radii follow the reference: distance to the
- * neighbouring pixel along image rows, last row repeated, times 2/sqrt(12). */
+ * neighbouring pixel along image rows, last row repeated, times 2/sqrt(12).  Camera modes 0..3: see MIPNERF_CAMERA_FLOATS; modes 2 and 3
+ * (distorted COLMAP cameras) cost two 8-step Newton solves per ray, the pixel's and its neighbour's. */
 int mipnerf_generate_rays(int64_t num_rays, const float* cameras, const int32_t* cam_idx,
                           const int32_t* pix_idx, const mipnerf_rays_out* out, void* stream);
 /* The same with a camera table of DOUBLES and float64 arithmetic, results rounded to float32 once at the end: `RenderGen`
  * (render_video.py:29-112) forms its rays in float64 numpy from the float64 poses of create_spheric_poses and casts with .float()
  * (render_video.py:131); the radii are the norm of a DIFFERENCE of neighbouring directions (1e-3 of their size), which float32
- * arithmetic gets to 1e-4 relative only. */
+ * arithmetic gets to 1e-4 relative only.  Same camera modes, same bits per (camera, pixel) as the float32 entry point has among its
+ * own callers; the Newton solves of modes 2 and 3 run in float64 too. */
 int mipnerf_generate_rays_f64(int64_t num_rays, const double* cameras, const int32_t* cam_idx,
                               const int32_t* pix_idx, const mipnerf_rays_out* out, void* stream);
 /* One training batch of an epoch straight into caller-owned buffers (the static inputs of a captured training step):
@@ -233,7 +250,8 @@ int mipnerf_generate_rays_f64(int64_t num_rays, const double* cameras, const int
  * ray i = global pixel id order[b * batch_size + i] over the concatenation of the `n_images` images of the `cameras` table,
  * image c found in the int64 table offsets[0..n_images] (pixel counts, cumulative; offsets[0] = 0), pixel id - offsets[c],
  * the arithmetic of mipnerf_generate_rays; gt[i][0..2] = pixels[id][0..2] (pixels [offsets[n_images]][3] fp32).  Bit-identical
- * to mipnerf_generate_rays of the same (camera, pixel) pairs.  Rays whose index is past n_order are left unwritten.
+ * to mipnerf_generate_rays of the same (camera, pixel) pairs, whatever their camera modes (a table may mix modes 0..3).  Rays whose
+ * index is past n_order are left unwritten.
  * No host synchronisation, no allocation: capturable. */
 int mipnerf_gather_train_batch(int64_t batch_size, int64_t n_order, const int64_t* order, int32_t n_images,
                                const int64_t* offsets, const float* cameras, const float* pixels, const int64_t* step,

@@ -74,6 +74,7 @@ SIGNATURES = {
     "mipnerf_sample_along_rays_360": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P]),
     "mipnerf_cast_ipe_360": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     "mipnerf_gauss_360": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "mipnerf_num_camera_modes": (C.c_int, []),
     "mipnerf_generate_rays": (C.c_int, [_I64, _P, _P, _P, C.POINTER(RaysPtrs), _P]),
     "mipnerf_generate_rays_f64": (C.c_int, [_I64, _P, _P, _P, C.POINTER(RaysPtrs), _P]),
     "mipnerf_gather_train_batch": (C.c_int, [_I64, _I64, _P, _I32, _P, _P, _P, _P, _P, C.POINTER(RaysPtrs), _P, _P]),
@@ -194,6 +195,11 @@ def lib():
             fn.argtypes = args
         _lib = h
     return _lib
+
+
+def num_camera_modes() -> int:
+    """Camera modes `mipnerf_generate_rays` of the loaded library knows (4: Blender focal, pix2cam, radial-tangential, fisheye)."""
+    return int(lib().mipnerf_num_camera_modes())
 
 
 def last_error() -> str:

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/mipnerf_hip.h"
+#include "camera_models.hpp"
 #include "kernels.hpp"
 #include "mlp_variants_gen.hpp"
 #include "mlp_train_variants_gen.hpp"
@@ -734,6 +735,8 @@ int mipnerf_gauss_360(int64_t M, int32_t min_deg, int32_t max_deg, int32_t contr
 }
 
 // ---- device-side ray generation (datasets/datasets.py:116-168, 214-263) ---------------------------------------
+int mipnerf_num_camera_modes(void) { return camera_models::NUM_CAMERA_MODES; }
+
 int mipnerf_generate_rays(int64_t n, const float* cameras, const int32_t* cam_idx, const int32_t* pix_idx,
                           const mipnerf_rays_out* out, void* stream) {
     if (n < 1 || !cameras || !out || !out->origins || !out->directions || !out->viewdirs || !out->radii ||

@@ -7,6 +7,7 @@
 // (see raymath.hpp).
 #include <hip/hip_runtime.h>
 
+#include "camera_models.hpp"
 #include "ipe.hpp"
 #include "kernels.hpp"
 #include "raymath.hpp"
@@ -384,9 +385,11 @@ hipError_t launch_ray_prologue(int64_t B, int deg, const float* viewdirs, void* 
 // ---- device-side ray generation ----------------------------------------------------------------
 // datasets/datasets.py:214-263 (Blender._generate_rays) and :116-168 (Multicam._generate_rays) computed per pixel
 // on the device instead of materialising 52 B/ray for every pixel of every image on the host.
-// camera record (32 floats): c2w[3][4] | pix2cam[3][3] | W, H, near, far, lossmult, mode, focal | pad
+// camera record (32 floats): c2w[3][4] | pix2cam[3][3] | W, H, near, far, lossmult, mode, focal | distortion[4]
 //   mode 0 (Blender): camera_dir = ((x - W/2 + .5)/focal, -(y - H/2 + .5)/focal, -1)        datasets.py:226-228
 //   mode 1 (Multicam): camera_dir = pix2cam @ (x + .5, y + .5, 1)                             datasets.py:125-131
+//   mode 2 / 3 (COLMAP radial-tangential / equidistant fisheye, distortion[4] in the former pad): the mode-1 point undistorted by a
+//   fixed-count Newton solve, camera_models.hpp; mode 3 directions are of unit length
 // direction = c2w[:3,:3] @ camera_dir; origin = c2w[:3,3]; viewdir = direction / |direction|;
 // radius = |direction(y, x) - direction(y+1, x)| * 2/sqrt(12), last row repeats the previous one (datasets.py:246-253:
 // the neighbour is taken along axis 0 = image rows).
@@ -408,6 +411,14 @@ __device__ __forceinline__ void pixel_direction(const T* __restrict__ cam, T x, 
         c0 = cam[12] * px + cam[13] * py + cam[14];
         c1 = cam[15] * px + cam[16] * py + cam[17];
         c2 = cam[18] * px + cam[19] * py + cam[20];
+        if (cam[26] >= T(2)) {      // distorted COLMAP cameras (camera_models.hpp): (c0, -c1) is the distorted point, pix2cam's last row (0, 0, -1)
+            const T k[4] = {cam[28], cam[29], cam[30], cam[31]};
+            T c[3];
+            camera_models::undistorted_direction<T>(cam[26] == T(2) ? 2 : 3, k, c0, -c1, c);
+            c0 = c[0];
+            c1 = c[1];
+            c2 = c[2];
+        }
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) d[i] = cam[4 * i] * c0 + cam[4 * i + 1] * c1 + cam[4 * i + 2] * c2;

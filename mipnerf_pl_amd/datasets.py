@@ -162,6 +162,158 @@ def read_colmap_pinhole(fname):
     return np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
 
 
+# COLMAP camera models (src/colmap/sensor/models.h): id -> (name, number of parameters).  Ids 0-5 are read; the others are refused by name.
+COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8),
+                 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4), 9: ("RADIAL_FISHEYE", 5),
+                 10: ("THIN_PRISM_FISHEYE", 12)}
+COLMAP_MODELS_READ = 6
+CAMERA_NEWTON_STEPS = 8                 # csrc/camera_models.hpp
+ROUND_TRIP_TOL = 1e-6                   # normalised units: undistort, then distort, every border pixel (`check_invertible`)
+
+
+def read_colmap_cameras(fname):
+    """Every camera of a COLMAP `cameras.bin` as (camera_id, model_name, width, height, params): the models SIMPLE_PINHOLE, PINHOLE,
+    SIMPLE_RADIAL, RADIAL, OPENCV and OPENCV_FISHEYE, `params` the model's doubles in COLMAP's order.  Any other model raises
+    NotImplementedError with its name."""
+    cameras = []
+    with open(fname, "rb") as f:
+        (count,) = struct.unpack("<Q", f.read(8))
+        for _ in range(count):
+            camera_id, model_id, width, height = struct.unpack("<iiQQ", f.read(24))
+            if model_id not in COLMAP_MODELS or model_id >= COLMAP_MODELS_READ:
+                name = COLMAP_MODELS.get(model_id, (f"model id {model_id}", 0))[0]
+                raise NotImplementedError(f"{fname}: camera {camera_id} has the COLMAP model {name}; read are "
+                                          + ", ".join(COLMAP_MODELS[i][0] for i in range(COLMAP_MODELS_READ))
+                                          + " -- undistort the capture with COLMAP (colmap image_undistorter) first")
+            name, n = COLMAP_MODELS[model_id]
+            cameras.append((camera_id, name, int(width), int(height), struct.unpack("<" + "d" * n, f.read(8 * n))))
+    return cameras
+
+
+def read_colmap_image_cameras(fname):
+    """{image file name: camera_id} of a COLMAP `images.bin` (the poses and the 2D points are skipped)."""
+    out = {}
+    with open(fname, "rb") as f:
+        (count,) = struct.unpack("<Q", f.read(8))
+        for _ in range(count):
+            _image_id = struct.unpack("<i", f.read(4))
+            f.read(56)                                                   # qvec[4], tvec[3]
+            (camera_id,) = struct.unpack("<i", f.read(4))
+            name = b""
+            while True:
+                c = f.read(1)
+                if c in (b"\x00", b""):
+                    break
+                name += c
+            (n2d,) = struct.unpack("<Q", f.read(8))
+            f.seek(24 * n2d, 1)                                          # (x, y, point3D_id)
+            out[name.decode()] = camera_id
+    return out
+
+
+def colmap_intrinsics(model_name, params):
+    """(K, model of `ops.camera_record`, its four coefficients) of one `read_colmap_cameras` entry."""
+    p = [float(v) for v in params]
+    if model_name in ("SIMPLE_PINHOLE", "SIMPLE_RADIAL", "RADIAL"):
+        fx, fy, cx, cy, rest = p[0], p[0], p[1], p[2], p[3:]
+    else:
+        fx, fy, cx, cy, rest = p[0], p[1], p[2], p[3], p[4:]
+    K = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+    if model_name in ("SIMPLE_PINHOLE", "PINHOLE"):
+        return K, "pinhole", (0.0, 0.0, 0.0, 0.0)
+    if model_name == "OPENCV_FISHEYE":
+        return K, "fisheye", tuple(rest)
+    return K, "radial", tuple(rest + [0.0] * (4 - len(rest)))           # SIMPLE_RADIAL: k1; RADIAL: k1, k2; OPENCV: k1, k2, p1, p2
+
+
+def distort_points(model, coeffs, x, y):
+    """COLMAP's forward model in float64 numpy: undistorted normalised points -> distorted ones ('radial': k1, k2, p1, p2; 'fisheye':
+    k1..k4, where (x, y) = tan(theta) times a unit vector; 'pinhole': unchanged)."""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    if model == "pinhole":
+        return x, y
+    a, b, c, d = (float(v) for v in coeffs)
+    if model == "radial":
+        r2 = x * x + y * y
+        radial = 1.0 + a * r2 + b * r2 * r2
+        return x * radial + 2.0 * c * x * y + d * (r2 + 2.0 * x * x), y * radial + 2.0 * d * x * y + c * (r2 + 2.0 * y * y)
+    r = np.sqrt(x * x + y * y)
+    th = np.arctan(r)
+    t2 = th * th
+    thd = th * (1.0 + t2 * (a + t2 * (b + t2 * (c + t2 * d))))
+    s = np.where(r < 1e-8, 1.0, thd / np.where(r < 1e-8, 1.0, r))
+    return s * x, s * y
+
+
+def undistort_points(model, coeffs, xd, yd, steps=CAMERA_NEWTON_STEPS):
+    """The device's solve (csrc/camera_models.hpp) in float64 numpy: distorted normalised points -> ('radial') the undistorted points
+    (xu, yu), ('fisheye') the angle theta and the distorted radius theta_d.  `steps` Newton steps from the distorted point, a step with a
+    determinant below 1e-9 in magnitude is a zero step, a non-finite result falls back to the start."""
+    xd, yd = np.asarray(xd, np.float64), np.asarray(yd, np.float64)
+    a, b, c, d = (float(v) for v in coeffs)
+    with np.errstate(all="ignore"):
+        if model == "radial":
+            x, y = xd.copy(), yd.copy()
+            for _ in range(steps):
+                fx, fy = distort_points(model, coeffs, x, y)
+                fx, fy = fx - xd, fy - yd
+                r2 = x * x + y * y
+                radial = 1.0 + a * r2 + b * r2 * r2
+                dr = 2.0 * (a + 2.0 * b * r2)
+                j00 = radial + dr * x * x + 2.0 * c * y + 6.0 * d * x
+                j01 = dr * x * y + 2.0 * c * x + 2.0 * d * y
+                j11 = radial + dr * y * y + 2.0 * d * x + 6.0 * c * y
+                det = j00 * j11 - j01 * j01
+                ok = np.abs(det) > 1e-9
+                inv = 1.0 / np.where(ok, det, 1.0)
+                x = x - np.where(ok, (j11 * fx - j01 * fy) * inv, 0.0)
+                y = y - np.where(ok, (j00 * fy - j01 * fx) * inv, 0.0)
+            fin = np.isfinite(x) & np.isfinite(y)
+            return np.where(fin, x, xd), np.where(fin, y, yd)
+        thd = np.sqrt(xd * xd + yd * yd)
+        th = thd.copy()
+        for _ in range(steps):
+            t2 = th * th
+            f = th * (1.0 + t2 * (a + t2 * (b + t2 * (c + t2 * d)))) - thd
+            df = 1.0 + t2 * (3.0 * a + t2 * (5.0 * b + t2 * (7.0 * c + t2 * (9.0 * d))))
+            ok = np.abs(df) > 1e-9
+            th = th - np.where(ok, f / np.where(ok, df, 1.0), 0.0)
+        return np.where(np.isfinite(th), th, thd), thd
+
+
+def round_trip_error(model, coeffs, K, width, height):
+    """The largest distance, in normalised units, between a border pixel centre of a width x height image of the distorted camera (K,
+    model, coeffs) and the image of its undistorted point under the forward model: what the device's 8-step solve leaves."""
+    if model == "pinhole":
+        return 0.0
+    xs, ys = np.arange(width) + 0.5, np.arange(height) + 0.5
+    px = np.concatenate([xs, xs, np.full(height, 0.5), np.full(height, width - 0.5)])
+    py = np.concatenate([np.full(width, 0.5), np.full(width, height - 0.5), ys, ys])
+    xd, yd = (px - K[0, 2]) / K[0, 0], (py - K[1, 2]) / K[1, 1]
+    with np.errstate(all="ignore"):
+        if model == "radial":
+            xu, yu = undistort_points(model, coeffs, xd, yd)
+            bx, by = distort_points(model, coeffs, xu, yu)
+            err = np.sqrt((bx - xd) ** 2 + (by - yd) ** 2)
+        else:
+            th, thd = undistort_points(model, coeffs, xd, yd)
+            a, b, c, d = (float(v) for v in coeffs)
+            t2 = th * th
+            err = np.abs(th * (1.0 + t2 * (a + t2 * (b + t2 * (c + t2 * d)))) - thd)
+            err = np.where((th >= 0.0) & (th < np.pi), err, np.inf)           # a root outside [0, pi) is no viewing angle
+    return float(np.max(np.where(np.isfinite(err), err, np.inf)))
+
+
+def check_invertible(camera_id, model_name, model, coeffs, K, width, height):
+    """Refuse a camera whose image border lies outside the invertible domain of its distortion model (a strong barrel model folds back
+    before the border): every border pixel, undistorted as the device does and distorted back, must return to within 1e-6."""
+    err = round_trip_error(model, coeffs, K, width, height)
+    if not err <= ROUND_TRIP_TOL:
+        raise ValueError(f"COLMAP camera {camera_id} ({model_name}, distortion {tuple(coeffs)}): undistorting the border of its {width}x{height} "
+                         f"image and distorting it back misses by {err:.3g} in normalised units (limit {ROUND_TRIP_TOL:g}) -- the border lies "
+                         "outside the model's invertible domain; undistort the capture with COLMAP (colmap image_undistorter) first")
+
+
 def _image_files(imgdir):
     return [os.path.join(imgdir, f) for f in sorted(os.listdir(imgdir)) if f.endswith(("JPG", "jpg", "png"))]
 
@@ -217,13 +369,57 @@ def _shrink_on_device(files, factor, device):
         return ops.area_downscale(torch.from_numpy(decode_u8(files)).to(device), factor)
 
 
+def _capture_cameras(data_dir, files, factor, w, h):
+    """({camera_id: dict(name, model, distortion, K, K_inv)} in file order, [camera_id of every file of `files`]) of a capture's
+    sparse/0: K is divided by `factor` (the distortion coefficients are not: they live in normalised coordinates), K_inv = K^-1 with rows
+    1 and 2 negated.  One camera: every image is its.  Several: sparse/0/images.bin names each image's; they may differ in model and
+    parameters but not in image size, because the pixel table is stacked.  Every distorted camera passes `check_invertible` at (w, h)."""
+    fname = os.path.join(data_dir, "sparse", "0", "cameras.bin")
+    entries = read_colmap_cameras(fname)
+    if not entries:
+        raise ValueError(f"{fname} holds no camera")
+    sizes = {(cw, ch) for _, _, cw, ch, _ in entries}
+    if len(sizes) > 1:
+        raise ValueError(f"{fname}: its cameras differ in image size ({', '.join(f'{a}x{b}' for a, b in sorted(sizes))}); a capture whose "
+                         "images differ in size is not supported (the pixel table is stacked)")
+    cams = {}
+    for camera_id, name, _, _, params in entries:
+        K, model, coeffs = colmap_intrinsics(name, params)
+        K[:2, :] /= factor
+        K_inv = np.linalg.inv(K)
+        K_inv[1:, :] *= -1
+        check_invertible(camera_id, name, model, coeffs, K, w, h)
+        cams[camera_id] = dict(name=name, model=model, distortion=coeffs, K=K, K_inv=K_inv)
+    if len(cams) == 1:
+        return cams, [entries[0][0]] * len(files)
+    iname = os.path.join(data_dir, "sparse", "0", "images.bin")
+    if not os.path.exists(iname):
+        raise FileNotFoundError(f"{fname} holds {len(cams)} cameras, so {iname} is needed to tell each image's camera, and it is missing")
+    by_name = read_colmap_image_cameras(iname)
+    by_stem = {os.path.splitext(k)[0]: v for k, v in by_name.items()}
+    cam_of = []
+    for f in files:
+        base = os.path.basename(f)
+        cid = by_name.get(base, by_stem.get(os.path.splitext(base)[0]))
+        if cid is None:
+            raise ValueError(f"{iname} names no image {base}")
+        if cid not in cams:
+            raise ValueError(f"{iname}: image {base} belongs to camera {cid}, which {fname} does not hold")
+        cam_of.append(cid)
+    return cams, cam_of
+
+
 def load_realdata360(data_dir, split, white_bkgd=True, factor=0, device=None):
     """datasets.py:278-345.  `factor` must be > 0 (upstream divides by it at :312 and :335; with the shipped default 0 it
     produces infinities -- raised here instead).  Every 8th image is the test split.
     Without an images_<factor>/ folder but with images/ (a capture as COLMAP leaves it), the split's files of images/ are decoded to
     bytes, uploaded once and shrunk by `factor` on `device` straight into the pixel table (`ops.area_downscale`: the box mean rounded
     to a byte, i.e. the pixels an images_<factor>/ folder of those bytes would give); the first return value is then that [P, 3] device
-    tensor and info['sizes'] the (height, width) of every image."""
+    tensor and info['sizes'] the (height, width) of every image.
+    Cameras: `read_colmap_cameras` of sparse/0/cameras.bin (SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE; see
+    `_capture_cameras` for several cameras and for the refusals).  A distorted camera's record carries its model and coefficients and the
+    kernel undistorts every ray, so the photos are trained on and compared with as they are: info['models'] (COLMAP names), ['distortion']
+    [n, 4] and ['Ks'] [n, 3, 3] are per image; ['K'] / ['K_inv'] stay those of the file's first camera."""
     files, n_files, shrink = realdata360_files(data_dir, split, factor)
     images = None if shrink else np.stack([_read_image(f) for f in _image_files(os.path.join(data_dir, f"images_{factor}"))], axis=0)
     arr = np.load(os.path.join(data_dir, "poses_bounds.npy"))
@@ -241,13 +437,18 @@ def load_realdata360(data_dir, split, white_bkgd=True, factor=0, device=None):
     poses = np.concatenate([poses[:, :, 1:2], -poses[:, :, 0:1], poses[:, :, 2:]], axis=2).astype(np.float32)   # (down,right,back) -> (right,up,back)
     poses = spherify_poses(recenter_poses(poses))
     sel = _split_indices(n_files, split)
-    K = read_colmap_pinhole(os.path.join(data_dir, "sparse", "0", "cameras.bin"))
-    K[:2, :] /= factor
-    K_inv = np.linalg.inv(K)
-    K_inv[1:, :] *= -1
     h, w = (int(v) for v in shape[1:3])
-    records = [ops.camera_record(poses[i, :3, :4], w, h, float(bds[i, 0]), float(bds[i, 1]), pix2cam=K_inv) for i in sel]
-    info = dict(h=h, w=w, K=K, K_inv=K_inv, bds=bds[sel], camtoworlds=poses[sel][:, :3, :4], focal=poses[0, -1, -1])
+    all_files = _image_files(os.path.join(data_dir, "images" if shrink else f"images_{factor}"))
+    cams, cam_of = _capture_cameras(data_dir, all_files, factor, w, h)
+    first = cams[next(iter(cams))]
+    K, K_inv = first["K"], first["K_inv"]
+    per_image = [cams[cam_of[i]] for i in sel]
+    records = [ops.camera_record(poses[i, :3, :4], w, h, float(bds[i, 0]), float(bds[i, 1]), pix2cam=c["K_inv"],
+                                 **({} if c["model"] == "pinhole" else dict(model=c["model"], distortion=c["distortion"])))
+               for i, c in zip(sel, per_image)]
+    info = dict(h=h, w=w, K=K, K_inv=K_inv, bds=bds[sel], camtoworlds=poses[sel][:, :3, :4], focal=poses[0, -1, -1],
+                models=[c["name"] for c in per_image], distortion=np.array([c["distortion"] for c in per_image], np.float64).reshape(-1, 4),
+                Ks=np.stack([c["K"] for c in per_image]) if per_image else np.zeros((0, 3, 3)))
     if pixels is not None:
         return pixels.view(-1, 3), records, dict(info, sizes=[(h, w)] * len(sel))
     imgs = [np.ascontiguousarray(images[i, ..., :3], dtype=np.float32) for i in sel]
@@ -498,7 +699,10 @@ class RenderGen(torch.utils.data.Dataset):
 class PathGen(RenderGen):
     """The render path of a captured scene: `gen_render_path` through the poses of `dataset` (a RealData360 split; `poses` [n, 3|4, 4]
     given: those instead), one float32 camera record per pose built as `load_realdata360` builds the data set's (its size and pix2cam),
-    near / far = the smallest / largest bound of the split.  Item i = Rays [h, w, k] of pose i."""
+    near / far = the smallest / largest bound of the split.  Item i = Rays [h, w, k] of pose i.
+    The records are IDEAL PINHOLE ones from the data set's `K_inv` (mode 1, no coefficients) even when the capture's camera is distorted:
+    a fly-through is rendered undistorted, as multinerf renders its paths.  `eval` and the validation loop of `train` take their rays from
+    the data set itself, i.e. from the distorted camera, because they are compared with the photos."""
 
     def __init__(self, dataset, n_views=30, poses=None, device=None):
         torch.utils.data.Dataset.__init__(self)

@@ -13,7 +13,7 @@ import argparse
 
 import torch
 
-from .evaluate import evaluate, summarize_results
+from .evaluate import distorted_frames, evaluate, summarize_results
 from .render_video import (add_common_args, cli_occupancy, cli_span_samples, flag_given, is_scene360, load_system, refuse_tighten_without_cull,
                            refuse_unbounded_cull)
 
@@ -47,7 +47,7 @@ def main(argv=None):
             white_bkgd = bool(hp["val.white_bkgd"])
         if scene360 and not flag_given(argv, "--base_size"):
             base_size = (dataset.w, dataset.h)
-        occupancy = cli_occupancy(args, system, (dataset[i][0] for i in range(len(dataset))))
+        occupancy = cli_occupancy(args, system, (dataset[i][0] for i in range(len(dataset))), distorted=distorted_frames(dataset))
         evaluate(system, dataset, args.out_dir, exp_name, scale=args.scale, save_image=args.save_image, chunk_size=args.chunk_size,
                  white_bkgd=white_bkgd, use_graph=args.use_graph, base_size=base_size, occupancy=occupancy, tighten=args.cull_tighten,
                  span_samples=cli_span_samples(args, system) if args.cull else None)

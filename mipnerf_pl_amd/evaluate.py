@@ -57,11 +57,30 @@ class FrameEvaluator:
         return self.rgb_u8, self.dist_u8, self.acc_u8
 
 
-def corner_ray_bound(frames):
+def _frame_flags(distorted):
+    """`distorted` of the cull defaults as one flag per frame: None / a bool for all frames, or a sequence with one entry per frame."""
+    if distorted is None or isinstance(distorted, (bool, np.bool_)):
+        return None if not distorted else True
+    flags = [bool(v) for v in distorted]
+    return flags if any(flags) else None
+
+
+def _end_points(rays):
+    """o + near d and o + far d of every pixel of a frame, on the frame's device: two [H, W, 3] tensors."""
+    return rays.origins + rays.near * rays.directions, rays.origins + rays.far * rays.directions
+
+
+def corner_ray_bound(frames, distorted=None):
     """The largest absolute coordinate of the segment end points o + near d and o + far d over the four corner rays of every frame of
-    `frames` (Rays of [H, W, k] tensors).  The end points are affine in the pixel position, so the corners bound every pixel's."""
+    `frames` (Rays of [H, W, k] tensors).  The end points are affine in the pixel position, so the corners bound every pixel's.
+    That argument fails for a frame of a distorted camera (camera record mode 2 or 3): for the frames `distorted` flags (True: all; a
+    sequence: one flag per frame) the maximum is taken over EVERY pixel, a reduction on the device where the rays already are."""
+    flags = _frame_flags(distorted)
     bound = 0.0
-    for rays in frames:
+    for i, rays in enumerate(frames):
+        if flags is True or (flags is not None and flags[i]):
+            bound = max([bound] + [float(p.abs().max()) for p in _end_points(rays)])
+            continue
         for y in (0, -1):
             for x in (0, -1):
                 o, d = rays.origins[y, x], rays.directions[y, x]
@@ -70,20 +89,25 @@ def corner_ray_bound(frames):
     return bound
 
 
-def cull_box(frames, grid):
+def cull_box(frames, grid, distorted=None):
     """The half-width B of the occupancy box [-B, B]^3 of `grid` points per axis that holds every ray segment of `frames` plus one cell:
-    B = B0 + h with h = 2 B / (grid - 1) the box's own cell, i.e. B = B0 (grid - 1) / (grid - 3)."""
+    B = B0 + h with h = 2 B / (grid - 1) the box's own cell, i.e. B = B0 (grid - 1) / (grid - 3).  `distorted`: see `corner_ray_bound`."""
     if grid < 4:
         raise ValueError("the occupancy grid needs at least 4 points per axis")
-    return corner_ray_bound(frames) * (grid - 1) / (grid - 3)
+    return corner_ray_bound(frames, distorted) * (grid - 1) / (grid - 3)
 
 
-def corner_ray_radius(frames):
+def corner_ray_radius(frames, distorted=None):
     """The largest distance from the centre of the segment end points o + near d and o + far d over the four corner rays of every frame of
     `frames` (Rays of [H, W, k] tensors).  The norm of an end point is convex in the pixel position, so the corners bound every pixel's, and
-    convex in t, so the two ends bound the whole segment."""
+    convex in t, so the two ends bound the whole segment.  Convexity in the pixel position fails under lens distortion: for the frames
+    `distorted` flags (as in `corner_ray_bound`) the maximum is taken over every pixel, on the device."""
+    flags = _frame_flags(distorted)
     radius = 0.0
-    for rays in frames:
+    for i, rays in enumerate(frames):
+        if flags is True or (flags is not None and flags[i]):
+            radius = max([radius] + [float(p.double().norm(dim=-1).max()) for p in _end_points(rays)])
+            continue
         for y in (0, -1):
             for x in (0, -1):
                 o, d = rays.origins[y, x], rays.directions[y, x]
@@ -92,20 +116,29 @@ def corner_ray_radius(frames):
     return radius
 
 
-def cull_far_radius(frames, grid):
+def cull_far_radius(frames, grid, distorted=None):
     """The far radius R of a contracted-space occupancy grid of `grid` points per axis for `frames`: `corner_ray_radius` times
     (grid - 1) / (grid - 3), the allowance `cull_box` makes.  The lattice's density is 0 beyond |z| = 2 - 1 / R, so nothing a ray reaches
-    may lie beyond it."""
+    may lie beyond it.  `distorted`: see `corner_ray_radius`."""
     if grid < 4:
         raise ValueError("the occupancy grid needs at least 4 points per axis")
-    return max(corner_ray_radius(frames) * (grid - 1) / (grid - 3), 1.0 + 1e-3)
+    return max(corner_ray_radius(frames, distorted) * (grid - 1) / (grid - 3), 1.0 + 1e-3)
 
 
-def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bound=None, verbose=True, space=None, far_radius=None):
+def distorted_frames(dataset):
+    """One flag per image of `dataset`: whether its camera record is a distorted one (mode 2 or 3), for the `distorted` argument of the
+    cull defaults.  None for a data set without a camera table."""
+    cams = getattr(dataset, "cameras", None)
+    return None if cams is None else [bool(v) for v in (cams[:, 26] >= 2).tolist()]
+
+
+def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bound=None, verbose=True, space=None, far_radius=None,
+                    distorted=None):
     """`ops.field_occupancy` of the system's field on grid^3 points over [-bound, bound]^3 (default: `cull_box` of `frames`), printing the
     occupied share of the grid once.  The unbounded-scene model is refused unless `space='contracted'`: the grid then spans
     [-bound, bound]^3 of the contracted space (default 2, all of it) with the density 0 beyond |z| = 2 - 1 / far_radius (default:
-    `cull_far_radius` of `frames`), and a bounded model is refused."""
+    `cull_far_radius` of `frames`), and a bounded model is refused.  `distorted` flags the frames of distorted cameras, whose default
+    bound / far radius is taken over every pixel (`corner_ray_bound`)."""
     unbounded = bool(getattr(system.mip_nerf, "unbounded", False))
     if space is None:
         if unbounded:
@@ -114,7 +147,7 @@ def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bou
         if bound is None:
             if frames is None:
                 raise ValueError("scene_occupancy: give the frames to be rendered or a bound")
-            bound = cull_box(frames, grid)
+            bound = cull_box(frames, grid, distorted)
         occ = ops.field_occupancy(system, grid=grid, lo=-float(bound), hi=float(bound), threshold=threshold, dilate=dilate)
         if verbose:
             print("cull: occupied share of the {0}^3 grid over +-{1:.4f} (threshold {2:g}, dilate {3}): {4:.4f}".format(
@@ -127,7 +160,7 @@ def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bou
     if far_radius is None:
         if frames is None:
             raise ValueError("scene_occupancy: give the frames to be rendered or a far_radius")
-        far_radius = cull_far_radius(frames, grid)
+        far_radius = cull_far_radius(frames, grid, distorted)
     bound = 2.0 if bound is None else float(bound)
     occ = ops.field_occupancy(system, grid=grid, lo=-bound, hi=bound, threshold=threshold, dilate=dilate, space=space, far_radius=float(far_radius))
     if verbose:

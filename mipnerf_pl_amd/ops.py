@@ -186,10 +186,22 @@ def volumetric_rendering_packed(rgb_sigma, t_samples, dirs, white_bkgd):
     return comp_rgb, distance, acc, weights
 
 
-def camera_record(c2w, width, height, near, far, focal=None, pix2cam=None, lossmult=1.0, dtype=torch.float32):
+CAMERA_MODES = {"pinhole": 1, "radial": 2, "fisheye": 3}      # rec[26] of a pix2cam record (0: the Blender focal formula)
+
+
+def camera_record(c2w, width, height, near, far, focal=None, pix2cam=None, lossmult=1.0, dtype=torch.float32, model="pinhole",
+                  distortion=None):
     """One row of the camera table of `generate_rays` (32 numbers, include/mipnerf_hip.h): Blender pinhole camera
     when `focal` is given (datasets.py:226-228), Multicam when `pix2cam` is given (datasets.py:125-131).
-    dtype=torch.float64: a table for float64 ray arithmetic (RenderGen, render_video.py:29-112)."""
+    dtype=torch.float64: a table for float64 ray arithmetic (RenderGen, render_video.py:29-112).
+    `model='radial'` with `distortion=(k1, k2, p1, p2)` (COLMAP SIMPLE_RADIAL / RADIAL / OPENCV) or `model='fisheye'` with
+    `distortion=(k1, k2, k3, k4)` (OPENCV_FISHEYE): a distorted camera, whose rays the kernel undistorts per pixel (csrc/camera_models.hpp).
+    `pix2cam` must then be K^-1 with rows 1 and 2 negated (last row (0, 0, -1)), as `datasets.load_realdata360` builds it.  A fisheye
+    camera's directions are of unit length, so its near / far are distances along the ray."""
+    if model not in CAMERA_MODES:
+        raise ValueError(f"camera_record: model must be one of {sorted(CAMERA_MODES)}, got {model!r}")
+    if (model != "pinhole" or distortion is not None) and pix2cam is None:
+        raise ValueError("camera_record: a distorted camera (model / distortion) needs pix2cam, not focal")
     rec = torch.zeros(32, dtype=dtype)
     rec[0:12] = torch.as_tensor(c2w, dtype=dtype)[:3, :4].reshape(-1)
     if (focal is None) == (pix2cam is None):
@@ -200,6 +212,24 @@ def camera_record(c2w, width, height, near, far, focal=None, pix2cam=None, lossm
     else:
         rec[27] = float(focal)
     rec[21], rec[22], rec[23], rec[24], rec[25] = float(width), float(height), float(near), float(far), float(lossmult)
+    if model != "pinhole":
+        coeffs = [0.0] * 4 if distortion is None else [float(v) for v in distortion]
+        if len(coeffs) != 4:
+            raise ValueError(f"camera_record: distortion holds 4 coefficients ({'k1, k2, p1, p2' if model == 'radial' else 'k1, k2, k3, k4'}), "
+                             f"got {len(coeffs)}")
+        if rec[18:21].tolist() != [0.0, 0.0, -1.0]:
+            raise ValueError("camera_record: a distorted camera needs a pix2cam whose last row is (0, 0, -1) (K^-1 with rows 1 and 2 negated), "
+                             f"got {rec[18:21].tolist()}")
+        if L.num_camera_modes() <= CAMERA_MODES[model]:
+            raise RuntimeError(f"camera_record: the loaded library knows camera modes 0..{L.num_camera_modes() - 1} only; it would render a "
+                               f"{model!r} camera as a pinhole")
+        rec[26] = float(CAMERA_MODES[model])
+        rec[28:32] = torch.tensor(coeffs, dtype=dtype)
+    elif distortion is not None:
+        if len(tuple(distortion)) != 4:
+            raise ValueError(f"camera_record: distortion holds 4 coefficients, got {len(tuple(distortion))}")
+        if any(float(v) != 0.0 for v in distortion):
+            raise ValueError("camera_record: model='pinhole' has no distortion; give model='radial' or 'fisheye'")
     return rec
 
 

@@ -169,16 +169,17 @@ def refuse_unbounded_cull(args, system):
         raise SystemExit(f"--cull_space {space}: this checkpoint holds a bounded model; its occupancy grid lies in world space -- drop --cull_space")
 
 
-def cli_occupancy(args, system, frames):
-    """The occupancy grid the --cull flags ask for (None without --cull); `frames`: an iterable of the Rays [H, W, k] to be rendered."""
+def cli_occupancy(args, system, frames, distorted=None):
+    """The occupancy grid the --cull flags ask for (None without --cull); `frames`: an iterable of the Rays [H, W, k] to be rendered,
+    `distorted`: which of them come from a distorted camera (`evaluate.distorted_frames`; a path of pinhole records has none)."""
     if not args.cull:
         return None
     space = getattr(args, "cull_space", None)
     if space is None:
         return scene_occupancy(system, frames if args.cull_bound is None else None, grid=args.cull_grid, threshold=args.cull_threshold,
-                               dilate=args.cull_dilate, bound=args.cull_bound)
+                               dilate=args.cull_dilate, bound=args.cull_bound, distorted=distorted)
     return scene_occupancy(system, frames if args.cull_far_radius is None else None, grid=args.cull_grid, threshold=args.cull_threshold,
-                           dilate=args.cull_dilate, bound=args.cull_bound, space=space, far_radius=args.cull_far_radius)
+                           dilate=args.cull_dilate, bound=args.cull_bound, space=space, far_radius=args.cull_far_radius, distorted=distorted)
 
 
 def build_parser():
