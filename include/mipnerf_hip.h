@@ -417,6 +417,14 @@ int mipnerf_uncontract_vertices(int64_t num_vertices, float far_radius, const fl
  * mipnerf_occupancy_build: one lane per cell, a wave's ballot is two words; dilation is three separable passes on the packed words
  * (`scratch`: as many words again, needed only when dilate > 0).  No atomics: two runs give the same bytes.  Does not allocate or
  * synchronise (graph-capturable).
+ * mipnerf_occupancy_refresh: the lattice a training run keeps while its field changes.  For every lattice point p: d = decay *
+ * running[p] (one fp32 multiply) and running[p] = (fresh[p] > d || isnan(fresh[p]) || isnan(d)) ? fresh[p] : d -- the larger of the
+ * decayed old value and the fresh one, where a NaN of `fresh` is kept and a NaN (or the 0 * inf of decay = 0) left in `running` is
+ * replaced by `fresh`.  Then `bits` becomes exactly what mipnerf_occupancy_build(dims, running, threshold, dilate, bits, scratch) writes
+ * (the call launches those kernels after k_lattice_decay_max: 12 bytes per point, 16-byte loads and stores where both lattices are
+ * 16-byte aligned, a scalar tail).  `fresh` and `running` [nz, ny, nx] must not overlap; decay in [0, 1] (NaN refused); the other
+ * arguments as mipnerf_occupancy_build (`scratch` only when dilate > 0).  No atomics: two runs give the same bytes.  Does not allocate or
+ * synchronise (graph-capturable).
  * mipnerf_ray_occupancy: live [num_rays] bytes (1 / 0).  Per ray the coarse level's deterministic fence posts t_0 .. t_N (those of
  * mipnerf_sample_along_rays with t_rand = NULL: near + (far - near) * linspace(0, 1, N + 1)[i], or linear in disparity); frustum i has
  * the end points p0 = o + t_i d and p1 = o + t_{i+1} d, the half-width rho = cone_scale * radii * t_{i+1}, per axis the bounding
@@ -472,6 +480,8 @@ int mipnerf_uncontract_vertices(int64_t num_vertices, float far_radius, const fl
 int64_t mipnerf_occupancy_words(int32_t nx, int32_t ny, int32_t nz);
 int mipnerf_occupancy_build(const int32_t* dims_host, const float* grid, float threshold, int32_t dilate, uint32_t* bits,
                             uint32_t* scratch, void* stream);
+int mipnerf_occupancy_refresh(const int32_t* dims_host, const float* fresh, float* running, float decay, float threshold, int32_t dilate,
+                              uint32_t* bits, uint32_t* scratch, void* stream);
 int mipnerf_ray_occupancy(const int32_t* dims_host, const float* lo_host, const float* hi_host, const uint32_t* bits, int64_t num_rays,
                           int32_t num_samples, const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale,
                           uint8_t* live, void* stream);

@@ -96,6 +96,7 @@ SIGNATURES = {
     "mipnerf_isosurface_emit": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _F, _P, _SZ, _P, _P, _P, _P, _P]),
     "mipnerf_occupancy_words": (_I64, [_I32, _I32, _I32]),
     "mipnerf_occupancy_build": (C.c_int, [C.POINTER(_I32), _P, _F, _I32, _P, _P, _P]),
+    "mipnerf_occupancy_refresh": (C.c_int, [C.POINTER(_I32), _P, _P, _F, _F, _I32, _P, _P, _P]),
     "mipnerf_ray_occupancy": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _I64, _I32, C.POINTER(RaysPtrs), _I32, _I32, _F,
                                         _P, _P]),
     "mipnerf_ray_span": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _I64, _I32, C.POINTER(RaysPtrs), _I32, _I32, _F,

@@ -43,6 +43,41 @@ SCENE360_DATASETS = ("llff", "realdata360")
 SCENE360_PRESET = {'nerf.unbounded': True, 'train.white_bkgd': False, 'val.white_bkgd': False, 'exp_name': 'scene360'}
 
 
+# Span training (train_occupancy.TrainOccupancy): not reference keys, so they stay out of DEFAULTS (which is the reference's lego.yaml)
+# and are read with `train_occupancy_settings`.  `decay` and `interval` are instant-ngp's choices, not measurements of this project;
+# `threshold` is the rendering default of `--cull` (a foggy field needs a higher one).
+TRAIN_OCCUPANCY_DEFAULTS = {
+    'train.occupancy.enabled': False, 'train.occupancy.grid': 128, 'train.occupancy.threshold': 0.01, 'train.occupancy.dilate': 1,
+    'train.occupancy.decay': 0.95, 'train.occupancy.interval': 16, 'train.occupancy.bound': None, 'train.occupancy.far_radius': None,
+    'train.occupancy.span_samples': None,
+}
+
+
+def train_occupancy_settings(config):
+    """The `train.occupancy.*` keys of a configuration without the prefix, TRAIN_OCCUPANCY_DEFAULTS where a key is absent; a grid below
+    4 points per axis, an interval below 1 step and a decay outside [0, 1] are refused."""
+    n = len('train.occupancy.')
+    s = {k[n:]: config.get(k, v) for k, v in TRAIN_OCCUPANCY_DEFAULTS.items()}
+    unknown = sorted(k for k in config if str(k).startswith('train.occupancy.') and k not in TRAIN_OCCUPANCY_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown key(s) {unknown}; train.occupancy has {sorted(TRAIN_OCCUPANCY_DEFAULTS)}")
+    s['enabled'] = bool(s['enabled'])
+    s['grid'], s['dilate'], s['interval'] = int(s['grid']), int(s['dilate']), int(s['interval'])
+    s['threshold'], s['decay'] = float(s['threshold']), float(s['decay'])
+    for k in ('bound', 'far_radius'):
+        s[k] = None if s[k] is None else float(s[k])
+    s['span_samples'] = None if s['span_samples'] is None else int(s['span_samples'])
+    if s['grid'] < 4:
+        raise ValueError(f"train.occupancy.grid must be at least 4 points per axis (got {s['grid']})")
+    if s['interval'] < 1:
+        raise ValueError(f"train.occupancy.interval must be at least 1 step (got {s['interval']})")
+    if not 0.0 <= s['decay'] <= 1.0:
+        raise ValueError(f"train.occupancy.decay must be in [0, 1] (got {s['decay']})")
+    if s['dilate'] < 0:
+        raise ValueError(f"train.occupancy.dilate must be >= 0 (got {s['dilate']})")
+    return s
+
+
 def parse_value(v):
     """One leaf: a string through ast.literal_eval when it parses, a list as a tuple."""
     if isinstance(v, str):

@@ -1063,6 +1063,23 @@ int mipnerf_occupancy_build(const int32_t* dims, const float* grid, float thresh
     return MIPNERF_OK;
 }
 
+int mipnerf_occupancy_refresh(const int32_t* dims, const float* fresh, float* running, float decay, float threshold, int32_t dilate,
+                              uint32_t* bits, uint32_t* scratch, void* stream) {
+    const float unit_lo[3] = {0.f, 0.f, 0.f}, unit_hi[3] = {1.f, 1.f, 1.f};
+    if (int rc = lattice_check("occupancy_refresh", dims, unit_lo, unit_hi)) return rc;
+    if (!fresh || !running || !bits) return fail(MIPNERF_E_INVALID, "occupancy_refresh: null argument");
+    if (!(decay >= 0.0f && decay <= 1.0f)) return fail(MIPNERF_E_INVALID, "occupancy_refresh: decay must be in [0, 1] (got %g)", (double)decay);
+    if (std::isnan(threshold)) return fail(MIPNERF_E_INVALID, "occupancy_refresh: the threshold is NaN");
+    if (dilate < 0) return fail(MIPNERF_E_INVALID, "occupancy_refresh: dilate must be >= 0 (got %d)", dilate);
+    if (dilate > 0 && !scratch) return fail(MIPNERF_E_INVALID, "occupancy_refresh: dilate > 0 needs the scratch words");
+    if (dilate > 0 && scratch == bits) return fail(MIPNERF_E_INVALID, "occupancy_refresh: bits and scratch must not be the same buffer");
+    const size_t bytes = sizeof(float) * (size_t)dims[0] * dims[1] * dims[2];
+    const uintptr_t f0 = (uintptr_t)fresh, r0 = (uintptr_t)running;
+    if (f0 < r0 + bytes && r0 < f0 + bytes) return fail(MIPNERF_E_INVALID, "occupancy_refresh: fresh and running must not overlap");
+    HIP_TRY(mip::launch_occupancy_refresh(dims, fresh, running, decay, threshold, dilate, bits, scratch, S(stream)));
+    return MIPNERF_OK;
+}
+
 // what the four ray calls check before anything is launched; > 0: a return code, 0: launch, -1: zero rays, nothing to do
 static int ray_occupancy_check(const char* name, const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B,
                                int32_t N, const mipnerf_rays* rays, float cone_scale, const uint8_t* live) {

@@ -274,6 +274,9 @@ hipError_t launch_iso_emit(const int dims[3], const float lo[3], const float hi[
 // bits / scratch: (ny - 1) * (nz - 1) * ceil((nx - 1) / 32) words each; scratch is touched only when dilate > 0
 hipError_t launch_occupancy_build(const int dims[3], const float* f, float thr, int dilate, unsigned* bits, unsigned* scratch,
                                   hipStream_t st);
+// running = max(decay * running, fresh) per lattice point (a NaN of fresh is kept, one of decay * running replaced), then the build of it
+hipError_t launch_occupancy_refresh(const int dims[3], const float* fresh, float* running, float decay, float thr, int dilate,
+                                    unsigned* bits, unsigned* scratch, hipStream_t st);
 hipError_t launch_ray_occupancy(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
                                 const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
                                 int disparity, int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st);

@@ -2,6 +2,8 @@
 //   k_occ_raw / k_occ_dilate_*   occupancy bits of any fp32 lattice [nz, ny, nx]: one lane per cell, the wave's __ballot is two packed
 //                                words; dilation as three separable passes on the packed words (shifts and ORs along x, word ORs along
 //                                y and z);
+//   k_lattice_decay_max          the lattice a training run keeps: running = max(decay * running, fresh) per point, 16-byte loads and
+//                                stores, before the same bit passes;
 //   k_ray_occupancy              one wavefront per ray: lanes take the coarse level's frusta lane, lane + 64, ..., test the cell range of
 //                                each frustum's bounding box with word masks, the wave reduces with a ballot;
 //   k_ray_span                   the same wave and the same per-frustum test: the smallest and the largest hitting frustum of a ray
@@ -128,6 +130,47 @@ hipError_t launch_occupancy_build(const int dims[3], const float* f, float thr, 
         hipLaunchKernelGGL(k_occ_dilate_axis, grid, block, 0, st, g, 2, dilate, scratch, bits);
     }
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// a lattice that follows a field while it trains: running = max(decay * running, fresh), then the bits of it
+// ------------------------------------------------------------------------------------------
+// d = decay * r (one fp32 multiply); the new value is f where f > d or either is NaN, otherwise d: a NaN in `fresh` is kept, a NaN (or the
+// 0 * inf of decay = 0) left in `running` is replaced
+__device__ __forceinline__ float occ_decay_max(float f, float r, float decay) {
+    const float d = decay * r;
+    return (f > d || f != f || d != d) ? f : d;
+}
+
+// Elementwise, 12 B per point (two loads, one store).  Thread q takes points 4q .. 4q + 3 as one 16-byte load of each lattice and one
+// 16-byte store (the launcher chooses vec4 = n / 4 when both lattices are 16-byte aligned, otherwise vec4 = 0); the n - 4 * vec4
+// points of the tail go one per thread to the threads after them.
+__global__ void __launch_bounds__(256)
+k_lattice_decay_max(int64_t n, int64_t vec4, const float* __restrict__ fresh, float* __restrict__ running, float decay) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < vec4) {
+        const float4 f = reinterpret_cast<const float4*>(fresh)[q];
+        float4 r = reinterpret_cast<const float4*>(running)[q];
+        r.x = occ_decay_max(f.x, r.x, decay);
+        r.y = occ_decay_max(f.y, r.y, decay);
+        r.z = occ_decay_max(f.z, r.z, decay);
+        r.w = occ_decay_max(f.w, r.w, decay);
+        reinterpret_cast<float4*>(running)[q] = r;
+        return;
+    }
+    const int64_t p = 4 * vec4 + (q - vec4);
+    if (p < n) running[p] = occ_decay_max(fresh[p], running[p], decay);
+}
+
+hipError_t launch_occupancy_refresh(const int dims[3], const float* fresh, float* running, float decay, float thr, int dilate,
+                                    unsigned* bits, unsigned* scratch, hipStream_t st) {
+    const int64_t n = (int64_t)dims[0] * dims[1] * dims[2];
+    const bool aligned = (((uintptr_t)fresh | (uintptr_t)running) & 15) == 0;
+    const int64_t vec4 = aligned ? n / 4 : 0;
+    const int64_t threads = vec4 + (n - 4 * vec4);
+    hipLaunchKernelGGL(k_lattice_decay_max, dim3(occ_grid_for(threads, 256)), dim3(256), 0, st, n, vec4, fresh, running, decay);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return launch_occupancy_build(dims, running, thr, dilate, bits, scratch, st);
 }
 
 // ------------------------------------------------------------------------------------------

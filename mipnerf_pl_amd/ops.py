@@ -705,7 +705,10 @@ class Occupancy:
     [nz - 1, ny - 1, ceil((nx - 1) / 32)], cell i of an x row is bit i & 31 of word i >> 5, padding bits are 0; `dims` =
     (nx, ny, nz) lattice POINTS, `lo` / `hi` the box in (x, y, z) order, h = (hi - lo) / float(n - 1).  `space`: None -- the box lies in
     world coordinates (the bounded model) -- or 'contracted' -- in the contracted coordinates of the unbounded-scene model;
-    `ray_occupancy` / `ray_span` / `model.CulledFrame` dispatch on it."""
+    `ray_occupancy` / `ray_span` / `model.CulledFrame` dispatch on it.  Attributes `threshold` / `dilate`: what the bits were built with
+    (None when unknown; `occupancy_grid` sets them); `occupancy_refresh` rebuilds the bits with these."""
+    threshold = None
+    dilate = None
 
     def __init__(self, bits, dims, lo, hi, space=None):
         if space not in (None, "contracted"):
@@ -744,7 +747,36 @@ def occupancy_grid(lattice, threshold, lo, hi, dilate=1):
         scratch = torch.empty(shape, dtype=torch.uint32, device=g.device) if dilate > 0 else None
         L.check(L.lib().mipnerf_occupancy_build(cdims, _ptr(g), float(threshold), dilate, _ptr(bits), _ptr(scratch), _stream()),
                 "occupancy_build")
-    return Occupancy(bits, dims, [float(v) for v in clo], [float(v) for v in chi])
+    occ = Occupancy(bits, dims, [float(v) for v in clo], [float(v) for v in chi])
+    occ.threshold, occ.dilate = float(threshold), dilate
+    return occ
+
+
+def occupancy_refresh(occ, fresh, running, decay, scratch=None):
+    """The grid of a field that is still training (include/mipnerf_hip.h, mipnerf_occupancy_refresh), IN PLACE: `running` (fp32 device
+    lattice [nz, ny, nx] of `occ.dims`) becomes max(decay * running, fresh) per point -- a NaN of `fresh` is kept, a NaN of decay * running
+    replaced by `fresh` --, then `occ.bits` becomes what `occupancy_grid(running, occ.threshold, ..., dilate=occ.dilate)` holds.  The bits
+    tensor keeps its storage (a captured graph that reads it sees the new grid at its next replay).  `scratch`: uint32 words of the shape of
+    `occ.bits`, needed when occ.dilate > 0 (allocated when None, which a graph capture must avoid).  Returns `occ`."""
+    if occ.threshold is None or occ.dilate is None:
+        raise ValueError("occupancy_refresh: the Occupancy does not say which threshold and dilate its bits were built with "
+                         "(set occ.threshold and occ.dilate)")
+    nx, ny, nz = occ.dims
+    for name, t in (("fresh", fresh), ("running", running)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (nz, ny, nx)):
+            raise ValueError(f"occupancy_refresh: {name} must be a contiguous fp32 device lattice [nz, ny, nx] = {(nz, ny, nx)}")
+    bits = occ.bits
+    if not (bits.dtype == torch.uint32 and bits.is_contiguous() and tuple(bits.shape) == (nz - 1, ny - 1, (nx - 1 + 31) // 32)):
+        raise ValueError("occupancy_refresh: occ.bits does not have the words of occ.dims")
+    _, cdims, _, _ = _lattice_args("occupancy_refresh", occ.dims, occ.lo, occ.hi)
+    with torch.cuda.device(bits.device):
+        if occ.dilate > 0 and scratch is None:
+            scratch = torch.empty_like(bits)
+        if scratch is not None and (scratch.dtype != torch.uint32 or scratch.numel() < bits.numel() or not scratch.is_contiguous()):
+            raise ValueError("occupancy_refresh: scratch holds as many uint32 words as occ.bits")
+        L.check(L.lib().mipnerf_occupancy_refresh(cdims, _ptr(fresh), _ptr(running), float(decay), float(occ.threshold), int(occ.dilate), _ptr(bits),
+                                                  _ptr(scratch), _stream()), "occupancy_refresh")
+    return occ
 
 
 def field_occupancy(model_or_system, grid=128, lo=None, hi=None, threshold=0.01, dilate=1, cov_scale=1.0, precision=None, space=None,

@@ -16,6 +16,12 @@ monitor='val/psnr', mode='max', save_top_k=2)` of Lightning 1.5 do for `MipNeRFS
 * out_dir/logs/<exp_name>/version_<k>/: metrics.csv (Lightning's CSVLogger columns), hparams.yaml, val images as PNGs;
   out_dir/ckpt/<exp_name>/: last.ckpt and the best two `epoch={e}-step={s}.ckpt` by val/psnr, with Lightning 1.5's checkpoint keys plus
   `mipnerf_trainer` (position in the epoch, RNG states, top-k record) for an exact resume (`checkpoint.resume_path`).
+* `train.occupancy.enabled True` (off by default; `config.TRAIN_OCCUPANCY_DEFAULTS`): span training.  A `train_occupancy.TrainOccupancy`
+  grid is refreshed from the current field before every step s with s % `train.occupancy.interval` == 0 (outside the graph, same
+  stream), and every step -- the captured one through `GraphedTrainStep(occupancy=...)`, the eager ones through `Trainer._tighten` --
+  samples each ray on its occupied span [near', far'] of `ops.ray_span` instead of [near, far]; a ray that touches nothing keeps
+  [near, far].  metrics.csv gains `train/live_share` and `train/span_share`, the checkpoint's `mipnerf_trainer` entry gains `occupancy`
+  (the running lattice and its settings) and a resumed run continues exactly.  Validation frames stay un-culled.
 * num_gpus > 1: the command starts one child process per rank (nccl when every rank has its own device, gloo otherwise); rank 0 alone
   logs and writes checkpoints.
 
@@ -198,7 +204,8 @@ class CSVLog:
     """Lightning's CSVLogger layout: <save_dir>/<name>/version_<k>/{metrics.csv, hparams.yaml}; images go to .../images/."""
     COLUMNS = ("step", "lr", "train/loss", "train/psnr", "val/loss", "val/psnr")
 
-    def __init__(self, save_dir, name, hparams):
+    def __init__(self, save_dir, name, hparams, extra_columns=()):
+        self.COLUMNS = tuple(self.COLUMNS) + tuple(extra_columns)
         root = os.path.join(save_dir, name)
         os.makedirs(root, exist_ok=True)
         versions = [int(d.split("_")[1]) for d in os.listdir(root) if d.startswith("version_") and d.split("_")[1].isdigit()]
@@ -246,6 +253,8 @@ def read_metrics(path):
 # the loop
 # ---------------------------------------------------------------------------------------------------------------------
 class Trainer:
+    SPAN_COLUMNS = ("train/live_share", "train/span_share")     # logged only with train.occupancy.enabled
+
     def __init__(self, hparams, precision="bf16", use_graph=True, log_every_n_steps=50, rank=0, world=1, device=None, verbose=True):
         from .system import MipNeRFSystem
         self.hp = hp = dict(hparams)
@@ -265,6 +274,11 @@ class Trainer:
         self.global_step, self.epoch, self.batch = 0, 0, 0
         self.topk = TopK(2)
         self._resume_ckpt = None
+        self.occ, self._span = None, None
+        if cfg.train_occupancy_settings(hp)["enabled"]:
+            from .train_occupancy import TrainOccupancy, check_spaces
+            self.occ = TrainOccupancy.for_system(system, hp, self.dev)
+            check_spaces(system.mip_nerf, self.occ.occupancy, "train.occupancy")
         if hp.get("checkpoint.resume_path"):
             self._resume_ckpt = torch.load(hp["checkpoint.resume_path"], map_location="cpu", weights_only=False)
             system.load_state_dict(self._resume_ckpt["state_dict"], strict=True)
@@ -286,7 +300,8 @@ class Trainer:
         self.logger = None
         if self.rank == 0:
             os.makedirs(self.ckpt_dir, exist_ok=True)
-            self.logger = CSVLog(os.path.join(hp["out_dir"], "logs"), hp["exp_name"], hp)
+            self.logger = CSVLog(os.path.join(hp["out_dir"], "logs"), hp["exp_name"], hp,
+                                 extra_columns=self.SPAN_COLUMNS if self.occ is not None else ())
 
     # -- set-up ------------------------------------------------------------------------------------------------------
     def _make_graph_step(self):
@@ -302,7 +317,8 @@ class Trainer:
         def batch_source():
             ops.gather_train_batch(self.order, d["offsets"], d["cameras"], d["pixels"], opt._dev_step, self.epoch_base,
                                    step.rays, step.gt)
-        step = GraphedTrainStep(self.system, opt, self.B, self.dev, use_graph=True, batch_source=batch_source)
+        occ = {} if self.occ is None else dict(occupancy=self.occ.occupancy, span_samples=self.occ.span_samples)
+        step = GraphedTrainStep(self.system, opt, self.B, self.dev, use_graph=True, batch_source=batch_source, **occ)
         self.gstep = step
 
     def _capture(self):
@@ -320,6 +336,8 @@ class Trainer:
         if own is not None:
             self.global_step, self.epoch, self.batch = int(own["global_step"]), int(own["epoch"]), int(own["batch"])
             self.topk.load_state_dict(own["topk"])
+            if self.occ is not None and own.get("occupancy") is not None:
+                self.occ.load_state_dict(own["occupancy"])
             rng = own["rng"]
             torch.set_rng_state(rng["torch"])
             torch.cuda.set_rng_state(rng["cuda"], self.dev)
@@ -336,11 +354,34 @@ class Trainer:
         self.sched._last_lr = list(lrs)
 
     # -- one step -----------------------------------------------------------------------------------------------------
+    def _tighten(self, batch):
+        """(rays, rgbs) with every ray's near / far replaced by its occupied span [near', far'] of `ops.ray_span` on the run's grid --
+        what the captured step does in its static buffers, for the eager routes.  Keeps (live, first, last) for the log."""
+        from . import ops
+        rays, rgbs = batch
+        m = self.system.mip_nerf
+        self._span_n = int(self.occ.span_samples or m.num_samples)
+        live, first, last, near, far = ops.ray_span(self.occ.occupancy, rays, self._span_n, disparity=m.disparity)
+        self._span = (live, first, last)
+        return rays._replace(near=near, far=far), rgbs
+
+    def _span_stats(self):
+        """(live share, span share) of the last step's batch, from the captured step's static buffers or the last `_tighten`."""
+        if self._span is None:
+            return self.gstep.span_stats()
+        live, first, last = self._span
+        live = live.bool()
+        n = int(live.sum())
+        share = float((last[live] - first[live] + 1).double().mean()) / self._span_n if n else float("nan")
+        return n / float(max(live.numel(), 1)), share
+
     def _eager_step(self, b, bs):
         """One step off the graph: the epoch's short last batch on the graph route, every batch otherwise.  Returns (loss, psnr)."""
         system, opt = self.system, self.opt
         ids = self.order[b * self.B:b * self.B + bs]
         batch = system.train_dataset.rays_at(ids)
+        if self.occ is not None:
+            batch = self._tighten(batch)
         opt.zero_grad()
         if self.graph_route:
             loss = system.training_step_native(batch, b)
@@ -368,6 +409,7 @@ class Trainer:
             if self.gstep.use_graph and self.gstep._graphs is None:
                 self._capture()
             s = self.gstep()
+            self._span = None           # the spans of this step are in the captured step's buffers
             return s[0], s[5]
         return self._eager_step(b, bs)
 
@@ -409,13 +451,14 @@ class Trainer:
     def checkpoint(self):
         """Lightning 1.5's checkpoint dict, plus the trainer's own position / RNG states / top-k record."""
         sched = self.sched.state_dict()
+        occ = {} if self.occ is None else {"occupancy": self.occ.state_dict()}
         return {"epoch": self.epoch, "global_step": self.global_step, "pytorch-lightning_version": PL_VERSION,
                 "state_dict": _cpu(self.system.state_dict()), "callbacks": {},
                 "optimizer_states": [_cpu(self.opt.state_dict())], "lr_schedulers": [_cpu(sched)],
                 "hparams_name": "hparams", "hyper_parameters": dict(self.system.hparams),
                 TRAINER_KEY: {"global_step": self.global_step, "epoch": self.epoch, "batch": self.batch, "topk": self.topk.state_dict(),
                               "rng": {"torch": torch.get_rng_state(), "cuda": torch.cuda.get_rng_state(self.dev),
-                                      "numpy": np.random.get_state(), "python": random.getstate()}}}
+                                      "numpy": np.random.get_state(), "python": random.getstate()}, **occ}}
 
     def _save(self, val_psnr):
         name, drop = self.topk.update(val_psnr, self.epoch, self.global_step - 1)
@@ -453,6 +496,8 @@ class Trainer:
             for b in range(self.batch, self.spe):
                 if self.global_step >= stop:
                     break
+                if self.occ is not None and (self.occ.refresh_due(self.global_step) or self.occ.refreshes == 0):
+                    self.occ.refresh(self.system)       # from the field as it is BEFORE this step; the first one from the untrained field
                 loss, psnr = self._step(b)
                 self.sched.step()
                 self.global_step += 1
@@ -462,6 +507,8 @@ class Trainer:
                 if self.global_step % self.log_every == 0 or self.global_step >= max_steps:
                     lr = self.opt.last_lr() if self.graph_route else self.opt.param_groups[0]["lr"]
                     row = {"lr": lr, "train/loss": float(loss), "train/psnr": float(psnr)}
+                    if self.occ is not None:
+                        row.update(zip(self.SPAN_COLUMNS, self._span_stats()))
                     self.logger.log(self.global_step - 1, row)
                     self._say(f"epoch {self.epoch} step {self.global_step}/{max_steps} loss {row['train/loss']:.5f} "
                               f"psnr {row['train/psnr']:.3f} lr {lr:.3g} ({(time.time() - t0) / max(self.global_step, 1) * 1e3:.2f} ms/step)")
@@ -481,16 +528,23 @@ class Trainer:
         return self
 
     def _check_replicas(self):
-        """Every rank's parameters and moments equal rank 0's (one broadcast at the end of training)."""
+        """Every rank's parameters and moments equal rank 0's (one broadcast at the end of training); with span training also a checksum
+        of the occupancy grid's words, which every rank refreshes from its own replica."""
         import torch.distributed as dist
         mine = torch.cat([self.system.mip_nerf.mlp._flat_param, self.opt.exp_avg, self.opt.exp_avg_sq])
         ref = mine.clone()
         dist.broadcast(ref, 0)
-        same = torch.tensor([int(torch.equal(mine, ref))], device=self.dev)
+        equal = torch.equal(mine, ref)
+        if self.occ is not None:
+            mine = self.occ.checksum().reshape(1)
+            ref = mine.clone()
+            dist.broadcast(ref, 0)
+            equal = equal and torch.equal(mine, ref)
+        same = torch.tensor([int(equal)], device=self.dev)
         dist.all_reduce(same, op=dist.ReduceOp.MIN)
         if not bool(same.item()):
             raise RuntimeError("[train] the replicas' parameters diverged")
-        self._say(f"replicas identical on {self.world} ranks")
+        self._say(f"replicas identical on {self.world} ranks" + (" (occupancy grid included)" if self.occ is not None else ""))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,11 @@ i.e. MipNeRFSystem.training_step + loss.backward() + optimizer.step() + schedule
 device memory.  With world_size > 1 the step is two graphs around one eager RCCL all-reduce of the flat gradient buffer
 (SUM; the 1/world mean is folded into the Adam kernel): graph A = draws + forward + backward, graph B = Adam + re-pack.
 
+With `occupancy` (an `ops.Occupancy`, e.g. the one `train_occupancy.TrainOccupancy` keeps fresh) the step trains every ray on its occupied
+span: right after the batch source, `ops.ray_span` (inside the graph; it reads the grid's words where they live, so a refresh between two
+replays is seen by the next one) writes `live`, `first`, `last`, `near_span`, `far_span`, and the step samples [near_span, far_span];
+`self.rays.near` / `.far` keep the gathered values.  A dead ray keeps [near, far] and is still trained.
+
 Inputs live in static buffers (`self.rays`, `self.gt`): write the next batch there (copy_ or device-side ray generation
 straight into them) and call the object, or give a `batch_source`: a callable issued first inside the step (inside the captured
 graph) that writes the batch itself, e.g. `ops.gather_train_batch` with the batch index read from the device (train.py).  Returns the static scalars tensor [6] = loss, mse_c, mse_f, distloss_c,
@@ -28,7 +33,8 @@ from .rays import Rays
 
 
 class GraphedTrainStep:
-    def __init__(self, system, optimizer, num_rays: int, device: torch.device, use_graph: bool = True, batch_source=None):
+    def __init__(self, system, optimizer, num_rays: int, device: torch.device, use_graph: bool = True, batch_source=None,
+                 occupancy=None, span_samples=None):
         from .optim import FlatAdam
         if not isinstance(optimizer, FlatAdam):
             raise TypeError("GraphedTrainStep needs the flat optimiser (system.fused_adam = True)")
@@ -70,6 +76,20 @@ class GraphedTrainStep:
         self.ws = self.ctx.scratch("train_step", need)
         mlp.gather_foreign_grads()
         self._rp = L.RaysPtrs(*[t.data_ptr() for t in self.rays])
+        self.occupancy = occupancy
+        if occupancy is not None:
+            from .train_occupancy import check_spaces
+            check_spaces(model, occupancy, "GraphedTrainStep")
+            self.span_samples = int(span_samples or model.num_samples)
+            if not 1 <= self.span_samples <= L.MAX_SAMPLES:
+                raise ValueError(f"GraphedTrainStep: span_samples must be in [1, {L.MAX_SAMPLES}] (got {self.span_samples})")
+            self.live = torch.zeros(self.B, dtype=torch.uint8, device=device)
+            self.first = torch.zeros(self.B, dtype=torch.int32, device=device)
+            self.last = torch.zeros(self.B, dtype=torch.int32, device=device)
+            self.near_span = torch.zeros(self.B, 1, device=device)
+            self.far_span = torch.zeros(self.B, 1, device=device)
+            # the step reads near' / far' where it read near / far
+            self._rp = L.RaysPtrs(*[t.data_ptr() for t in self.rays._replace(near=self.near_span, far=self.far_span)])
         ptrs = [p.data_ptr() for p in mlp.ordered_params()]
         self._params = (C.c_void_p * len(ptrs))(*ptrs)
 
@@ -78,6 +98,9 @@ class GraphedTrainStep:
         m, B, N = self.model, self.B, self.N
         if self.batch_source is not None:
             self.batch_source()
+        if self.occupancy is not None:
+            ops.ray_span(self.occupancy, self.rays, self.span_samples, disparity=m.disparity,
+                         out=(self.live, self.first, self.last, self.near_span, self.far_span))
         t_rand = u_rand = dz = None
         if self.randomized:
             draws = torch.rand(2, B, N + 1, device=self.dev)        # one launch for both draws
@@ -144,6 +167,14 @@ class GraphedTrainStep:
         if self.opt._dev_step is not None:
             self.opt._dev_step.fill_(int(st["step"]))
         L.check(L.lib().mipnerf_set_params(self.ctx.handle, self._params, ops._stream()), "mipnerf_set_params")
+
+    def span_stats(self):
+        """(live share, span share) of the last step's batch: the share of rays with an occupied frustum and the mean of
+        (last - first + 1) / span_samples over them (NaN when none is live).  A host read-back of the static buffers."""
+        live = self.live.bool()
+        n = int(live.sum())
+        share = float((self.last[live] - self.first[live] + 1).double().mean()) / self.span_samples if n else float("nan")
+        return n / float(self.B), share
 
     def allreduce_stats(self):
         """(mean ms, count) of the event pairs recorded around the gradient all-reduce since the last call (synchronises)."""
