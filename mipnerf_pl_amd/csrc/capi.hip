@@ -14,6 +14,7 @@
 #include "../../include/mipnerf_hip.h"
 #include "camera_models.hpp"
 #include "kernels.hpp"
+#include "lane_buckets.hpp"
 #include "mlp_variants_gen.hpp"
 #include "mlp_train_variants_gen.hpp"
 #include "mlp_f32r_variants_gen.hpp"
@@ -21,6 +22,8 @@
 #include "mlp_plan_gen.hpp"
 
 // binary tables of the training kernels (mlp_train_plan.TrainPlan.blob()), linked in through train_tables.c (.incbin)
+
+static_assert(MIPNERF_MAX_SAMPLES == mip::kPdfMaxBins, "the public sample-count limit is 64 lanes x kMaxSamplesPerLane (lane_buckets.hpp)");
 
 namespace {
 
@@ -1080,9 +1083,11 @@ int mipnerf_occupancy_refresh(const int32_t* dims, const float* fresh, float* ru
     return MIPNERF_OK;
 }
 
-// what the four ray calls check before anything is launched; > 0: a return code, 0: launch, -1: zero rays, nothing to do
+// what the four ray calls check before anything is launched, and the launch arguments they share; > 0: a return code, 0: launch,
+// -1: zero rays, nothing to do
 static int ray_occupancy_check(const char* name, const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B,
-                               int32_t N, const mipnerf_rays* rays, float cone_scale, const uint8_t* live) {
+                               int32_t N, const mipnerf_rays* rays, int32_t outside_occupied, float cone_scale, uint8_t* live,
+                               mip::RayClassify* out) {
     if (int rc = lattice_check(name, dims, lo, hi)) return rc;
     for (int a = 0; a < 3; ++a)
         if (!(hi[a] > lo[a])) return fail(MIPNERF_E_INVALID, "%s: the box needs hi > lo on every axis", name);
@@ -1092,42 +1097,59 @@ static int ray_occupancy_check(const char* name, const int32_t* dims, const floa
     if (B == 0) return -1;
     if (!bits || !rays || !rays->origins || !rays->directions || !rays->radii || !rays->near || !rays->far || !live)
         return fail(MIPNERF_E_INVALID, "%s: null argument", name);
+    static_assert(sizeof(int) == sizeof(int32_t), "dims / first / last are int32");
+    mip::RayClassify a{};             // occupancy of a world grid, no disparity, no span outputs: the callers set what differs
+    a.dims = dims; a.lo = lo; a.hi = hi; a.bits = bits;
+    a.B = B; a.N = N;
+    a.origins = rays->origins; a.dirs = rays->directions; a.radii = rays->radii; a.nearp = rays->near; a.farp = rays->far;
+    a.outside_occupied = outside_occupied != 0; a.cone_scale = cone_scale;
+    a.live = live;
+    *out = a;
     return 0;
 }
 
 int mipnerf_ray_occupancy(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
                           const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale, uint8_t* live,
                           void* stream) {
-    if (int rc = ray_occupancy_check("ray_occupancy", dims, lo, hi, bits, B, N, rays, cone_scale, live)) return rc < 0 ? MIPNERF_OK : rc;
-    HIP_TRY(mip::launch_ray_occupancy(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
-                                      disparity != 0, outside_occupied != 0, cone_scale, live, S(stream)));
+    mip::RayClassify a;
+    if (int rc = ray_occupancy_check("ray_occupancy", dims, lo, hi, bits, B, N, rays, outside_occupied, cone_scale, live, &a))
+        return rc < 0 ? MIPNERF_OK : rc;
+    a.disparity = disparity != 0;
+    HIP_TRY(mip::launch_ray_classify(a, S(stream)));
     return MIPNERF_OK;
 }
 
 int mipnerf_ray_span(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
                      const mipnerf_rays* rays, int32_t disparity, int32_t outside_occupied, float cone_scale, uint8_t* live,
                      int32_t* first, int32_t* last, float* near_out, float* far_out, void* stream) {
-    if (int rc = ray_occupancy_check("ray_span", dims, lo, hi, bits, B, N, rays, cone_scale, live)) return rc < 0 ? MIPNERF_OK : rc;
-    static_assert(sizeof(int) == sizeof(int32_t), "first / last are int32");
-    HIP_TRY(mip::launch_ray_span(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
-                                 disparity != 0, outside_occupied != 0, cone_scale, live, first, last, near_out, far_out, S(stream)));
+    mip::RayClassify a;
+    if (int rc = ray_occupancy_check("ray_span", dims, lo, hi, bits, B, N, rays, outside_occupied, cone_scale, live, &a))
+        return rc < 0 ? MIPNERF_OK : rc;
+    a.disparity = disparity != 0;
+    a.span = true; a.first = first; a.last = last; a.near_out = near_out; a.far_out = far_out;
+    HIP_TRY(mip::launch_ray_classify(a, S(stream)));
     return MIPNERF_OK;
 }
 
 int mipnerf_ray_occupancy_360(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
                               const mipnerf_rays* rays, int32_t outside_occupied, float cone_scale, uint8_t* live, void* stream) {
-    if (int rc = ray_occupancy_check("ray_occupancy_360", dims, lo, hi, bits, B, N, rays, cone_scale, live)) return rc < 0 ? MIPNERF_OK : rc;
-    HIP_TRY(mip::launch_ray_occupancy_360(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
-                                          outside_occupied != 0, cone_scale, live, S(stream)));
+    mip::RayClassify a;
+    if (int rc = ray_occupancy_check("ray_occupancy_360", dims, lo, hi, bits, B, N, rays, outside_occupied, cone_scale, live, &a))
+        return rc < 0 ? MIPNERF_OK : rc;
+    a.contracted = true;
+    HIP_TRY(mip::launch_ray_classify(a, S(stream)));
     return MIPNERF_OK;
 }
 
 int mipnerf_ray_span_360(const int32_t* dims, const float* lo, const float* hi, const uint32_t* bits, int64_t B, int32_t N,
                          const mipnerf_rays* rays, int32_t outside_occupied, float cone_scale, uint8_t* live, int32_t* first,
                          int32_t* last, float* near_out, float* far_out, void* stream) {
-    if (int rc = ray_occupancy_check("ray_span_360", dims, lo, hi, bits, B, N, rays, cone_scale, live)) return rc < 0 ? MIPNERF_OK : rc;
-    HIP_TRY(mip::launch_ray_span_360(dims, lo, hi, bits, B, N, rays->origins, rays->directions, rays->radii, rays->near, rays->far,
-                                     outside_occupied != 0, cone_scale, live, first, last, near_out, far_out, S(stream)));
+    mip::RayClassify a;
+    if (int rc = ray_occupancy_check("ray_span_360", dims, lo, hi, bits, B, N, rays, outside_occupied, cone_scale, live, &a))
+        return rc < 0 ? MIPNERF_OK : rc;
+    a.contracted = true;
+    a.span = true; a.first = first; a.last = last; a.near_out = near_out; a.far_out = far_out;
+    HIP_TRY(mip::launch_ray_classify(a, S(stream)));
     return MIPNERF_OK;
 }
 

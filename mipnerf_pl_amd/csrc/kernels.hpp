@@ -277,22 +277,25 @@ hipError_t launch_occupancy_build(const int dims[3], const float* f, float thr, 
 // running = max(decay * running, fresh) per lattice point (a NaN of fresh is kept, one of decay * running replaced), then the build of it
 hipError_t launch_occupancy_refresh(const int dims[3], const float* fresh, float* running, float decay, float thr, int dilate,
                                     unsigned* bits, unsigned* scratch, hipStream_t st);
-hipError_t launch_ray_occupancy(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                                const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                                int disparity, int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st);
-// live [B] as launch_ray_occupancy; first / last / near_out / far_out [B] may each be NULL (not written)
-hipError_t launch_ray_span(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                           const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                           int disparity, int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last,
-                           float* near_out, float* far_out, hipStream_t st);
-// the same two calls for a grid laid out in contracted coordinates (the unbounded-scene model: inverse-depth fence posts, no disparity flag)
-hipError_t launch_ray_occupancy_360(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                                    const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                                    int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st);
-hipError_t launch_ray_span_360(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                               const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                               int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last, float* near_out,
-                               float* far_out, hipStream_t st);
+// Ray classification against the bits: live [B] = does any coarse frustum of the ray touch an occupied cell; span: also the smallest and the
+// largest hitting frustum and their outer fence posts.  contracted: the grid is laid out in contracted coordinates (the unbounded-scene
+// model: inverse-depth fence posts, no disparity flag).  Both choices give the same `live`.
+struct RayClassify {
+    const int* dims;                // [3] lattice points per axis
+    const float *lo, *hi;           // [3] each
+    const unsigned* bits;
+    int64_t B;
+    int N;
+    const float *origins, *dirs, *radii, *nearp, *farp;
+    int disparity;                  // world grid only
+    int outside_occupied;
+    float cone_scale;
+    bool span, contracted;
+    unsigned char* live;
+    int *first, *last;              // span only; each may be NULL (not written)
+    float *near_out, *far_out;
+};
+hipError_t launch_ray_classify(const RayClassify& a, hipStream_t st);     // hipErrorInvalidValue: N > 1024
 int64_t compact_num_blocks(int64_t n);           // entries of block_sum
 // in / out: the 7 ray fields in the order of mipnerf_rays (an out entry may be NULL: that field is not gathered)
 hipError_t launch_compact_rays(int64_t n, const unsigned char* live, const float* const in[7], float* const out[7], int* out_index,

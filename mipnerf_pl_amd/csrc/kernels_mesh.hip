@@ -11,12 +11,11 @@
 
 #include "ipe.hpp"
 #include "kernels.hpp"
+#include "lane_buckets.hpp"
 #include "lattice.hpp"
 #include "raymath.hpp"
 
 namespace mip {
-
-static inline unsigned mesh_grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 // Two threads per lattice point, as k_integrated_pos_enc: no means or covariances go through memory.
 template <typename OutT, int L>
@@ -52,16 +51,16 @@ hipError_t launch_lattice_ipe(const int dims[3], const float lo[3], const float 
     for (int a = 0; a < 3; ++a) { g.lo[a] = lo[a]; g.hi[a] = hi[a]; }
     const int64_t threads = 2 * count;
     if (bf16)
-        hipLaunchKernelGGL((k_lattice_ipe<__bf16, 16>), dim3(mesh_grid_for(threads, 256)), dim3(256), 0, st, g, first, count, cov_scale,
+        hipLaunchKernelGGL((k_lattice_ipe<__bf16, 16>), dim3(grid_for(threads, 256)), dim3(256), 0, st, g, first, count, cov_scale,
                            min_deg, (__bf16*)enc);
     else
-        hipLaunchKernelGGL((k_lattice_ipe<float, 16>), dim3(mesh_grid_for(threads, 256)), dim3(256), 0, st, g, first, count, cov_scale,
+        hipLaunchKernelGGL((k_lattice_ipe<float, 16>), dim3(grid_for(threads, 256)), dim3(256), 0, st, g, first, count, cov_scale,
                            min_deg, (float*)enc);
     return hipGetLastError();
 }
 
 hipError_t launch_store_sigma(int64_t count, const float* rgb_sigma, float* sigma, hipStream_t st) {
-    hipLaunchKernelGGL(k_store_sigma, dim3(mesh_grid_for(count, 256)), dim3(256), 0, st, count, (const float4*)rgb_sigma, sigma);
+    hipLaunchKernelGGL(k_store_sigma, dim3(grid_for(count, 256)), dim3(256), 0, st, count, (const float4*)rgb_sigma, sigma);
     return hipGetLastError();
 }
 

@@ -18,11 +18,10 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "lane_buckets.hpp"
 #include "raymath360.hpp"
 
 namespace mip {
-
-static inline unsigned occ_grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
 // cells (nx - 1, ny - 1, nz - 1), words per x row of cells
 struct OccGrid {
@@ -122,9 +121,9 @@ hipError_t launch_occupancy_build(const int dims[3], const float* f, float thr, 
     const int64_t waves = (int64_t)g.cy * g.cz * ((g.wx + 1) / 2);
     const int64_t words = (int64_t)g.cy * g.cz * g.wx;
     unsigned* raw = dilate > 0 ? scratch : bits;
-    hipLaunchKernelGGL(k_occ_raw, dim3(occ_grid_for(waves, 4)), dim3(256), 0, st, g, dims[0], dims[1], f, thr, raw);
+    hipLaunchKernelGGL(k_occ_raw, dim3(grid_for(waves, 4)), dim3(256), 0, st, g, dims[0], dims[1], f, thr, raw);
     if (dilate > 0) {
-        const dim3 grid(occ_grid_for(words, 256)), block(256);
+        const dim3 grid(grid_for(words, 256)), block(256);
         hipLaunchKernelGGL(k_occ_dilate_x, grid, block, 0, st, g, dilate, scratch, bits);
         hipLaunchKernelGGL(k_occ_dilate_axis, grid, block, 0, st, g, 1, dilate, bits, scratch);
         hipLaunchKernelGGL(k_occ_dilate_axis, grid, block, 0, st, g, 2, dilate, scratch, bits);
@@ -168,7 +167,7 @@ hipError_t launch_occupancy_refresh(const int dims[3], const float* fresh, float
     const bool aligned = (((uintptr_t)fresh | (uintptr_t)running) & 15) == 0;
     const int64_t vec4 = aligned ? n / 4 : 0;
     const int64_t threads = vec4 + (n - 4 * vec4);
-    hipLaunchKernelGGL(k_lattice_decay_max, dim3(occ_grid_for(threads, 256)), dim3(256), 0, st, n, vec4, fresh, running, decay);
+    hipLaunchKernelGGL(k_lattice_decay_max, dim3(grid_for(threads, 256)), dim3(256), 0, st, n, vec4, fresh, running, decay);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     return launch_occupancy_build(dims, running, thr, dilate, bits, scratch, st);
 }
@@ -375,71 +374,27 @@ static OccBox occ_box(const int dims[3], const float lo[3], const float hi[3]) {
     return box;
 }
 
-static OccRayArgs occ_ray_args(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                               const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                               int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last, float* near_out,
-                               float* far_out) {
+// one launcher for the four kernels: a.span chooses the body, a.contracted the rule
+hipError_t launch_ray_classify(const RayClassify& a, hipStream_t st) {
     OccRayArgs g;
-    g.B = B; g.N = N;
-    g.box = occ_box(dims, lo, hi);
-    g.bits = bits;
-    g.origins = origins; g.dirs = dirs; g.radii = radii; g.nearp = nearp; g.farp = farp;
-    g.outside_occupied = outside_occupied; g.cone_scale = cone_scale;
-    g.live = live; g.first = first; g.last = last; g.near_out = near_out; g.far_out = far_out;
-    return g;
+    g.B = a.B; g.N = a.N;
+    g.box = occ_box(a.dims, a.lo, a.hi);
+    g.bits = a.bits;
+    g.origins = a.origins; g.dirs = a.dirs; g.radii = a.radii; g.nearp = a.nearp; g.farp = a.farp;
+    g.outside_occupied = a.outside_occupied; g.cone_scale = a.cone_scale;
+    g.live = a.live; g.first = a.first; g.last = a.last; g.near_out = a.near_out; g.far_out = a.far_out;
+    const dim3 grid(grid_for(g.B, kOccRaysPerBlock)), block(64 * kOccRaysPerBlock);
+    const bool ok = for_lane_bucket(a.N, [&](auto k) {
+        if (a.contracted) {
+            if (a.span) hipLaunchKernelGGL((k_ray_span_360<decltype(k)::value>), grid, block, 0, st, g);
+            else hipLaunchKernelGGL((k_ray_occupancy_360<decltype(k)::value>), grid, block, 0, st, g);
+        } else {
+            if (a.span) hipLaunchKernelGGL((k_ray_span<decltype(k)::value>), grid, block, 0, st, g, a.disparity);
+            else hipLaunchKernelGGL((k_ray_occupancy<decltype(k)::value>), grid, block, 0, st, g, a.disparity);
+        }
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
-
-// the K buckets of the per-ray kernels (kernels_ray.hip)
-#define MIP_OCC_BUCKETS(KERNEL, N, ...)                                                                      \
-    do {                                                                                                     \
-        const dim3 grid(occ_grid_for(g.B, kOccRaysPerBlock)), block(64 * kOccRaysPerBlock);                  \
-        const int K = ((N) + 63) / 64;                                                                       \
-        if (K <= 1) hipLaunchKernelGGL((KERNEL<1>), grid, block, 0, st, __VA_ARGS__);                        \
-        else if (K <= 2) hipLaunchKernelGGL((KERNEL<2>), grid, block, 0, st, __VA_ARGS__);                   \
-        else if (K <= 4) hipLaunchKernelGGL((KERNEL<4>), grid, block, 0, st, __VA_ARGS__);                   \
-        else if (K <= 8) hipLaunchKernelGGL((KERNEL<8>), grid, block, 0, st, __VA_ARGS__);                   \
-        else hipLaunchKernelGGL((KERNEL<16>), grid, block, 0, st, __VA_ARGS__);                              \
-    } while (0)
-
-hipError_t launch_ray_occupancy(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                                const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                                int disparity, int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st) {
-    const OccRayArgs g = occ_ray_args(dims, lo, hi, bits, B, N, origins, dirs, radii, nearp, farp, outside_occupied, cone_scale, live,
-                                      nullptr, nullptr, nullptr, nullptr);
-    MIP_OCC_BUCKETS(k_ray_occupancy, N, g, disparity);
-    return hipGetLastError();
-}
-
-hipError_t launch_ray_span(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                           const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                           int disparity, int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last,
-                           float* near_out, float* far_out, hipStream_t st) {
-    const OccRayArgs g = occ_ray_args(dims, lo, hi, bits, B, N, origins, dirs, radii, nearp, farp, outside_occupied, cone_scale, live,
-                                      first, last, near_out, far_out);
-    MIP_OCC_BUCKETS(k_ray_span, N, g, disparity);
-    return hipGetLastError();
-}
-
-// the same two for a grid in contracted coordinates (Occ360Rule)
-hipError_t launch_ray_occupancy_360(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                                    const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                                    int outside_occupied, float cone_scale, unsigned char* live, hipStream_t st) {
-    const OccRayArgs g = occ_ray_args(dims, lo, hi, bits, B, N, origins, dirs, radii, nearp, farp, outside_occupied, cone_scale, live,
-                                      nullptr, nullptr, nullptr, nullptr);
-    MIP_OCC_BUCKETS(k_ray_occupancy_360, N, g);
-    return hipGetLastError();
-}
-
-hipError_t launch_ray_span_360(const int dims[3], const float lo[3], const float hi[3], const unsigned* bits, int64_t B, int N,
-                               const float* origins, const float* dirs, const float* radii, const float* nearp, const float* farp,
-                               int outside_occupied, float cone_scale, unsigned char* live, int* first, int* last, float* near_out,
-                               float* far_out, hipStream_t st) {
-    const OccRayArgs g = occ_ray_args(dims, lo, hi, bits, B, N, origins, dirs, radii, nearp, farp, outside_occupied, cone_scale, live,
-                                      first, last, near_out, far_out);
-    MIP_OCC_BUCKETS(k_ray_span_360, N, g);
-    return hipGetLastError();
-}
-#undef MIP_OCC_BUCKETS
 
 // ------------------------------------------------------------------------------------------
 // compaction: exclusive scan of the live bytes, gather in order
@@ -617,7 +572,7 @@ hipError_t launch_scatter_frame(int64_t n, int64_t count, int num_levels, const 
         lv.c_rgb[l] = on ? c_rgb[l] : nullptr; lv.c_dist[l] = on ? c_dist[l] : nullptr; lv.c_acc[l] = on ? c_acc[l] : nullptr;
         lv.f_rgb[l] = on ? f_rgb[l] : nullptr; lv.f_dist[l] = on ? f_dist[l] : nullptr; lv.f_acc[l] = on ? f_acc[l] : nullptr;
     }
-    hipLaunchKernelGGL(k_scatter_frame, dim3(occ_grid_for(n, 256)), dim3(256), 0, st, n, count, index, live, nearp,
+    hipLaunchKernelGGL(k_scatter_frame, dim3(grid_for(n, 256)), dim3(256), 0, st, n, count, index, live, nearp,
                        white_bkgd ? 1.0f : 0.0f, lv);
     return hipGetLastError();
 }

@@ -10,6 +10,7 @@
 #include "camera_models.hpp"
 #include "ipe.hpp"
 #include "kernels.hpp"
+#include "lane_buckets.hpp"
 #include "raymath.hpp"
 #include "raywave.hpp"
 
@@ -206,8 +207,6 @@ k_composite_resample(int64_t B, int N, const float4* __restrict__ rgb_sigma, con
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-static inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
 hipError_t launch_sample_along_rays(int64_t B, int N, const float* nearp, const float* farp,
                                     const float* t_rand, int disparity, float* t_out, hipStream_t st) {
     const int64_t total = B * (int64_t)(N + 1);
@@ -266,79 +265,40 @@ hipError_t launch_volumetric_rendering(int64_t B, int N, const float* rgb_sigma,
                                        float* weights, hipStream_t st) {
     const dim3 grid(grid_for(B, 4)), block(256);
     const float4* c = reinterpret_cast<const float4*>(rgb_sigma);
-    const int K = (N + 63) / 64;
-#define MIP_VR(KK)                                                                                        \
-    hipLaunchKernelGGL((k_volumetric_rendering<KK>), grid, block, 0, st, B, N, c, t, dirs, white_bkgd,  \
-                       comp_rgb, distance, acc, weights)
-    switch (K) {
-        // the K buckets EVERY per-ray kernel uses (1, 2, 4, 8, 16 samples per lane): a ray's sums associate by K, so one set of buckets lets
-        // the fused launches (k_composite_resample, k_composite_train) reproduce the per-stage kernels bit for bit at every N <= 1024
-        case 1: MIP_VR(1); break;
-        case 2: MIP_VR(2); break;
-        case 3: case 4: MIP_VR(4); break;
-        case 5: case 6: case 7: case 8: MIP_VR(8); break;
-        case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: MIP_VR(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MIP_VR
-    return hipGetLastError();
+    const bool ok = for_lane_bucket(N, [&](auto k) {
+        hipLaunchKernelGGL((k_volumetric_rendering<decltype(k)::value>), grid, block, 0, st, B, N, c, t, dirs, white_bkgd, comp_rgb,
+                           distance, acc, weights);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_piecewise_constant_pdf(int64_t B, int N, const float* bins, const float* weights, int n_draws,
                                          const float* u_rand, bool blur, float padding, float* out,
                                          hipStream_t st) {
-    if (N > kPdfMaxBins || N < 1) return hipErrorInvalidValue;
     const dim3 grid(grid_for(B, kRaysPerBlock)), block(64 * kRaysPerBlock);
-    // s = 1/num_samples ; jitter range (s - eps32) evaluated in double like the Python reference
-    const double s = 1.0 / (double)n_draws;
-    const float u_step = (float)s;
-    const float u_jitter = (float)(s - (double)1.1920928955078125e-07f);
-    const int K = (N + 63) / 64;
-#define MIP_PDF(KK)                                                                                          \
-    do {                                                                                                     \
-        if (blur)                                                                                            \
-            hipLaunchKernelGGL((k_piecewise_constant_pdf<KK, true>), grid, block, 0, st, B, N, bins, weights, \
-                               n_draws, u_rand, padding, u_step, u_jitter, out);                            \
-        else                                                                                                 \
-            hipLaunchKernelGGL((k_piecewise_constant_pdf<KK, false>), grid, block, 0, st, B, N, bins, weights, \
-                               n_draws, u_rand, padding, u_step, u_jitter, out);                            \
-    } while (0)
-    switch (K) {
-        case 1: MIP_PDF(1); break;
-        case 2: MIP_PDF(2); break;
-        case 3: case 4: MIP_PDF(4); break;
-        case 5: case 6: case 7: case 8: MIP_PDF(8); break;
-        case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: MIP_PDF(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MIP_PDF
-    return hipGetLastError();
+    const DrawStep u = draw_step(n_draws);
+    const bool ok = for_lane_bucket(N, [&](auto k) {
+        if (blur)
+            hipLaunchKernelGGL((k_piecewise_constant_pdf<decltype(k)::value, true>), grid, block, 0, st, B, N, bins, weights, n_draws,
+                               u_rand, padding, u.u_step, u.u_jitter, out);
+        else
+            hipLaunchKernelGGL((k_piecewise_constant_pdf<decltype(k)::value, false>), grid, block, 0, st, B, N, bins, weights, n_draws,
+                               u_rand, padding, u.u_step, u.u_jitter, out);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_composite_resample(int64_t B, int N, const float* rgb_sigma, const float* t, const float* dirs, int white_bkgd,
                                      float* comp_rgb, float* distance, float* acc, float* weights, const float* bins,
                                      const float* u_rand, float padding, float* t_new, hipStream_t st) {
-    if (N > kPdfMaxBins || N < 1) return hipErrorInvalidValue;
     const dim3 grid(grid_for(B, kRaysPerBlock)), block(64 * kRaysPerBlock);
     const float4* c = reinterpret_cast<const float4*>(rgb_sigma);
-    const int n_draws = N + 1;
-    const double s = 1.0 / (double)n_draws;           // as launch_piecewise_constant_pdf
-    const float u_step = (float)s;
-    const float u_jitter = (float)(s - (double)1.1920928955078125e-07f);
-    const int K = (N + 63) / 64;
-#define MIP_CR(KK)                                                                                                       \
-    hipLaunchKernelGGL((k_composite_resample<KK>), grid, block, 0, st, B, N, c, t, dirs, white_bkgd, comp_rgb, distance, acc, \
-                       weights, bins, u_rand, padding, u_step, u_jitter, t_new)
-    switch (K) {      // the same K buckets as the stand-alone kernels use, so both routes give the same bits
-        case 1: MIP_CR(1); break;
-        case 2: MIP_CR(2); break;
-        case 3: case 4: MIP_CR(4); break;
-        case 5: case 6: case 7: case 8: MIP_CR(8); break;
-        case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: MIP_CR(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MIP_CR
-    return hipGetLastError();
+    const DrawStep u = draw_step(N + 1);
+    const bool ok = for_lane_bucket(N, [&](auto k) {
+        hipLaunchKernelGGL((k_composite_resample<decltype(k)::value>), grid, block, 0, st, B, N, c, t, dirs, white_bkgd, comp_rgb,
+                           distance, acc, weights, bins, u_rand, padding, u.u_step, u.u_jitter, t_new);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // pos_enc(viewdirs) and the coarse level's fence posts (sample_along_rays, t part) in ONE launch: both only read per-ray inputs

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "lane_buckets.hpp"
 #include "raymath.hpp"
 
 namespace mip {
@@ -94,19 +95,18 @@ k_cast_ipe_bwd(int64_t B, int N, int min_deg, int ndeg, int disable_integration,
 // One wavefront per ray; mirrors k_piecewise_constant_pdf<K, BLUR = true> (kernels_ray.hip) up to the CDF, then walks the
 // reference's autograd backwards: t'_j = b0 + (u_j - c0)/(c1 - c0) (b1 - b0) -> cdf -> cumsum -> pdf = v / sum v -> v = blur + pad ->
 // blur = (max(w_{i-1}, w_i) + max(w_i, w_{i+1})) / 2 with torch.maximum's tie rule (half each).
-constexpr int kMaxBins = 1024;     // N <= 1024 (MIPNERF_MAX_SAMPLES); LDS rows: 512 entries for K <= 8, 1024 for the K = 16 bucket
-template <int K> struct GradRow { static constexpr int kBins = K <= 8 ? 512 : kMaxBins; };
+// LDS rows as the forward's: PdfRow<K> (lane_buckets.hpp)
 template <int K>
 __global__ void __launch_bounds__(64)
 k_resample_bwd(int64_t B, int N, const float* __restrict__ bins, const float* __restrict__ weights,
                const float* __restrict__ u_rand, float padding, float u_step, float u_jitter,
                const float* __restrict__ d_t_new, float* __restrict__ d_weights) {
-    __shared__ float s_w[GradRow<K>::kBins + 2];
-    __shared__ float s_cdf[GradRow<K>::kBins + 2];
-    __shared__ float s_bins[GradRow<K>::kBins + 2];
-    __shared__ float s_g0[GradRow<K>::kBins + 2];     // gradient w.r.t. cdf[i] from the draws whose lower entry is i
-    __shared__ float s_g1[GradRow<K>::kBins + 2];     // ... w.r.t. cdf[i + 1] from the same draws
-    __shared__ float s_dv[GradRow<K>::kBins + 2];
+    __shared__ float s_w[PdfRow<K>::kBins + 2];
+    __shared__ float s_cdf[PdfRow<K>::kBins + 2];
+    __shared__ float s_bins[PdfRow<K>::kBins + 2];
+    __shared__ float s_g0[PdfRow<K>::kBins + 2];     // gradient w.r.t. cdf[i] from the draws whose lower entry is i
+    __shared__ float s_g1[PdfRow<K>::kBins + 2];     // ... w.r.t. cdf[i + 1] from the same draws
+    __shared__ float s_dv[PdfRow<K>::kBins + 2];
     const int lane = threadIdx.x;
     const int64_t b = blockIdx.x;
     const float* wb = weights + b * (int64_t)N;
@@ -262,30 +262,19 @@ hipError_t launch_cast_ipe_bwd(int64_t B, int N, int min_deg, int max_deg, int d
                                const float* origins, const float* dirs, const float* radii, const float* d_enc, float* d_t,
                                hipStream_t st) {
     const int64_t M = B * (int64_t)N;
-    hipLaunchKernelGGL(k_cast_ipe_bwd, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, B, N, min_deg, max_deg - min_deg,
+    hipLaunchKernelGGL(k_cast_ipe_bwd, dim3(grid_for(M, 256)), dim3(256), 0, st, B, N, min_deg, max_deg - min_deg,
                        disable_integration, t, origins, dirs, radii, d_enc, d_t);
     return hipGetLastError();
 }
 
 hipError_t launch_resample_bwd(int64_t B, int N, const float* bins, const float* weights, const float* u_rand, float padding,
                                const float* d_t_new, float* d_weights, hipStream_t st) {
-    if (N > kMaxBins || N < 1) return hipErrorInvalidValue;
-    const int n_draws = N + 1;
-    const double s = 1.0 / (double)n_draws;
-    const float u_step = (float)s, u_jitter = (float)(s - (double)1.1920928955078125e-07f);
-    const int K = (N + 63) / 64;
-#define MIP_RB(KK) hipLaunchKernelGGL((k_resample_bwd<KK>), dim3((unsigned)B), dim3(64), 0, st, B, N, bins, weights, u_rand, padding, \
-                                      u_step, u_jitter, d_t_new, d_weights)
-    switch (K) {
-        case 1: MIP_RB(1); break;
-        case 2: MIP_RB(2); break;
-        case 3: case 4: MIP_RB(4); break;
-        case 5: case 6: case 7: case 8: MIP_RB(8); break;
-        case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: MIP_RB(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MIP_RB
-    return hipGetLastError();
+    const DrawStep u = draw_step(N + 1);
+    const bool ok = for_lane_bucket(N, [&](auto k) {
+        hipLaunchKernelGGL((k_resample_bwd<decltype(k)::value>), dim3((unsigned)B), dim3(64), 0, st, B, N, bins, weights, u_rand, padding,
+                           u.u_step, u.u_jitter, d_t_new, d_weights);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace mip

@@ -6,6 +6,7 @@
 #include <math.h>
 
 #include "kernels.hpp"
+#include "lane_buckets.hpp"
 #include "raymath.hpp"
 #include "raywave.hpp"
 
@@ -230,41 +231,26 @@ k_composite_train(int64_t B, int N, const float4* __restrict__ rgb_sigma, const 
     }
 }
 
-static inline unsigned gridf(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
 hipError_t launch_composite_train(int64_t B, int N, const float* rgb_sigma, const float* t, const float* dirs, int white_bkgd,
                                   float* comp_rgb, float* distance, float* acc, float* weights, float* ray_loss, float g_const,
                                   float* d_w, const float* u_rand, float padding, float* t_new, hipStream_t st, const float* bins) {
-    if (N > kPdfMaxBins || N < 1) return hipErrorInvalidValue;
-    const dim3 grid(gridf(B, kRaysPerBlock)), block(64 * kRaysPerBlock);
+    const dim3 grid(grid_for(B, kRaysPerBlock)), block(64 * kRaysPerBlock);
     const float4* c = reinterpret_cast<const float4*>(rgb_sigma);
-    const int n_draws = N + 1;
-    const double s = 1.0 / (double)n_draws;           // as launch_piecewise_constant_pdf
-    const float u_step = (float)s;
-    const float u_jitter = (float)(s - (double)1.1920928955078125e-07f);
-    const int K = (N + 63) / 64;
-#define MIP_CT(KK)                                                                                                                   \
-    do {                                                                                                                             \
-        if (t_new) hipLaunchKernelGGL((k_composite_train<KK, true>), grid, block, 0, st, B, N, c, t, dirs, white_bkgd, comp_rgb, distance, \
-                                      acc, weights, ray_loss, g_const, d_w, u_rand, padding, u_step, u_jitter, t_new, bins);              \
-        else hipLaunchKernelGGL((k_composite_train<KK, false>), grid, block, 0, st, B, N, c, t, dirs, white_bkgd, comp_rgb, distance, acc, \
-                                weights, ray_loss, g_const, d_w, u_rand, padding, u_step, u_jitter, t_new, bins);                         \
-    } while (0)
-    switch (K) {      // the K buckets every stand-alone per-ray kernel uses (1, 2, 4, 8, 16), so the fused route gives the same bits at every N <= 1024
-        case 1: MIP_CT(1); break;
-        case 2: MIP_CT(2); break;
-        case 3: case 4: MIP_CT(4); break;
-        case 5: case 6: case 7: case 8: MIP_CT(8); break;
-        case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: MIP_CT(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MIP_CT
-    return hipGetLastError();
+    const DrawStep u = draw_step(N + 1);
+    const bool ok = for_lane_bucket(N, [&](auto k) {
+        if (t_new)
+            hipLaunchKernelGGL((k_composite_train<decltype(k)::value, true>), grid, block, 0, st, B, N, c, t, dirs, white_bkgd, comp_rgb,
+                               distance, acc, weights, ray_loss, g_const, d_w, u_rand, padding, u.u_step, u.u_jitter, t_new, bins);
+        else
+            hipLaunchKernelGGL((k_composite_train<decltype(k)::value, false>), grid, block, 0, st, B, N, c, t, dirs, white_bkgd, comp_rgb,
+                               distance, acc, weights, ray_loss, g_const, d_w, u_rand, padding, u.u_step, u.u_jitter, t_new, bins);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_activate(int64_t M, const float* raw, float rgb_padding, float density_bias, const float* dnoise,
                            float dnoise_scale, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(k_activate, dim3(gridf(M, 256)), dim3(256), 0, st, M, (const float4*)raw, rgb_padding,
+    hipLaunchKernelGGL(k_activate, dim3(grid_for(M, 256)), dim3(256), 0, st, M, (const float4*)raw, rgb_padding,
                        density_bias, dnoise, dnoise_scale, (float4*)out);
     return hipGetLastError();
 }
@@ -272,40 +258,22 @@ hipError_t launch_activate(int64_t M, const float* raw, float rgb_padding, float
 hipError_t launch_volumetric_rendering_bwd(int64_t B, int N, const float* rgb_sigma, const float* t, const float* dirs,
                                            int white_bkgd, const float* g_rgb, const float* g_dist, const float* g_acc,
                                            const float* g_w, float rgb_padding, float* d_raw, hipStream_t st, float* d_t) {
-    const dim3 grid(gridf(B, 4)), block(256);
-    const int K = (N + 63) / 64;
-#define MIP_VB(KK)                                                                                                  \
-    hipLaunchKernelGGL((k_volumetric_rendering_bwd<KK>), grid, block, 0, st, B, N, (const float4*)rgb_sigma, t, dirs, \
-                       white_bkgd, g_rgb, g_dist, g_acc, g_w, rgb_padding, (float4*)d_raw, d_t)
-    switch (K) {
-        case 1: MIP_VB(1); break;
-        case 2: MIP_VB(2); break;
-        case 3: case 4: MIP_VB(4); break;
-        case 5: case 6: case 7: case 8: MIP_VB(8); break;
-        case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: MIP_VB(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MIP_VB
-    return hipGetLastError();
+    const dim3 grid(grid_for(B, 4)), block(256);
+    const bool ok = for_lane_bucket(N, [&](auto k) {
+        hipLaunchKernelGGL((k_volumetric_rendering_bwd<decltype(k)::value>), grid, block, 0, st, B, N, (const float4*)rgb_sigma, t, dirs,
+                           white_bkgd, g_rgb, g_dist, g_acc, g_w, rgb_padding, (float4*)d_raw, d_t);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_distloss(int64_t B, int N, const float* weights, const float* t, float* ray_loss, const float* g_ray,
                            float g_const, float* d_w, hipStream_t st, float* d_t) {
-    const dim3 grid(gridf(B, 4)), block(256);
-    const int K = (N + 63) / 64;
-#define MIP_DL(KK) hipLaunchKernelGGL((k_distloss<KK>), grid, block, 0, st, B, N, weights, t, ray_loss, g_ray, g_const, d_w, d_t)
-    switch (K) {
-        case 1: MIP_DL(1); break;
-        case 2: MIP_DL(2); break;
-        case 3: case 4: MIP_DL(4); break;
-        case 5: case 6: case 7: case 8: MIP_DL(8); break;
-        case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: MIP_DL(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef MIP_DL
-    return hipGetLastError();
+    const dim3 grid(grid_for(B, 4)), block(256);
+    const bool ok = for_lane_bucket(N, [&](auto k) {
+        hipLaunchKernelGGL((k_distloss<decltype(k)::value>), grid, block, 0, st, B, N, weights, t, ray_loss, g_ray, g_const, d_w, d_t);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
-
 
 // ---- loss of nerf_system.py:99-111 and its gradient w.r.t. the rendered colours, one launch --------------------------
 //   mse_l = sum_b mask_b sum_c (rgb_l[b,c] - gt[b,c])^2 / sum_b mask_b       (mask = lossmult, or ones)

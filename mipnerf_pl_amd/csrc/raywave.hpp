@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "lane_buckets.hpp"
 #include "raymath.hpp"
 
 namespace mip {
@@ -147,11 +148,8 @@ __device__ __forceinline__ void composite_ray(bool active, int lane, int N, cons
 //   BLUR = true : weights are blur-pooled and `padding` added first (resample path)
 //   BLUR = false: weights used as given
 // ------------------------------------------------------------------------------------------
-constexpr int kPdfMaxBins = 1024;     // N <= 1024 = 64 lanes x 16 samples (MIPNERF_MAX_SAMPLES)
 constexpr int kRaysPerBlock = 4;
-// LDS row length of a kernel instantiated for K samples per lane: the K <= 8 buckets keep their 512-entry rows (24 KiB per block: six blocks per CU);
-// only the K = 16 bucket (512 < N <= 1024) pays for 1024-entry rows
-template <int K> struct PdfRow { static constexpr int kBins = K <= 8 ? 512 : kPdfMaxBins; };
+// (kPdfMaxBins and the LDS row length PdfRow<K> of a kernel instantiated for K samples per lane live in lane_buckets.hpp)
 
 // s_w / s_bins hold the ray's weights [N] and bins [N+1] (staged by the caller, block barrier done); every wave of the block
 // must call this (it contains block barriers); out_row = nullptr: no stores (a wave shadowing the last ray)

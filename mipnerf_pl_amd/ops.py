@@ -825,6 +825,19 @@ def _contracted_grid(occ, disparity, name):
     return contracted
 
 
+def _classify_rays(name, occ, rays, n, num_samples, disparity, outside_occupied, cone_scale, contracted, outs):
+    """the call `ray_occupancy` and `ray_span` share: mipnerf_<name> (or, for a contracted grid, mipnerf_<name>_360, which takes no disparity
+    flag) on n > 0 rays with the output tensors `outs`"""
+    import ctypes as C
+    _, cdims, clo, chi = _lattice_args(name, occ.dims, occ.lo, occ.hi)
+    fn = name + "_360" if contracted else name
+    flags = () if contracted else (int(bool(disparity)),)
+    with torch.cuda.device(occ.bits.device):
+        rp, keep = _rays_ptrs(rays, n, name)
+        L.check(getattr(L.lib(), "mipnerf_" + fn)(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), *flags,
+                                                  int(bool(outside_occupied)), float(cone_scale), *[_ptr(t) for t in outs], _stream()), fn)
+
+
 def ray_occupancy(occ, rays, num_samples, disparity=False, outside_occupied=True, cone_scale=1.0, out=None):
     """live uint8 [n]: 1 where some coarse frustum of the ray touches an occupied cell of `occ`.  Frustum i of the coarse level's
     deterministic fence posts t_0 .. t_N has the end points p0 = o + t_i d, p1 = o + t_{i+1} d, the half-width rho = cone_scale * radii *
@@ -834,7 +847,6 @@ def ray_occupancy(occ, rays, num_samples, disparity=False, outside_occupied=True
     A grid with `occ.space == 'contracted'` (the unbounded-scene model): the fence posts are the inverse-depth ones of `sample_t_360` and
     each frustum's image under `contract` is bounded by the closed form of include/mipnerf_hip.h (mipnerf_ray_occupancy_360);
     `disparity=True` is refused."""
-    import ctypes as C
     contracted = _contracted_grid(occ, disparity, "ray_occupancy")
     n = int(rays.origins.shape[0])
     dev = occ.bits.device
@@ -843,15 +855,7 @@ def ray_occupancy(occ, rays, num_samples, disparity=False, outside_occupied=True
         raise ValueError("ray_occupancy: out must be a contiguous uint8 tensor with one byte per ray")
     if n == 0:
         return live
-    _, cdims, clo, chi = _lattice_args("ray_occupancy", occ.dims, occ.lo, occ.hi)
-    with torch.cuda.device(dev):
-        rp, keep = _rays_ptrs(rays, n, "ray_occupancy")
-        if contracted:
-            L.check(L.lib().mipnerf_ray_occupancy_360(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp),
-                                                      int(bool(outside_occupied)), float(cone_scale), _ptr(live), _stream()), "ray_occupancy_360")
-        else:
-            L.check(L.lib().mipnerf_ray_occupancy(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(disparity)),
-                                                  int(bool(outside_occupied)), float(cone_scale), _ptr(live), _stream()), "ray_occupancy")
+    _classify_rays("ray_occupancy", occ, rays, n, num_samples, disparity, outside_occupied, cone_scale, contracted, (live,))
     return live
 
 
@@ -866,7 +870,6 @@ def ray_span(occ, rays, num_samples, disparity=False, outside_occupied=True, con
     out lies only in cells whose 8 lattice corners are at or below the threshold, after dilation.
     A grid with `occ.space == 'contracted'`: the rules of `ray_occupancy` for such a grid (mipnerf_ray_span_360); near' / far' are the fence
     posts of `sample_t_360`, bit for bit, and `disparity=True` is refused."""
-    import ctypes as C
     contracted = _contracted_grid(occ, disparity, "ray_span")
     n = int(rays.origins.shape[0])
     dev = occ.bits.device
@@ -880,15 +883,7 @@ def ray_span(occ, rays, num_samples, disparity=False, outside_occupied=True, con
             raise ValueError("ray_span: out holds contiguous device tensors with one element per ray: uint8, int32, int32, fp32, fp32")
     if n == 0:
         return tuple(out)
-    _, cdims, clo, chi = _lattice_args("ray_span", occ.dims, occ.lo, occ.hi)
-    with torch.cuda.device(dev):
-        rp, keep = _rays_ptrs(rays, n, "ray_span")
-        if contracted:
-            L.check(L.lib().mipnerf_ray_span_360(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(outside_occupied)),
-                                                 float(cone_scale), *[_ptr(t) for t in out], _stream()), "ray_span_360")
-        else:
-            L.check(L.lib().mipnerf_ray_span(cdims, clo, chi, _ptr(occ.bits), n, int(num_samples), C.byref(rp), int(bool(disparity)),
-                                             int(bool(outside_occupied)), float(cone_scale), *[_ptr(t) for t in out], _stream()), "ray_span")
+    _classify_rays("ray_span", occ, rays, n, num_samples, disparity, outside_occupied, cone_scale, contracted, out)
     return tuple(out)
 
 

@@ -498,22 +498,47 @@ def test_one_wave_per_simd_kernel_ring_replayed():
         assert chunk == ngroups * 16
 
 
+def _call_extents(src, name):
+    """(start, end) of every call `name(...)` in src, end at its matching parenthesis"""
+    out = []
+    for m in re.finditer(r"\b" + name + r"\(", src):
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"(": 1, ")": -1}.get(src[i], 0)
+            i += 1
+        out.append((m.start(), i))
+    return out
+
+
 def test_sample_count_limit_is_one_number_everywhere():
-    """num_samples <= 1024 = 64 lanes x 16 samples: the header, the ctypes layer, the LDS row constants and the samples-per-lane dispatch of
-    every per-ray kernel (buckets 1, 2, 4, 8, 16) say the same."""
+    """num_samples <= 1024 = 64 lanes x 16 samples: the header, the ctypes layer and the LDS row constant say the same, and every per-ray
+    kernel (a template on K, the samples a lane holds) is launched through the one samples-per-lane dispatcher of lane_buckets.hpp."""
     csrc = os.path.join(REPO, "mipnerf_pl_amd", "csrc")
     hdr = open(os.path.join(REPO, "include", "mipnerf_hip.h")).read()
-    assert int(re.search(r"#define MIPNERF_MAX_SAMPLES (\d+)", hdr).group(1)) == L.MAX_SAMPLES == 1024
-    assert "constexpr int kPdfMaxBins = 1024;" in open(os.path.join(csrc, "raywave.hpp")).read()
-    assert "constexpr int kMaxBins = 1024;" in open(os.path.join(csrc, "kernels_resample_grad.hip")).read()
-    n = 0
-    for f in ("kernels_ray.hip", "kernels_train.hip", "kernels_resample_grad.hip"):
-        src = open(os.path.join(csrc, f)).read()
-        for m in re.finditer(r"case 5: case 6: case 7: case 8: (MIP_\w+)\(8\); break;\s*\n\s*case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16: (MIP_\w+)\(16\); break;\s*\n\s*default: return hipErrorInvalidValue;", src):
-            assert m.group(1) == m.group(2)
-            n += 1
-        assert src.count("(8); break;") == src.count("(16); break;"), f          # no dispatch without the 16-samples-per-lane bucket
-    assert n == 7
+    rules = open(os.path.join(csrc, "lane_buckets.hpp")).read()
+    per_lane = int(re.search(r"constexpr int kMaxSamplesPerLane = (\d+);", rules).group(1))
+    assert int(re.search(r"#define MIPNERF_MAX_SAMPLES (\d+)", hdr).group(1)) == L.MAX_SAMPLES == 1024 == 64 * per_lane
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp"))}
+    assert "constexpr int kPdfMaxBins = 64 * kMaxSamplesPerLane;" in rules
+    assert sum(len(re.findall(r"\bkPdfMaxBins\s*=[^=]", s)) for s in sources.values()) == 1          # defined there and nowhere else
+    assert not any(re.search(r"\bkMaxBins\b", s) for s in sources.values())
+    assert re.search(r"static_assert\(MIPNERF_MAX_SAMPLES == mip::kPdfMaxBins\b", sources["capi.hip"])
+    launched = set()
+    for f in ("kernels_ray.hip", "kernels_train.hip", "kernels_resample_grad.hip", "kernels_occupancy.hip"):
+        src = sources[f]
+        assert "switch (K)" not in src and "case 16" not in src and not re.search(r"#\s*define\s+MIP_", src), f
+        per_ray = set(re.findall(r"template <int K[^>]*>\s*__global__[^;{]*?\b(k_\w+)\(", src))      # kernel templates whose first argument is K
+        inside = _call_extents(src, "for_lane_bucket")
+        for m in re.finditer(r"hipLaunchKernelGGL\(\(?\s*(k_\w+)", src):
+            if m.group(1) in per_ray:
+                assert any(a < m.start() < b for a, b in inside), (f, m.group(1))
+                assert re.match(r"<decltype\(k\)::value[,>]", src[m.end():]), (f, m.group(1))        # K is the dispatcher's constant
+                launched.add(m.group(1))
+        assert launched >= per_ray, (f, per_ray - launched)                                         # no per-ray kernel is left unlaunched
+    assert len(launched) == 11, sorted(launched)
+    # the sampler's draw step (the forward and its backward must draw the same u): one statement
+    jitter = r"u_jitter = [^\n]*1\.1920928955078125e-07f"
+    assert len(re.findall(jitter, rules)) == 1 == sum(len(re.findall(jitter, s)) for s in sources.values())
 
 
 def _type_list(params):
