@@ -111,11 +111,12 @@ def maxdiff(a, b):
 import torch.nn.functional as F  # noqa: E402
 
 
-def mlp_functional(p, samples_enc, viewdirs_enc, skip_index, pre=None):
+def mlp_functional(p, samples_enc, viewdirs_enc, skip_index, pre=None, post=None):
     """models/mip_nerf.py:75-111 through torch ops on a dict of state_dict-named tensors, in THEIR dtype (float64 leaves give the
     float64 reference and its autograd gradients).  viewdirs_enc=None is MLP.forward(x, None) (:99-110): colour and density heads
     both read the trunk, extra_layer / view_layers are unused.  `pre` (a list) receives every hidden layer's pre-activation, trunk
-    layers first, then the view layers."""
+    layers first, then the view layers.  `post` (a list) receives every hidden layer's activation and the bottleneck, in the order
+    they are computed: trunk layers, bottleneck, view layers."""
     def lin(name, x):
         return F.linear(x, p[name + ".weight"], p[name + ".bias"])
 
@@ -123,7 +124,10 @@ def mlp_functional(p, samples_enc, viewdirs_enc, skip_index, pre=None):
         h = lin(name, x)
         if pre is not None:
             pre.append(h)
-        return torch.relu(h)
+        h = torch.relu(h)
+        if post is not None:
+            post.append(h)
+        return h
     num_samples = samples_enc.shape[1]
     inputs = samples_enc
     x = inputs
@@ -134,6 +138,8 @@ def mlp_functional(p, samples_enc, viewdirs_enc, skip_index, pre=None):
     raw_density = lin("density_layer", x)
     if viewdirs_enc is not None:
         bottleneck = lin("extra_layer", x)
+        if post is not None:
+            post.append(bottleneck)
         vd = viewdirs_enc[:, None, :].expand(-1, num_samples, -1)
         x = torch.cat([bottleneck, vd], dim=-1)
         for i in range(sum(1 for k in p if k.startswith("view_layers.") and k.endswith(".weight"))):
@@ -163,13 +169,16 @@ def f32_boundary_rows(M):
     return sorted({0, M - 1} | {r for r in F32_BOUNDARY_ROWS if r < M})
 
 
-def mlp_grads(params, enc, venc, d_raw, skip_index, dtype, enc_grad=False, pre=None):
+def mlp_grads(params, enc, venc, d_raw, skip_index, dtype, enc_grad=False, pre=None, post=None):
     """raw and the autograd gradients of sum(raw * d_raw) of mlp_functional in `dtype`, on the CPU: (raw, {name: grad or None for
-    a parameter the architecture does not use}, d_enc or None)"""
+    a parameter the architecture does not use}, d_enc or None).  The tensors handed to `post` keep their gradient (.grad: the
+    delta of that activation)."""
     p = {k: torch.from_numpy(v).to(dtype).requires_grad_(True) for k, v in params.items()}
     e = torch.from_numpy(enc).to(dtype).requires_grad_(enc_grad)
     v = None if venc is None else torch.from_numpy(venc).to(dtype)
-    raw = mlp_functional(p, e, v, skip_index, pre)
+    raw = mlp_functional(p, e, v, skip_index, pre, post)
+    for t in post or ():
+        t.retain_grad()
     (raw * torch.from_numpy(d_raw).to(dtype)).sum().backward()
     return raw.detach(), {k: None if t.grad is None else t.grad.detach() for k, t in p.items()}, e.grad
 

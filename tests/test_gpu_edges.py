@@ -1,7 +1,9 @@
 """Edge sizes of the hot path (the tier's "empty and ragged inputs, maximum sizes"): zero rays, and a batch whose per-sample
 buffers pass 4 GiB (every sample / byte offset in the kernels has to be 64-bit).  Ragged sizes (rays not a multiple of the
 256-sample tile, N not a multiple of 64) are covered next to the stages they concern (test_gpu_forward.py: fwd_ragged_100x128,
-test_gpu_train.py: ragged training shapes, ragged last chunk of a frame)."""
+test_gpu_train.py: ragged training shapes, ragged last chunk of a frame; test_gpu_f32_backward.py: the fp32 MLP backward against
+float64; test_gpu_mlp_exact.py: the bf16 and fp32 MLP forward and the bf16 training kernels bit for bit against float64 in exact
+integer arithmetic, M = 1 ... 4097 around the 32-sample wave tile and the 256-sample workgroup tile)."""
 import numpy as np
 import pytest
 import torch
