@@ -476,7 +476,23 @@ int mipnerf_uncontract_vertices(int64_t num_vertices, float far_radius, const fl
  * mipnerf_scatter_frame: writes every pixel of every level once (comp_rgb, distance, acc of `full`; weights / t_samples are not
  * touched): pixel index[j], j < count, takes slot j of `compact`; a pixel with live = 0 takes what volumetric_rendering (mip.py:395-400)
  * yields for all-zero weights: rgb = 1 with white_bkgd != 0 else 0, acc = 0, distance = near[pixel].  1 <= num_levels <= 4.  Does not
- * allocate or synchronise. */
+ * allocate or synchronise.
+ * mipnerf_bucket_rays: a sample count per ray that follows its occupied span.  S = span_samples (the frusta count first / last were found
+ * with), N = num_samples (the count the renderer uses), ladder c_0 < c_1 < ... < c_{B-1} with 1 <= c_0, c_{B-1} == N and 1 <= B <= 8.  For a
+ * live ray with span [first, last]: need = ((last - first + 1) * N + S - 1) / S in integer division (1 <= need <= N) and bucket = the
+ * smallest b with c_b >= need; a dead ray has bucket -1.  A ray of bucket b is meant to be rendered with c_b samples per level on
+ * [near', far'], so its coarse spacing is at most the untightened ray's: (far' - near') / c_b <= (far - near) / N.  The call is a stable
+ * B-way partition of the rays by bucket (counts per 1024 rays and bucket, one single-workgroup scan, per-ray ranks; no atomics): segment b
+ * begins at base_0 = 0, base_{b+1} = round_up(base_b + count_b, 64), and within a bucket the rays keep their original order.  out_rays
+ * (a NULL field is skipped) holds num_rays + 64 * B rays; the padding slots between the segments are never written.  slot[ray] (int32)
+ * is the compact slot of the ray, or -1 for a dead ray; counts_host [B] receives the counts: one read-back and one stream
+ * SYNCHRONISATION per call -- it cannot be captured into a hipGraph.  `rays` are read as given: pass the span arrays near' / far' as its
+ * near / far to gather tightened rays.  workspace: mipnerf_bucket_rays_workspace_bytes(num_rays, num_buckets), 16-byte aligned;
+ * num_rays < 2^31; num_rays = 0 returns zero counts without a launch.  S and N in [1, MIPNERF_MAX_SAMPLES].
+ * mipnerf_gather_frame: writes every pixel of every level once (comp_rgb, distance, acc of `full`): a pixel with slot >= 0 copies compact
+ * slot `slot` (slot < compact_rows, the rows the compact outputs hold; a slot outside them is treated as dead); a pixel with slot < 0 gets
+ * the dead-pixel rule of mipnerf_scatter_frame: rgb = 1 with white_bkgd != 0 else 0, acc = 0, distance = near[pixel], the ORIGINAL near.
+ * 1 <= num_levels <= 4.  Does not allocate or synchronise. */
 int64_t mipnerf_occupancy_words(int32_t nx, int32_t ny, int32_t nz);
 int mipnerf_occupancy_build(const int32_t* dims_host, const float* grid, float threshold, int32_t dilate, uint32_t* bits,
                             uint32_t* scratch, void* stream);
@@ -500,6 +516,13 @@ int mipnerf_compact_rays(int64_t num_rays, const uint8_t* live, const mipnerf_ra
 int mipnerf_scatter_frame(int64_t num_rays, int64_t count, int32_t num_levels, const int32_t* index, const uint8_t* live,
                           const float* near, int32_t white_bkgd, const mipnerf_level_out* compact, const mipnerf_level_out* full,
                           void* stream);
+size_t mipnerf_bucket_rays_workspace_bytes(int64_t num_rays, int32_t num_buckets);
+int mipnerf_bucket_rays(int64_t num_rays, const uint8_t* live, const int32_t* first, const int32_t* last, int32_t span_samples,
+                        int32_t num_samples, int32_t num_buckets, const int32_t* ladder_host, const mipnerf_rays* rays,
+                        const mipnerf_rays_out* out_rays, int32_t* slot, void* workspace, size_t workspace_bytes, int64_t* counts_host,
+                        void* stream);
+int mipnerf_gather_frame(int64_t num_rays, int64_t compact_rows, int32_t num_levels, const int32_t* slot, const float* near,
+                         int32_t white_bkgd, const mipnerf_level_out* compact, const mipnerf_level_out* full, void* stream);
 
 /* ---- training side ---------------------------------------------------------------------- */
 /* activations (mip_nerf.py:236-238): raw [M,4] = (raw_rgb, raw_density) -> rgb_sigma [M,4];

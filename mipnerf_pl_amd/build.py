@@ -51,6 +51,7 @@ UNITS = [
     ("kernels_downscale.hip", ["-ffp-contract=off"]),   # float(q) / 255.f stays one rounded division
     ("kernels_mesh.hip", ["-ffp-contract=off"]),        # lattice means lo + float(i) * h and the shared IPE round as stated in the header
     ("kernels_occupancy.hip", ["-ffp-contract=off"]),   # frustum end points o + t * d and floor((x - lo) / h) round as stated in the header
+    ("kernels_bucket.hip", []),                         # integer ranks and copies only: no floating-point arithmetic to contract
     ("selftest.hip", ["-ffp-contract=off"]),
     ("capi.hip", []),
 ]

@@ -1201,6 +1201,71 @@ int mipnerf_scatter_frame(int64_t n, int64_t count, int32_t num_levels, const in
     return MIPNERF_OK;
 }
 
+// ---- adaptive sample counts for whole frames (kernels_bucket.hip) ----------------------------------------------------------
+// workspace of the partition: the B counts (8 bytes each, padded to 256) | block_sum [B][bucket_num_blocks(n)]
+size_t mipnerf_bucket_rays_workspace_bytes(int64_t n, int32_t num_buckets) {
+    if (n < 0 || n >= (1LL << 31) || num_buckets < 1 || num_buckets > mip::kMaxBuckets) return 0;
+    return 256 + 4 * (((size_t)num_buckets * (size_t)mip::bucket_num_blocks(n) + 63) / 64 * 64);
+}
+
+int mipnerf_bucket_rays(int64_t n, const uint8_t* live, const int32_t* first, const int32_t* last, int32_t span_samples,
+                        int32_t num_samples, int32_t num_buckets, const int32_t* ladder, const mipnerf_rays* rays,
+                        const mipnerf_rays_out* out_rays, int32_t* slot, void* workspace, size_t workspace_bytes, int64_t* counts_host,
+                        void* stream) {
+    if (n < 0 || n >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "bucket_rays: bad ray count");
+    if (span_samples < 1 || span_samples > MIPNERF_MAX_SAMPLES || num_samples < 1 || num_samples > MIPNERF_MAX_SAMPLES)
+        return fail(MIPNERF_E_INVALID, "bucket_rays: span_samples and num_samples must be in [1, %d]", MIPNERF_MAX_SAMPLES);
+    if (num_buckets < 1 || num_buckets > mip::kMaxBuckets)
+        return fail(MIPNERF_E_INVALID, "bucket_rays: the ladder has 1 to %d entries (got %d)", mip::kMaxBuckets, num_buckets);
+    if (!ladder || !counts_host) return fail(MIPNERF_E_INVALID, "bucket_rays: null argument");
+    mip::BucketRule rule{};
+    rule.S = span_samples; rule.N = num_samples; rule.B = num_buckets;
+    for (int b = 0; b < num_buckets; ++b) {
+        if (ladder[b] < 1 || (b > 0 && ladder[b] <= ladder[b - 1]))
+            return fail(MIPNERF_E_INVALID, "bucket_rays: the ladder must be strictly increasing from at least 1");
+        rule.c[b] = ladder[b];
+    }
+    if (ladder[num_buckets - 1] != num_samples)
+        return fail(MIPNERF_E_INVALID, "bucket_rays: the ladder must end at num_samples (%d != %d)", ladder[num_buckets - 1], num_samples);
+    for (int b = 0; b < num_buckets; ++b) counts_host[b] = 0;
+    if (n == 0) return MIPNERF_OK;
+    if (!live || !first || !last || !rays || !out_rays || !slot || !workspace) return fail(MIPNERF_E_INVALID, "bucket_rays: null argument");
+    if ((uintptr_t)workspace & 15) return fail(MIPNERF_E_INVALID, "bucket_rays: the workspace must be 16-byte aligned");
+    const size_t need = mipnerf_bucket_rays_workspace_bytes(n, num_buckets);
+    if (workspace_bytes < need) return fail(MIPNERF_E_WORKSPACE, "bucket_rays: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    const float* in[7] = {rays->origins, rays->directions, rays->viewdirs, rays->radii, rays->lossmult, rays->near, rays->far};
+    float* out[7] = {out_rays->origins, out_rays->directions, out_rays->viewdirs, out_rays->radii, out_rays->lossmult, out_rays->near, out_rays->far};
+    for (int q = 0; q < 7; ++q)
+        if (out[q] && !in[q]) return fail(MIPNERF_E_INVALID, "bucket_rays: an output field has no input");
+    unsigned long long* header = (unsigned long long*)workspace;
+    HIP_TRY(mip::launch_bucket_rays(n, rule, live, first, last, in, out, slot, (unsigned*)((char*)workspace + 256), header, S(stream)));
+    unsigned long long host_counts[mip::kMaxBuckets] = {};
+    HIP_TRY(hipMemcpyAsync(host_counts, header, sizeof(unsigned long long) * num_buckets, hipMemcpyDeviceToHost, S(stream)));
+    HIP_TRY(hipStreamSynchronize(S(stream)));
+    for (int b = 0; b < num_buckets; ++b) counts_host[b] = (int64_t)host_counts[b];
+    return MIPNERF_OK;
+}
+
+int mipnerf_gather_frame(int64_t n, int64_t compact_rows, int32_t num_levels, const int32_t* slot, const float* nearp, int32_t white_bkgd,
+                         const mipnerf_level_out* compact, const mipnerf_level_out* full, void* stream) {
+    if (n < 0 || n >= (1LL << 31) || compact_rows < 0 || compact_rows >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "gather_frame: bad ray count");
+    if (num_levels < 1 || num_levels > mip::kMaxScatterLevels) return fail(MIPNERF_E_INVALID, "gather_frame: num_levels must be in [1, %d]", mip::kMaxScatterLevels);
+    if (n == 0) return MIPNERF_OK;
+    if (!slot || !nearp || !full || (compact_rows > 0 && !compact)) return fail(MIPNERF_E_INVALID, "gather_frame: null argument");
+    const float* c_rgb[mip::kMaxScatterLevels]; const float* c_dist[mip::kMaxScatterLevels]; const float* c_acc[mip::kMaxScatterLevels];
+    float* f_rgb[mip::kMaxScatterLevels]; float* f_dist[mip::kMaxScatterLevels]; float* f_acc[mip::kMaxScatterLevels];
+    for (int l = 0; l < num_levels; ++l) {
+        f_rgb[l] = full[l].comp_rgb; f_dist[l] = full[l].distance; f_acc[l] = full[l].acc;
+        c_rgb[l] = compact_rows ? compact[l].comp_rgb : nullptr; c_dist[l] = compact_rows ? compact[l].distance : nullptr;
+        c_acc[l] = compact_rows ? compact[l].acc : nullptr;
+        if (!f_rgb[l] || !f_dist[l] || !f_acc[l] || (compact_rows > 0 && (!c_rgb[l] || !c_dist[l] || !c_acc[l])))
+            return fail(MIPNERF_E_INVALID, "gather_frame: level %d has a null comp_rgb, distance or acc", l);
+    }
+    HIP_TRY(mip::launch_gather_frame(n, compact_rows, num_levels, slot, nearp, white_bkgd, c_rgb, c_dist, c_acc, f_rgb, f_dist, f_acc,
+                                     S(stream)));
+    return MIPNERF_OK;
+}
+
 // ---- training-side entry points ------------------------------------------------------------------
 int mipnerf_activate(int64_t M, const float* raw, float rgb_padding, float density_bias, const float* density_randn,
                      float density_noise, float* rgb_sigma, void* stream) {

@@ -305,6 +305,24 @@ hipError_t launch_scatter_frame(int64_t n, int64_t count, int num_levels, const 
                                 int white_bkgd, const float* const c_rgb[], const float* const c_dist[], const float* const c_acc[],
                                 float* const f_rgb[], float* const f_dist[], float* const f_acc[], hipStream_t st);
 
+// ---- kernels_bucket.hip: the live rays of a frame partitioned by the sample count their occupied span needs, and the way back ------
+constexpr int kMaxBuckets = 8;
+// need = ((last - first + 1) * N + S - 1) / S, bucket = the smallest b with c[b] >= need (c strictly increasing, c[B - 1] == N); dead: -1
+struct BucketRule {
+    int S, N, B;
+    int c[kMaxBuckets];
+};
+int64_t bucket_num_blocks(int64_t n);            // block_sum holds B * bucket_num_blocks(n) entries
+// segment b starts at base_0 = 0, base_{b+1} = round_up(base_b + count_b, 64); header[b] = count_b; slot [n]: the compact slot or -1;
+// in / out as launch_compact_rays, out holding n + 64 * B rays
+hipError_t launch_bucket_rays(int64_t n, const BucketRule& rule, const unsigned char* live, const int* first, const int* last,
+                              const float* const in[7], float* const out[7], int* slot, unsigned* block_sum, unsigned long long* header,
+                              hipStream_t st);
+// pixel p takes compact slot slot[p] when 0 <= slot[p] < rows, otherwise the dead-pixel values of launch_scatter_frame
+hipError_t launch_gather_frame(int64_t n, int64_t rows, int num_levels, const int* slot, const float* nearp, int white_bkgd,
+                               const float* const c_rgb[], const float* const c_dist[], const float* const c_acc[], float* const f_rgb[],
+                               float* const f_dist[], float* const f_acc[], hipStream_t st);
+
 // ---- selftest.hip -------------------------------------------------------------------------------
 // returns 0 if the MFMA fragment layouts and the LDS-DMA path behave as the kernels assume;
 // otherwise a bit mask (1: bf16 32x32x16 layout, 2: f32 32x32x2 layout, 4: global_load_lds)

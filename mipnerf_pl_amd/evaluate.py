@@ -28,16 +28,18 @@ DEFAULT_CHUNK = 12288        # eval.py / render_video.py --chunk_size
 class FrameEvaluator:
     """Everything one image size needs: the frame's `GraphedFrame` (or its eager form) and the device buffers of the image bytes."""
 
-    def __init__(self, model, height, width, chunk_size, white_bkgd, device, use_graph=True, occupancy=None, tighten=False, span_samples=None):
+    def __init__(self, model, height, width, chunk_size, white_bkgd, device, use_graph=True, occupancy=None, tighten=False, span_samples=None,
+                 adaptive=False, ladder=None):
         from .model import CulledFrame, GraphedFrame
         self.h, self.w = int(height), int(width)
         n = self.h * self.w
         if occupancy is None:
-            if tighten:
-                raise ValueError("FrameEvaluator: tighten=True needs an occupancy grid")
+            if tighten or adaptive:
+                raise ValueError("FrameEvaluator: tighten=True / adaptive=True need an occupancy grid")
             self.frame = GraphedFrame(model, n, chunk_size, white_bkgd, device, capture=use_graph)
         else:       # rays that touch no occupied cell are skipped; the live count varies per frame, so the chunks run eagerly
-            self.frame = CulledFrame(model, n, chunk_size, white_bkgd, device, occupancy, tighten=tighten, span_samples=span_samples)
+            self.frame = CulledFrame(model, n, chunk_size, white_bkgd, device, occupancy, tighten=tighten, span_samples=span_samples,
+                                     adaptive=adaptive, ladder=ladder)
         self.vis_ws = torch.empty(ops.visualize_workspace_floats(n), dtype=torch.float32, device=device)
         self.rgb_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
         self.dist_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
@@ -169,15 +171,19 @@ def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bou
     return occ
 
 
-def report_live_share(shares, spans=None):
+def report_live_share(shares, spans=None, samples=None):
     """The closing line of a culled run: the mean share of rays rendered per frame and, for a tightened run (`spans`), the mean share
     of [near, far] between the live rays' first and last occupied coarse frustum (`CulledFrame.span_share`; frames without a live ray do
-    not count)."""
+    not count); for an adaptive run (`samples`) also the mean share of the model's sample count the live rays were rendered with
+    (`CulledFrame.sample_share`)."""
     if shares:
         line = "cull: mean live share per frame: {:.4f} ({} frames)".format(float(np.mean(shares)), len(shares))
         spans = [v for v in (spans or []) if v == v]
         if spans:
             line += "; mean span share of the live rays: {:.4f}".format(float(np.mean(spans)))
+        samples = [v for v in (samples or []) if v == v]
+        if samples:
+            line += "; mean sample share of the live rays: {:.4f}".format(float(np.mean(samples)))
         print(line)
 
 
@@ -213,12 +219,13 @@ def write_metrics(folder, psnrs, ssims):
 
 
 def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chunk_size=DEFAULT_CHUNK, white_bkgd=True, use_graph=True,
-             base_size=(800, 800), occupancy=None, tighten=False, span_samples=None):
+             base_size=(800, 800), occupancy=None, tighten=False, span_samples=None, adaptive=False, ladder=None):
     """eval.py:main after the checkpoint is loaded: every image of `dataset` (a test split of `datasets.dataset_dict`) rendered by
     `system.mip_nerf`, PSNR / SSIM recorded, the images written when `save_image`.  Returns (psnrs, ssims) as lists of floats.
     `occupancy` (an `ops.Occupancy`, e.g. `scene_occupancy`; for the unbounded-scene model one with `space='contracted'`): rays that touch
     no occupied cell are not rendered (`model.CulledFrame`); None is the full path.  `tighten` / `span_samples` are `CulledFrame`'s (live rays rendered on their occupied span -- not the untightened
-    frame --; the frusta count of the classification)."""
+    frame --; the frusta count of the classification), and so are `adaptive` / `ladder` (every live ray rendered with a sample count that
+    follows its occupied span; implies `tighten`)."""
     if scale not in (1, 4):
         raise ValueError("scale must be 1 or 4 (eval.py --scale)")
     model = system.mip_nerf
@@ -227,7 +234,7 @@ def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chun
     for i in range(scale):
         os.makedirs(os.path.join(folder, str(2 ** i)), exist_ok=True)
     slots = image_slots(dataset.sizes, scale, base_size[0])
-    evaluators, psnrs, ssims, shares, spans = {}, [], [], [], []
+    evaluators, psnrs, ssims, shares, spans, samples = {}, [], [], [], [], []
     with torch.no_grad():
         for idx in range(len(dataset)):
             rays, gt = dataset[idx]
@@ -235,12 +242,14 @@ def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chun
             ev = evaluators.get((h, w))
             if ev is None:
                 ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten,
-                                                         span_samples=span_samples)
+                                                         span_samples=span_samples, adaptive=adaptive, ladder=ladder)
             rgb, dist, acc = ev.render(rays)
             if occupancy is not None:
                 shares.append(ev.frame.live_count / float(h * w))
-                if tighten:         # the spans are there already; an untightened run launches and reads back nothing more
+                if tighten or adaptive:         # the spans are there already; an untightened run launches and reads back nothing more
                     spans.append(ev.frame.span_share)
+                if adaptive:
+                    samples.append(ev.frame.sample_share)
             psnr, ssim = ops.eval_errors(rgb, gt[..., :3])
             psnrs.append(psnr.item())
             ssims.append(ssim.item())
@@ -249,7 +258,7 @@ def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chun
                 save_images(*ev.images(rgb, dist, acc), os.path.join(folder, sub), n)
     write_metrics(folder, psnrs, ssims)
     generate_video(folder)
-    report_live_share(shares, spans)
+    report_live_share(shares, spans, samples)
     return psnrs, ssims
 
 

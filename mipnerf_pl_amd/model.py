@@ -813,16 +813,26 @@ class GraphedFrame:
         self.acc = [torch.zeros(self.n, device=device) for _ in range(L_)]
         self.graph = None
 
-    def _run_chunks(self, count: Optional[int] = None):
-        """`count` (default: all n): only the first `count` rays of the static buffers are rendered (CulledFrame's compacted rays)."""
-        m, N = self.model, self.model.num_samples
-        total = self.n if count is None else int(count)
-        bounds = [(lo, min(total, lo + self.chunk)) for lo in range(0, total, self.chunk)]
+    def _scratch_key(self, model, b):
+        """key of the per-sample scratch of a b-ray chunk: b for the frame's own model, (b, num_samples) for another one"""
+        return b if model is self.model else (b, int(model.num_samples))
+
+    def _run_chunks(self, count: Optional[int] = None, jobs=None):
+        """`count` (default: all n): only the first `count` rays of the static buffers are rendered (CulledFrame's compacted rays).
+        `jobs` (instead of `count`): a list of (model, lo, hi) -- rows lo .. hi - 1 of the static buffers are rendered by chunk forwards of
+        `model` (this frame's model or one that differs from it in num_samples only), all jobs' chunks round-robin over the same lanes
+        inside one fork / join (CulledFrame's buckets)."""
+        if jobs is None:
+            total = self.n if count is None else int(count)
+            jobs = [(self.model, 0, total)]
+        bounds = [(m, lo, min(hi, lo + self.chunk)) for m, start, hi in jobs for lo in range(int(start), int(hi), self.chunk)]
         if not bounds:
             return
         lanes = min(self.lanes, len(bounds))
-        ctx = m.mlp.native(self.dev)
-        need = int(L.lib().mipnerf_workspace_bytes(ctx.handle, min(self.n, self.chunk)))
+        need = 0
+        for m in {id(m): m for m, _, _ in bounds}.values():
+            ctx = m.mlp.native(self.dev)
+            need = max(need, int(L.lib().mipnerf_workspace_bytes(ctx.handle, min(self.n, self.chunk))))
         if getattr(self, "_lane_ws", None) is None or len(self._lane_ws) != lanes or self._lane_ws[0].numel() < need:
             self._lane_ws = [torch.empty(need, dtype=torch.uint8, device=self.dev) for _ in range(lanes)]
             self._lane_streams = [torch.cuda.Stream(device=self.dev) for _ in range(lanes)] if lanes > 1 else []
@@ -830,13 +840,14 @@ class GraphedFrame:
         cur = torch.cuda.current_stream()
         for s_ in self._lane_streams:            # fork (inside a capture the lanes join the captured graph)
             s_.wait_stream(cur)
-        for ci, (lo, hi) in enumerate(bounds):
+        for ci, (m, lo, hi) in enumerate(bounds):
             lane = ci % lanes
-            b = hi - lo
+            b, N = hi - lo, m.num_samples
             scratch = self._scratch[lane]
-            if b not in scratch:      # per-sample outputs nobody reads after the chunk: shared by all chunks of that size on this lane
-                scratch[b] = [(torch.empty(b, N, device=self.dev), torch.empty(b, N + 1, device=self.dev)) for _ in range(m.num_levels)]
-            out = [(self.rgb[l][lo:hi], self.dist[l][lo:hi], self.acc[l][lo:hi], scratch[b][l][0], scratch[b][l][1])
+            key = self._scratch_key(m, b)
+            if key not in scratch:    # per-sample outputs nobody reads after the chunk: shared by all chunks of that size on this lane
+                scratch[key] = [(torch.empty(b, N, device=self.dev), torch.empty(b, N + 1, device=self.dev)) for _ in range(m.num_levels)]
+            out = [(self.rgb[l][lo:hi], self.dist[l][lo:hi], self.acc[l][lo:hi], scratch[key][l][0], scratch[key][l][1])
                    for l in range(m.num_levels)]
             rays = Rays(*[x[lo:hi] for x in self.static_in])
             if lanes > 1:
@@ -886,6 +897,33 @@ class GraphedFrame:
         return self.rgb[0], self.rgb[-1], self.dist[-1]
 
 
+def sibling_with_samples(model: "MipNerf", num_samples: int) -> "MipNerf":
+    """A `MipNerf` with the constructor arguments of `model` except `num_samples` (the native context fixes the count at creation), whose
+    `mlp` holds the SAME `Parameter` objects: `NativeContext.sync_params` keys on (data_ptr, _version), so a changed parameter re-packs the
+    sibling's weight streams at its next forward and nothing goes stale."""
+    a = model.mlp.arch
+    with torch.device("meta"):          # its own parameters are dropped two lines below: no storage, no initialisation
+        sib = MipNerf(num_samples=int(num_samples), num_levels=model.num_levels, resample_padding=model.resample_padding,
+                      stop_resample_grad=model.stop_resample_grad, use_viewdirs=model.use_viewdirs, disparity=model.disparity,
+                      ray_shape=model.ray_shape, min_deg_point=model.min_deg_point, max_deg_point=model.max_deg_point,
+                      deg_view=model.deg_view, density_noise=model.density_noise, density_bias=model.density_bias,
+                      rgb_padding=model.rgb_padding, disable_integration=model.disable_integration, mlp_net_depth=a["net_depth"],
+                      mlp_net_width=a["net_width"], mlp_net_depth_condition=a["net_depth_condition"],
+                      mlp_net_width_condition=a["net_width_condition"], mlp_skip_index=a["skip_index"],
+                      mlp_num_rgb_channels=a["num_rgb_channels"], mlp_num_density_channels=a["num_density_channels"],
+                      precision="bf16" if model.precision == L.PREC_BF16 else "fp32", unbounded=model.unbounded)
+    _share_parameters(sib, model)
+    return sib.eval()
+
+
+def _share_parameters(sib: "MipNerf", model: "MipNerf") -> None:
+    """the sibling's mlp takes the Parameter objects `model.mlp` holds now, and the model's precision"""
+    for ms, mm in zip(sib.mlp.modules(), model.mlp.modules()):
+        for k in ms._parameters:
+            ms._parameters[k] = mm._parameters[k]
+    sib.precision = sib.mlp.precision = model.precision
+
+
 class CulledFrame:
     """Whole-frame rendering that skips the rays a trained field's occupancy grid (`ops.field_occupancy`) proves empty.  The call contract
     is `GraphedFrame`'s: `__call__(flat_rays) -> (coarse_rgb [n, 3], fine_rgb [n, 3], distance [n])`, `.acc[l]`, `.n`, `.chunk`,
@@ -911,11 +949,24 @@ class CulledFrame:
     (last - first + 1) / span_samples over the live rays of the last call (NaN when none was live).
     An unbounded=True model is accepted exactly when `occupancy.space == 'contracted'` (`ops.field_occupancy(..., space='contracted')`; a
     bounded model with such a grid is refused, and the reverse): the classification walks the inverse-depth fence posts of the model's
-    coarse level, and a tightened ray is sampled in inverse depth on [near', far']."""
+    coarse level, and a tightened ray is sampled in inverse depth on [near', far'].
+    `adaptive=True` (opt-in, implies `tighten`; without it nothing below is launched): every live ray is rendered with a sample count that
+    follows its occupied span.  S = `span_samples`, N = `model.num_samples`, `ladder` c_0 < c_1 < ... < c_{B-1} with 1 <= c_0,
+    c_{B-1} == N and 1 <= B <= 8 (default `ops.sample_ladder(N)`: the distinct values of ceil(N * k / 4), k = 1..4).  For a live ray with
+    span [first, last]: need = ((last - first + 1) * N + S - 1) / S in integer division (1 <= need <= N) and bucket = the smallest b with
+    c_b >= need; a dead ray has bucket -1.  A ray of bucket b is rendered with c_b samples per level on [near', far'], the fence posts
+    `ops.ray_span` yields, so its coarse spacing is at most the untightened ray's.  Per frame: `ops.ray_span`, `ops.bucket_rays` (a
+    stable partition into 64-ray-aligned segments; the B counts reach the host by one read-back and one synchronisation), for every
+    non-empty bucket ceil(count_b / chunk) chunk forwards over its segment by a sibling model of c_b samples (`sibling_with_samples`: the
+    same `Parameter` objects, so a parameter update re-packs every sibling), all buckets' chunks on the same lanes, and
+    `ops.gather_frame` (a culled pixel's distance = the original near).  Pixels of bucket b are bit for bit what `GraphedFrame` over the
+    sibling with c_b samples yields on the same rays with near / far replaced by near' / far'; the frame is NOT the untightened frame, and
+    what is guaranteed is the guarantee of `tighten`.  `.bucket_counts` (rays per bucket of the last call), `.ladder`, `.sample_share`
+    (the mean of c_bucket / N over the live rays, from the counts: no read-back; NaN when no ray is live)."""
 
     def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, occupancy,
                  lanes: Optional[int] = None, outside_occupied: bool = True, cone_scale: float = 1.0, tighten: bool = False,
-                 span_samples: Optional[int] = None):
+                 span_samples: Optional[int] = None, adaptive: bool = False, ladder=None):
         unbounded, contracted = bool(getattr(model, "unbounded", False)), getattr(occupancy, "space", None) == "contracted"
         if unbounded and not contracted:
             raise NotImplementedError("CulledFrame: unbounded=True models are not supported (their field lives in a contracted space) unless "
@@ -924,8 +975,16 @@ class CulledFrame:
             raise ValueError("CulledFrame: the occupancy grid lies in the contracted space of unbounded=True models; this model is bounded")
         self.model, self.n, self.chunk, self.white_bkgd, self.dev = model, int(num_rays), int(chunk), bool(white_bkgd), device
         self.occupancy, self.outside_occupied, self.cone_scale = occupancy, bool(outside_occupied), float(cone_scale)
+        self.adaptive = bool(adaptive)
+        if ladder is not None and not self.adaptive:
+            raise ValueError("CulledFrame: a ladder belongs to adaptive=True")
+        self.ladder = ops.sample_ladder(model.num_samples, ladder) if self.adaptive else None
+        self.bucket_counts = None
+        tighten = bool(tighten) or self.adaptive
         # the compacted rays and their results live in an eager GraphedFrame: its chunk loop, lanes and scratch render the first live_count rays
-        self._compact = GraphedFrame(model, num_rays, chunk, white_bkgd, device, lanes=lanes, capture=False)
+        # (adaptive: the buckets' 64-ray-aligned segments, which need 64 more rows per bucket)
+        rows = self.n + ops.BUCKET_ALIGN * len(self.ladder) if self.adaptive else num_rays
+        self._compact = GraphedFrame(model, rows, chunk, white_bkgd, device, lanes=lanes, capture=False)
         self.static_in = Rays(*[torch.zeros(self.n, k, device=device) for k in (3, 3, 3, 1, 1, 1, 1)])
         L_ = model.num_levels
         self.rgb = [torch.zeros(self.n, 3, device=device) for _ in range(L_)]
@@ -944,10 +1003,52 @@ class CulledFrame:
             self.last = torch.zeros(self.n, dtype=torch.int32, device=device)
             self.near_span = torch.zeros(self.n, 1, device=device)
             self.far_span = torch.zeros(self.n, 1, device=device)
+        if self.adaptive:
+            self.slot = torch.full((max(self.n, 1),), -1, dtype=torch.int32, device=device)
+            need = int(L.lib().mipnerf_bucket_rays_workspace_bytes(self.n, len(self.ladder)))
+            self._bucket_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+            # one model per ladder entry: the frame's own for c_{B-1} == N, a sibling that shares its parameters for every smaller count
+            self._bucket_models = [model if c == model.num_samples else sibling_with_samples(model, c) for c in self.ladder]
 
     @property
     def span_samples(self) -> int:
         return int(self.model.num_samples) if self._span_samples is None else self._span_samples
+
+    @property
+    def sample_share(self) -> float:
+        """adaptive only: the mean of c_bucket / N over the live rays of the last call, from the bucket counts (NaN when none was live)"""
+        if not self.adaptive:
+            raise AttributeError("CulledFrame.sample_share belongs to adaptive=True")
+        if not self.bucket_counts or self.live_count == 0:
+            return float("nan")
+        return sum(k * c for k, c in zip(self.bucket_counts, self.ladder)) / float(self.live_count * self.ladder[-1])
+
+    def _render_buckets(self, src: Rays) -> None:
+        """the adaptive route behind the classification: partition, one set of chunk forwards per non-empty bucket, gather"""
+        m, c = self.model, self._compact
+        self.bucket_counts = ops.bucket_rays(self.live, self.first, self.last, src, self.span_samples, self.ladder, c.static_in,
+                                             self.slot[:self.n], workspace=self._bucket_ws)
+        self.live_count = sum(self.bucket_counts)
+        bases = ops.bucket_bases(self.bucket_counts)
+        jobs = []
+        for b in reversed(range(len(self.ladder))):              # the longest forwards first: the lanes end on the short ones
+            if self.bucket_counts[b]:
+                sib = self._bucket_models[b]
+                if sib is not m:
+                    _share_parameters(sib, m)                    # the Parameter objects and the precision the model has NOW
+                jobs.append((sib, bases[b], bases[b] + self.bucket_counts[b]))
+        # per-sample scratch per bucket and tail size only (the synchronisation in bucket_rays came after the join of the last frame's
+        # lanes, so nothing still reads the others)
+        keep = set()
+        for sib, lo, hi in jobs:
+            keep.add(c._scratch_key(sib, min(c.n, self.chunk)))
+            keep.add(c._scratch_key(sib, (hi - lo) % self.chunk))
+        for scratch in getattr(c, "_scratch", []):
+            for key in [key for key in scratch if key not in keep]:
+                del scratch[key]
+        c._run_chunks(jobs=jobs)
+        ops.gather_frame(self.slot[:self.n], [(c.rgb[l], c.dist[l], c.acc[l]) for l in range(m.num_levels)],
+                         [(self.rgb[l], self.dist[l], self.acc[l]) for l in range(m.num_levels)], self.static_in.near, self.white_bkgd)
 
     @property
     def span_share(self) -> float:
@@ -968,6 +1069,8 @@ class CulledFrame:
             raise ValueError(f"CulledFrame built for {self.n} rays, got {rays.origins.shape[0]}")
         if self.n == 0:
             self.live_count = 0
+            if self.adaptive:
+                self.bucket_counts = [0] * len(self.ladder)
             return self.rgb[0], self.rgb[-1], self.dist[-1]
         m, c = self.model, self._compact
         with torch.cuda.device(self.dev), torch.no_grad():
@@ -982,6 +1085,9 @@ class CulledFrame:
             else:
                 ops.ray_occupancy(self.occupancy, src, self.span_samples, disparity=m.disparity, outside_occupied=self.outside_occupied,
                                   cone_scale=self.cone_scale, out=self.live)
+            if self.adaptive:
+                self._render_buckets(src)
+                return self.rgb[0], self.rgb[-1], self.dist[-1]
             self.live_count = ops.compact_rays(self.live, src, c.static_in, self.index, workspace=self._ws)
             # the ragged tail differs from frame to frame: keep the per-sample scratch of the full chunk and of this tail only (the
             # synchronisation in compact_rays came after the join of the last frame's lanes, so nothing still reads the others)

@@ -935,3 +935,113 @@ def scatter_frame(index, count, compact_outputs, full_outputs, live, near, white
     with torch.cuda.device(live.device):
         L.check(L.lib().mipnerf_scatter_frame(n, int(count), nl, _ptr(index), _ptr(live), _ptr(near), int(bool(white_bkgd)), comp, full,
                                               _stream()), "scatter_frame")
+
+
+# ---- adaptive sample counts for whole frames (csrc/kernels_bucket.hip) ------------------------------------------------------
+MAX_BUCKETS = 8
+BUCKET_ALIGN = 64
+LADDER_RULE = ("a ladder is 1 to 8 strictly increasing sample counts c_0 < c_1 < ... < c_{B-1} with 1 <= c_0 and c_{B-1} == num_samples")
+
+
+def sample_ladder(num_samples, ladder=None):
+    """The sample counts adaptive rendering chooses from, as a tuple c_0 < c_1 < ... < c_{B-1} with 1 <= c_0, c_{B-1} == num_samples and
+    1 <= B <= 8.  `ladder=None`: the default ladder, the distinct values of ceil(num_samples * k / 4), k = 1..4 (32, 64, 96, 128 for 128
+    samples).  A given ladder is validated against that rule and returned as a tuple of ints."""
+    N = int(num_samples)
+    if not 1 <= N <= L.MAX_SAMPLES:
+        raise ValueError(f"sample_ladder: num_samples must be in [1, {L.MAX_SAMPLES}] (got {N})")
+    if ladder is None:
+        return tuple(sorted({(N * k + 3) // 4 for k in range(1, 5)}))
+    try:
+        lad = tuple(int(c) for c in ladder)
+        exact = all(float(c) == float(i) for c, i in zip(ladder, lad))
+    except (TypeError, ValueError):
+        lad, exact = (), False
+    if not (exact and 1 <= len(lad) <= MAX_BUCKETS and lad[0] >= 1 and all(a < b for a, b in zip(lad, lad[1:])) and lad[-1] == N):
+        raise ValueError(f"sample_ladder: {LADDER_RULE} (num_samples {N}, got {ladder!r})")
+    return lad
+
+
+def bucket_bases(counts):
+    """Where the segments of `bucket_rays` begin: base_0 = 0, base_{b+1} = round_up(base_b + count_b, 64).  Returns B + 1 values; the last
+    is the number of rows the partition spans."""
+    bases = [0]
+    for c in counts:
+        bases.append((bases[-1] + int(c) + BUCKET_ALIGN - 1) // BUCKET_ALIGN * BUCKET_ALIGN)
+    return bases
+
+
+def bucket_rays(live, first, last, rays, span_samples, ladder, out_rays, slot, workspace=None):
+    """A stable B-way partition of the rays by the sample count their occupied span needs (include/mipnerf_hip.h, mipnerf_bucket_rays).
+    S = `span_samples` (the frusta count `ray_span` found first / last with), N = ladder[-1] (the count the model renders with), `ladder`
+    c_0 < c_1 < ... < c_{B-1} with 1 <= c_0, c_{B-1} == N and 1 <= B <= 8 (`sample_ladder`).  For a live ray with span [first, last]:
+    need = ((last - first + 1) * N + S - 1) / S in integer division (1 <= need <= N) and bucket = the smallest b with c_b >= need; a dead
+    ray has bucket -1.  A ray of bucket b is meant to be rendered with c_b samples per level on [near', far'], so its coarse spacing is at
+    most the untightened ray's.  Segment b begins at base_0 = 0, base_{b+1} = round_up(base_b + count_b, 64) (`bucket_bases`); within a
+    bucket the rays keep their original order.  `rays`: 7 flat [n, k] fields, read as given (pass near' / far' as near / far); `out_rays`:
+    7 preallocated [n + 64 * B, k] fp32 fields, whose padding rows are never written; `slot` int32 [n]: the compact slot of every ray, -1
+    for a dead one.  Returns the list of the B counts: one read-back and one stream synchronisation per call, which is why the call cannot
+    be captured into a graph."""
+    import ctypes as C
+    n = int(live.numel())
+    lad = tuple(int(c) for c in ladder)
+    B = len(lad)
+    if not 1 <= B <= MAX_BUCKETS:
+        raise ValueError(f"bucket_rays: {LADDER_RULE}")
+    if live.dtype != torch.uint8 or not live.is_contiguous():
+        raise ValueError("bucket_rays: live is a contiguous uint8 tensor [n]")
+    for t, name in ((first, "first"), (last, "last"), (slot, "slot")):
+        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != live.device:
+            raise ValueError(f"bucket_rays: {name} is a contiguous int32 tensor [n] on the device of live")
+    rows = n + BUCKET_ALIGN * B
+    counts = (C.c_int64 * B)()
+    clad = (C.c_int32 * B)(*lad)
+    if n == 0:
+        L.check(L.lib().mipnerf_bucket_rays(0, None, None, None, int(span_samples), lad[-1], B, clad, None, None, None, None, 0, counts, None),
+                "bucket_rays")
+        return [0] * B
+    with torch.cuda.device(live.device):
+        need = int(L.lib().mipnerf_bucket_rays_workspace_bytes(n, B))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=live.device) if workspace is None else workspace
+        rp, keep = _rays_ptrs(rays, n, "bucket_rays")
+        for k, t in zip(type(out_rays)._fields, out_rays):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != live.device or t.dim() != 2 or t.shape[0] < rows \
+                    or t.shape[1] != getattr(rays, k).shape[-1]:
+                raise ValueError(f"bucket_rays: out_rays.{k} must be a contiguous fp32 device tensor with at least n + 64 * B = {rows} rows")
+        op = L.RaysPtrs(*[t.data_ptr() for t in out_rays])
+        L.check(L.lib().mipnerf_bucket_rays(n, _ptr(live), _ptr(first), _ptr(last), int(span_samples), lad[-1], B, clad, C.byref(rp), C.byref(op),
+                                            _ptr(slot), _ptr(ws), ws.numel(), counts, _stream()), "bucket_rays")
+    return [int(c) for c in counts]
+
+
+def gather_frame(slot, compact_outputs, full_outputs, near, white_bkgd):
+    """Writes every pixel of every level once (include/mipnerf_hip.h, mipnerf_gather_frame).  `compact_outputs` / `full_outputs`: per level
+    (rgb [m, 3], distance [m], acc [m]) with m = the rows of the compact buffers and m = n.  A pixel with slot >= 0 copies compact slot
+    `slot` (which must lie below the rows of the compact outputs); a pixel with slot < 0 gets the dead-pixel rule of `scatter_frame`:
+    rgb = 1 with `white_bkgd` else 0, acc = 0, distance = near, the ORIGINAL near."""
+    n = int(slot.numel())
+    if n == 0:
+        return
+    if slot.dtype != torch.int32 or not slot.is_contiguous() or not slot.is_cuda:
+        raise ValueError("gather_frame: slot is a contiguous int32 device tensor [n]")
+    nl = len(full_outputs)
+    if len(compact_outputs) != nl:
+        raise ValueError("gather_frame: compact and full outputs have different level counts")
+    comp, full = (L.LevelOut * nl)(), (L.LevelOut * nl)()
+    keep, rows = [], None
+    for l in range(nl):
+        for arr, outs, is_full in ((comp, compact_outputs[l], False), (full, full_outputs[l], True)):
+            rgb, dist, acc = outs
+            for t, width in ((rgb, 3), (dist, 1), (acc, 1)):
+                if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or (is_full and t.numel() < n * width):
+                    raise ValueError("gather_frame: outputs are contiguous fp32 device tensors; the full ones hold n rows")
+                if not is_full:
+                    rows = t.numel() // width if rows is None else min(rows, t.numel() // width)
+            arr[l] = L.LevelOut(rgb.data_ptr(), dist.data_ptr(), acc.data_ptr(), None, None)
+            keep += [rgb, dist, acc]
+    near = _f32c(near, "near")
+    if near.numel() < n:
+        raise ValueError("gather_frame: near holds one value per pixel")
+    with torch.cuda.device(slot.device):
+        L.check(L.lib().mipnerf_gather_frame(n, int(rows or 0), nl, _ptr(slot), _ptr(near), int(bool(white_bkgd)), comp if rows else None, full,
+                                             _stream()), "gather_frame")

@@ -27,10 +27,12 @@ CAMERA_ANGLE_X = 0.6911112070083618       # render_video.py --camera_angle_x def
 
 
 def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_angle_x=CAMERA_ANGLE_X, chunk_size=DEFAULT_CHUNK,
-                 white_bkgd=True, n_poses=120, use_graph=True, occupancy=None, tighten=False, span_samples=None):
+                 white_bkgd=True, n_poses=120, use_graph=True, occupancy=None, tighten=False, span_samples=None, adaptive=False,
+                 ladder=None):
     """render_video.py:run_render after the checkpoint is loaded.  Returns the output folder.  `occupancy` (an `ops.Occupancy`): rays
     that touch no occupied cell are not rendered (`model.CulledFrame`); None is the full path.  `tighten` / `span_samples` are
-    `CulledFrame`'s (live rays rendered on their occupied span; the frusta count of the classification) and need an `occupancy`."""
+    `CulledFrame`'s (live rays rendered on their occupied span; the frusta count of the classification) and need an `occupancy`; so do
+    `adaptive` / `ladder` (every live ray rendered with a sample count that follows its occupied span; implies `tighten`)."""
     from .datasets import RenderGen
     model = system.mip_nerf
     device = next(model.parameters()).device
@@ -40,7 +42,7 @@ def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_
     focal = .5 * base_size[0] / np.tan(.5 * camera_angle_x)
     dataset = RenderGen(focal, base_size, scale, device=device, n_poses=n_poses)
     nums = len(dataset) // scale
-    evaluators, shares, spans = {}, [], []
+    evaluators, shares, spans, samples = {}, [], [], []
     with torch.no_grad():
         for idx in range(len(dataset)):
             rays = dataset[idx]
@@ -48,20 +50,22 @@ def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_
             ev = evaluators.get((h, w))
             if ev is None:
                 ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten,
-                                                         span_samples=span_samples)
+                                                         span_samples=span_samples, adaptive=adaptive, ladder=ladder)
             images = ev.images(*ev.render(rays))
             if occupancy is not None:
                 shares.append(ev.frame.live_count / float(h * w))
-                if tighten:
+                if tighten or adaptive:
                     spans.append(ev.frame.span_share)
+                if adaptive:
+                    samples.append(ev.frame.sample_share)
             save_images(*images, os.path.join(folder, str(int(base_size[0] / w))), idx % nums)
     generate_video(folder)
-    report_live_share(shares, spans)
+    report_live_share(shares, spans, samples)
     return folder
 
 
 def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAULT_CHUNK, white_bkgd=False, use_graph=True, occupancy=None,
-                tighten=False, span_samples=None):
+                tighten=False, span_samples=None, adaptive=False, ladder=None):
     """The interpolated path through the poses of `dataset` (a `datasets.RealData360` split), every frame as in `render_video`.
     Returns the output folder."""
     from .datasets import PathGen
@@ -71,18 +75,21 @@ def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAU
     os.makedirs(os.path.join(folder, "1"), exist_ok=True)
     path = PathGen(dataset, n_views, device=device)
     h, w = path.sizes[0]
-    ev = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten, span_samples=span_samples)
-    shares, spans = [], []
+    ev = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten, span_samples=span_samples,
+                        adaptive=adaptive, ladder=ladder)
+    shares, spans, samples = [], [], []
     with torch.no_grad():
         for idx in range(len(path)):
             images = ev.images(*ev.render(path[idx]))
             if occupancy is not None:
                 shares.append(ev.frame.live_count / float(h * w))
-                if tighten:
+                if tighten or adaptive:
                     spans.append(ev.frame.span_share)
+                if adaptive:
+                    samples.append(ev.frame.sample_share)
             save_images(*images, os.path.join(folder, "1"), idx)
     generate_video(folder)
-    report_live_share(shares, spans)
+    report_live_share(shares, spans, samples)
     return folder
 
 
@@ -134,6 +141,14 @@ def add_common_args(p):
                    "samples sit elsewhere; the dropped parts of a ray lie only in cells the grid proves empty", action="store_true")
     p.add_argument("--cull_span_samples", help="--cull: coarse frusta per ray the classification uses (default: the checkpoint's num_samples)",
                    type=int, default=None)
+    p.add_argument("--cull_adaptive", help="--cull: render every live ray with a sample count that follows its occupied span (implies "
+                   "--cull_tighten): a ray whose span covers a quarter of its coarse frusta gets a quarter of the samples, on [near', far'], "
+                   "from the ladder of --cull_ladder.  Not the untightened frame.  Guaranteed: a ray's coarse sample spacing is never wider "
+                   "than the untightened frame's, and the parts of a ray it no longer samples lie only in cells the grid proves empty",
+                   action="store_true")
+    p.add_argument("--cull_ladder", help="--cull_adaptive: the sample counts to choose from, 1 to 8 strictly increasing values that end at the "
+                   "rendered count (default: the distinct values of ceil(N k / 4), k = 1..4: 32 64 96 128 for 128 samples)", type=int,
+                   nargs="+", default=None, metavar="C")
     p.add_argument("--render_samples", help="samples per ray and level to render with (default: the checkpoint's num_samples; the parameters do "
                    "not depend on it); independent of --cull", type=int, default=None)
     return p
@@ -147,6 +162,32 @@ def refuse_tighten_without_cull(args):
         raise SystemExit("--cull_space / --cull_far_radius describe the grid of --cull: give --cull as well")
     if getattr(args, "cull_far_radius", None) is not None and getattr(args, "cull_space", None) is None:
         raise SystemExit("--cull_far_radius belongs to --cull_space contracted")
+
+
+def refuse_adaptive_without_cull(args):
+    """--cull_adaptive is a way of culling and --cull_ladder belongs to it: anything else exits with a message before anything is loaded,
+    and so does a ladder that is not 1 to 8 strictly increasing counts from at least 1 (that it ends at the rendered count is checked by
+    `cli_ladder`, which knows the count)."""
+    from .ops import LADDER_RULE, MAX_BUCKETS
+    if getattr(args, "cull_adaptive", False) and not args.cull:
+        raise SystemExit("--cull_adaptive chooses the sample counts of the rays that --cull keeps: give --cull as well")
+    ladder = getattr(args, "cull_ladder", None)
+    if ladder is not None and not getattr(args, "cull_adaptive", False):
+        raise SystemExit("--cull_ladder lists the sample counts of --cull_adaptive: give --cull_adaptive as well")
+    if ladder is not None and not (1 <= len(ladder) <= MAX_BUCKETS and ladder[0] >= 1 and all(a < b for a, b in zip(ladder, ladder[1:]))):
+        raise SystemExit(f"--cull_ladder {' '.join(str(c) for c in ladder)}: {LADDER_RULE}")
+
+
+def cli_ladder(args, system):
+    """The validated ladder of --cull_adaptive against the count the system renders with (None without the flag); a bad one exits with
+    the rule in the message."""
+    if not getattr(args, "cull_adaptive", False):
+        return None
+    from .ops import sample_ladder
+    try:
+        return sample_ladder(int(system.mip_nerf.num_samples), args.cull_ladder)
+    except ValueError as e:
+        raise SystemExit(f"--cull_ladder: {e}")
 
 
 def cli_span_samples(args, system):
@@ -220,12 +261,14 @@ def load_system(args):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     refuse_tighten_without_cull(args)
+    refuse_adaptive_without_cull(args)
     if args.gen_video_only:
         if args.render_images_dir is None:
             raise SystemExit("only generate video, you must give the different scale image base dir (--render_images_dir)")
         return generate_video(args.render_images_dir)
     system = load_system(args)
     refuse_unbounded_cull(args, system)
+    ladder = cli_ladder(args, system)
     system = system.to(torch.device("cuda")).eval()
     hp = system.hparams
     if (args.path or ("interp" if is_scene360(hp) else "spheric")) == "interp":
@@ -244,7 +287,7 @@ def main(argv=None):
         return render_path(system, dataset, args.out_dir, hp["exp_name"], n_views=args.n_views, chunk_size=args.chunk_size,
                            white_bkgd=args.white_bkgd if flag_given(argv, "--white_bkgd") else bool(hp["val.white_bkgd"]),
                            use_graph=args.use_graph, occupancy=occupancy, tighten=args.cull_tighten,
-                           span_samples=cli_span_samples(args, system) if args.cull else None)
+                           span_samples=cli_span_samples(args, system) if args.cull else None, adaptive=args.cull_adaptive, ladder=ladder)
     occupancy = None
     if args.cull:
         from .datasets import RenderGen
@@ -254,7 +297,7 @@ def main(argv=None):
     return render_video(system, args.out_dir, system.hparams["exp_name"], args.scale, base_size=args.base_size,
                         camera_angle_x=args.camera_angle_x, chunk_size=args.chunk_size, white_bkgd=args.white_bkgd,
                         n_poses=args.n_poses, use_graph=args.use_graph, occupancy=occupancy, tighten=args.cull_tighten,
-                        span_samples=cli_span_samples(args, system) if args.cull else None)
+                        span_samples=cli_span_samples(args, system) if args.cull else None, adaptive=args.cull_adaptive, ladder=ladder)
 
 
 if __name__ == "__main__":
