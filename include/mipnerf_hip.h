@@ -257,6 +257,44 @@ int mipnerf_gather_train_batch(int64_t batch_size, int64_t n_order, const int64_
                                const int64_t* offsets, const float* cameras, const float* pixels, const int64_t* step,
                                const int64_t* epoch_base, const mipnerf_rays_out* out, float* gt, void* stream);
 
+/* ---- error-guided batch sampling (train_guided.TrainGuided): which pixels a training batch holds --------------------------------
+ * Every training image is cut into tiles of T x T pixels (smaller at the right and bottom edges); the tiles are the CELLS, numbered
+ * image by image, row-major inside an image.  `table` (device, int64 [n_images + 1][4]): row i = (first cell of image i, first pixel of
+ * image i, W_i, H_i), the last row = (n_cells, N = pixel count, 0, 0).  Cell c has n_c pixels.  State per cell: err (float, starts at 1),
+ * sum (uint64), cnt (uint32), seen (uint8), q and cdf (uint32).  header (device, 4 x uint64): Q, A, cells visited since the start, n_cells.
+ * The rule, integers wherever a sum crosses cells, so two runs give the same bytes:
+ *   per draw    se = ((d0 d0) + d1 d1) + d2 d2 in float32 without contraction, d = rgb - gt; fx = (uint64) floor((double) se 2^24 + 0.5);
+ *               a draw whose se is not finite or negative is not counted; sum_c += fx, cnt_c += 1 (integer vector atomics)
+ *   fold        per cell with cnt_c > 0: mean = (float)(((double) sum_c / (double) cnt_c) 2^-24), err_c += rate (mean - err_c) in float32
+ *               without contraction, seen_c = 1; then sum_c = cnt_c = 0
+ *   mass        ef_c = (uint64) floor((double) err_c 2^20 + 0.5), a_c = n_c ef_c, A = sum a_c; share_c = (double) n_c / (double) N;
+ *               p_c = (1 - mix) share_c + mix (A > 0 ? (double) a_c / (double) A : share_c) in float64, in this order;
+ *               q_c = max(1, (uint64) floor(p_c 2^30)); cdf = inclusive integer scan of q, Q = cdf[n_cells - 1] (< 2^31: n_cells < 2^30)
+ *   draw j      from two integers r0 = r[j], r1 = r[n_draws + j] in [0, 2^32) (int64): t = (r0 Q) >> 32, c = the first cell with cdf[c] > t,
+ *               k = (r1 n_c) >> 32, the pixel is column x0 + k % w_c, row y0 + k / w_c of the cell; order[j] = first pixel of the image +
+ *               y W + x; slot = (ring_start + j) % ring_len; weight[slot] = (float)(share_c / ((double) q_c / (double) Q)), cell[slot] = c
+ * so a pixel is drawn with probability q_c / (Q n_c) to within 2^-32 / n_c, sum_c P_c w_c = 1 to float32 rounding and
+ * w <= (1 + 1e-5) / (1 - mix).
+ * mipnerf_guided_apply: lossmult[i] *= weight[(b batch_size + i) % ring_len] for the rays i of batch b; mipnerf_guided_accumulate: the
+ * per-draw line above for ray i into cell[(b batch_size + i) % ring_len] (a ring entry outside [0, n_cells) is skipped).  Both take
+ * b = *step - *epoch_base from the device, as mipnerf_gather_train_batch does, or, with step == NULL, b = host_batch; a ray with b < 0 or
+ * b batch_size + i >= n_order is left alone.  Neither allocates or synchronises: capturable.
+ * mipnerf_guided_refresh: fold + mass + scan in place (block totals, one single-workgroup pass over them, apply: no workgroup reads what
+ * another wrote in the same launch), then the header.  scratch: at least 2 ceil(n_cells / 256) + 2 uint64 words.  0 <= mix < 1,
+ * 0 < rate <= 1, 1 <= n_cells < 2^30.  mipnerf_guided_draw reads Q from the header on the device; n_draws = 0 returns without a launch.
+ * Neither allocates or synchronises. */
+int mipnerf_guided_apply(int64_t batch_size, int64_t n_order, int64_t ring_len, const float* weight, const int64_t* step,
+                         const int64_t* epoch_base, int64_t host_batch, float* lossmult, void* stream);
+int mipnerf_guided_accumulate(int64_t batch_size, int64_t n_order, int64_t ring_len, const int32_t* cell, int64_t n_cells,
+                              const int64_t* step, const int64_t* epoch_base, int64_t host_batch, const float* rgb, const float* gt,
+                              uint64_t* sum, uint32_t* cnt, void* stream);
+int mipnerf_guided_refresh(int32_t n_images, const int64_t* table, int32_t tile, int64_t n_cells, float rate, double mix, float* err,
+                           uint64_t* sum, uint32_t* cnt, uint8_t* seen, uint32_t* q, uint32_t* cdf, uint64_t* scratch,
+                           size_t scratch_words, uint64_t* header, void* stream);
+int mipnerf_guided_draw(int64_t n_draws, const int64_t* r, int32_t n_images, const int64_t* table, int32_t tile, int64_t n_cells,
+                        const uint32_t* cdf, const uint64_t* header, int64_t* order, float* weight, int32_t* cell, int64_t ring_len,
+                        int64_t ring_start, void* stream);
+
 /* ---- unbounded scenes (mip-NeRF 360) --------------------------------------------------------------------------------
  * Correct versions of what the reference's dead code aims at (models/mip.py:106-124 sample_along_rays_360, :38-47 full
  * lift_gaussian, :424-447 contract / parameterization, :292-319 integrated_pos_enc_360); they follow Barron et al.,

@@ -111,6 +111,10 @@ SIGNATURES = {
     "mipnerf_bucket_rays": (C.c_int, [_I64, _P, _P, _P, _I32, _I32, _I32, C.POINTER(_I32), C.POINTER(RaysPtrs), C.POINTER(RaysPtrs), _P, _P, _SZ,
                                       C.POINTER(_I64), _P]),
     "mipnerf_gather_frame": (C.c_int, [_I64, _I64, _I32, _P, _P, _I32, C.POINTER(LevelOut), C.POINTER(LevelOut), _P]),
+    "mipnerf_guided_apply": (C.c_int, [_I64, _I64, _I64, _P, _P, _P, _I64, _P, _P]),
+    "mipnerf_guided_accumulate": (C.c_int, [_I64, _I64, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "mipnerf_guided_refresh": (C.c_int, [_I32, _P, _I32, _I64, _F, C.c_double, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
+    "mipnerf_guided_draw": (C.c_int, [_I64, _P, _I32, _P, _I32, _I64, _P, _P, _P, _P, _P, _I64, _I64, _P]),
     "mipnerf_activate": (C.c_int, [_I64, _P, _F, _F, _P, _F, _P, _P]),
     "mipnerf_volumetric_rendering_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _F, _P, _P]),
     "mipnerf_distloss": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P]),

@@ -52,6 +52,7 @@ UNITS = [
     ("kernels_mesh.hip", ["-ffp-contract=off"]),        # lattice means lo + float(i) * h and the shared IPE round as stated in the header
     ("kernels_occupancy.hip", ["-ffp-contract=off"]),   # frustum end points o + t * d and floor((x - lo) / h) round as stated in the header
     ("kernels_bucket.hip", []),                         # integer ranks and copies only: no floating-point arithmetic to contract
+    ("kernels_guided.hip", ["-ffp-contract=off"]),      # err + rate * (mean - err) and the float64 mixture round as stated in the header
     ("selftest.hip", ["-ffp-contract=off"]),
     ("capi.hip", []),
 ]

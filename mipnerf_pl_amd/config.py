@@ -78,6 +78,50 @@ def train_occupancy_settings(config):
     return s
 
 
+# Error-guided batch sampling (train_guided.TrainGuided): not reference keys either, read with `train_guided_settings`.  `tile` (pixels),
+# `interval` (steps between two refreshes of the map), `mix` (lambda: the share of a batch drawn in proportion to the error) and `rate`
+# (alpha of the running error) are choices, not measurements of this project.
+TRAIN_GUIDED_DEFAULTS = {
+    'train.guided.enabled': False, 'train.guided.tile': 16, 'train.guided.interval': 64, 'train.guided.mix': 0.5, 'train.guided.rate': 0.25,
+}
+
+
+def train_guided_settings(config):
+    """The `train.guided.*` keys of a configuration without the prefix, TRAIN_GUIDED_DEFAULTS where a key is absent.  Refused: an unknown
+    `train.guided.*` key, tile < 1, interval < 1, mix outside [0, 1), rate outside (0, 1]."""
+    n = len('train.guided.')
+    s = {k[n:]: config.get(k, v) for k, v in TRAIN_GUIDED_DEFAULTS.items()}
+    unknown = sorted(k for k in config if str(k).startswith('train.guided.') and k not in TRAIN_GUIDED_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown key(s) {unknown}; train.guided has {sorted(TRAIN_GUIDED_DEFAULTS)}")
+    s['enabled'] = bool(s['enabled'])
+    s['tile'], s['interval'] = int(s['tile']), int(s['interval'])
+    s['mix'], s['rate'] = float(s['mix']), float(s['rate'])
+    if s['tile'] < 1:
+        raise ValueError(f"train.guided.tile must be at least 1 pixel (got {s['tile']})")
+    if s['interval'] < 1:
+        raise ValueError(f"train.guided.interval must be at least 1 step (got {s['interval']})")
+    if not 0.0 <= s['mix'] < 1.0:
+        raise ValueError(f"train.guided.mix must be in [0, 1) (got {s['mix']})")
+    if not 0.0 < s['rate'] <= 1.0:
+        raise ValueError(f"train.guided.rate must be in (0, 1] (got {s['rate']})")
+    return s
+
+
+def check_train_guided(config):
+    """`train_guided_settings(config)`, and with the sampler enabled the configurations it does not serve are refused by key: more than
+    one rank (one map per run; no collective is built) and a loss that ignores `lossmult` (the importance weights ride on it)."""
+    s = train_guided_settings(config)
+    if s['enabled']:
+        if int(config.get('num_gpus', 1)) > 1:
+            raise NotImplementedError(f"train.guided.enabled needs num_gpus 1 (got num_gpus {config.get('num_gpus')}): the error map is "
+                                      "kept per run and is not shared between ranks")
+        if config.get('loss.disable_multiscale_loss', False):
+            raise ValueError("train.guided.enabled cannot be combined with loss.disable_multiscale_loss True: that loss ignores the "
+                             "per-ray lossmult, which carries the importance weights")
+    return s
+
+
 def parse_value(v):
     """One leaf: a string through ast.literal_eval when it parses, a list as a tuple."""
     if isinstance(v, str):

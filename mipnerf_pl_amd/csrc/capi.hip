@@ -771,6 +771,61 @@ int mipnerf_gather_train_batch(int64_t batch_size, int64_t n_order, const int64_
     return MIPNERF_OK;
 }
 
+// ---- error-guided batch sampling (kernels_guided.hip) --------------------------------------------------------------------------
+int mipnerf_guided_apply(int64_t batch_size, int64_t n_order, int64_t ring_len, const float* weight, const int64_t* step,
+                         const int64_t* epoch_base, int64_t host_batch, float* lossmult, void* stream) {
+    if (batch_size < 1 || n_order < 0 || ring_len < 1 || !weight || !lossmult)
+        return fail(MIPNERF_E_INVALID, "guided_apply: bad argument");
+    if ((step == nullptr) != (epoch_base == nullptr))
+        return fail(MIPNERF_E_INVALID, "guided_apply: step and epoch_base must both be given (device batch index) or both null (host_batch)");
+    HIP_TRY(mip::launch_guided_apply(batch_size, n_order, ring_len, weight, step, epoch_base, host_batch, lossmult, S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_guided_accumulate(int64_t batch_size, int64_t n_order, int64_t ring_len, const int32_t* cell, int64_t n_cells,
+                              const int64_t* step, const int64_t* epoch_base, int64_t host_batch, const float* rgb, const float* gt,
+                              uint64_t* sum, uint32_t* cnt, void* stream) {
+    if (batch_size < 1 || n_order < 0 || ring_len < 1 || n_cells < 1 || !cell || !rgb || !gt || !sum || !cnt)
+        return fail(MIPNERF_E_INVALID, "guided_accumulate: bad argument");
+    if ((step == nullptr) != (epoch_base == nullptr))
+        return fail(MIPNERF_E_INVALID, "guided_accumulate: step and epoch_base must both be given (device batch index) or both null (host_batch)");
+    HIP_TRY(mip::launch_guided_accumulate(batch_size, n_order, ring_len, cell, n_cells, step, epoch_base, host_batch, rgb, gt,
+                                          reinterpret_cast<unsigned long long*>(sum), cnt, S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_guided_refresh(int32_t n_images, const int64_t* table, int32_t tile, int64_t n_cells, float rate, double mix, float* err,
+                           uint64_t* sum, uint32_t* cnt, uint8_t* seen, uint32_t* q, uint32_t* cdf, uint64_t* scratch,
+                           size_t scratch_words, uint64_t* header, void* stream) {
+    if (n_images < 1 || !table || tile < 1 || !err || !sum || !cnt || !seen || !q || !cdf || !scratch || !header)
+        return fail(MIPNERF_E_INVALID, "guided_refresh: bad argument");
+    if (n_cells < 1 || n_cells >= ((int64_t)1 << 30))
+        return fail(MIPNERF_E_INVALID, "guided_refresh: n_cells must be in [1, 2^30) (got %lld)", (long long)n_cells);
+    if (!(rate > 0.0f && rate <= 1.0f)) return fail(MIPNERF_E_INVALID, "guided_refresh: rate must be in (0, 1] (got %g)", (double)rate);
+    if (!(mix >= 0.0 && mix < 1.0)) return fail(MIPNERF_E_INVALID, "guided_refresh: mix must be in [0, 1) (got %g)", mix);
+    if (scratch_words < (size_t)(2 * mip::guided_num_blocks(n_cells) + 2))
+        return fail(MIPNERF_E_WORKSPACE, "guided_refresh: scratch holds %zu words, %lld are needed", scratch_words,
+                    (long long)(2 * mip::guided_num_blocks(n_cells) + 2));
+    HIP_TRY(mip::launch_guided_refresh(n_images, table, tile, n_cells, rate, mix, err, reinterpret_cast<unsigned long long*>(sum), cnt, seen, q,
+                                       cdf, reinterpret_cast<unsigned long long*>(scratch), reinterpret_cast<unsigned long long*>(header),
+                                       S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_guided_draw(int64_t n_draws, const int64_t* r, int32_t n_images, const int64_t* table, int32_t tile, int64_t n_cells,
+                        const uint32_t* cdf, const uint64_t* header, int64_t* order, float* weight, int32_t* cell, int64_t ring_len,
+                        int64_t ring_start, void* stream) {
+    if (n_draws < 0 || n_images < 1 || !table || tile < 1 || n_cells < 1 || n_cells >= ((int64_t)1 << 30) || !cdf || !header || !weight ||
+        !cell || ring_len < 1 || ring_start < 0)
+        return fail(MIPNERF_E_INVALID, "guided_draw: bad argument");
+    if (n_draws > ring_len) return fail(MIPNERF_E_INVALID, "guided_draw: %lld draws do not fit a ring of %lld", (long long)n_draws, (long long)ring_len);
+    if (n_draws == 0) return MIPNERF_OK;
+    if (!r || !order) return fail(MIPNERF_E_INVALID, "guided_draw: null argument");
+    HIP_TRY(mip::launch_guided_draw(n_draws, r, n_images, table, tile, n_cells, cdf, reinterpret_cast<const unsigned long long*>(header), order,
+                                    weight, cell, ring_len, ring_start, S(stream)));
+    return MIPNERF_OK;
+}
+
 // ---- evaluation metrics (utils/metrics.py:191-197) ---------------------------------------------------------------
 int64_t mipnerf_eval_workspace_floats(int32_t height, int32_t width) {
     return height > 0 && width > 0 ? mip::eval_errors_partial_floats(height, width) : 0;

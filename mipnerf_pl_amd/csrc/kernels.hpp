@@ -323,6 +323,21 @@ hipError_t launch_gather_frame(int64_t n, int64_t rows, int num_levels, const in
                                const float* const c_rgb[], const float* const c_dist[], const float* const c_acc[], float* const f_rgb[],
                                float* const f_dist[], float* const f_acc[], hipStream_t st);
 
+// ---- kernels_guided.hip (error-guided batch sampling: include/mipnerf_hip.h, mipnerf_guided_*) ------------------------------
+// table [n_images + 1][4] int64 (first cell, first pixel, W, H; last row n_cells, n_pixels, 0, 0); header [4] 64-bit words: Q, A, cells visited, n_cells
+int64_t guided_num_blocks(int64_t n_cells);      // scratch holds guided_num_blocks(n_cells) 64-bit words followed by twice as many 32-bit words
+hipError_t launch_guided_apply(int64_t B, int64_t n_order, int64_t ring, const float* weight, const int64_t* step, const int64_t* epoch_base,
+                               int64_t host_batch, float* lossmult, hipStream_t st);
+hipError_t launch_guided_accumulate(int64_t B, int64_t n_order, int64_t ring, const int* cell, int64_t n_cells, const int64_t* step,
+                                    const int64_t* epoch_base, int64_t host_batch, const float* rgb, const float* gt,
+                                    unsigned long long* sum, unsigned* cnt, hipStream_t st);
+hipError_t launch_guided_refresh(int n_images, const int64_t* table, int T, int64_t n_cells, float rate, double mix, float* err,
+                                 unsigned long long* sum, unsigned* cnt, unsigned char* seen, unsigned* q, unsigned* cdf,
+                                 unsigned long long* scratch, unsigned long long* header, hipStream_t st);
+hipError_t launch_guided_draw(int64_t n, const int64_t* r, int n_images, const int64_t* table, int T, int64_t n_cells, const unsigned* cdf,
+                              const unsigned long long* header, int64_t* order, float* weight, int* cell, int64_t ring, int64_t ring_start,
+                              hipStream_t st);
+
 // ---- selftest.hip -------------------------------------------------------------------------------
 // returns 0 if the MFMA fragment layouts and the LDS-DMA path behave as the kernels assume;
 // otherwise a bit mask (1: bf16 32x32x16 layout, 2: f32 32x32x2 layout, 4: global_load_lds)

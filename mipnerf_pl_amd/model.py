@@ -608,6 +608,10 @@ class MipNerf(torch.nn.Module):
                         torch.empty(B, N, device=dev), torch.empty(B, N + 1, device=dev))
                 outs[lvl] = L.LevelOut(*[t.data_ptr() for t in tens])
                 ret.append(tens)
+        elif getattr(self, "keep_fine_rgb", False):      # the fine level's colours alone, for a caller that records the step's errors
+            self.last_fine_rgb = torch.empty(B, 3, device=dev)
+            outs = (L.LevelOut * self.num_levels)()
+            outs[self.num_levels - 1] = L.LevelOut(self.last_fine_rgb.data_ptr(), None, None, None, None)
         flags = L.FLAG_WHITE_BKGD if white_bkgd else 0
         L.check(L.lib().mipnerf_train_step(ctx.handle, B, C.byref(rp), gt.data_ptr(), t_rand.data_ptr() if randomized else None,
                                            u_rand.data_ptr() if randomized else None, None if dz is None else dz.data_ptr(),

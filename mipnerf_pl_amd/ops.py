@@ -1045,3 +1045,104 @@ def gather_frame(slot, compact_outputs, full_outputs, near, white_bkgd):
     with torch.cuda.device(slot.device):
         L.check(L.lib().mipnerf_gather_frame(n, int(rows or 0), nl, _ptr(slot), _ptr(near), int(bool(white_bkgd)), comp if rows else None, full,
                                              _stream()), "gather_frame")
+
+
+# ---------------------------------------------------------------------------------------------
+# error-guided batch sampling (include/mipnerf_hip.h, mipnerf_guided_*; train_guided.TrainGuided)
+# ---------------------------------------------------------------------------------------------
+GUIDED_BLOCK = 256      # cells per workgroup of the refresh kernels (csrc/kernels_guided.hip): sizes the scratch words
+
+
+class GuidedState:
+    """The device state of one error map: `table` int64 [n_images + 1, 4] (first cell, first pixel, W, H; last row n_cells, N, 0, 0), per
+    cell `err` fp32 (ones), `sum` int64 and `cnt` int32 (the bits of the uint64 / uint32 counters), `seen` uint8, `q` / `cdf` int32, the
+    `scratch` words and the `header` int64 [4] = Q, A, cells visited, n_cells of the last refresh; the rings `weight` fp32 / `cell` int32
+    of length `ring_len`.  `table`: a [n_images + 1, 4] integer array (`train_guided.cell_table`)."""
+
+    def __init__(self, table, tile, ring_len, device):
+        t = torch.as_tensor(table, dtype=torch.int64).reshape(-1, 4)
+        if t.shape[0] < 2 or int(tile) < 1 or int(ring_len) < 1:
+            raise ValueError("GuidedState: needs at least one image, tile >= 1 and ring_len >= 1")
+        self.dev = torch.device(device)
+        self.tile, self.ring_len = int(tile), int(ring_len)
+        self.n_images, self.n_cells, self.n_pixels = t.shape[0] - 1, int(t[-1, 0]), int(t[-1, 1])
+        if not 1 <= self.n_cells < (1 << 30):
+            raise ValueError(f"GuidedState: the table has {self.n_cells} cells; 1 .. 2^30 - 1 are supported")
+        self.table = t.to(self.dev).contiguous()
+        n, z = self.n_cells, dict(device=self.dev)
+        self.err = torch.ones(n, dtype=torch.float32, **z)
+        self.sum = torch.zeros(n, dtype=torch.int64, **z)
+        self.cnt = torch.zeros(n, dtype=torch.int32, **z)
+        self.seen = torch.zeros(n, dtype=torch.uint8, **z)
+        self.q = torch.zeros(n, dtype=torch.int32, **z)
+        self.cdf = torch.zeros(n, dtype=torch.int32, **z)
+        self.scratch = torch.zeros(2 * ((n + GUIDED_BLOCK - 1) // GUIDED_BLOCK) + 2, dtype=torch.int64, **z)
+        self.header = torch.zeros(4, dtype=torch.int64, **z)
+        self.weight = torch.ones(self.ring_len, dtype=torch.float32, **z)
+        self.cell = torch.zeros(self.ring_len, dtype=torch.int32, **z)
+
+
+def _guided_batch(who, state, rows, tensors, n_order, step, epoch_base, batch, batch_size):
+    """(B, step pointer, epoch_base pointer, host batch index) of a guided_apply / guided_accumulate call, checked."""
+    for name, t, dtype, width in tensors:
+        if not (t.is_cuda and t.device == state.dev and t.dtype == dtype and t.is_contiguous()) or t.numel() != rows * width:
+            raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of {rows} x {width} values on {state.dev}")
+    if (step is None) != (epoch_base is None):
+        raise ValueError(f"{who}: step and epoch_base go together")
+    for name, t in (("step", step), ("epoch_base", epoch_base)):
+        if t is not None and not (t.is_cuda and t.device == state.dev and t.dtype == torch.int64 and t.numel() >= 1):
+            raise ValueError(f"{who}: {name} must be an int64 tensor on {state.dev}")
+    B = rows if batch_size is None else int(batch_size)
+    if B != rows and (step is not None or B < rows or int(n_order) - int(batch) * B > rows):
+        raise ValueError(f"{who}: a batch of {B} rays in buffers of {rows} needs a host batch index whose rays end with the order")
+    return B, _ptr(step), _ptr(epoch_base), int(batch)
+
+
+def guided_apply(state, lossmult, n_order, step=None, epoch_base=None, batch=0, batch_size=None):
+    """lossmult[i] *= state.weight[(b * B + i) % ring_len] IN PLACE for the rays of batch b: b = step[0] - epoch_base[0] read on the device
+    (capturable), or, without them, the host's `batch`.  A ray with b < 0 or b * B + i >= n_order is left alone.  `batch_size`: B when
+    `lossmult` holds fewer rows (the epoch's short last batch)."""
+    B, sp, ep, b = _guided_batch("guided_apply", state, lossmult.shape[0], [("lossmult", lossmult, torch.float32, 1)], n_order, step,
+                                 epoch_base, batch, batch_size)
+    with torch.cuda.device(state.dev):
+        L.check(L.lib().mipnerf_guided_apply(B, int(n_order), state.ring_len, _ptr(state.weight), sp, ep, b, _ptr(lossmult), _stream()),
+                "guided_apply")
+    return lossmult
+
+
+def guided_accumulate(state, rgb, gt, n_order, step=None, epoch_base=None, batch=0, batch_size=None):
+    """The squared error of every ray of batch b (rgb, gt [rows, 3] fp32) into state.sum / state.cnt of the cell its ring slot names:
+    integer adds, so two runs give the same bytes.  Batch index as in `guided_apply`."""
+    B, sp, ep, b = _guided_batch("guided_accumulate", state, rgb.shape[0], [("rgb", rgb, torch.float32, 3), ("gt", gt, torch.float32, 3)],
+                                 n_order, step, epoch_base, batch, batch_size)
+    with torch.cuda.device(state.dev):
+        L.check(L.lib().mipnerf_guided_accumulate(B, int(n_order), state.ring_len, _ptr(state.cell), state.n_cells, sp, ep, b, _ptr(rgb),
+                                                  _ptr(gt), _ptr(state.sum), _ptr(state.cnt), _stream()), "guided_accumulate")
+
+
+def guided_refresh(state, rate, mix):
+    """Fold state.sum / state.cnt into state.err (rate = alpha), zero them, and rebuild state.q / state.cdf for the mixture `mix` (lambda),
+    all IN PLACE; state.header receives Q, A, the cells visited since the start and n_cells.  No synchronisation."""
+    with torch.cuda.device(state.dev):
+        L.check(L.lib().mipnerf_guided_refresh(state.n_images, _ptr(state.table), state.tile, state.n_cells, float(rate), float(mix),
+                                               _ptr(state.err), _ptr(state.sum), _ptr(state.cnt), _ptr(state.seen), _ptr(state.q),
+                                               _ptr(state.cdf), _ptr(state.scratch), state.scratch.numel(), _ptr(state.header), _stream()),
+                "guided_refresh")
+    return state
+
+
+def guided_draw(state, r, order, ring_start=0):
+    """`order[j]` = the pixel id of draw j from the integers r[0, j], r[1, j] in [0, 2^32) (int64 [2, n]) and the cdf of the last refresh;
+    the rings take the draw's importance weight and cell at slot (ring_start + j) % ring_len.  `order`: a contiguous int64 tensor (or
+    slice) of n entries, written IN PLACE."""
+    n = int(order.numel())
+    for name, t, numel in (("r", r, 2 * n), ("order", order, n)):
+        if not (t.is_cuda and t.device == state.dev and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == numel):
+            raise ValueError(f"guided_draw: {name} must be a contiguous int64 tensor of {numel} entries on {state.dev}")
+    if n > state.ring_len or int(ring_start) < 0:
+        raise ValueError(f"guided_draw: {n} draws do not fit a ring of {state.ring_len}")
+    with torch.cuda.device(state.dev):
+        L.check(L.lib().mipnerf_guided_draw(n, _ptr(r), state.n_images, _ptr(state.table), state.tile, state.n_cells, _ptr(state.cdf),
+                                            _ptr(state.header), _ptr(order), _ptr(state.weight), _ptr(state.cell), state.ring_len,
+                                            int(ring_start), _stream()), "guided_draw")
+    return order

@@ -22,6 +22,13 @@ monitor='val/psnr', mode='max', save_top_k=2)` of Lightning 1.5 do for `MipNeRFS
   samples each ray on its occupied span [near', far'] of `ops.ray_span` instead of [near, far]; a ray that touches nothing keeps
   [near, far].  metrics.csv gains `train/live_share` and `train/span_share`, the checkpoint's `mipnerf_trainer` entry gains `occupancy`
   (the running lattice and its settings) and a resumed run continues exactly.  Validation frames stay un-culled.
+* `train.guided.enabled True` (off by default; `config.TRAIN_GUIDED_DEFAULTS`): error-guided batches.  The epoch's permutation is not
+  drawn; before every batch b of an epoch with b % `train.guided.interval` == 0 a `train_guided.TrainGuided` folds the errors of the last
+  batches into its per-tile map and draws the pixel ids of the next `interval` batches into the order buffer (outside the graph, same
+  stream); every step -- the captured one through `GraphedTrainStep(guided=...)`, the eager ones through `ops.guided_apply` /
+  `ops.guided_accumulate` with the host's batch index -- multiplies `lossmult` by the draws' importance weights and records the fine
+  level's squared errors.  metrics.csv gains `train/guided_ess` and `train/guided_visited`, the checkpoint's `mipnerf_trainer` entry gains
+  `guided` and a resumed run continues exactly.  Refused: `num_gpus` > 1 and `loss.disable_multiscale_loss True`.
 * num_gpus > 1: the command starts one child process per rank (nccl when every rank has its own device, gloo otherwise); rank 0 alone
   logs and writes checkpoints.
 
@@ -258,6 +265,9 @@ class Trainer:
     def __init__(self, hparams, precision="bf16", use_graph=True, log_every_n_steps=50, rank=0, world=1, device=None, verbose=True):
         from .system import MipNeRFSystem
         self.hp = hp = dict(hparams)
+        guided = cfg.check_train_guided(hp)["enabled"]        # refusals by key, before anything touches the device
+        if guided and int(world) > 1:
+            raise NotImplementedError("train.guided.enabled needs num_gpus 1: the error map is kept per run and is not shared between ranks")
         self.rank, self.world = int(rank), int(world)
         self.verbose = verbose and self.rank == 0
         self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -275,6 +285,7 @@ class Trainer:
         self.topk = TopK(2)
         self._resume_ckpt = None
         self.occ, self._span = None, None
+        self.guided, self._guided_sd = None, None
         if cfg.train_occupancy_settings(hp)["enabled"]:
             from .train_occupancy import TrainOccupancy, check_spaces
             self.occ = TrainOccupancy.for_system(system, hp, self.dev)
@@ -293,6 +304,14 @@ class Trainer:
         self.spe = steps_per_epoch(len(ds), self.B, self.world)
         self.last_bs = last_batch_size(len(ds), self.B, self.world)
         self.order = torch.zeros(self.n_local, dtype=torch.int64, device=self.dev)
+        if guided:
+            from .train_guided import TrainGuided
+            self.guided = TrainGuided.for_system(system, hp, self.dev)
+            if self._guided_sd is not None:
+                self.guided.load_state_dict(self._guided_sd, self.order)
+            # the eager routes record the fine level's colours: the one-call native step copies them out, the autograd route's forward hands them over
+            system.mip_nerf.keep_fine_rgb = True
+            system.mip_nerf.register_forward_hook(lambda m, args, ret: setattr(m, "last_fine_rgb", ret[-1][0].detach()))
         self.gstep = None
         if self.graph_route:
             self._make_graph_step()
@@ -301,7 +320,8 @@ class Trainer:
         if self.rank == 0:
             os.makedirs(self.ckpt_dir, exist_ok=True)
             self.logger = CSVLog(os.path.join(hp["out_dir"], "logs"), hp["exp_name"], hp,
-                                 extra_columns=self.SPAN_COLUMNS if self.occ is not None else ())
+                                 extra_columns=(self.SPAN_COLUMNS if self.occ is not None else ())
+                                 + (self.guided.COLUMNS if self.guided is not None else ()))
 
     # -- set-up ------------------------------------------------------------------------------------------------------
     def _make_graph_step(self):
@@ -318,6 +338,8 @@ class Trainer:
             ops.gather_train_batch(self.order, d["offsets"], d["cameras"], d["pixels"], opt._dev_step, self.epoch_base,
                                    step.rays, step.gt)
         occ = {} if self.occ is None else dict(occupancy=self.occ.occupancy, span_samples=self.occ.span_samples)
+        if self.guided is not None:
+            occ.update(guided=self.guided.state, guided_index=(opt._dev_step, self.epoch_base, self.n_local))
         step = GraphedTrainStep(self.system, opt, self.B, self.dev, use_graph=True, batch_source=batch_source, **occ)
         self.gstep = step
 
@@ -338,6 +360,7 @@ class Trainer:
             self.topk.load_state_dict(own["topk"])
             if self.occ is not None and own.get("occupancy") is not None:
                 self.occ.load_state_dict(own["occupancy"])
+            self._guided_sd = own.get("guided")         # loaded once the order buffer exists
             rng = own["rng"]
             torch.set_rng_state(rng["torch"])
             torch.cuda.set_rng_state(rng["cuda"], self.dev)
@@ -380,6 +403,9 @@ class Trainer:
         system, opt = self.system, self.opt
         ids = self.order[b * self.B:b * self.B + bs]
         batch = system.train_dataset.rays_at(ids)
+        if self.guided is not None:
+            from . import ops
+            ops.guided_apply(self.guided.state, batch[0].lossmult, self.n_local, batch=b, batch_size=self.B)
         if self.occ is not None:
             batch = self._tighten(batch)
         opt.zero_grad()
@@ -392,6 +418,9 @@ class Trainer:
                 p.grad = None
             loss = system.training_step(batch, b)
             loss.backward()
+        if self.guided is not None:
+            gt = batch[1][..., :3].contiguous()
+            ops.guided_accumulate(self.guided.state, system.mip_nerf.last_fine_rgb.contiguous(), gt, self.n_local, batch=b, batch_size=self.B)
         if self.world > 1:
             import torch.distributed as dist
             system.mip_nerf.mlp.gather_foreign_grads()
@@ -452,6 +481,8 @@ class Trainer:
         """Lightning 1.5's checkpoint dict, plus the trainer's own position / RNG states / top-k record."""
         sched = self.sched.state_dict()
         occ = {} if self.occ is None else {"occupancy": self.occ.state_dict()}
+        if self.guided is not None:
+            occ["guided"] = self.guided.state_dict(self.order)
         return {"epoch": self.epoch, "global_step": self.global_step, "pytorch-lightning_version": PL_VERSION,
                 "state_dict": _cpu(self.system.state_dict()), "callbacks": {},
                 "optimizer_states": [_cpu(self.opt.state_dict())], "lr_schedulers": [_cpu(sched)],
@@ -489,8 +520,9 @@ class Trainer:
             torch.cuda.set_rng_state(states[1], self.dev)
         t0 = time.time()
         while self.global_step < stop:
-            order = epoch_order(len(ds), int(hp["seed"]), self.epoch, self.rank, self.world, ds.device)
-            self.order.copy_(order)
+            if self.guided is None:     # (a guided run draws its order segment by segment, below)
+                order = epoch_order(len(ds), int(hp["seed"]), self.epoch, self.rank, self.world, ds.device)
+                self.order.copy_(order)
             if self.graph_route:
                 self.epoch_base.fill_(self.opt.steps - self.batch)
             for b in range(self.batch, self.spe):
@@ -498,6 +530,8 @@ class Trainer:
                     break
                 if self.occ is not None and (self.occ.refresh_due(self.global_step) or self.occ.refreshes == 0):
                     self.occ.refresh(self.system)       # from the field as it is BEFORE this step; the first one from the untrained field
+                if self.guided is not None and self.guided.refresh_due(b):
+                    self.guided.refresh(self.order, b, self.B, self.n_local)      # the errors up to batch b - 1; the ids of batches b .. b + interval - 1
                 loss, psnr = self._step(b)
                 self.sched.step()
                 self.global_step += 1
@@ -509,6 +543,8 @@ class Trainer:
                     row = {"lr": lr, "train/loss": float(loss), "train/psnr": float(psnr)}
                     if self.occ is not None:
                         row.update(zip(self.SPAN_COLUMNS, self._span_stats()))
+                    if self.guided is not None:
+                        row.update(zip(self.guided.COLUMNS, self.guided.stats(b, self.n_local)))
                     self.logger.log(self.global_step - 1, row)
                     self._say(f"epoch {self.epoch} step {self.global_step}/{max_steps} loss {row['train/loss']:.5f} "
                               f"psnr {row['train/psnr']:.3f} lr {lr:.3g} ({(time.time() - t0) / max(self.global_step, 1) * 1e3:.2f} ms/step)")
@@ -607,6 +643,7 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = build_parser().parse_args(argv)
     hp = cfg.resolve(args)
+    cfg.check_train_guided(hp)          # before any rank is started
     world = int(hp["num_gpus"])
     if world > 1 and os.environ.get("MIPNERF_TRAIN_CHILD") != "1":
         rc = launch_ranks(argv, world, args.child_timeout)

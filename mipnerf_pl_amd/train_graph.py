@@ -14,6 +14,14 @@ span: right after the batch source, `ops.ray_span` (inside the graph; it reads t
 replays is seen by the next one) writes `live`, `first`, `last`, `near_span`, `far_span`, and the step samples [near_span, far_span];
 `self.rays.near` / `.far` keep the gathered values.  A dead ray keeps [near, far] and is still trained.
 
+With `guided` (an `ops.GuidedState`, e.g. the one `train_guided.TrainGuided` refreshes) and `guided_index` = (step, epoch_base, n_order) --
+the device batch index the batch source reads, and the length of its order -- the step weighs and records what an error-guided sampler drew:
+`ops.guided_apply` right after the batch source (before `ops.ray_span`) multiplies `self.rays.lossmult` by the ring's importance weights,
+the `out` argument of mipnerf_train_step copies the fine level's colours into the static `self.fine_rgb`, and `ops.guided_accumulate` after
+it adds their squared errors to the state's integer counters -- inside the same graph (graph A of the collective form), before the optimiser
+kernel advances the step counter.  Both read the rings where they live, so a refresh between two replays is seen by the next one.  Without
+`guided` the object issues exactly the calls it issued before.
+
 Inputs live in static buffers (`self.rays`, `self.gt`): write the next batch there (copy_ or device-side ray generation
 straight into them) and call the object, or give a `batch_source`: a callable issued first inside the step (inside the captured
 graph) that writes the batch itself, e.g. `ops.gather_train_batch` with the batch index read from the device (train.py).  Returns the static scalars tensor [6] = loss, mse_c, mse_f, distloss_c,
@@ -34,7 +42,7 @@ from .rays import Rays
 
 class GraphedTrainStep:
     def __init__(self, system, optimizer, num_rays: int, device: torch.device, use_graph: bool = True, batch_source=None,
-                 occupancy=None, span_samples=None):
+                 occupancy=None, span_samples=None, guided=None, guided_index=None):
         from .optim import FlatAdam
         if not isinstance(optimizer, FlatAdam):
             raise TypeError("GraphedTrainStep needs the flat optimiser (system.fused_adam = True)")
@@ -90,6 +98,15 @@ class GraphedTrainStep:
             self.far_span = torch.zeros(self.B, 1, device=device)
             # the step reads near' / far' where it read near / far
             self._rp = L.RaysPtrs(*[t.data_ptr() for t in self.rays._replace(near=self.near_span, far=self.far_span)])
+        self.guided, self._outs = guided, None
+        if guided is not None:
+            if batch_source is None or guided_index is None:
+                raise ValueError("GraphedTrainStep: guided needs a batch_source (lossmult is re-written before it is weighted) and "
+                                 "guided_index = (step, epoch_base, n_order)")
+            self.guided_step, self.guided_base, self.guided_n_order = guided_index[0], guided_index[1], int(guided_index[2])
+            self.fine_rgb = torch.zeros(self.B, 3, device=device)
+            self._outs = (L.LevelOut * model.num_levels)()
+            self._outs[model.num_levels - 1] = L.LevelOut(self.fine_rgb.data_ptr(), None, None, None, None)
         ptrs = [p.data_ptr() for p in mlp.ordered_params()]
         self._params = (C.c_void_p * len(ptrs))(*ptrs)
 
@@ -98,6 +115,8 @@ class GraphedTrainStep:
         m, B, N = self.model, self.B, self.N
         if self.batch_source is not None:
             self.batch_source()
+        if self.guided is not None:
+            ops.guided_apply(self.guided, self.rays.lossmult, self.guided_n_order, self.guided_step, self.guided_base)
         if self.occupancy is not None:
             ops.ray_span(self.occupancy, self.rays, self.span_samples, disparity=m.disparity,
                          out=(self.live, self.first, self.last, self.near_span, self.far_span))
@@ -112,8 +131,10 @@ class GraphedTrainStep:
             self.ctx.handle, B, C.byref(self._rp), self.gt.data_ptr(), None if t_rand is None else t_rand.data_ptr(),
             None if u_rand is None else u_rand.data_ptr(), None if dz is None else dz.data_ptr(), flags,
             float(self.hp['loss.coarse_loss_mult']), 0.01, int(bool(self.hp['loss.disable_multiscale_loss'])),
-            self.ws.data_ptr(), self.ws.numel(), m.mlp._flat_grad.data_ptr(), 0, self.scalars.data_ptr(), None, ops._stream()),
+            self.ws.data_ptr(), self.ws.numel(), m.mlp._flat_grad.data_ptr(), 0, self.scalars.data_ptr(), self._outs, ops._stream()),
             "train_step")
+        if self.guided is not None:
+            ops.guided_accumulate(self.guided, self.fine_rgb, self.gt, self.guided_n_order, self.guided_step, self.guided_base)
 
     def _update(self):
         self.opt.launch_scheduled(count_on_host=False)
@@ -157,7 +178,8 @@ class GraphedTrainStep:
     def _snapshot(self):
         mlp, st = self.model.mlp, self.opt.state[self.opt._key()]
         return (mlp._flat_param.clone(), st["exp_avg"].clone(), st["exp_avg_sq"].clone(),
-                None if self.opt._dev_step is None else self.opt._dev_step.clone())
+                None if self.opt._dev_step is None else self.opt._dev_step.clone(),
+                None if self.guided is None else (self.guided.sum.clone(), self.guided.cnt.clone()))
 
     def _restore(self, snap):
         mlp, st = self.model.mlp, self.opt.state[self.opt._key()]
@@ -166,6 +188,9 @@ class GraphedTrainStep:
         st["exp_avg_sq"].copy_(snap[2])
         if self.opt._dev_step is not None:
             self.opt._dev_step.fill_(int(st["step"]))
+        if self.guided is not None:             # the warm-up's errors are not a training step's
+            self.guided.sum.copy_(snap[4][0])
+            self.guided.cnt.copy_(snap[4][1])
         L.check(L.lib().mipnerf_set_params(self.ctx.handle, self._params, ops._stream()), "mipnerf_set_params")
 
     def span_stats(self):
