@@ -379,6 +379,30 @@ int mipnerf_area_downscale(int32_t num_images, int32_t height, int32_t width, in
 size_t mipnerf_density_grid_workspace_bytes(const mipnerf_ctx* ctx, int64_t chunk_points, int precision);
 int mipnerf_density_grid(mipnerf_ctx* ctx, const int32_t* dims_host, const float* lo_host, const float* hi_host, float cov_scale,
                          int precision, float* sigma, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- the density lattice as the proposal level of a forward (ABI 6 grows; bounded model, inference) ----
+ * Trilinear value of an fp32 device lattice [nz, ny, nx] (the layout above; mipnerf_density_grid's output is one) at a point,
+ * stated once in csrc/lattice_sample.hpp: per axis u = (x - lo) * inv_h with inv_h = float(n - 1) / (hi - lo) computed once on the host
+ * (no division on the device), u clamped to [0, n - 1] (a point outside the box takes the edge value), i0 = min(int(floorf(u)), n - 2),
+ * f = u - float(i0) (a point on the hi face gives f = 1); the 8 corners are blended along x, then y, then z, each step as
+ * (1 - f) * a + f * b in fp32 without contraction, so non-negative corners give a non-negative value.  A non-finite coordinate gives 0;
+ * a NaN among the 8 corners propagates.
+ * mipnerf_lattice_density: the stage on its own.  One thread per sample: rgb_sigma[b, i] = (0, 0, 0, value at the mean of
+ * conical_frustum_to_gaussian(t[b, i], t[b, i + 1]) of ray b) -- the mean mipnerf_cast_rays returns, bit for bit --, [B, N, 4] as
+ * mipnerf_mlp_forward writes it.  MIPNERF_E_INVALID before any device call for a null pointer, an axis below 2 points, hi <= lo or
+ * num_samples outside 1 .. MIPNERF_MAX_SAMPLES; num_rays = 0 returns without a launch.  Does not allocate or synchronise.
+ * mipnerf_forward_proposal: mipnerf_forward with level 0's encoding and MLP launch replaced by that kernel, writing into the same
+ * rgb_sigma buffer; the ray prologue, level 0's compositing + resampling and all of level 1 are mipnerf_forward's launches (options 3
+ * and 4 apply as there: same bits either way).  Level 0's outputs are what compositing yields for colour 0 and the lattice's density:
+ * comp_rgb = the background times (1 - acc) -- the lattice's silhouette, not a coarse render --, acc, distance, weights and t_samples as
+ * usual; level 1 draws its samples from those weights.  The picture is NOT mipnerf_forward's: the fine samples sit elsewhere.  Needs
+ * mipnerf_workspace_bytes and no more.  MIPNERF_E_UNSUPPORTED for cfg.unbounded = 1 (a contracted lattice is not implemented) and for
+ * num_levels != 2; MIPNERF_E_INVALID for the lattice argument errors above.  No density noise.  Graph-capturable like mipnerf_forward. */
+int mipnerf_lattice_density(const int32_t* dims_host, const float* lo_host, const float* hi_host, const float* lattice, int64_t num_rays,
+                            int32_t num_samples, const float* t_samples, const float* origins, const float* directions, const float* radii,
+                            float* rgb_sigma, void* stream);
+int mipnerf_forward_proposal(mipnerf_ctx* ctx, int64_t num_rays, const mipnerf_rays* rays, const int32_t* dims_host, const float* lo_host,
+                             const float* hi_host, const float* lattice, const float* t_rand, const float* u_rand, uint32_t flags,
+                             int precision, void* workspace, size_t workspace_bytes, const mipnerf_level_out* out, void* stream);
 /* Marching tetrahedra on the Kuhn split of ANY fp32 device lattice grid [nz, ny, nx] (it need not be a density): every cell is cut
  * into the six tetrahedra (c, c + e_p0, c + e_p0 + e_p1, c + (1,1,1)), p the permutations of the axes in lexicographic order; 16
  * sign cases, none ambiguous, face diagonals of neighbouring cells coincide, so a surface that stays off the box is a closed,

@@ -87,7 +87,10 @@ SIGNATURES = {
     "mipnerf_area_downscale": (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _I64, _P]),
     "mipnerf_density_grid_workspace_bytes": (_SZ, [_P, _I64, C.c_int]),
     "mipnerf_density_grid": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _F, C.c_int, _P, _P, _SZ, _P]),
-    "mipnerf_density_grid_360_workspace_bytes": (_SZ, [_P, _I64, C.c_int]),
+    "mipnerf_lattice_density": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
+    "mipnerf_forward_proposal": (C.c_int, [_P, _I64, C.POINTER(RaysPtrs), C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _P, _P, _P,
+                                           C.c_uint32, C.c_int, _P, _SZ, C.POINTER(LevelOut), _P]),
+    "mipnerf_density_grid_360_workspace_bytes":(_SZ, [_P, _I64, C.c_int]),
     "mipnerf_density_grid_360": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _F, C.c_int, _F, C.c_int, _P, _P, _SZ, _P]),
     "mipnerf_lattice_ipe_360": (C.c_int, [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _I64, _I64, _F, C.c_int, _I32, _I32, _P, C.c_int, _P]),
     "mipnerf_uncontract_vertices": (C.c_int, [_I64, _F, _P, _P, _P, _P, _P]),

@@ -53,6 +53,7 @@ UNITS = [
     ("kernels_occupancy.hip", ["-ffp-contract=off"]),   # frustum end points o + t * d and floor((x - lo) / h) round as stated in the header
     ("kernels_bucket.hip", []),                         # integer ranks and copies only: no floating-point arithmetic to contract
     ("kernels_guided.hip", ["-ffp-contract=off"]),      # err + rate * (mean - err) and the float64 mixture round as stated in the header
+    ("kernels_proposal.hip", ["-ffp-contract=off"]),    # the frustum mean and the trilinear blend round as stated in lattice_sample.hpp
     ("selftest.hip", ["-ffp-contract=off"]),
     ("capi.hip", []),
 ]

@@ -15,6 +15,7 @@
 #include "camera_models.hpp"
 #include "kernels.hpp"
 #include "lane_buckets.hpp"
+#include "lattice_sample.hpp"
 #include "mlp_variants_gen.hpp"
 #include "mlp_train_variants_gen.hpp"
 #include "mlp_f32r_variants_gen.hpp"
@@ -1905,9 +1906,16 @@ size_t mipnerf_workspace_bytes(const mipnerf_ctx* c, int64_t B) {
            (c->cfg.unbounded ? 2 * align256((size_t)B * (c->cfg.num_samples + 1) * 4) : 0);       // inverse-depth fence posts of two levels
 }
 
-int mipnerf_forward(mipnerf_ctx* c, int64_t B, const mipnerf_rays* rays, const float* t_rand, const float* u_rand,
-                    const float* density_randn, uint32_t flags, int precision, void* workspace, size_t workspace_bytes,
-                    const mipnerf_level_out* out, void* stream) {
+// the proposal level of mipnerf_forward_proposal: level 0 takes its density from this lattice instead of the encoding + MLP launch
+struct ProposalLevel {
+    mip::LatticeBox box;
+    const float* lattice;
+};
+
+// the level loop of mipnerf_forward (prop == nullptr: its launches exactly) and of mipnerf_forward_proposal
+static int forward_levels(mipnerf_ctx* c, int64_t B, const mipnerf_rays* rays, const float* t_rand, const float* u_rand,
+                          const float* density_randn, uint32_t flags, int precision, void* workspace, size_t workspace_bytes,
+                          const mipnerf_level_out* out, void* stream, const ProposalLevel* prop) {
     if (!c || !rays || !out || !workspace || B < 1) return fail(MIPNERF_E_INVALID, "forward: bad argument");
     if (!rays->origins || !rays->directions || !rays->viewdirs || !rays->radii || !rays->near || !rays->far)
         return fail(MIPNERF_E_INVALID, "forward: a Rays field is null");
@@ -1985,29 +1993,35 @@ int mipnerf_forward(mipnerf_ctx* c, int64_t B, const mipnerf_rays* rays, const f
                                                   cfg.resample_padding, o.t_samples, stream))) return rc;
         }
         have_resampled = false;
-        if (!fused && !cfg.unbounded &&
-            (rc = mipnerf_cast_ipe(B, N, cfg.min_deg_point, cfg.max_deg_point, cfg.disable_integration, o.t_samples,
-                                   rays->origins, rays->directions, rays->radii, enc, precision, stream))) return rc;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (c->time_mlp == 1) {
-            if (c->ev_used + 2 > c->ev.size()) {
-                for (int i = 0; i < 64; ++i) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->ev.push_back(e); }
+        if (prop && lvl == 0) {
+            // proposal level: no encoding and no MLP launch; k_lattice_density writes (0, 0, 0, sigma) where the MLP kernel would have
+            HIP_TRY(mip::launch_lattice_density(prop->box, prop->lattice, B, N, o.t_samples, rays->origins, rays->directions, rays->radii,
+                                                rgb_sigma, S(stream)));
+        } else {
+            if (!fused && !cfg.unbounded &&
+                (rc = mipnerf_cast_ipe(B, N, cfg.min_deg_point, cfg.max_deg_point, cfg.disable_integration, o.t_samples,
+                                       rays->origins, rays->directions, rays->radii, enc, precision, stream))) return rc;
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            if (c->time_mlp == 1) {
+                if (c->ev_used + 2 > c->ev.size()) {
+                    for (int i = 0; i < 64; ++i) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->ev.push_back(e); }
+                }
+                e0 = c->ev[c->ev_used]; e1 = c->ev[c->ev_used + 1]; c->ev_used += 2;
+                HIP_TRY(hipEventRecord(e0, S(stream)));
             }
-            e0 = c->ev[c->ev_used]; e1 = c->ev[c->ev_used + 1]; c->ev_used += 2;
-            HIP_TRY(hipEventRecord(e0, S(stream)));
+            if (fused) {
+                if (max_deg_span_is_16(cfg) == false)
+                    return fail(MIPNERF_E_UNSUPPORTED, "fused IPE is generated for max_deg-min_deg == 16");
+                const mip::RayInputs ri = {o.t_samples, rays->origins, rays->directions, rays->radii, cfg.min_deg_point,
+                                           cfg.disable_integration};
+                HIP_TRY(launch_bf16_variant(c, nullptr, viewenc, rgb_sigma, nullptr, (int64_t)M, N, true, &ri, dnoise, S(stream)));
+            } else if (pre_form) {
+                HIP_TRY(launch_bf16_pre(c, enc, 1, viewenc, rgb_sigma, nullptr, (int64_t)M, N, pre_x, pre_acc, dnoise, S(stream)));
+            } else if ((rc = mlp_forward_noise(c, (int64_t)M, N, enc, viewenc, precision, rgb_sigma, nullptr, dnoise, stream))) {
+                return rc;
+            }
+            if (c->time_mlp == 1) HIP_TRY(hipEventRecord(e1, S(stream)));
         }
-        if (fused) {
-            if (max_deg_span_is_16(cfg) == false)
-                return fail(MIPNERF_E_UNSUPPORTED, "fused IPE is generated for max_deg-min_deg == 16");
-            const mip::RayInputs ri = {o.t_samples, rays->origins, rays->directions, rays->radii, cfg.min_deg_point,
-                                       cfg.disable_integration};
-            HIP_TRY(launch_bf16_variant(c, nullptr, viewenc, rgb_sigma, nullptr, (int64_t)M, N, true, &ri, dnoise, S(stream)));
-        } else if (pre_form) {
-            HIP_TRY(launch_bf16_pre(c, enc, 1, viewenc, rgb_sigma, nullptr, (int64_t)M, N, pre_x, pre_acc, dnoise, S(stream)));
-        } else if ((rc = mlp_forward_noise(c, (int64_t)M, N, enc, viewenc, precision, rgb_sigma, nullptr, dnoise, stream))) {
-            return rc;
-        }
-        if (c->time_mlp == 1) HIP_TRY(hipEventRecord(e1, S(stream)));
         if (c->fuse_small && lvl + 1 < cfg.num_levels) {
             // compositing of this level + the next level's fence posts in one launch (weights go registers -> LDS, not through HBM)
             const mipnerf_level_out& nx = out[lvl + 1];
@@ -2022,6 +2036,53 @@ int mipnerf_forward(mipnerf_ctx* c, int64_t B, const mipnerf_rays* rays, const f
                                                o.distance, o.acc, o.weights, stream))) return rc;
     }
     return MIPNERF_OK;
+}
+
+int mipnerf_forward(mipnerf_ctx* c, int64_t B, const mipnerf_rays* rays, const float* t_rand, const float* u_rand,
+                    const float* density_randn, uint32_t flags, int precision, void* workspace, size_t workspace_bytes,
+                    const mipnerf_level_out* out, void* stream) {
+    return forward_levels(c, B, rays, t_rand, u_rand, density_randn, flags, precision, workspace, workspace_bytes, out, stream, nullptr);
+}
+
+// ---- the density lattice as the proposal level (kernels_proposal.hip, lattice_sample.hpp) ------------------------------------------
+static int proposal_box(const char* who, const int32_t* dims, const float* lo, const float* hi, const float* lattice, mip::LatticeBox* box) {
+    if (!lattice) return fail(MIPNERF_E_INVALID, "%s: null argument (lattice)", who);
+    if (int rc = lattice_check(who, dims, lo, hi)) return rc;
+    box->nx = dims[0]; box->ny = dims[1]; box->nz = dims[2];
+    for (int a = 0; a < 3; ++a) {
+        if (!(hi[a] > lo[a])) return fail(MIPNERF_E_INVALID, "%s: the box needs hi > lo on every axis", who);
+        box->lo[a] = lo[a];
+        box->inv_h[a] = (float)(dims[a] - 1) / (hi[a] - lo[a]);
+        if (!std::isfinite(box->inv_h[a])) return fail(MIPNERF_E_INVALID, "%s: the box is too thin: (n - 1) / (hi - lo) is not finite", who);
+    }
+    return MIPNERF_OK;
+}
+
+int mipnerf_lattice_density(const int32_t* dims, const float* lo, const float* hi, const float* lattice, int64_t B, int32_t N,
+                            const float* t, const float* origins, const float* dirs, const float* radii, float* rgb_sigma, void* stream) {
+    mip::LatticeBox box;
+    if (int rc = proposal_box("lattice_density", dims, lo, hi, lattice, &box)) return rc;
+    if (N < 1 || N > MIPNERF_MAX_SAMPLES) return fail(MIPNERF_E_INVALID, "lattice_density: num_samples must be in [1, %d] (got %d)", MIPNERF_MAX_SAMPLES, N);
+    if (B < 0 || B >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "lattice_density: bad ray count %lld", (long long)B);
+    if (B == 0) return MIPNERF_OK;
+    if (!t || !origins || !dirs || !radii || !rgb_sigma) return fail(MIPNERF_E_INVALID, "lattice_density: null argument");
+    HIP_TRY(mip::launch_lattice_density(box, lattice, B, N, t, origins, dirs, radii, rgb_sigma, S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_forward_proposal(mipnerf_ctx* c, int64_t B, const mipnerf_rays* rays, const int32_t* dims, const float* lo, const float* hi,
+                             const float* lattice, const float* t_rand, const float* u_rand, uint32_t flags, int precision,
+                             void* workspace, size_t workspace_bytes, const mipnerf_level_out* out, void* stream) {
+    ProposalLevel prop;
+    if (int rc = proposal_box("forward_proposal", dims, lo, hi, lattice, &prop.box)) return rc;
+    prop.lattice = lattice;
+    if (!c) return fail(MIPNERF_E_INVALID, "forward_proposal: null argument (ctx)");
+    if (c->cfg.unbounded)
+        return fail(MIPNERF_E_UNSUPPORTED, "forward_proposal: the unbounded-scene model lives in a contracted space; a lattice proposal for it is not implemented");
+    if (c->cfg.num_levels != 2)
+        return fail(MIPNERF_E_UNSUPPORTED, "forward_proposal: the lattice replaces the coarse level of a two-level model (num_levels = %d)", c->cfg.num_levels);
+    if (B >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "forward_proposal: bad ray count %lld", (long long)B);
+    return forward_levels(c, B, rays, t_rand, u_rand, nullptr, flags, precision, workspace, workspace_bytes, out, stream, &prop);
 }
 
 // ---- instrumentation -----------------------------------------------------------------------------------

@@ -338,6 +338,12 @@ hipError_t launch_guided_draw(int64_t n, const int64_t* r, int n_images, const i
                               const unsigned long long* header, int64_t* order, float* weight, int* cell, int64_t ring, int64_t ring_start,
                               hipStream_t st);
 
+// ---- kernels_proposal.hip: the density lattice as the proposal level (lattice_sample.hpp states the arithmetic) ---------------
+struct LatticeBox;
+// rgb_sigma [B, N, 4] = (0, 0, 0, trilinear lattice value at the mean of frustum [t_i, t_{i+1}]); B * N <= 256 * (2^31 - 1)
+hipError_t launch_lattice_density(const LatticeBox& g, const float* lattice, int64_t B, int N, const float* t, const float* origins,
+                                  const float* dirs, const float* radii, float* rgb_sigma, hipStream_t st);
+
 // ---- selftest.hip -------------------------------------------------------------------------------
 // returns 0 if the MFMA fragment layouts and the LDS-DMA path behave as the kernels assume;
 // otherwise a bit mask (1: bf16 32x32x16 layout, 2: f32 32x32x2 layout, 4: global_load_lds)

@@ -14,8 +14,9 @@ import argparse
 import torch
 
 from .evaluate import distorted_frames, evaluate, summarize_results
-from .render_video import (add_common_args, cli_ladder, cli_occupancy, cli_span_samples, flag_given, is_scene360, load_system,
-                           refuse_adaptive_without_cull, refuse_tighten_without_cull, refuse_unbounded_cull)
+from .render_video import (add_common_args, cli_ladder, cli_occupancy, cli_proposal, cli_span_samples, flag_given, is_scene360, load_system,
+                           refuse_adaptive_without_cull, refuse_proposal_without_grid, refuse_scene360_proposal, refuse_tighten_without_cull,
+                           refuse_unbounded_cull)
 
 
 def build_parser():
@@ -31,8 +32,10 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     refuse_tighten_without_cull(args)
     refuse_adaptive_without_cull(args)
+    refuse_proposal_without_grid(args)
     system = load_system(args)
     refuse_unbounded_cull(args, system)
+    refuse_scene360_proposal(args, system)
     ladder = cli_ladder(args, system)
     hp = system.hparams
     exp_name = hp["exp_name"]
@@ -50,9 +53,11 @@ def main(argv=None):
         if scene360 and not flag_given(argv, "--base_size"):
             base_size = (dataset.w, dataset.h)
         occupancy = cli_occupancy(args, system, (dataset[i][0] for i in range(len(dataset))), distorted=distorted_frames(dataset))
+        proposal = cli_proposal(args, system, (dataset[i][0] for i in range(len(dataset))), distorted=distorted_frames(dataset))
         evaluate(system, dataset, args.out_dir, exp_name, scale=args.scale, save_image=args.save_image, chunk_size=args.chunk_size,
                  white_bkgd=white_bkgd, use_graph=args.use_graph, base_size=base_size, occupancy=occupancy, tighten=args.cull_tighten,
-                 span_samples=cli_span_samples(args, system) if args.cull else None, adaptive=args.cull_adaptive, ladder=ladder)
+                 span_samples=cli_span_samples(args, system) if args.cull else None, adaptive=args.cull_adaptive, ladder=ladder,
+                 proposal=proposal)
     summary = summarize_results(args.out_dir, [exp_name], args.scale)
     print("PSNR | SSIM | Average")
     print(summary)

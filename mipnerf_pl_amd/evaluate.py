@@ -29,17 +29,17 @@ class FrameEvaluator:
     """Everything one image size needs: the frame's `GraphedFrame` (or its eager form) and the device buffers of the image bytes."""
 
     def __init__(self, model, height, width, chunk_size, white_bkgd, device, use_graph=True, occupancy=None, tighten=False, span_samples=None,
-                 adaptive=False, ladder=None):
+                 adaptive=False, ladder=None, proposal=None):
         from .model import CulledFrame, GraphedFrame
         self.h, self.w = int(height), int(width)
         n = self.h * self.w
         if occupancy is None:
             if tighten or adaptive:
                 raise ValueError("FrameEvaluator: tighten=True / adaptive=True need an occupancy grid")
-            self.frame = GraphedFrame(model, n, chunk_size, white_bkgd, device, capture=use_graph)
+            self.frame = GraphedFrame(model, n, chunk_size, white_bkgd, device, capture=use_graph, proposal=proposal)
         else:       # rays that touch no occupied cell are skipped; the live count varies per frame, so the chunks run eagerly
             self.frame = CulledFrame(model, n, chunk_size, white_bkgd, device, occupancy, tighten=tighten, span_samples=span_samples,
-                                     adaptive=adaptive, ladder=ladder)
+                                     proposal=proposal, adaptive=adaptive, ladder=ladder)
         self.vis_ws = torch.empty(ops.visualize_workspace_floats(n), dtype=torch.float32, device=device)
         self.rgb_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
         self.dist_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=device)
@@ -171,6 +171,26 @@ def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bou
     return occ
 
 
+def scene_proposal(system, frames=None, grid=256, bound=None, verbose=True, distorted=None):
+    """`ops.field_proposal` of the system's field on grid^3 points over [-bound, bound]^3 (default: `cull_box` of `frames`, the box that
+    holds every ray segment plus one cell), printing the lattice size and its build time once.  The unbounded-scene model is refused."""
+    import time
+    if bool(getattr(system.mip_nerf, "unbounded", False)):
+        raise NotImplementedError("lattice proposals: unbounded=True models are not supported (their field lives in a contracted space; a "
+                                  "contracted proposal lattice is not implemented)")
+    if bound is None:
+        if frames is None:
+            raise ValueError("scene_proposal: give the frames to be rendered or a bound")
+        bound = cull_box(frames, grid, distorted)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    prop = ops.field_proposal(system, grid=grid, lo=-float(bound), hi=float(bound))
+    torch.cuda.synchronize()
+    if verbose:
+        print("proposal: {0}^3 density lattice over +-{1:.4f} built in {2:.1f} ms".format(grid, float(bound), 1e3 * (time.perf_counter() - t0)))
+    return prop
+
+
 def report_live_share(shares, spans=None, samples=None):
     """The closing line of a culled run: the mean share of rays rendered per frame and, for a tightened run (`spans`), the mean share
     of [near, far] between the live rays' first and last occupied coarse frustum (`CulledFrame.span_share`; frames without a live ray do
@@ -219,13 +239,14 @@ def write_metrics(folder, psnrs, ssims):
 
 
 def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chunk_size=DEFAULT_CHUNK, white_bkgd=True, use_graph=True,
-             base_size=(800, 800), occupancy=None, tighten=False, span_samples=None, adaptive=False, ladder=None):
+             base_size=(800, 800), occupancy=None, tighten=False, span_samples=None, adaptive=False, ladder=None, proposal=None):
     """eval.py:main after the checkpoint is loaded: every image of `dataset` (a test split of `datasets.dataset_dict`) rendered by
     `system.mip_nerf`, PSNR / SSIM recorded, the images written when `save_image`.  Returns (psnrs, ssims) as lists of floats.
     `occupancy` (an `ops.Occupancy`, e.g. `scene_occupancy`; for the unbounded-scene model one with `space='contracted'`): rays that touch
     no occupied cell are not rendered (`model.CulledFrame`); None is the full path.  `tighten` / `span_samples` are `CulledFrame`'s (live rays rendered on their occupied span -- not the untightened
     frame --; the frusta count of the classification), and so are `adaptive` / `ladder` (every live ray rendered with a sample count that
-    follows its occupied span; implies `tighten`)."""
+    follows its occupied span; implies `tighten`).  `proposal` (an `ops.ProposalGrid`, e.g. `scene_proposal`; bounded models): the coarse
+    level's density comes from that lattice instead of an MLP pass -- not the two-level frame; works with and without `occupancy`."""
     if scale not in (1, 4):
         raise ValueError("scale must be 1 or 4 (eval.py --scale)")
     model = system.mip_nerf
@@ -242,7 +263,7 @@ def evaluate(system, dataset, out_dir, exp_name, scale=1, save_image=False, chun
             ev = evaluators.get((h, w))
             if ev is None:
                 ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten,
-                                                         span_samples=span_samples, adaptive=adaptive, ladder=ladder)
+                                                         span_samples=span_samples, adaptive=adaptive, ladder=ladder, proposal=proposal)
             rgb, dist, acc = ev.render(rays)
             if occupancy is not None:
                 shares.append(ev.frame.live_count / float(h * w))

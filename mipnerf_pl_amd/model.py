@@ -673,10 +673,16 @@ class MipNerf(torch.nn.Module):
         return native_step_loss(self, rays, gt_rgb, randomized, white_bkgd, coarse_loss_mult, distloss_mult, disable_multiscale_loss,
                                 t_rand, u_rand, density_randn)
 
-    def _forward_native(self, rays, randomized, white_bkgd, t_rand=None, u_rand=None, density_randn=None, out=None, ws=None):
+    def _forward_native(self, rays, randomized, white_bkgd, t_rand=None, u_rand=None, density_randn=None, out=None, ws=None,
+                        proposal=None):
         """`out` (optional): preallocated per-level tuples (comp_rgb, distance, acc, weights, t_samples) to write into
         (contiguous fp32 HIP tensors of the right shapes) instead of fresh tensors.  `ws` (optional): a private workspace
-        (uint8, >= mipnerf_workspace_bytes) for a caller that keeps several forwards in flight on different streams."""
+        (uint8, >= mipnerf_workspace_bytes) for a caller that keeps several forwards in flight on different streams.
+        `proposal` (optional, an `ops.ProposalGrid`; bounded two-level models, inference): the coarse level's density comes from that
+        lattice instead of an encoding + MLP launch (mipnerf_forward_proposal); level 0's comp_rgb is then the lattice's silhouette
+        against the background, not a coarse render, and the fine level is NOT the two-level model's: its samples sit elsewhere."""
+        if proposal is not None:
+            ops._refuse_proposal_model(self, "MipNerf._forward_native(proposal=)")
         dev = rays.origins.device
         B, N = rays.origins.shape[0], self.num_samples
         ctx = self.mlp.native(dev)
@@ -707,6 +713,14 @@ class MipNerf(torch.nn.Module):
             ws = ctx.workspace(B)
         flags = L.FLAG_WHITE_BKGD if white_bkgd else 0
         dz = self._density_randn(randomized, B, dev, density_randn)     # mip_nerf.py:232-233
+        if proposal is not None:
+            if dz is not None:
+                raise NotImplementedError("MipNerf._forward_native(proposal=): density noise belongs to training; lattice proposals are inference only")
+            L.check(L.lib().mipnerf_forward_proposal(ctx.handle, B, C.byref(rp), proposal.cdims, proposal.clo, proposal.chi,
+                                                     proposal.lattice.data_ptr(), t_rand.data_ptr() if randomized else None,
+                                                     u_rand.data_ptr() if randomized else None, flags, self.precision, ws.data_ptr(),
+                                                     ws.numel(), outs, ops._stream()), "mipnerf_forward_proposal")
+            return ret
         L.check(L.lib().mipnerf_forward(ctx.handle, B, C.byref(rp), t_rand.data_ptr() if randomized else None,
                                         u_rand.data_ptr() if randomized else None, None if dz is None else dz.data_ptr(),
                                         flags, self.precision, ws.data_ptr(), ws.numel(), outs, ops._stream()), "mipnerf_forward")
@@ -798,10 +812,17 @@ class GraphedFrame:
     take the chunks round-robin, each with its own workspace and per-sample scratch: the small kernels and the kernel boundaries
     of one lane run while the other lane's MLP kernel owns the CUs.
     Every level's acc is kept too: `acc[l]` [n] (fine level: `acc[-1]`), filled by each call next to what it returns.
-    `capture=False` runs the same chunk launches eagerly on every call instead of replaying a graph."""
+    `capture=False` runs the same chunk launches eagerly on every call instead of replaying a graph.
+    `proposal` (opt-in, an `ops.ProposalGrid`; None launches exactly what it launched before): every chunk forward takes its coarse
+    density from that lattice (`MipNerf._forward_native(proposal=)`).  The returned `rgb[0]` is then the lattice's silhouette against the
+    background, not a coarse render, and the frame is NOT the two-level frame.  The captured graph bakes in the lattice pointer: assigning
+    another `ProposalGrid` object to `.proposal` forces a recapture, as a changed precision does."""
 
     def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, lanes: Optional[int] = None,
-                 capture: bool = True):
+                 capture: bool = True, proposal=None):
+        if proposal is not None:
+            ops._refuse_proposal_model(model, "GraphedFrame(proposal=)")
+        self.proposal = proposal
         self.model, self.n, self.chunk, self.white_bkgd, self.dev = model, int(num_rays), int(chunk), bool(white_bkgd), device
         self.capture = bool(capture)
         self.lanes = max(1, int(lanes if lanes is not None else os.environ.get("MIPNERF_FRAME_LANES", "2")))
@@ -856,9 +877,9 @@ class GraphedFrame:
             rays = Rays(*[x[lo:hi] for x in self.static_in])
             if lanes > 1:
                 with torch.cuda.stream(self._lane_streams[lane]):
-                    m._forward_native(rays, False, self.white_bkgd, out=out, ws=self._lane_ws[lane])
+                    m._forward_native(rays, False, self.white_bkgd, out=out, ws=self._lane_ws[lane], proposal=self.proposal)
             else:
-                m._forward_native(rays, False, self.white_bkgd, out=out, ws=self._lane_ws[0])
+                m._forward_native(rays, False, self.white_bkgd, out=out, ws=self._lane_ws[0], proposal=self.proposal)
         for s_ in self._lane_streams:            # join
             cur.wait_stream(s_)
 
@@ -866,7 +887,8 @@ class GraphedFrame:
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():     # warm-up on a side stream: lazy init, workspace growth, packing
-            self.model._forward_native(Rays(*[x[:min(self.n, self.chunk)] for x in self.static_in]), False, self.white_bkgd)
+            self.model._forward_native(Rays(*[x[:min(self.n, self.chunk)] for x in self.static_in]), False, self.white_bkgd,
+                                       proposal=self.proposal)
         torch.cuda.current_stream().wait_stream(s)
         graph = torch.cuda.CUDAGraph()
         try:
@@ -885,8 +907,10 @@ class GraphedFrame:
         self.model.mlp.native(self.dev)         # re-pack OUTSIDE the graph when a parameter changed
         if self.graph is not None and getattr(self, "_captured_precision", None) != self.model.precision:
             self.graph = None                   # MipNerf.set_precision since the capture: the graph holds the other precision's launches
+        if self.graph is not None and getattr(self, "_captured_proposal", None) is not self.proposal:
+            self.graph = None                   # another ProposalGrid (or none) since the capture: the graph holds the other lattice's pointer
         if self.graph is None:
-            self._captured_precision = self.model.precision
+            self._captured_precision, self._captured_proposal = self.model.precision, self.proposal
             if self.capture:
                 self._capture()
             else:
@@ -966,11 +990,16 @@ class CulledFrame:
     `ops.gather_frame` (a culled pixel's distance = the original near).  Pixels of bucket b are bit for bit what `GraphedFrame` over the
     sibling with c_b samples yields on the same rays with near / far replaced by near' / far'; the frame is NOT the untightened frame, and
     what is guaranteed is the guarantee of `tighten`.  `.bucket_counts` (rays per bucket of the last call), `.ladder`, `.sample_share`
-    (the mean of c_bucket / N over the live rays, from the counts: no read-back; NaN when no ray is live)."""
+    (the mean of c_bucket / N over the live rays, from the counts: no read-back; NaN when no ray is live).
+    `proposal` (opt-in, an `ops.ProposalGrid`; bounded models; None launches exactly what it launched before): every chunk forward of the
+    live rays -- plain, tightened or adaptive, the siblings included, all with the same grid -- takes its coarse density from that lattice
+    (`GraphedFrame(proposal=)`).  Live pixels are bit for bit what `GraphedFrame(proposal=)` yields on the same (tightened) rays; the
+    returned `rgb[0]` is then the lattice's silhouette against the background, not a coarse render.  `.proposal` may be reassigned
+    between calls."""
 
     def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, occupancy,
                  lanes: Optional[int] = None, outside_occupied: bool = True, cone_scale: float = 1.0, tighten: bool = False,
-                 span_samples: Optional[int] = None, adaptive: bool = False, ladder=None):
+                 span_samples: Optional[int] = None, proposal=None, adaptive: bool = False, ladder=None):
         unbounded, contracted = bool(getattr(model, "unbounded", False)), getattr(occupancy, "space", None) == "contracted"
         if unbounded and not contracted:
             raise NotImplementedError("CulledFrame: unbounded=True models are not supported (their field lives in a contracted space) unless "
@@ -988,7 +1017,7 @@ class CulledFrame:
         # the compacted rays and their results live in an eager GraphedFrame: its chunk loop, lanes and scratch render the first live_count rays
         # (adaptive: the buckets' 64-ray-aligned segments, which need 64 more rows per bucket)
         rows = self.n + ops.BUCKET_ALIGN * len(self.ladder) if self.adaptive else num_rays
-        self._compact = GraphedFrame(model, rows, chunk, white_bkgd, device, lanes=lanes, capture=False)
+        self._compact = GraphedFrame(model, rows, chunk, white_bkgd, device, lanes=lanes, capture=False, proposal=proposal)
         self.static_in = Rays(*[torch.zeros(self.n, k, device=device) for k in (3, 3, 3, 1, 1, 1, 1)])
         L_ = model.num_levels
         self.rgb = [torch.zeros(self.n, 3, device=device) for _ in range(L_)]
@@ -1013,6 +1042,16 @@ class CulledFrame:
             self._bucket_ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
             # one model per ladder entry: the frame's own for c_{B-1} == N, a sibling that shares its parameters for every smaller count
             self._bucket_models = [model if c == model.num_samples else sibling_with_samples(model, c) for c in self.ladder]
+
+    @property
+    def proposal(self):
+        return self._compact.proposal
+
+    @proposal.setter
+    def proposal(self, grid) -> None:
+        if grid is not None:
+            ops._refuse_proposal_model(self.model, "CulledFrame(proposal=)")
+        self._compact.proposal = grid
 
     @property
     def span_samples(self) -> int:

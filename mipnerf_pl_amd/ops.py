@@ -606,6 +606,59 @@ def density_grid(mlp_or_model, dims, lo, hi, cov_scale=1.0, precision=None, chun
     return sigma
 
 
+# ---- the density lattice as the proposal level of a forward (csrc/kernels_proposal.hip) ------------------------------------------
+class ProposalGrid:
+    """An fp32 device lattice [nz, ny, nx] over the box lo .. hi ((x, y, z) order; the layout of `density_grid`) that stands in for the
+    coarse level's density: `lattice_density`, `MipNerf._forward_native(proposal=)`, `model.GraphedFrame` / `CulledFrame(proposal=)`.
+    Keeps the host arrays `dims`, `lo`, `hi` the C ABI reads (`cdims`, `clo`, `chi`) next to the tensor.  The lattice must stay alive and in
+    place while a captured frame uses it; a frame handed ANOTHER ProposalGrid object re-captures."""
+
+    def __init__(self, lattice, lo, hi):
+        g = _f32c(lattice, "lattice")
+        if g.dim() != 3:
+            raise ValueError(f"ProposalGrid: expected a [nz, ny, nx] lattice, got {tuple(g.shape)}")
+        dims, self.cdims, self.clo, self.chi = _lattice_args("ProposalGrid", (g.shape[2], g.shape[1], g.shape[0]), lo, hi)
+        if min(dims) < 2:
+            raise ValueError(f"ProposalGrid: a lattice needs at least 2 points per axis (got {dims})")
+        self.lattice, self.dims = g, tuple(dims)
+        self.lo, self.hi = tuple(float(v) for v in self.clo), tuple(float(v) for v in self.chi)
+        if not all(h > l for l, h in zip(self.lo, self.hi)):
+            raise ValueError(f"ProposalGrid: the box needs hi > lo on every axis (got {self.lo} .. {self.hi})")
+
+
+def _refuse_proposal_model(model, name):
+    """lattice proposals replace the coarse level of a bounded two-level model: anything else is refused with a message"""
+    if bool(getattr(model, "unbounded", False)):
+        raise NotImplementedError(f"{name}: unbounded=True models are not supported (their field lives in a contracted space; a contracted "
+                                  "proposal lattice is not implemented)")
+    if int(getattr(model, "num_levels", 2)) != 2:
+        raise NotImplementedError(f"{name}: the lattice replaces the coarse level of a two-level model (num_levels = {model.num_levels})")
+
+
+def field_proposal(model_or_system, grid=256, lo=None, hi=None, cov_scale=1.0, precision=None):
+    """`density_grid` of the field on grid^3 (or (nx, ny, nz)) points over lo .. hi, wrapped into a `ProposalGrid`.  unbounded=True
+    models are refused (their field lives in a contracted space)."""
+    _field_mlp(model_or_system, "field_proposal")
+    if lo is None or hi is None:
+        raise ValueError("field_proposal: give the box lo .. hi the lattice spans (the rays to be rendered should stay inside it: outside, a "
+                         "sample takes the value of the nearest face)")
+    return ProposalGrid(density_grid(model_or_system, grid, lo, hi, cov_scale=cov_scale, precision=precision), lo, hi)
+
+
+def lattice_density(grid, t_samples, origins, directions, radii):
+    """The proposal level on its own (mipnerf_lattice_density): the trilinear value of `grid` (a `ProposalGrid`) at the mean of every
+    conical frustum [t_i, t_{i+1}] -- the means `cast_rays` returns, bit for bit -- as [B, N].  A point outside the box takes the edge
+    value, a non-finite one 0 (the rules of include/mipnerf_hip.h)."""
+    t_samples = _f32c(t_samples, "t_samples")
+    B, N1 = t_samples.shape
+    out = torch.empty(B, N1 - 1, 4, device=t_samples.device, dtype=torch.float32)
+    o, d, r = _f32c(origins, "origins"), _f32c(directions, "directions"), _f32c(radii, "radii")
+    with torch.cuda.device(t_samples.device):
+        L.check(L.lib().mipnerf_lattice_density(grid.cdims, grid.clo, grid.chi, _ptr(grid.lattice), B, N1 - 1, _ptr(t_samples), _ptr(o), _ptr(d),
+                                                _ptr(r), _ptr(out), _stream()), "lattice_density")
+    return out[..., 3]
+
+
 def lattice_ipe_360(dims, lo, hi, cov_scale=1.0, space="contracted", min_deg=0, max_deg=16, precision=L.PREC_FP32, fragments=False,
                     first=0, count=None, device="cuda"):
     """The lattice encoder of the unbounded-scene model alone (mipnerf_lattice_ipe_360): rows [count, 42 * (max_deg - min_deg)] of the

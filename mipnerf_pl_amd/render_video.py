@@ -21,18 +21,19 @@ import os
 import numpy as np
 import torch
 
-from .evaluate import DEFAULT_CHUNK, FrameEvaluator, generate_video, report_live_share, save_images, scene_occupancy
+from .evaluate import DEFAULT_CHUNK, FrameEvaluator, generate_video, report_live_share, save_images, scene_occupancy, scene_proposal
 
 CAMERA_ANGLE_X = 0.6911112070083618       # render_video.py --camera_angle_x default (Blender's lego)
 
 
 def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_angle_x=CAMERA_ANGLE_X, chunk_size=DEFAULT_CHUNK,
                  white_bkgd=True, n_poses=120, use_graph=True, occupancy=None, tighten=False, span_samples=None, adaptive=False,
-                 ladder=None):
+                 ladder=None, proposal=None):
     """render_video.py:run_render after the checkpoint is loaded.  Returns the output folder.  `occupancy` (an `ops.Occupancy`): rays
     that touch no occupied cell are not rendered (`model.CulledFrame`); None is the full path.  `tighten` / `span_samples` are
     `CulledFrame`'s (live rays rendered on their occupied span; the frusta count of the classification) and need an `occupancy`; so do
-    `adaptive` / `ladder` (every live ray rendered with a sample count that follows its occupied span; implies `tighten`)."""
+    `adaptive` / `ladder` (every live ray rendered with a sample count that follows its occupied span; implies `tighten`).  `proposal`
+    (an `ops.ProposalGrid`): the coarse level's density comes from that lattice instead of an MLP pass (not the two-level frame)."""
     from .datasets import RenderGen
     model = system.mip_nerf
     device = next(model.parameters()).device
@@ -50,7 +51,7 @@ def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_
             ev = evaluators.get((h, w))
             if ev is None:
                 ev = evaluators[(h, w)] = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten,
-                                                         span_samples=span_samples, adaptive=adaptive, ladder=ladder)
+                                                         span_samples=span_samples, adaptive=adaptive, ladder=ladder, proposal=proposal)
             images = ev.images(*ev.render(rays))
             if occupancy is not None:
                 shares.append(ev.frame.live_count / float(h * w))
@@ -65,7 +66,7 @@ def render_video(system, out_dir, exp_name, scale, base_size=(800, 800), camera_
 
 
 def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAULT_CHUNK, white_bkgd=False, use_graph=True, occupancy=None,
-                tighten=False, span_samples=None, adaptive=False, ladder=None):
+                tighten=False, span_samples=None, adaptive=False, ladder=None, proposal=None):
     """The interpolated path through the poses of `dataset` (a `datasets.RealData360` split), every frame as in `render_video`.
     Returns the output folder."""
     from .datasets import PathGen
@@ -76,7 +77,7 @@ def render_path(system, dataset, out_dir, exp_name, n_views=30, chunk_size=DEFAU
     path = PathGen(dataset, n_views, device=device)
     h, w = path.sizes[0]
     ev = FrameEvaluator(model, h, w, chunk_size, white_bkgd, device, use_graph, occupancy, tighten=tighten, span_samples=span_samples,
-                        adaptive=adaptive, ladder=ladder)
+                        adaptive=adaptive, ladder=ladder, proposal=proposal)
     shares, spans, samples = [], [], []
     with torch.no_grad():
         for idx in range(len(path)):
@@ -149,6 +150,12 @@ def add_common_args(p):
     p.add_argument("--cull_ladder", help="--cull_adaptive: the sample counts to choose from, 1 to 8 strictly increasing values that end at the "
                    "rendered count (default: the distinct values of ceil(N k / 4), k = 1..4: 32 64 96 128 for 128 samples)", type=int,
                    nargs="+", default=None, metavar="C")
+    p.add_argument("--proposal_grid", help="take the coarse level's density from a lattice of the field's own density with this many points per "
+                   "axis (bare: 256) instead of an MLP pass: one MLP launch per chunk instead of two.  Not the two-level frame: the fine "
+                   "samples sit elsewhere.  Bounded checkpoints only; works with and without --cull", type=int, nargs="?", const=256, default=None,
+                   metavar="N")
+    p.add_argument("--proposal_bound", help="--proposal_grid: the lattice spans [-B, B]^3 (default: the largest coordinate any ray of the "
+                   "cameras to be rendered reaches between near and far, plus one cell)", type=float, default=None)
     p.add_argument("--render_samples", help="samples per ray and level to render with (default: the checkpoint's num_samples; the parameters do "
                    "not depend on it); independent of --cull", type=int, default=None)
     return p
@@ -210,6 +217,37 @@ def refuse_unbounded_cull(args, system):
         raise SystemExit(f"--cull_space {space}: this checkpoint holds a bounded model; its occupancy grid lies in world space -- drop --cull_space")
 
 
+def refuse_proposal_without_grid(args):
+    """--proposal_bound describes the lattice of --proposal_grid: without it the command exits before anything is loaded; so does a
+    lattice too small to hold a box."""
+    grid = getattr(args, "proposal_grid", None)
+    if getattr(args, "proposal_bound", None) is not None and grid is None:
+        raise SystemExit("--proposal_bound describes the lattice of --proposal_grid: give --proposal_grid as well")
+    if grid is not None and grid < 4:
+        raise SystemExit(f"--proposal_grid {grid}: the lattice needs at least 4 points per axis")
+    if getattr(args, "proposal_bound", None) is not None and not args.proposal_bound > 0:
+        raise SystemExit(f"--proposal_bound {args.proposal_bound}: the half-width of the box must be positive")
+
+
+def refuse_scene360_proposal(args, system):
+    """--proposal_grid belongs to bounded checkpoints: a llff / realdata360 checkpoint (and any unbounded-scene model) exits with a
+    message before anything is rendered."""
+    if getattr(args, "proposal_grid", None) is None:
+        return
+    if is_scene360(system.hparams) or bool(getattr(system.mip_nerf, "unbounded", False)):
+        raise SystemExit("--proposal_grid: this checkpoint holds a captured scene ({}); the proposal lattice is implemented for bounded "
+                         "(Blender) checkpoints only -- its rays leave any box and the unbounded-scene model lives in a contracted space.  "
+                         "Render it without --proposal_grid".format(system.hparams.get("dataset_name")))
+
+
+def cli_proposal(args, system, frames, distorted=None):
+    """The proposal lattice the --proposal flags ask for (None without --proposal_grid); `frames` / `distorted` as in `cli_occupancy`."""
+    if getattr(args, "proposal_grid", None) is None:
+        return None
+    return scene_proposal(system, frames if args.proposal_bound is None else None, grid=args.proposal_grid, bound=args.proposal_bound,
+                          distorted=distorted)
+
+
 def cli_occupancy(args, system, frames, distorted=None):
     """The occupancy grid the --cull flags ask for (None without --cull); `frames`: an iterable of the Rays [H, W, k] to be rendered,
     `distorted`: which of them come from a distorted camera (`evaluate.distorted_frames`; a path of pinhole records has none)."""
@@ -262,12 +300,14 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     refuse_tighten_without_cull(args)
     refuse_adaptive_without_cull(args)
+    refuse_proposal_without_grid(args)
     if args.gen_video_only:
         if args.render_images_dir is None:
             raise SystemExit("only generate video, you must give the different scale image base dir (--render_images_dir)")
         return generate_video(args.render_images_dir)
     system = load_system(args)
     refuse_unbounded_cull(args, system)
+    refuse_scene360_proposal(args, system)
     ladder = cli_ladder(args, system)
     system = system.to(torch.device("cuda")).eval()
     hp = system.hparams
@@ -279,25 +319,29 @@ def main(argv=None):
         dataset = RealData360(args.data, split=args.split, white_bkgd=hp["val.white_bkgd"],
                               batch_type="all_images" if args.split == "train" else "single_image",
                               factor=args.factor if args.factor is not None else int(hp.get("factor", 4)), device=dev)
-        occupancy = None
-        if args.cull:
+        occupancy = proposal = None
+        if args.cull or args.proposal_grid is not None:
             from .datasets import PathGen
             path = PathGen(dataset, args.n_views, device=dev)
             occupancy = cli_occupancy(args, system, (path[i] for i in range(len(path))))
+            proposal = cli_proposal(args, system, (path[i] for i in range(len(path))))
         return render_path(system, dataset, args.out_dir, hp["exp_name"], n_views=args.n_views, chunk_size=args.chunk_size,
                            white_bkgd=args.white_bkgd if flag_given(argv, "--white_bkgd") else bool(hp["val.white_bkgd"]),
                            use_graph=args.use_graph, occupancy=occupancy, tighten=args.cull_tighten,
-                           span_samples=cli_span_samples(args, system) if args.cull else None, adaptive=args.cull_adaptive, ladder=ladder)
-    occupancy = None
-    if args.cull:
+                           span_samples=cli_span_samples(args, system) if args.cull else None, adaptive=args.cull_adaptive, ladder=ladder,
+                           proposal=proposal)
+    occupancy = proposal = None
+    if args.cull or args.proposal_grid is not None:
         from .datasets import RenderGen
         focal = .5 * args.base_size[0] / np.tan(.5 * args.camera_angle_x)
         gen = RenderGen(focal, args.base_size, args.scale, device=next(system.parameters()).device, n_poses=args.n_poses)
         occupancy = cli_occupancy(args, system, (gen[i] for i in range(len(gen))))
+        proposal = cli_proposal(args, system, (gen[i] for i in range(len(gen))))
     return render_video(system, args.out_dir, system.hparams["exp_name"], args.scale, base_size=args.base_size,
                         camera_angle_x=args.camera_angle_x, chunk_size=args.chunk_size, white_bkgd=args.white_bkgd,
                         n_poses=args.n_poses, use_graph=args.use_graph, occupancy=occupancy, tighten=args.cull_tighten,
-                        span_samples=cli_span_samples(args, system) if args.cull else None, adaptive=args.cull_adaptive, ladder=ladder)
+                        span_samples=cli_span_samples(args, system) if args.cull else None, adaptive=args.cull_adaptive, ladder=ladder,
+                        proposal=proposal)
 
 
 if __name__ == "__main__":
