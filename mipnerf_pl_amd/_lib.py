@@ -158,8 +158,65 @@ DIAG_SIGNATURES = {
     "mipnerf_handoff_probe": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P]),
 }
 
+
+# include/mipnerf_preview.h: the baked-lattice preview renderer in its own library (mipnerf_pl_amd.preview); the drop-in library keeps
+# its ABI version and its entry points
+PREVIEW_LIB_PATH = os.environ.get("MIPNERF_PREVIEW_LIB", os.path.join(HERE, "csrc", "libmipnerf_preview.so"))
+PREVIEW_ABI = 1
+
+
+class PreviewField(C.Structure):
+    _fields_ = [("dims", _I32 * 3), ("lo", _F * 3), ("hi", _F * 3), ("degree", _I32), ("rows", _P), ("occupancy", _P)]
+
+
+class PreviewParams(C.Structure):
+    _fields_ = [("step_scale", _F), ("t_min", _F), ("max_steps", _I32), ("background", _F * 3)]
+
+
+PREVIEW_SIGNATURES = {
+    "mipnerf_preview_abi_version": (C.c_int, []),
+    "mipnerf_preview_last_error": (C.c_char_p, []),
+    "mipnerf_preview_pack": (C.c_int, [C.POINTER(_I32), _I32, _P, _P, _P, _P, _P]),
+    "mipnerf_preview_march": (C.c_int, [C.POINTER(PreviewField), C.POINTER(PreviewParams), _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 _diag = None
+_preview = None
+
+
+def preview_lib():
+    """Load (once) libmipnerf_preview.so.  No fallback: a missing library is an error."""
+    global _preview
+    if _preview is None:
+        if not os.path.exists(PREVIEW_LIB_PATH):
+            raise RuntimeError(f"{PREVIEW_LIB_PATH} is missing: the baked-lattice renderer has no fallback. "
+                               "Build it with `python -m mipnerf_pl_amd.build` (needs hipcc / ROCm).")
+        try:
+            import torch  # noqa: F401  (same HIP runtime instance, see lib())
+        except ImportError:
+            pass
+        h = C.CDLL(PREVIEW_LIB_PATH)
+        for name, (res, args) in PREVIEW_SIGNATURES.items():
+            fn = getattr(h, name)
+            fn.restype = res
+            fn.argtypes = args
+        if h.mipnerf_preview_abi_version() != PREVIEW_ABI:
+            raise RuntimeError(f"{PREVIEW_LIB_PATH}: ABI {h.mipnerf_preview_abi_version()}, this binding speaks {PREVIEW_ABI}: rebuild")
+        _preview = h
+    return _preview
+
+
+def preview_check(rc: int, what: str = "") -> None:
+    if rc == OK:
+        return
+    msg = (preview_lib().mipnerf_preview_last_error() or b"").decode(errors="replace")
+    msg = f"{what}: {msg}" if what else msg
+    if rc == E_UNSUPPORTED:
+        raise NotImplementedError(msg)
+    if rc == E_INVALID:
+        raise ValueError(msg)
+    raise RuntimeError(f"{msg} (code {rc})")
 
 
 def diag_lib():

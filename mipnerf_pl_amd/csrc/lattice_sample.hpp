@@ -20,13 +20,9 @@ struct LatticeBox {          // by-value kernel argument: what the host derives 
     float inv_h[3];          // float(n - 1) / (hi - lo)
 };
 
-MIP_HD float lattice_trilinear(const float* __restrict__ lattice, const LatticeBox& g, float x, float y, float z) {
-    const float big = 3.4028234663852886e38f;
-    if (!(fabsf(x) <= big && fabsf(y) <= big && fabsf(z) <= big)) return 0.0f;      // NaN fails the comparison too
+// The index rule alone (mipnerf_preview_march samples packed rows with it, preview_march.hpp): cell c and fractions f of a FINITE point p.
+MIP_HD void lattice_cell(const LatticeBox& g, const float p[3], int c[3], float f[3]) {
     const int n[3] = {g.nx, g.ny, g.nz};
-    const float p[3] = {x, y, z};
-    int c[3];
-    float f[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         float u = (p[a] - g.lo[a]) * g.inv_h[a];
@@ -35,6 +31,15 @@ MIP_HD float lattice_trilinear(const float* __restrict__ lattice, const LatticeB
         c[a] = i < n[a] - 2 ? i : n[a] - 2;
         f[a] = u - (float)c[a];
     }
+}
+
+MIP_HD float lattice_trilinear(const float* __restrict__ lattice, const LatticeBox& g, float x, float y, float z) {
+    const float big = 3.4028234663852886e38f;
+    if (!(fabsf(x) <= big && fabsf(y) <= big && fabsf(z) <= big)) return 0.0f;      // NaN fails the comparison too
+    const float p[3] = {x, y, z};
+    int c[3];
+    float f[3];
+    lattice_cell(g, p, c, f);
     const int64_t sy = g.nx, sz = (int64_t)g.nx * g.ny;
     const float* q = lattice + ((int64_t)c[2] * g.ny + c[1]) * g.nx + c[0];
     // the 8 corner loads first, then the blend

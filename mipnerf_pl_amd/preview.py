@@ -1,0 +1,532 @@
+"""Bake a trained field into a dense lattice of density + spherical-harmonic colour and render frames from the lattice alone.
+
+The PlenOctrees / Plenoxels idea in its simplest dense form (include/mipnerf_preview.h states the row layout and the marching rules):
+
+    bake_field(system)          `ops.density_grid` -> sigma, `ops.occupancy_grid` -> bits, `ops.field_at` once per direction of a Fibonacci
+                                sphere at the lattice Gaussians of the points next to an occupied cell, `fit_sh`, mipnerf_preview_pack
+    render_rays(baked, rays)    mipnerf_preview_march: no MLP, one wavefront per ray
+    PreviewFrame                the frame-shaped wrapper (`render` / `images` like `evaluate.FrameEvaluator`)
+
+    python -m mipnerf_pl_amd.preview --ckpt CKPT --out_dir OUT [--grid 256 | --grid NX NY NZ] [--sh_degree 0|1|2] [--bound B]
+        [--threshold 0.01] [--dilate 1] [--step 0.5] [--t_min 1e-3] [--precision fp32|bf16] [--n_poses 120] [--scale 1]
+        [--save_baked] [--baked FILE] [--data DIR --compare]
+
+renders the spherical path of `render_video` to OUT/preview_spheric/<exp_name>/ and prints one `preview:` line.
+
+THE BAKED PICTURE IS NOT THE MLP'S PICTURE: colour is a low-order expansion in the view direction fitted to `n_dirs` directions, density
+and colour are blended trilinearly between lattice points, and the march takes point samples (no cones: the preview is not anti-aliased).
+`--data DIR --compare` measures how far below the MLP it scores.  Bounded two-level models only.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+SH_C0 = 0.28209479177387814
+SH_C1 = 0.4886025119029199
+SH_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
+ROW_HALVES = {0: 4, 1: 16, 2: 32}
+# Choices, not measurements: half a cell per step keeps two samples in every cell a ray crosses; a march that stops at T < 1e-3 leaves out
+# at most 1e-3 of any output; 32 directions over-determine the 9 coefficients of degree 2 about 3.5 times.
+DEFAULT_STEP_SCALE = 0.5
+DEFAULT_T_MIN = 1e-3
+DEFAULT_MAX_STEPS = 4096
+DEFAULT_N_DIRS = 32
+
+
+def _check_degree(degree, who):
+    if degree not in (0, 1, 2):
+        raise NotImplementedError(f"{who}: the spherical-harmonic degree must be 0, 1 or 2 (got {degree!r})")
+    return int(degree)
+
+
+def sh_basis(dirs, degree):
+    """The real spherical harmonics up to `degree` (0..2) at unit directions [..., 3] -> [..., (degree + 1)^2], in the order and signs of
+    PlenOctrees: [C0, -C1 y, C1 z, -C1 x, C20 xy, C21 yz, C22 (2zz - xx - yy), C23 xz, C24 (xx - yy)].  Pure torch; the dtype of `dirs`."""
+    degree = _check_degree(degree, "sh_basis")
+    x, y, z = dirs[..., 0], dirs[..., 1], dirs[..., 2]
+    out = [torch.full_like(x, SH_C0)]
+    if degree >= 1:
+        out += [-SH_C1 * y, SH_C1 * z, -SH_C1 * x]
+    if degree >= 2:
+        out += [SH_C2[0] * x * y, SH_C2[1] * y * z, SH_C2[2] * (2.0 * z * z - x * x - y * y), SH_C2[3] * x * z, SH_C2[4] * (x * x - y * y)]
+    return torch.stack(out, -1)
+
+
+def fit_sh(rgb, dirs, degree):
+    """Least-squares coefficients of colours seen from K directions: rgb [M, K, 3], unit dirs [K, 3] -> [M, (degree + 1)^2, 3] (the
+    dtype of `rgb`).  The float64 pseudo-inverse of the [K, (degree + 1)^2] basis matrix, applied as one float64 matmul."""
+    degree = _check_degree(degree, "fit_sh")
+    if rgb.dim() != 3 or rgb.shape[-1] != 3 or dirs.shape != (rgb.shape[1], 3):
+        raise ValueError(f"fit_sh: expected rgb [M, K, 3] and dirs [K, 3], got {tuple(rgb.shape)} and {tuple(dirs.shape)}")
+    basis = sh_basis(dirs.to(device=rgb.device, dtype=torch.float64), degree)
+    if basis.shape[0] < basis.shape[1]:
+        raise ValueError(f"fit_sh: {basis.shape[0]} directions do not determine the {basis.shape[1]} coefficients of degree {degree}")
+    pinv = torch.linalg.pinv(basis.cpu()).to(rgb.device)              # [(degree + 1)^2, K]; a few hundred numbers, on the host
+    return torch.matmul(pinv, rgb.to(torch.float64)).to(rgb.dtype)
+
+
+def bake_directions(K=DEFAULT_N_DIRS):
+    """K unit directions of a Fibonacci sphere, [K, 3] float64 on the host."""
+    if K < 1:
+        raise ValueError("bake_directions: K must be positive")
+    i = torch.arange(K, dtype=torch.float64)
+    z = 1.0 - (2.0 * i + 1.0) / K
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    r = torch.sqrt(torch.clamp(1.0 - z * z, min=0.0))
+    return torch.stack([r * torch.cos(phi), r * torch.sin(phi), z], -1)
+
+
+def _dims3(grid):
+    dims = [int(d) for d in (grid if hasattr(grid, "__len__") else (grid,) * 3)]
+    if len(dims) != 3:
+        raise ValueError(f"the lattice has three sizes (nx, ny, nz), got {grid!r}")
+    return tuple(dims)
+
+
+def check_lattice(dims, who):
+    """The lattices the library takes: at least 2 points per axis and 7 nx ny nz < 2^31 (the occupancy grid's rule)."""
+    dims = _dims3(dims)
+    if min(dims) < 2:
+        raise ValueError(f"{who}: a lattice needs at least 2 points per axis (got {dims})")
+    if 7 * dims[0] * dims[1] * dims[2] >= 2 ** 31:
+        raise ValueError(f"{who}: the lattice {dims} is too large: 7 nx ny nz must stay below 2^31")
+    return dims
+
+
+def _box3(v):
+    return tuple(float(np.float32(x)) for x in (v if hasattr(v, "__len__") else (v,) * 3))
+
+
+class BakedField:
+    """A baked lattice: `rows` fp16 [nz, ny, nx, W] (W = 4 / 16 / 32 for degree 0 / 1 / 2; row[0] = sigma, row[1 + 3k + c] = coefficient k
+    of channel c), `dims` = (nx, ny, nz), the box `lo` .. `hi` in (x, y, z) order, `degree`, `occupancy` (an `ops.Occupancy` over the
+    same lattice, or None: every cell is marched) and the density `threshold` its bits were built with."""
+
+    def __init__(self, rows, dims, lo, hi, degree, occupancy=None, threshold=None):
+        self.degree = _check_degree(degree, "BakedField")
+        self.dims = check_lattice(dims, "BakedField")
+        self.lo, self.hi = _box3(lo), _box3(hi)
+        if not all(h > l for l, h in zip(self.lo, self.hi)):
+            raise ValueError(f"BakedField: the box needs hi > lo on every axis (got {self.lo} .. {self.hi})")
+        nx, ny, nz = self.dims
+        if rows.dtype != torch.float16 or tuple(rows.shape) != (nz, ny, nx, ROW_HALVES[self.degree]) or not rows.is_contiguous():
+            raise ValueError(f"BakedField: rows must be contiguous fp16 [nz, ny, nx, W] = {(nz, ny, nx, ROW_HALVES[self.degree])}, "
+                             f"got {rows.dtype} {tuple(rows.shape)}")
+        if occupancy is not None and (tuple(occupancy.dims) != self.dims or tuple(occupancy.bits.shape) != (nz - 1, ny - 1, (nx + 30) // 32)):
+            raise ValueError("BakedField: the occupancy grid must lie on the rows' lattice")
+        self.rows, self.occupancy = rows, occupancy
+        self.threshold = None if threshold is None else float(threshold)
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the rows and the occupancy words."""
+        n = self.rows.numel() * 2
+        return n + (self.occupancy.bits.numel() * 4 if self.occupancy is not None else 0)
+
+    def baked_share(self) -> float:
+        """Share of the lattice points that carry colour coefficients (a read-back)."""
+        if self.rows.shape[-1] <= 1:
+            return 0.0
+        return float((self.rows[..., 1:4] != 0).any(-1).float().mean())         # the three DC coefficients
+
+    def save(self, path):
+        """Everything in one .npz (the rows as fp16, the bits as uint32)."""
+        occ = self.occupancy
+        arrays = dict(rows=self.rows.cpu().numpy(), dims=np.array(self.dims, np.int32), lo=np.array(self.lo, np.float32),
+                      hi=np.array(self.hi, np.float32), degree=np.int32(self.degree),
+                      threshold=np.float32(np.nan if self.threshold is None else self.threshold))
+        if occ is not None:
+            arrays["occupancy"] = occ.bits.cpu().numpy().view(np.uint32)
+            arrays["dilate"] = np.int32(-1 if occ.dilate is None else occ.dilate)
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+        return path
+
+    @staticmethod
+    def stored_degree(path) -> int:
+        """The degree of a saved lattice, without reading its rows."""
+        with np.load(path) as z:
+            return int(z["degree"])
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        from .ops import Occupancy
+        with np.load(path) as z:
+            dims, lo, hi = tuple(int(v) for v in z["dims"]), z["lo"], z["hi"]
+            rows = torch.from_numpy(z["rows"]).to(device)
+            thr = float(z["threshold"])
+            occ = None
+            if "occupancy" in z.files:
+                occ = Occupancy(torch.from_numpy(z["occupancy"].view(np.int32)).to(device).view(torch.uint32), dims, lo, hi)
+                occ.threshold, occ.dilate = (None if np.isnan(thr) else thr), (None if int(z["dilate"]) < 0 else int(z["dilate"]))
+            return cls(rows, dims, lo, hi, int(z["degree"]), occ, None if np.isnan(thr) else thr)
+
+
+def refuse_model(model_or_system, who):
+    """The bake covers the bounded two-level model; anything else is refused with the reason."""
+    m = getattr(model_or_system, "mip_nerf", model_or_system)
+    if bool(getattr(m, "unbounded", False)):
+        raise NotImplementedError(f"{who}: unbounded=True models are not supported (their field lives in a contracted space; a contracted "
+                                  "lattice is not implemented)")
+    if int(getattr(m, "num_levels", 2)) != 2:
+        raise NotImplementedError(f"{who}: only the two-level model is baked (num_levels = {m.num_levels}): the lattice stands for the "
+                                  "field its fine level renders")
+
+
+def occupied_cells(occ):
+    """The bits of an `ops.Occupancy` as a bool tensor [nz - 1, ny - 1, nx - 1] on its device."""
+    nx, ny, nz = occ.dims
+    words = occ.bits.view(torch.int32)
+    shifts = torch.arange(32, dtype=torch.int32, device=words.device)
+    bits = (words[..., None] >> shifts) & 1                         # the arithmetic shift's sign copies are masked away
+    return bits.reshape(nz - 1, ny - 1, -1)[..., :nx - 1].bool()
+
+
+def baked_points(occ):
+    """bool [nz, ny, nx]: the lattice points next to an occupied cell (any of the up to 8 cells around a point), so every corner of an
+    occupied cell is among them."""
+    nx, ny, nz = occ.dims
+    cells = occupied_cells(occ)
+    pts = torch.zeros(nz, ny, nx, dtype=torch.bool, device=cells.device)
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                pts[dz:dz + nz - 1, dy:dy + ny - 1, dx:dx + nx - 1] |= cells
+    return pts
+
+
+def lattice_gaussians(dims, lo, hi, cov_scale, index):
+    """Means [M, 3] and variances [M, 3] (fp32, the device of `index`) of the lattice Gaussians at the flat point indices `index`, as
+    `ops.density_grid` states them: mean = lo + float32(i) * h, variance = cov_scale * h * h / 12, h = (hi - lo) / float32(n - 1)."""
+    nx, ny, nz = dims
+    lo32, hi32 = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+    h = (hi32 - lo32) / np.array([nx - 1, ny - 1, nz - 1], np.float32)
+    var = (np.float32(cov_scale) * h * h) / np.float32(12.0)
+    dev = index.device
+    ijk = torch.stack([index % nx, (index // nx) % ny, index // (nx * ny)], -1).to(torch.float32)
+    means = torch.from_numpy(lo32).to(dev) + ijk * torch.from_numpy(h).to(dev)
+    return means, torch.from_numpy(var).to(dev).expand(index.shape[0], 3).contiguous()
+
+
+def pack_rows(sigma, coef, degree, mask=None, out=None):
+    """mipnerf_preview_pack: fp16 rows [nz, ny, nx, W] of sigma fp32 [nz, ny, nx] and coef fp32 [nz, ny, nx, (degree + 1)^2, 3]; `mask`
+    (uint8 / bool per point, optional): 0 = the colour coefficients are written as zeros."""
+    degree = _check_degree(degree, "pack_rows")
+    nz, ny, nx = sigma.shape
+    nb = (degree + 1) ** 2
+    if sigma.dtype != torch.float32 or coef.dtype != torch.float32 or not sigma.is_contiguous() or not coef.is_contiguous() or \
+            coef.numel() != sigma.numel() * nb * 3:
+        raise ValueError("pack_rows: sigma fp32 [nz, ny, nx] and coef fp32 [nz, ny, nx, (degree + 1)^2, 3], contiguous")
+    if mask is not None:
+        mask = mask.to(torch.uint8).contiguous()
+        if mask.numel() != sigma.numel():
+            raise ValueError("pack_rows: one mask byte per lattice point")
+    if out is None:
+        out = torch.empty(nz, ny, nx, ROW_HALVES[degree], dtype=torch.float16, device=sigma.device)
+    cdims = (C.c_int32 * 3)(nx, ny, nz)
+    with torch.cuda.device(sigma.device):
+        L.preview_check(L.preview_lib().mipnerf_preview_pack(cdims, degree, sigma.data_ptr(), coef.data_ptr(),
+                                                             None if mask is None else mask.data_ptr(), out.data_ptr(),
+                                                             torch.cuda.current_stream().cuda_stream), "preview_pack")
+    return out
+
+
+def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=0.01, dilate=1, n_dirs=DEFAULT_N_DIRS, cov_scale=1.0,
+               precision=None, chunk=None):
+    """Bake the field of a bounded two-level model into a `BakedField` of `grid`^3 (or (nx, ny, nz)) points over lo .. hi.
+
+    sigma = `ops.density_grid`; bits = `ops.occupancy_grid(sigma, threshold, dilate)`; a point is baked iff any of the up to 8 cells around
+    it is occupied; at the baked points `ops.field_at` runs once per direction of `bake_directions(n_dirs)` on the lattice Gaussian
+    (variance cov_scale h^2 / 12), `chunk` points at a time (default 2^20), then `fit_sh` and mipnerf_preview_pack.  The MLP is reached
+    through those public ops only.  `precision`: 'fp32' / 'bf16' (default: the model's)."""
+    from . import ops
+    refuse_model(model_or_system, "bake_field")
+    degree = _check_degree(degree, "bake_field")
+    dims = check_lattice(grid, "bake_field")
+    if lo is None or hi is None:
+        raise ValueError("bake_field: give the box lo .. hi the lattice spans (the rays to be rendered are marched inside it only)")
+    if (degree + 1) ** 2 > n_dirs:
+        raise ValueError(f"bake_field: {n_dirs} directions do not determine the {(degree + 1) ** 2} coefficients of degree {degree}")
+    chunk = (1 << 20) if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("bake_field: chunk must be positive")
+    lo, hi = _box3(lo), _box3(hi)
+    nx, ny, nz = dims
+    nb = (degree + 1) ** 2
+    with torch.no_grad():
+        sigma = ops.density_grid(model_or_system, dims, lo, hi, cov_scale=cov_scale, precision=precision)
+        dev = sigma.device
+        occ = ops.occupancy_grid(sigma, threshold, lo, hi, dilate=dilate)
+        mask = baked_points(occ)
+        dirs = bake_directions(n_dirs)
+        dirs32 = dirs.to(device=dev, dtype=torch.float32)
+        rows = torch.empty(nz, ny, nx, ROW_HALVES[degree], dtype=torch.float16, device=dev)
+        # dense coefficients only for a slab of z layers at a time (at least 2: the library's smallest lattice)
+        layers = min(nz, max(2, (1 << 24) // (nx * ny)))
+        starts = list(range(0, nz, layers))
+        if len(starts) > 1 and nz - starts[-1] < 2:
+            starts[-1] = nz - 2                                       # the last slab overlaps the one before it by a layer
+        for z0 in starts:
+            z1 = min(z0 + layers, nz)
+            coef = torch.zeros(z1 - z0, ny, nx, nb, 3, dtype=torch.float32, device=dev)
+            index = torch.nonzero(mask[z0:z1].reshape(-1)).reshape(-1) + z0 * ny * nx
+            for c0 in range(0, index.numel(), chunk):
+                idx = index[c0:c0 + chunk]
+                means, var = lattice_gaussians(dims, lo, hi, cov_scale, idx)
+                rgb = torch.empty(idx.numel(), n_dirs, 3, dtype=torch.float32, device=dev)
+                for k in range(n_dirs):
+                    rgb[:, k] = ops.field_at(model_or_system, means, var, dirs32[k].expand(idx.numel(), 3), precision=precision)[:, :3]
+                coef.view(-1, nb, 3)[idx - z0 * ny * nx] = fit_sh(rgb, dirs, degree)
+            pack_rows(sigma[z0:z1], coef, degree, mask=mask[z0:z1], out=rows[z0:z1])
+    return BakedField(rows, dims, lo, hi, degree, occ, threshold)
+
+
+def _background(white_bkgd):
+    if isinstance(white_bkgd, (bool, np.bool_, int)):
+        return (1.0, 1.0, 1.0) if white_bkgd else (0.0, 0.0, 0.0)
+    return tuple(float(v) for v in white_bkgd)
+
+
+def march(baked, origins, directions, near, far, background, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS,
+          out=None, steps=None, use_occupancy=True):
+    """mipnerf_preview_march on flat fp32 device tensors: origins / directions [B, 3], near / far [B] -> (rgb [B, 3], acc [B], distance
+    [B]) (`out`: these three, preallocated).  `steps`: an int32 [B] tensor that receives the samples evaluated per ray."""
+    B = origins.shape[0]
+    dev = baked.rows.device
+    for name, t, shape in (("origins", origins, (B, 3)), ("directions", directions, (B, 3)), ("near", near, (B,)), ("far", far, (B,))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != int(np.prod(shape)):
+            raise ValueError(f"march: {name} must be a contiguous fp32 tensor of {shape} on {dev}")
+    if out is None:
+        out = (torch.empty(B, 3, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev))
+    rgb, acc, dist = out
+    if steps is not None and (steps.dtype != torch.int32 or steps.numel() != B or not steps.is_contiguous()):
+        raise ValueError("march: steps must be a contiguous int32 tensor with one entry per ray")
+    occ = baked.occupancy if use_occupancy else None
+    field = L.PreviewField((C.c_int32 * 3)(*baked.dims), (C.c_float * 3)(*baked.lo), (C.c_float * 3)(*baked.hi), baked.degree,
+                           baked.rows.data_ptr(), None if occ is None else occ.bits.data_ptr())
+    params = L.PreviewParams(float(step_scale), float(t_min), int(max_steps), (C.c_float * 3)(*_background(background)))
+    with torch.cuda.device(dev):
+        L.preview_check(L.preview_lib().mipnerf_preview_march(C.byref(field), C.byref(params), B, origins.data_ptr(), directions.data_ptr(),
+                                                              near.data_ptr(), far.data_ptr(), rgb.data_ptr(), acc.data_ptr(), dist.data_ptr(),
+                                                              None if steps is None else steps.data_ptr(),
+                                                              torch.cuda.current_stream().cuda_stream), "preview_march")
+    return rgb, acc, dist
+
+
+def render_rays(baked, rays, white_bkgd, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS):
+    """`rays` (a `Rays` of [..., k] tensors) marched through `baked`: (rgb [..., 3], distance [...], acc [...]).  The defaults of
+    `step_scale` and `t_min` are choices (see the top of this module), not measurements."""
+    shape = rays.origins.shape[:-1]
+    flat = [t.reshape(-1, t.shape[-1]).float().contiguous() for t in (rays.origins, rays.directions, rays.near, rays.far)]
+    rgb, acc, dist = march(baked, flat[0], flat[1], flat[2].reshape(-1), flat[3].reshape(-1), white_bkgd, step_scale, t_min, max_steps)
+    return rgb.reshape(*shape, 3), dist.reshape(shape), acc.reshape(shape)
+
+
+class PreviewFrame:
+    """One image size of a baked field: static output buffers and the device buffers of the image bytes; `render` / `images` are shaped
+    like `evaluate.FrameEvaluator`'s, so `evaluate.save_images` and the PNG kernels serve both."""
+
+    def __init__(self, baked, height, width, white_bkgd=True, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS):
+        from . import ops
+        self.baked, self.h, self.w = baked, int(height), int(width)
+        self.white_bkgd, self.step_scale, self.t_min, self.max_steps = white_bkgd, float(step_scale), float(t_min), int(max_steps)
+        n, dev = self.h * self.w, baked.rows.device
+        self.out = (torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev))
+        self.steps = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.vis_ws = torch.empty(ops.visualize_workspace_floats(n), dtype=torch.float32, device=dev)
+        self.rgb_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=dev)
+        self.dist_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=dev)
+        self.acc_u8 = torch.empty(self.h, self.w, 3, dtype=torch.uint8, device=dev)
+
+    def render(self, rays):
+        """Rays [H, W, k] -> (rgb [H, W, 3], distance [H, W], acc [H, W]): views of the frame's static outputs."""
+        n = self.h * self.w
+        o, d = rays.origins.reshape(n, 3).float().contiguous(), rays.directions.reshape(n, 3).float().contiguous()
+        near, far = rays.near.reshape(n).float().contiguous(), rays.far.reshape(n).float().contiguous()
+        rgb, acc, dist = march(self.baked, o, d, near, far, self.white_bkgd, self.step_scale, self.t_min, self.max_steps, out=self.out,
+                               steps=self.steps)
+        return rgb.view(self.h, self.w, 3), dist.view(self.h, self.w), acc.view(self.h, self.w)
+
+    def images(self, rgb, dist, acc):
+        from . import ops
+        ops.image_to_u8(rgb, out=self.rgb_u8)
+        ops.visualize_map(dist, out=self.dist_u8, workspace=self.vis_ws)
+        ops.visualize_map(acc, out=self.acc_u8, workspace=self.vis_ws)
+        return self.rgb_u8, self.dist_u8, self.acc_u8
+
+
+# ---- the command -----------------------------------------------------------------------------------------------------------------
+def build_parser():
+    from .evaluate import DEFAULT_CHUNK
+    from .render_video import CAMERA_ANGLE_X, _bool
+    p = argparse.ArgumentParser(prog="python -m mipnerf_pl_amd.preview")
+    p.add_argument("--ckpt", help="Path to ckpt.")
+    p.add_argument("--out_dir", help="Output directory.", type=str, required=True)
+    p.add_argument("--grid", help="lattice points per axis: one number, or NX NY NZ", type=int, nargs="+", default=[256], metavar="N")
+    p.add_argument("--sh_degree", help="degree of the view-dependent colour (default 1, or the degree of --baked)", type=int, default=None)
+    p.add_argument("--bound", help="the lattice spans [-B, B]^3 (default: the largest coordinate any ray of the cameras to be rendered reaches "
+                   "between near and far, plus one cell)", type=float, default=None)
+    p.add_argument("--threshold", help="a cell is marched when the density at one of its corners exceeds this; scene dependent", type=float,
+                   default=0.01)
+    p.add_argument("--dilate", help="occupied cells grow by this many cells in every direction", type=int, default=1)
+    p.add_argument("--step", help="march step in units of the smallest cell edge (a choice: 0.5 keeps two samples per cell)", type=float,
+                   default=DEFAULT_STEP_SCALE)
+    p.add_argument("--t_min", help="stop a ray when its transmittance falls below this (a choice; 0: never)", type=float, default=DEFAULT_T_MIN)
+    p.add_argument("--precision", help="MLP precision of the bake (default: the checkpoint's)", choices=["fp32", "bf16"], default=None)
+    p.add_argument("--n_poses", help="poses on the spherical path", type=int, default=120)
+    p.add_argument("--scale", help="pyramid levels of the spherical path", type=int, default=1)
+    p.add_argument("--save_baked", help="write the baked lattice to <out_dir>/preview_spheric/<exp_name>/baked.npz", action="store_true")
+    p.add_argument("--baked", help="render a lattice saved by --save_baked instead of baking one", type=str, default=None, metavar="FILE")
+    p.add_argument("--data", help="--compare: path to the data whose test split is rendered both ways", default=None)
+    p.add_argument("--compare", help="render the test split of --data from the lattice and with the MLP: mean PSNR of each against the photos "
+                   "and of the lattice against the MLP", action="store_true")
+    p.add_argument("--base_size", help="source image size: W H", type=int, nargs=2, default=[800, 800])
+    p.add_argument("--camera_angle_x", help="camera_angle_x in source dataset", type=float, default=CAMERA_ANGLE_X)
+    p.add_argument("--white_bkgd", help="Train set image background color.", type=_bool, default=True)
+    p.add_argument("--chunk_size", help="--compare: chunk size of the MLP render", type=int, default=DEFAULT_CHUNK)
+    p.add_argument("--n_dirs", help="view directions the colour is fitted to (a choice)", type=int, default=DEFAULT_N_DIRS)
+    return p
+
+
+def refuse_arguments(args):
+    """Everything that can be refused from the command line alone, before any file is opened."""
+    if len(args.grid) not in (1, 3):
+        raise SystemExit(f"--grid {' '.join(str(g) for g in args.grid)}: give one number or NX NY NZ")
+    dims = _dims3(args.grid if len(args.grid) == 3 else args.grid[0])
+    if min(dims) < 2:
+        raise SystemExit(f"--grid {' '.join(str(g) for g in args.grid)}: the lattice needs at least 2 points per axis")
+    if 7 * dims[0] * dims[1] * dims[2] >= 2 ** 31:
+        raise SystemExit(f"--grid {' '.join(str(g) for g in args.grid)}: too large: 7 nx ny nz must stay below 2^31")
+    if args.sh_degree is not None and args.sh_degree not in (0, 1, 2):
+        raise SystemExit(f"--sh_degree {args.sh_degree}: the degree must be 0, 1 or 2")
+    if not args.step > 0:
+        raise SystemExit(f"--step {args.step}: the step must be positive")
+    if not 0 <= args.t_min < 1:
+        raise SystemExit(f"--t_min {args.t_min}: must lie in [0, 1)")
+    if args.bound is not None and not args.bound > 0:
+        raise SystemExit(f"--bound {args.bound}: the half-width of the box must be positive")
+    if args.compare and args.data is None:
+        raise SystemExit("--compare renders the test split of a data set both ways: give --data")
+    if args.baked is not None and args.save_baked:
+        raise SystemExit("--save_baked writes the lattice this run bakes; --baked renders one that exists already: give one of them")
+    if args.ckpt is None:
+        raise SystemExit("give --ckpt: the checkpoint names the experiment (and is what --compare renders with the MLP)")
+    return dims
+
+
+def refuse_baked_degree(args):
+    """--baked of another degree than --sh_degree, when both are given: refused after reading the file's degree alone."""
+    if args.baked is None:
+        return
+    stored = BakedField.stored_degree(args.baked)
+    if args.sh_degree is not None and args.sh_degree != stored:
+        raise SystemExit(f"--baked {args.baked} holds a lattice of degree {stored}, --sh_degree asks for {args.sh_degree}: drop one of them")
+
+
+def refuse_checkpoint(system):
+    """Captured-scene and unbounded checkpoints, and one-level models: refused before anything is moved to the device."""
+    from .render_video import is_scene360
+    if is_scene360(system.hparams) or bool(getattr(system.mip_nerf, "unbounded", False)):
+        raise SystemExit("preview: this checkpoint holds a captured scene ({}); the baked lattice is implemented for bounded (Blender) "
+                         "checkpoints only -- its rays leave any box and the unbounded-scene model lives in a contracted space".format(
+                             system.hparams.get("dataset_name")))
+    try:
+        refuse_model(system, "preview")
+    except NotImplementedError as e:
+        raise SystemExit(str(e))
+
+
+def _psnr(a, b):
+    """PSNR of two [H, W, 3] images by the evaluation's own kernel."""
+    from . import ops
+    return float(ops.eval_errors(a, b)[0])
+
+
+def main(argv=None):
+    from .evaluate import FrameEvaluator, cull_box, generate_video, save_images
+    from .render_video import load_system
+    args = build_parser().parse_args(argv)
+    dims = refuse_arguments(args)
+    refuse_baked_degree(args)
+    system = load_system(args)
+    refuse_checkpoint(system)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    system = system.to(dev).eval()
+    hp = system.hparams
+    exp_name = hp["exp_name"]
+    from .datasets import RenderGen, dataset_dict
+    focal = .5 * args.base_size[0] / np.tan(.5 * args.camera_angle_x)
+    path = RenderGen(focal, args.base_size, args.scale, device=dev, n_poses=args.n_poses)
+    dataset = None
+    if args.compare:
+        dataset = dataset_dict[hp["dataset_name"]](data_dir=args.data, split="test", white_bkgd=hp["val.white_bkgd"],
+                                                  batch_type=hp["val.batch_type"], device=dev)
+    folder = os.path.join(args.out_dir, "preview_spheric", exp_name)
+    nums = len(path) // args.scale
+    for i in range(args.scale):
+        os.makedirs(os.path.join(folder, str(2 ** i)), exist_ok=True)
+    with torch.no_grad():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if args.baked is not None:
+            baked = BakedField.load(args.baked, dev)
+        else:
+            bound = args.bound
+            if bound is None:
+                if min(dims) < 4:
+                    raise SystemExit("--grid: the default box needs at least 4 points per axis; give --bound")
+                frames = [path[i] for i in range(len(path))] + ([dataset[i][0] for i in range(len(dataset))] if dataset is not None else [])
+                bound = cull_box(frames, min(dims))
+            baked = bake_field(system, grid=dims, degree=1 if args.sh_degree is None else args.sh_degree, lo=-float(bound), hi=float(bound),
+                               threshold=args.threshold, dilate=args.dilate, n_dirs=args.n_dirs, precision=args.precision)
+        torch.cuda.synchronize()
+        bake_ms = 1e3 * (time.perf_counter() - t0)
+        if args.save_baked:
+            print("preview: lattice saved to {}".format(baked.save(os.path.join(folder, "baked.npz"))))
+        frames, times = {}, []
+        for idx in range(len(path)):
+            h, w = path.sizes[idx]
+            fr = frames.get((h, w))
+            if fr is None:
+                fr = frames[(h, w)] = PreviewFrame(baked, h, w, args.white_bkgd, args.step, args.t_min)
+            rays = path[idx]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fr.render(rays)
+            torch.cuda.synchronize()
+            times.append(1e3 * (time.perf_counter() - t0))
+            save_images(*fr.images(*out), os.path.join(folder, str(int(args.base_size[0] / w))), idx % nums)
+        generate_video(folder)
+        print("preview: lattice {0} x {1} x {2}, degree {3}, baked share {4:.4f}, {5:.1f} MiB, {6} {7:.1f} ms, mean {8:.3f} ms per frame "
+              "({9} frames)".format(*baked.dims, baked.degree, baked.baked_share(), baked.nbytes / 2 ** 20,
+                                    "loaded in" if args.baked is not None else "baked in", bake_ms, float(np.mean(times)), len(times)))
+        if dataset is not None:
+            white = bool(hp["val.white_bkgd"])
+            mlp_frames, p_baked, p_mlp, p_both = {}, [], [], []
+            for idx in range(len(dataset)):
+                rays, gt = dataset[idx]
+                h, w = int(gt.shape[0]), int(gt.shape[1])
+                if (h, w) not in mlp_frames:
+                    mlp_frames[(h, w)] = (FrameEvaluator(system.mip_nerf, h, w, args.chunk_size, white, dev),
+                                          PreviewFrame(baked, h, w, white, args.step, args.t_min))
+                ev, fr = mlp_frames[(h, w)]
+                want = ev.render(rays)[0]
+                got = fr.render(rays)[0]
+                p_baked.append(_psnr(got, gt[..., :3]))
+                p_mlp.append(_psnr(want, gt[..., :3]))
+                p_both.append(_psnr(got, want))
+            print("preview: mean PSNR over {0} test images: baked vs photos {1:.3f}, MLP vs photos {2:.3f}, baked vs MLP {3:.3f}".format(
+                len(dataset), float(np.mean(p_baked)), float(np.mean(p_mlp)), float(np.mean(p_both))))
+    return folder
+
+
+if __name__ == "__main__":
+    main()
