@@ -16,7 +16,7 @@ default architecture; (3, 11) and (33, 65) for w128, noview, d6s3, dc2, the unbo
 (inference only) and w200c72 (zero-padded on the 256 / 128 kernels).
 
 What this cannot prove: rounding behaviour and accumulation accuracy on real-valued data, which stay with the emulation and
-oracle tests.  Every run records, per case (gpu_util.record, tags "mlp_exact ..."), the number of mismatching entries per
+oracle tests and, stage by stage against float64 on the kernels' own saved operands, with tests/test_gpu_mlp_local.py.  Every run records, per case (gpu_util.record, tags "mlp_exact ..."), the number of mismatching entries per
 tensor and the first one's index -- for raw also that sample's index modulo 32, modulo 256 and its ray s // N."""
 import warnings
 
