@@ -55,7 +55,7 @@ k_activate(int64_t M, const float4* __restrict__ raw, float rgb_padding, float d
 //   w_i = (1 - e^{-x_i}) T_i,  x_i = sigma_i * delta_i,  T_i = exp(-sum_{j<i} x_j)
 //   G_i  = dL/dw_i = sum_c g_rgb_c (c_ic - [white]) + g_acc + g_dist * tmid_i + g_w_i
 //   dL/dx_i = G_i T_{i+1} - sum_{k>i} G_k w_k ,  dL/dsigma_i = delta_i dL/dx_i ,  dL/dc_i = w_i g_rgb
-//   d raw_rgb = dL/dc * (1+2p) s (1-s),  s = (c + p)/(1+2p) ;  d raw_density = dL/dsigma * (1 - e^{-sigma})
+//   d raw_rgb = dL/dc * (1+2p) s (1-s),  s = (c + p)/(1+2p) ;  d raw_density = dL/dsigma * -expm1(-sigma)
 template <int K>
 __global__ void __launch_bounds__(256)
 k_volumetric_rendering_bwd(int64_t B, int N, const float4* __restrict__ rgb_sigma, const float* __restrict__ t,
@@ -135,7 +135,7 @@ k_volumetric_rendering_bwd(int64_t B, int N, const float4* __restrict__ rgb_sigm
             o.x = w[k] * gr * sc * s0 * (1.0f - s0);
             o.y = w[k] * gg * sc * s1 * (1.0f - s1);
             o.z = w[k] * gb * sc * s2 * (1.0f - s2);
-            o.w = dsig * (1.0f - expf(-c[k].w));          // softplus'(x) = sigmoid(x) = 1 - e^{-softplus(x)}
+            o.w = dsig * density_activation_grad(c[k].w);
             d_raw[b * (int64_t)N + i0 + k] = o;
         }
     }

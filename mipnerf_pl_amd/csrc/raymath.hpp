@@ -106,6 +106,9 @@ MIP_HD float density_activation(float raw, float density_bias) {
     const float x = raw + density_bias;
     return x > 20.0f ? x : log1pf(expf(x));
 }
+// d density_activation / d raw from the activated value: softplus'(x) = sigmoid(x) = 1 - e^{-softplus(x)}.  expm1f, not
+// 1 - expf: for x below about -5 the difference cancels (17 % off at x = -15, exactly 0 below -16.6)
+MIP_HD float density_activation_grad(float sigma) { return -expm1f(-sigma); }
 
 // torch.linspace(start, end, steps)[i] in fp32 (ATen: start + step*i below the midpoint,
 // end - step*(steps-1-i) above).  ATen's kernels contract the multiply-add (FMA on the CPU

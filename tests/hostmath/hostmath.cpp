@@ -33,6 +33,9 @@ void hm_act(int n, const float* raw_rgb, const float* raw_density, float rgb_pad
         density[i] = mip::density_activation(raw_density[i], density_bias);
     }
 }
+void hm_density_grad(int n, const float* sigma, float* out) {
+    for (int i = 0; i < n; ++i) out[i] = mip::density_activation_grad(sigma[i]);
+}
 void hm_linspace(float start, float end, int steps, float* out) {
     for (int i = 0; i < steps; ++i) out[i] = mip::torch_linspace_at(start, end, steps, i);
 }

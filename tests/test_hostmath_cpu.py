@@ -67,6 +67,23 @@ def test_view_encoding_and_activations(hm, golden_dir):
     np.testing.assert_allclose(den, orc.softplus(dd - np.float32(1)), rtol=2e-6, atol=1e-9)
 
 
+def test_density_activation_grad_is_sigmoid(hm):
+    """density_activation_grad(softplus32(x)) against float64 sigmoid(x), x on a grid over [-30, 30]: the derivative the reference's
+    autograd takes.  Measured with g++ / glibc: 1.73e-7 relative at worst, at x = -15.9 (sigma's own rounding moves the factor by up to
+    one ulp, log1pf, expf and expm1f by theirs); bound 6 x 2^-24 = 3.6e-7, twice that.  1 - expf(-sigma) in its place is 17 % off at
+    x = -15 and exactly 0 below x = -16.6."""
+    x = np.linspace(-30.0, 30.0, 60001).astype(np.float32)
+    n = x.size
+    junk, sigma, fac = (np.empty(n, np.float32) for _ in range(3))
+    hm.hm_act.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    hm.hm_act(n, p(x), p(x), 0.001, 0.0, p(junk), p(sigma))
+    hm.hm_density_grad(n, p(sigma), p(fac))
+    want = 1.0 / (1.0 + np.exp(-x.astype(np.float64)))
+    rel = np.abs(fac.astype(np.float64) - want) / want
+    print(f"density_activation_grad: worst relative error {rel.max():.3g} at x = {x[rel.argmax()]}")
+    assert np.all(fac > 0) and rel.max() <= 6 * 2.0 ** -24
+
+
 @pytest.mark.parametrize("steps", [2, 3, 65, 129, 130, 257])
 def test_linspace_matches_torch(hm, steps):
     import torch
