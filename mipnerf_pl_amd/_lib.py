@@ -180,9 +180,28 @@ PREVIEW_SIGNATURES = {
     "mipnerf_preview_march": (C.c_int, [C.POINTER(PreviewField), C.POINTER(PreviewParams), _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# include/mipnerf_preview_mip.h: the preview over a cone-radius pyramid of lattices, in a fourth library; the preview library keeps its
+# ABI version and its entry points
+PREVIEW_MIP_LIB_PATH = os.environ.get("MIPNERF_PREVIEW_MIP_LIB", os.path.join(HERE, "csrc", "libmipnerf_preview_mip.so"))
+PREVIEW_MIP_ABI = 1
+PREVIEW_MIP_MAX_LEVELS = 8
+
+
+class PreviewPyramid(C.Structure):
+    _fields_ = [("levels", _I32), ("level", PreviewField * PREVIEW_MIP_MAX_LEVELS)]
+
+
+PREVIEW_MIP_SIGNATURES = {
+    "mipnerf_preview_mip_abi_version": (C.c_int, []),
+    "mipnerf_preview_mip_last_error": (C.c_char_p, []),
+    "mipnerf_preview_mip_march": (C.c_int, [C.POINTER(PreviewPyramid), C.POINTER(PreviewParams), _F, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                            _P, _P]),
+}
+
 _lib = None
 _diag = None
 _preview = None
+_preview_mip = None
 
 
 def preview_lib():
@@ -211,6 +230,41 @@ def preview_check(rc: int, what: str = "") -> None:
     if rc == OK:
         return
     msg = (preview_lib().mipnerf_preview_last_error() or b"").decode(errors="replace")
+    msg = f"{what}: {msg}" if what else msg
+    if rc == E_UNSUPPORTED:
+        raise NotImplementedError(msg)
+    if rc == E_INVALID:
+        raise ValueError(msg)
+    raise RuntimeError(f"{msg} (code {rc})")
+
+
+def preview_mip_lib():
+    """Load (once) libmipnerf_preview_mip.so.  No fallback: a missing library is an error."""
+    global _preview_mip
+    if _preview_mip is None:
+        if not os.path.exists(PREVIEW_MIP_LIB_PATH):
+            raise RuntimeError(f"{PREVIEW_MIP_LIB_PATH} is missing: the pyramid renderer has no fallback. "
+                               "Build it with `python -m mipnerf_pl_amd.build` (needs hipcc / ROCm).")
+        try:
+            import torch  # noqa: F401  (same HIP runtime instance, see lib())
+        except ImportError:
+            pass
+        h = C.CDLL(PREVIEW_MIP_LIB_PATH)
+        for name, (res, args) in PREVIEW_MIP_SIGNATURES.items():
+            fn = getattr(h, name)
+            fn.restype = res
+            fn.argtypes = args
+        if h.mipnerf_preview_mip_abi_version() != PREVIEW_MIP_ABI:
+            raise RuntimeError(f"{PREVIEW_MIP_LIB_PATH}: ABI {h.mipnerf_preview_mip_abi_version()}, this binding speaks {PREVIEW_MIP_ABI}: "
+                               "rebuild")
+        _preview_mip = h
+    return _preview_mip
+
+
+def preview_mip_check(rc: int, what: str = "") -> None:
+    if rc == OK:
+        return
+    msg = (preview_mip_lib().mipnerf_preview_mip_last_error() or b"").decode(errors="replace")
     msg = f"{what}: {msg}" if what else msg
     if rc == E_UNSUPPORTED:
         raise NotImplementedError(msg)

@@ -1,5 +1,6 @@
-"""Build libmipnerf_hip.so (the drop-in library), libmipnerf_diag.so (measurement tooling) and libmipnerf_preview.so (the baked-lattice
-preview renderer) for gfx950 in-tree (hipcc cross-compiles without a GPU).
+"""Build libmipnerf_hip.so (the drop-in library), libmipnerf_diag.so (measurement tooling), libmipnerf_preview.so (the baked-lattice
+preview renderer) and libmipnerf_preview_mip.so (the same renderer over a pyramid of lattices) for gfx950 in-tree (hipcc cross-compiles
+without a GPU).
 
     python -m mipnerf_pl_amd.build [--force]
 
@@ -91,6 +92,11 @@ DIAG_UNITS = [("kernels_diag.hip", []), ("diag_capi.hip", [])]
 PREVIEW_LIB = os.path.join(CSRC, "libmipnerf_preview.so")
 PREVIEW_UNITS = [("kernels_preview.hip", ["-ffp-contract=off"]),      # the slab test, o + t * d and the row blend round as stated in preview_march.hpp
                  ("preview_capi.hip", ["-ffp-contract=off"])]          # the world step step_scale * min(h) is formed on the host
+# the preview over a cone-radius pyramid of lattices (include/mipnerf_preview_mip.h): a fourth library, so the preview library keeps its
+# entry points as well
+PREVIEW_MIP_LIB = os.path.join(CSRC, "libmipnerf_preview_mip.so")
+PREVIEW_MIP_UNITS = [("kernels_preview_mip.hip", ["-ffp-contract=off"]),   # P7: the same roundings as kernels_preview.hip, bit for bit
+                     ("preview_mip_capi.hip", ["-ffp-contract=off"])]       # the spacings s_l and the world step are formed on the host
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall",
           "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result"]
 
@@ -150,17 +156,19 @@ def build(force: bool = False, verbose: bool = True) -> str:
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_hip.h"))
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_diag.h"))
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_preview.h"))
+    deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_preview_mip.h"))
     stamp = os.path.join(CSRC, ".build_stamp_" + os.path.basename(LIB))
     units = UNITS[:-1] + variant_units() + UNITS[-1:]          # capi.hip last
-    dig = _digest(deps, COMMON + sum((f for _, f in units + PREVIEW_UNITS), []))
-    if not force and os.path.exists(LIB) and os.path.exists(DIAG_LIB) and os.path.exists(PREVIEW_LIB) and os.path.exists(stamp) and open(stamp).read() == dig:
+    dig = _digest(deps, COMMON + sum((f for _, f in units + PREVIEW_UNITS + PREVIEW_MIP_UNITS), []))
+    if not force and os.path.exists(LIB) and os.path.exists(DIAG_LIB) and os.path.exists(PREVIEW_LIB) and os.path.exists(PREVIEW_MIP_LIB) and \
+            os.path.exists(stamp) and open(stamp).read() == dig:
         if verbose:
             print(f"[build] {LIB} is up to date")
         return LIB
     cc = hipcc()
     objs = []
     procs = []
-    for src, extra in units + DIAG_UNITS + PREVIEW_UNITS:
+    for src, extra in units + DIAG_UNITS + PREVIEW_UNITS + PREVIEW_MIP_UNITS:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
         cmd = [cc] + COMMON + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
@@ -177,7 +185,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
             print(f"[build] FAILED: {src}")
     if failed:
         raise RuntimeError("hipcc failed")
-    preview_objs = objs[len(units) + len(DIAG_UNITS):]
+    mip_objs = objs[len(units) + len(DIAG_UNITS) + len(PREVIEW_UNITS):]
+    preview_objs = objs[len(units) + len(DIAG_UNITS):len(units) + len(DIAG_UNITS) + len(PREVIEW_UNITS)]
     diag_objs = objs[len(units):len(units) + len(DIAG_UNITS)]
     objs = objs[:len(units)]
     objs.append(tables_object())
@@ -195,7 +204,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     subprocess.check_call(["gcc", "-shared", "-fPIC", "-o", os.path.join(stub_dir, "libamdhip64.so"), stub_c])
     rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
     # The dynamic symbol table is the C ABI and nothing else: a linker version script keeps `mipnerf_*` (the entry points
-    # include/mipnerf_hip.h / mipnerf_diag.h / mipnerf_preview.h declare) and makes every C++ launcher, kernel handle and table blob local.
+    # include/mipnerf_hip.h / mipnerf_diag.h / mipnerf_preview.h / mipnerf_preview_mip.h declare) and makes every C++ launcher, kernel handle and table blob local.
     vers = os.path.join(stub_dir, "exports.map")
     with open(vers, "w") as f:
         f.write("{ global: mipnerf_*; local: *; };\n")
@@ -210,6 +219,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
         print("[build]", " ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)
     cmd = ["g++", "-shared", "-fPIC", "-o", PREVIEW_LIB] + preview_objs + cmd[cmd.index("-Wl,--version-script=" + vers):]
+    if verbose:
+        print("[build]", " ".join(cmd))
+    subprocess.check_call(cmd, cwd=CSRC)
+    cmd = ["g++", "-shared", "-fPIC", "-o", PREVIEW_MIP_LIB] + mip_objs + cmd[cmd.index("-Wl,--version-script=" + vers):]
     if verbose:
         print("[build]", " ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)

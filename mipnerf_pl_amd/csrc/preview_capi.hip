@@ -6,8 +6,7 @@
 
 #include <string>
 
-#include "../../include/mipnerf_preview.h"
-#include "preview_march.hpp"
+#include "preview_field_host.hpp"
 
 namespace mip {
 hipError_t launch_preview_march(const PreviewField& f, const PreviewMarch& p, int degree, int64_t n_rays, const float* origins,
@@ -20,7 +19,10 @@ hipError_t launch_preview_pack(int64_t n, int degree, const float* sigma, const 
 namespace {
 
 thread_local std::string g_err;
-enum { PV_OK = 0, PV_E_INVALID = 1, PV_E_UNSUPPORTED = 2, PV_E_HIP = 3 };      // the codes of mipnerf_hip.h
+using mip::PV_OK;
+using mip::PV_E_INVALID;
+using mip::PV_E_UNSUPPORTED;
+using mip::PV_E_HIP;
 
 int fail(int code, const std::string& msg) {
     g_err = msg;
@@ -29,11 +31,7 @@ int fail(int code, const std::string& msg) {
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// dims of a lattice both entry points accept: >= 2 points per axis and 7 nx ny nz < 2^31 (the rule of mipnerf_occupancy_words)
-bool dims_ok(const int32_t* dims) {
-    if (dims[0] < 2 || dims[1] < 2 || dims[2] < 2) return false;
-    return 7ll * dims[0] * (long long)dims[1] < (1ll << 31) && 7ll * dims[0] * (long long)dims[1] * dims[2] < (1ll << 31);
-}
+bool dims_ok(const int32_t* dims) { return mip::preview_dims_ok(dims); }
 
 int hip_result(hipError_t e, const char* who) {
     if (e == hipSuccess) return PV_OK;
@@ -61,12 +59,8 @@ int mipnerf_preview_march(const mipnerf_preview_field_t* field, const mipnerf_pr
                           const float* origins, const float* directions, const float* near, const float* far, float* rgb, float* acc,
                           float* distance, int32_t* steps, void* stream) {
     if (!field || !params) return fail(PV_E_INVALID, "preview_march: field and params must not be null");
-    if (!field->rows) return fail(PV_E_INVALID, "preview_march: field.rows must not be null");
-    if (field->degree < 0 || field->degree > 2) return fail(PV_E_UNSUPPORTED, "preview_march: field.degree must be 0, 1 or 2");
-    if (!dims_ok(field->dims)) return fail(PV_E_INVALID, "preview_march: a lattice needs at least 2 points per axis and 7 nx ny nz < 2^31");
-    for (int a = 0; a < 3; ++a)
-        if (!(field->hi[a] > field->lo[a]) || !isfinite(field->lo[a]) || !isfinite(field->hi[a]))
-            return fail(PV_E_INVALID, "preview_march: the box needs finite lo < hi on every axis");
+    const char* why = "";
+    if (const int code = mip::preview_field_check(field, &why)) return fail(code, std::string("preview_march: ") + why);
     if (!(params->step_scale > 0.0f) || !isfinite(params->step_scale)) return fail(PV_E_INVALID, "preview_march: step_scale must be positive and finite");
     if (params->max_steps < 1) return fail(PV_E_INVALID, "preview_march: max_steps must be at least 1");
     if (!(params->t_min >= 0.0f && params->t_min < 1.0f)) return fail(PV_E_INVALID, "preview_march: t_min must lie in [0, 1)");
@@ -74,22 +68,9 @@ int mipnerf_preview_march(const mipnerf_preview_field_t* field, const mipnerf_pr
     if (n_rays == 0) return PV_OK;
     if (!origins || !directions || !near || !far || !rgb || !acc || !distance)
         return fail(PV_E_INVALID, "preview_march: origins, directions, near, far, rgb, acc and distance must not be null");
-    const int W = mip::preview_row_halves(field->degree);
-    if (reinterpret_cast<uintptr_t>(field->rows) % (W < 8 ? 8 : 16) != 0)
-        return fail(PV_E_INVALID, "preview_march: field.rows must be 16-byte aligned (8 for degree 0)");
+    if (!mip::preview_rows_aligned(field)) return fail(PV_E_INVALID, "preview_march: field.rows must be 16-byte aligned (8 for degree 0)");
     mip::PreviewField f;
-    f.box.nx = field->dims[0]; f.box.ny = field->dims[1]; f.box.nz = field->dims[2];
-    float hmin = INFINITY;
-    for (int a = 0; a < 3; ++a) {
-        const float span = field->hi[a] - field->lo[a];
-        f.box.lo[a] = field->lo[a];
-        f.hi[a] = field->hi[a];
-        f.box.inv_h[a] = (float)(field->dims[a] - 1) / span;        // as mipnerf_lattice_density forms it
-        hmin = fminf(hmin, span / (float)(field->dims[a] - 1));
-    }
-    f.rows = static_cast<const uint16_t*>(field->rows);
-    f.occ = field->occupancy;
-    f.words_x = (field->dims[0] - 1 + 31) / 32;
+    const float hmin = mip::preview_field_derive(field, &f);
     mip::PreviewMarch p;
     p.s = params->step_scale * hmin;
     p.t_min = params->t_min;

@@ -2,6 +2,8 @@
 // inlined into k_preview_march (kernels_preview.hip) and compiled with g++ by tests/hostmath/preview.cpp; both with -ffp-contract=off, so
 // every product and sum below rounds once, as written.  The cell index and the trilinear fractions are lattice_sample.hpp's
 // (lattice_cell); nothing here restates them.  How the samples of a ray are spread over lanes is the kernel's business, not this file's.
+// preview_mip.hpp (mipnerf_preview_mip_march) builds on this file: it calls preview_row and preview_shade, the two halves of
+// preview_sample, with its own mix of two rows in between.
 #pragma once
 
 #include <string.h>
@@ -126,16 +128,14 @@ struct alignas(2 * N) HalfChunk {      // N = 4: one 8-byte load; N = 8: one 16-
     uint16_t h[N];
 };
 
-// rule 4 on an occupied cell: the blended row's alpha and clamped colour
+// rule 4 on an occupied cell, first half: the trilinear blend of the 8 corner rows
 template <int DEG>
-MIP_HD void preview_sample(const PreviewField& f, const int c[3], const float fr[3], const float (&Y)[(DEG + 1) * (DEG + 1)], float s,
-                           float* alpha, float colour[3]) {
-    constexpr int W = preview_row_halves(DEG), N = W < 8 ? W : 8, CH = W / N, NB = preview_basis(DEG);
+MIP_HD void preview_row(const PreviewField& f, const int c[3], const float fr[3], float (&row)[preview_row_halves(DEG)]) {
+    constexpr int W = preview_row_halves(DEG), N = W < 8 ? W : 8, CH = W / N;
     typedef HalfChunk<N> Chunk;
     const int64_t sy = (int64_t)f.box.nx * CH, sz = sy * f.box.ny;        // in chunks
     const Chunk* q = reinterpret_cast<const Chunk*>(f.rows) + (((int64_t)c[2] * f.box.ny + c[1]) * f.box.nx + c[0]) * CH;
     const float gx = 1.0f - fr[0], gy = 1.0f - fr[1], gz = 1.0f - fr[2];
-    float row[W];
 #pragma unroll
     for (int k = 0; k < CH; ++k) {
         // the 8 corner loads of this chunk first, then the blend
@@ -152,6 +152,13 @@ MIP_HD void preview_sample(const PreviewField& f, const int c[3], const float fr
             row[k * N + e] = gz * v0 + fr[2] * v1;
         }
     }
+}
+
+// rule 4, second half: a blended row's alpha and clamped colour
+template <int DEG>
+MIP_HD void preview_shade(const float (&row)[preview_row_halves(DEG)], const float (&Y)[(DEG + 1) * (DEG + 1)], float s, float* alpha,
+                          float colour[3]) {
+    constexpr int NB = preview_basis(DEG);
     const float sigma = row[0] < 0.0f ? 0.0f : row[0];          // a NaN stays a NaN
     *alpha = 1.0f - expf(-(sigma * s));
 #pragma unroll
@@ -161,6 +168,15 @@ MIP_HD void preview_sample(const PreviewField& f, const int c[3], const float fr
         for (int k = 0; k < NB; ++k) v += row[1 + 3 * k + ch] * Y[k];
         colour[ch] = v < 0.0f ? 0.0f : v > 1.0f ? 1.0f : v;     // a NaN stays a NaN
     }
+}
+
+// rule 4 on an occupied cell: both halves, in this order
+template <int DEG>
+MIP_HD void preview_sample(const PreviewField& f, const int c[3], const float fr[3], const float (&Y)[(DEG + 1) * (DEG + 1)], float s,
+                           float* alpha, float colour[3]) {
+    float row[preview_row_halves(DEG)];
+    preview_row<DEG>(f, c, fr, row);
+    preview_shade<DEG>(row, Y, s, alpha, colour);
 }
 
 // rule 6

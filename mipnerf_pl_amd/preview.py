@@ -7,15 +7,21 @@ The PlenOctrees / Plenoxels idea in its simplest dense form (include/mipnerf_pre
     render_rays(baked, rays)    mipnerf_preview_march: no MLP, one wavefront per ray
     PreviewFrame                the frame-shaped wrapper (`render` / `images` like `evaluate.FrameEvaluator`)
 
+    bake_pyramid(system)        `bake_field` at grid, then at about half the points per axis, ...: a `BakedPyramid`
+    march_pyramid / render_rays of a pyramid    mipnerf_preview_mip_march (include/mipnerf_preview_mip.h): every sample reads the level (or
+                                the two levels) whose spacing brackets footprint * radius * t, the width of the ray's cone there
+
     python -m mipnerf_pl_amd.preview --ckpt CKPT --out_dir OUT [--grid 256 | --grid NX NY NZ] [--sh_degree 0|1|2] [--bound B]
         [--threshold 0.01] [--dilate 1] [--step 0.5] [--t_min 1e-3] [--precision fp32|bf16] [--n_poses 120] [--scale 1]
-        [--save_baked] [--baked FILE] [--data DIR --compare]
+        [--save_baked] [--baked FILE] [--data DIR --compare] [--mip [L]] [--footprint F]
 
 renders the spherical path of `render_video` to OUT/preview_spheric/<exp_name>/ and prints one `preview:` line.
 
 THE BAKED PICTURE IS NOT THE MLP'S PICTURE: colour is a low-order expansion in the view direction fitted to `n_dirs` directions, density
-and colour are blended trilinearly between lattice points, and the march takes point samples (no cones: the preview is not anti-aliased).
-`--data DIR --compare` measures how far below the MLP it scores.  Bounded two-level models only.
+and colour are blended trilinearly between lattice points, and without `--mip` the march takes point samples of one lattice (no cones:
+that preview is not anti-aliased).  With `--mip` the coarser lattices, baked at their own lattice Gaussians, are the field pre-filtered
+at their spacing, and the cone radius chooses between them.  `--data DIR --compare` measures how far below the MLP either scores.
+Bounded two-level models only.
 """
 from __future__ import annotations
 
@@ -39,6 +45,11 @@ DEFAULT_STEP_SCALE = 0.5
 DEFAULT_T_MIN = 1e-3
 DEFAULT_MAX_STEPS = 4096
 DEFAULT_N_DIRS = 32
+# Choices as well: with radii = dx / sqrt(3) (the data sets' convention) a footprint of sqrt(3) makes w = footprint * radius * t one pixel's
+# width; 4 levels reach 8 times the finest spacing, the 1 / 8 scale of the multi-scale Blender set.
+DEFAULT_FOOTPRINT = float(np.sqrt(3.0))
+DEFAULT_MIP_LEVELS = 4
+MAX_MIP_LEVELS = L.PREVIEW_MIP_MAX_LEVELS
 
 
 def _check_degree(degree, who):
@@ -139,6 +150,11 @@ class BakedField:
 
     def save(self, path):
         """Everything in one .npz (the rows as fp16, the bits as uint32)."""
+        with open(path, "wb") as f:
+            np.savez(f, **self._arrays())
+        return path
+
+    def _arrays(self):
         occ = self.occupancy
         arrays = dict(rows=self.rows.cpu().numpy(), dims=np.array(self.dims, np.int32), lo=np.array(self.lo, np.float32),
                       hi=np.array(self.hi, np.float32), degree=np.int32(self.degree),
@@ -146,9 +162,7 @@ class BakedField:
         if occ is not None:
             arrays["occupancy"] = occ.bits.cpu().numpy().view(np.uint32)
             arrays["dilate"] = np.int32(-1 if occ.dilate is None else occ.dilate)
-        with open(path, "wb") as f:
-            np.savez(f, **arrays)
-        return path
+        return arrays
 
     @staticmethod
     def stored_degree(path) -> int:
@@ -158,16 +172,88 @@ class BakedField:
 
     @classmethod
     def load(cls, path, device="cuda"):
-        from .ops import Occupancy
         with np.load(path) as z:
-            dims, lo, hi = tuple(int(v) for v in z["dims"]), z["lo"], z["hi"]
-            rows = torch.from_numpy(z["rows"]).to(device)
-            thr = float(z["threshold"])
-            occ = None
-            if "occupancy" in z.files:
-                occ = Occupancy(torch.from_numpy(z["occupancy"].view(np.int32)).to(device).view(torch.uint32), dims, lo, hi)
-                occ.threshold, occ.dilate = (None if np.isnan(thr) else thr), (None if int(z["dilate"]) < 0 else int(z["dilate"]))
-            return cls(rows, dims, lo, hi, int(z["degree"]), occ, None if np.isnan(thr) else thr)
+            if "rows" not in z.files:
+                raise ValueError(f"{path} holds a pyramid of lattices, not a single one: load it with BakedPyramid.load")
+            return cls._from_arrays({k: z[k] for k in z.files}, device)
+
+    @classmethod
+    def _from_arrays(cls, z, device):
+        from .ops import Occupancy
+        dims, lo, hi = tuple(int(v) for v in z["dims"]), z["lo"], z["hi"]
+        rows = torch.from_numpy(z["rows"]).to(device)
+        thr = float(z["threshold"])
+        occ = None
+        if "occupancy" in z:
+            occ = Occupancy(torch.from_numpy(z["occupancy"].view(np.int32)).to(device).view(torch.uint32), dims, lo, hi)
+            occ.threshold, occ.dilate = (None if np.isnan(thr) else thr), (None if int(z["dilate"]) < 0 else int(z["dilate"]))
+        return cls(rows, dims, lo, hi, int(z["degree"]), occ, None if np.isnan(thr) else thr)
+
+
+def lattice_spacing(dims, lo, hi) -> float:
+    """The smallest axis spacing of a lattice as the libraries form it: the fp32 (hi - lo) / float(n - 1), then the minimum."""
+    lo32, hi32 = np.asarray(_box3(lo), np.float32), np.asarray(_box3(hi), np.float32)
+    return float(((hi32 - lo32) / (np.asarray(_dims3(dims)) - 1).astype(np.float32)).min())
+
+
+class BakedPyramid:
+    """`levels`: 1 .. 8 `BakedField`s over ONE box (lo and hi equal bit for bit) with one degree, the finest first; the smallest axis
+    spacing increases strictly from level to level (rule P1 of include/mipnerf_preview_mip.h)."""
+
+    def __init__(self, levels):
+        levels = list(levels)
+        if not 1 <= len(levels) <= MAX_MIP_LEVELS or not all(isinstance(b, BakedField) for b in levels):
+            raise ValueError(f"BakedPyramid: 1 .. {MAX_MIP_LEVELS} BakedField levels (got {len(levels)})")
+        first = levels[0]
+        for i, b in enumerate(levels[1:], 1):
+            if np.asarray(b.lo, np.float32).tobytes() != np.asarray(first.lo, np.float32).tobytes() or \
+                    np.asarray(b.hi, np.float32).tobytes() != np.asarray(first.hi, np.float32).tobytes():
+                raise ValueError(f"BakedPyramid: level {i} spans {b.lo} .. {b.hi}, level 0 spans {first.lo} .. {first.hi}: one box for all")
+            if b.degree != first.degree:
+                raise ValueError(f"BakedPyramid: level {i} has degree {b.degree}, level 0 has degree {first.degree}")
+            if b.rows.device != first.rows.device:
+                raise ValueError("BakedPyramid: all levels live on one device")
+        self.spacings = tuple(lattice_spacing(b.dims, b.lo, b.hi) for b in levels)
+        if not all(a < b for a, b in zip(self.spacings, self.spacings[1:])):
+            raise ValueError(f"BakedPyramid: the smallest spacing must increase strictly from level to level (got {self.spacings})")
+        self.levels = levels
+
+    def __len__(self):
+        return len(self.levels)
+
+    lo = property(lambda self: self.levels[0].lo)
+    hi = property(lambda self: self.levels[0].hi)
+    degree = property(lambda self: self.levels[0].degree)
+    device = property(lambda self: self.levels[0].rows.device)
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the rows and the occupancy words of every level."""
+        return sum(b.nbytes for b in self.levels)
+
+    def save(self, path):
+        """Every level in one .npz: `levels` and the shared `degree`, then the arrays of `BakedField.save` of level i as `l<i>_<name>`."""
+        arrays = dict(levels=np.int32(len(self.levels)), degree=np.int32(self.degree))
+        for i, b in enumerate(self.levels):
+            for k, v in b._arrays().items():
+                arrays[f"l{i}_{k}"] = v
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+        return path
+
+    @staticmethod
+    def stored_levels(path):
+        """The level count of a saved pyramid without reading its rows; None: the file holds a single `BakedField`."""
+        with np.load(path) as z:
+            return int(z["levels"]) if "levels" in z.files else None
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        with np.load(path) as z:
+            if "levels" not in z.files:
+                raise ValueError(f"{path} holds a single lattice, not a pyramid: load it with BakedField.load")
+            return cls([BakedField._from_arrays({k[len(f"l{i}_"):]: z[k] for k in z.files if k.startswith(f"l{i}_")}, device)
+                        for i in range(int(z["levels"]))])
 
 
 def refuse_model(model_or_system, who):
@@ -289,6 +375,34 @@ def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=
     return BakedField(rows, dims, lo, hi, degree, occ, threshold)
 
 
+def pyramid_dims(grid, levels, lo, hi):
+    """The lattices of `bake_pyramid`: `grid`, then n_l = max(2, (n_{l-1} + 1) // 2) per axis, at most `levels` of them; the list ends early
+    when the next lattice's smallest spacing would not be larger (every axis already at 2 points)."""
+    if not 1 <= int(levels) <= MAX_MIP_LEVELS:
+        raise ValueError(f"a pyramid has 1 .. {MAX_MIP_LEVELS} levels (got {levels})")
+    out = [_dims3(grid)]
+    while len(out) < int(levels):
+        nxt = tuple(max(2, (n + 1) // 2) for n in out[-1])
+        if not lattice_spacing(nxt, lo, hi) > lattice_spacing(out[-1], lo, hi):
+            break
+        out.append(nxt)
+    return out
+
+
+def bake_pyramid(model_or_system, grid=256, levels=DEFAULT_MIP_LEVELS, degree=1, lo=None, hi=None, **kwargs):
+    """`bake_field` at `grid` and at each coarser lattice of `pyramid_dims`, over the same box and with the same arguments (`kwargs`:
+    threshold, dilate, n_dirs, cov_scale, precision, chunk), as a `BakedPyramid`.  Every level is what `bake_field` returns at its dims:
+    its lattice Gaussians have its own spacing, so a coarser level is the field pre-filtered at that spacing by the model's own integrated
+    encoding.  Level 0 is baked first, so `bake_field`'s refusals come from `bake_field`."""
+    if not 1 <= int(levels) <= MAX_MIP_LEVELS:
+        raise ValueError(f"bake_pyramid: a pyramid has 1 .. {MAX_MIP_LEVELS} levels (got {levels})")
+    first = bake_field(model_or_system, grid=grid, degree=degree, lo=lo, hi=hi, **kwargs)
+    fields = [first]
+    for dims in pyramid_dims(first.dims, levels, first.lo, first.hi)[1:]:
+        fields.append(bake_field(model_or_system, grid=dims, degree=degree, lo=lo, hi=hi, **kwargs))
+    return BakedPyramid(fields)
+
+
 def _background(white_bkgd):
     if isinstance(white_bkgd, (bool, np.bool_, int)):
         return (1.0, 1.0, 1.0) if white_bkgd else (0.0, 0.0, 0.0)
@@ -321,24 +435,68 @@ def march(baked, origins, directions, near, far, background, step_scale=DEFAULT_
     return rgb, acc, dist
 
 
-def render_rays(baked, rays, white_bkgd, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS):
-    """`rays` (a `Rays` of [..., k] tensors) marched through `baked`: (rgb [..., 3], distance [...], acc [...]).  The defaults of
-    `step_scale` and `t_min` are choices (see the top of this module), not measurements."""
+def march_pyramid(pyramid, origins, directions, radii, near, far, background, footprint=DEFAULT_FOOTPRINT, step_scale=DEFAULT_STEP_SCALE,
+                  t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS, out=None, steps=None, lod=None, use_occupancy=True):
+    """mipnerf_preview_mip_march on flat fp32 device tensors: origins / directions [B, 3], radii / near / far [B] -> (rgb [B, 3], acc [B],
+    distance [B]) (`out`: these three, preallocated).  `steps`: an int32 [B] tensor that receives the samples evaluated per ray; `lod`: an
+    fp32 [B] tensor that receives each ray's weighted mean level.  The step is `step_scale` times the spacing of level 0."""
+    B = origins.shape[0]
+    dev = pyramid.device
+    for name, t, shape in (("origins", origins, (B, 3)), ("directions", directions, (B, 3)), ("radii", radii, (B,)), ("near", near, (B,)),
+                           ("far", far, (B,))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != int(np.prod(shape)):
+            raise ValueError(f"march_pyramid: {name} must be a contiguous fp32 tensor of {shape} on {dev}")
+    if out is None:
+        out = (torch.empty(B, 3, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev))
+    rgb, acc, dist = out
+    if steps is not None and (steps.dtype != torch.int32 or steps.numel() != B or not steps.is_contiguous()):
+        raise ValueError("march_pyramid: steps must be a contiguous int32 tensor with one entry per ray")
+    if lod is not None and (lod.dtype != torch.float32 or lod.numel() != B or not lod.is_contiguous() or lod.device != dev):
+        raise ValueError("march_pyramid: lod must be a contiguous fp32 tensor with one entry per ray")
+    pyr = L.PreviewPyramid()
+    pyr.levels = len(pyramid)
+    for i, b in enumerate(pyramid.levels):
+        occ = b.occupancy if use_occupancy else None
+        pyr.level[i] = L.PreviewField((C.c_int32 * 3)(*b.dims), (C.c_float * 3)(*b.lo), (C.c_float * 3)(*b.hi), b.degree, b.rows.data_ptr(),
+                                      None if occ is None else occ.bits.data_ptr())
+    params = L.PreviewParams(float(step_scale), float(t_min), int(max_steps), (C.c_float * 3)(*_background(background)))
+    with torch.cuda.device(dev):
+        L.preview_mip_check(L.preview_mip_lib().mipnerf_preview_mip_march(
+            C.byref(pyr), C.byref(params), float(footprint), B, origins.data_ptr(), directions.data_ptr(), radii.data_ptr(), near.data_ptr(),
+            far.data_ptr(), rgb.data_ptr(), acc.data_ptr(), dist.data_ptr(), None if steps is None else steps.data_ptr(),
+            None if lod is None else lod.data_ptr(), torch.cuda.current_stream().cuda_stream), "preview_mip_march")
+    return rgb, acc, dist
+
+
+def render_rays(baked, rays, white_bkgd, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS,
+                footprint=DEFAULT_FOOTPRINT):
+    """`rays` (a `Rays` of [..., k] tensors) marched through `baked`: (rgb [..., 3], distance [...], acc [...]).  A `BakedField` is
+    marched with point samples by mipnerf_preview_march; a `BakedPyramid` by mipnerf_preview_mip_march with `rays.radii` and `footprint`.
+    The defaults of `step_scale`, `t_min` and `footprint` are choices (see the top of this module), not measurements."""
     shape = rays.origins.shape[:-1]
     flat = [t.reshape(-1, t.shape[-1]).float().contiguous() for t in (rays.origins, rays.directions, rays.near, rays.far)]
-    rgb, acc, dist = march(baked, flat[0], flat[1], flat[2].reshape(-1), flat[3].reshape(-1), white_bkgd, step_scale, t_min, max_steps)
+    if isinstance(baked, BakedPyramid):
+        radii = rays.radii.reshape(-1).float().contiguous()
+        rgb, acc, dist = march_pyramid(baked, flat[0], flat[1], radii, flat[2].reshape(-1), flat[3].reshape(-1), white_bkgd, footprint,
+                                       step_scale, t_min, max_steps)
+    else:
+        rgb, acc, dist = march(baked, flat[0], flat[1], flat[2].reshape(-1), flat[3].reshape(-1), white_bkgd, step_scale, t_min, max_steps)
     return rgb.reshape(*shape, 3), dist.reshape(shape), acc.reshape(shape)
 
 
 class PreviewFrame:
-    """One image size of a baked field: static output buffers and the device buffers of the image bytes; `render` / `images` are shaped
-    like `evaluate.FrameEvaluator`'s, so `evaluate.save_images` and the PNG kernels serve both."""
+    """One image size of a baked field or pyramid: static output buffers and the device buffers of the image bytes; `render` / `images`
+    are shaped like `evaluate.FrameEvaluator`'s, so `evaluate.save_images` and the PNG kernels serve both.  A `BakedPyramid` is marched
+    with the rays' radii and `footprint`, and the frame keeps a static `lod` buffer (each ray's weighted mean level)."""
 
-    def __init__(self, baked, height, width, white_bkgd=True, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS):
+    def __init__(self, baked, height, width, white_bkgd=True, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS,
+                 footprint=DEFAULT_FOOTPRINT):
         from . import ops
         self.baked, self.h, self.w = baked, int(height), int(width)
         self.white_bkgd, self.step_scale, self.t_min, self.max_steps = white_bkgd, float(step_scale), float(t_min), int(max_steps)
-        n, dev = self.h * self.w, baked.rows.device
+        self.mip, self.footprint = isinstance(baked, BakedPyramid), float(footprint)
+        n, dev = self.h * self.w, baked.device if self.mip else baked.rows.device
+        self.lod = torch.zeros(n, dtype=torch.float32, device=dev) if self.mip else None
         self.out = (torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev))
         self.steps = torch.zeros(n, dtype=torch.int32, device=dev)
         self.vis_ws = torch.empty(ops.visualize_workspace_floats(n), dtype=torch.float32, device=dev)
@@ -351,8 +509,13 @@ class PreviewFrame:
         n = self.h * self.w
         o, d = rays.origins.reshape(n, 3).float().contiguous(), rays.directions.reshape(n, 3).float().contiguous()
         near, far = rays.near.reshape(n).float().contiguous(), rays.far.reshape(n).float().contiguous()
-        rgb, acc, dist = march(self.baked, o, d, near, far, self.white_bkgd, self.step_scale, self.t_min, self.max_steps, out=self.out,
-                               steps=self.steps)
+        if self.mip:
+            rgb, acc, dist = march_pyramid(self.baked, o, d, rays.radii.reshape(n).float().contiguous(), near, far, self.white_bkgd,
+                                           self.footprint, self.step_scale, self.t_min, self.max_steps, out=self.out, steps=self.steps,
+                                           lod=self.lod)
+        else:
+            rgb, acc, dist = march(self.baked, o, d, near, far, self.white_bkgd, self.step_scale, self.t_min, self.max_steps, out=self.out,
+                                   steps=self.steps)
         return rgb.view(self.h, self.w, 3), dist.view(self.h, self.w), acc.view(self.h, self.w)
 
     def images(self, rgb, dist, acc):
@@ -393,6 +556,11 @@ def build_parser():
     p.add_argument("--white_bkgd", help="Train set image background color.", type=_bool, default=True)
     p.add_argument("--chunk_size", help="--compare: chunk size of the MLP render", type=int, default=DEFAULT_CHUNK)
     p.add_argument("--n_dirs", help="view directions the colour is fitted to (a choice)", type=int, default=DEFAULT_N_DIRS)
+    p.add_argument("--mip", help="anti-alias the preview with a pyramid of L lattices (1 .. 8), each with about half the points per axis of "
+                   "the one before, the level of every sample chosen by the ray's cone radius; the bare flag means 4 levels (a choice: they "
+                   "reach 8 times the finest spacing)", type=int, nargs="?", const=DEFAULT_MIP_LEVELS, default=None, metavar="L")
+    p.add_argument("--footprint", help="--mip: the cone is footprint * radius * t wide (a choice: the default sqrt(3) is one pixel's width)",
+                   type=float, default=None, metavar="F")
     return p
 
 
@@ -417,6 +585,12 @@ def refuse_arguments(args):
         raise SystemExit("--compare renders the test split of a data set both ways: give --data")
     if args.baked is not None and args.save_baked:
         raise SystemExit("--save_baked writes the lattice this run bakes; --baked renders one that exists already: give one of them")
+    if args.mip is not None and not 1 <= args.mip <= MAX_MIP_LEVELS:
+        raise SystemExit(f"--mip {args.mip}: a pyramid has 1 .. {MAX_MIP_LEVELS} levels")
+    if args.footprint is not None and args.mip is None:
+        raise SystemExit("--footprint scales the cone that chooses a pyramid level: give --mip as well")
+    if args.footprint is not None and not (args.footprint >= 0 and np.isfinite(args.footprint)):
+        raise SystemExit(f"--footprint {args.footprint}: must be finite and >= 0")
     if args.ckpt is None:
         raise SystemExit("give --ckpt: the checkpoint names the experiment (and is what --compare renders with the MLP)")
     return dims
@@ -429,6 +603,19 @@ def refuse_baked_degree(args):
     stored = BakedField.stored_degree(args.baked)
     if args.sh_degree is not None and args.sh_degree != stored:
         raise SystemExit(f"--baked {args.baked} holds a lattice of degree {stored}, --sh_degree asks for {args.sh_degree}: drop one of them")
+
+
+def refuse_baked_levels(args):
+    """--baked of a pyramid without --mip, or of another level count than --mip L: refused after reading the file's level count alone."""
+    if args.baked is None:
+        return
+    stored = BakedPyramid.stored_levels(args.baked)
+    if args.mip is None and stored is not None:
+        raise SystemExit(f"--baked {args.baked} holds a pyramid of {stored} levels: give --mip {stored} to render it")
+    if args.mip is not None and stored != args.mip:
+        raise SystemExit("--baked {0} holds {1}, --mip asks for {2} levels: give --mip {3}".format(
+            args.baked, "a single lattice" if stored is None else f"a pyramid of {stored} levels", args.mip,
+            "nothing; drop --mip" if stored is None else stored))
 
 
 def refuse_checkpoint(system):
@@ -456,6 +643,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     dims = refuse_arguments(args)
     refuse_baked_degree(args)
+    refuse_baked_levels(args)
+    footprint = DEFAULT_FOOTPRINT if args.footprint is None else args.footprint
     system = load_system(args)
     refuse_checkpoint(system)
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -477,7 +666,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if args.baked is not None:
-            baked = BakedField.load(args.baked, dev)
+            baked = BakedField.load(args.baked, dev) if args.mip is None else BakedPyramid.load(args.baked, dev)
         else:
             bound = args.bound
             if bound is None:
@@ -485,46 +674,71 @@ def main(argv=None):
                     raise SystemExit("--grid: the default box needs at least 4 points per axis; give --bound")
                 frames = [path[i] for i in range(len(path))] + ([dataset[i][0] for i in range(len(dataset))] if dataset is not None else [])
                 bound = cull_box(frames, min(dims))
-            baked = bake_field(system, grid=dims, degree=1 if args.sh_degree is None else args.sh_degree, lo=-float(bound), hi=float(bound),
-                               threshold=args.threshold, dilate=args.dilate, n_dirs=args.n_dirs, precision=args.precision)
+            how = dict(grid=dims, degree=1 if args.sh_degree is None else args.sh_degree, lo=-float(bound), hi=float(bound),
+                       threshold=args.threshold, dilate=args.dilate, n_dirs=args.n_dirs, precision=args.precision)
+            baked = bake_field(system, **how) if args.mip is None else bake_pyramid(system, levels=args.mip, **how)
         torch.cuda.synchronize()
         bake_ms = 1e3 * (time.perf_counter() - t0)
         if args.save_baked:
             print("preview: lattice saved to {}".format(baked.save(os.path.join(folder, "baked.npz"))))
         frames, times = {}, []
+        lod_sum, lod_rays = 0.0, 0
         for idx in range(len(path)):
             h, w = path.sizes[idx]
             fr = frames.get((h, w))
             if fr is None:
-                fr = frames[(h, w)] = PreviewFrame(baked, h, w, args.white_bkgd, args.step, args.t_min)
+                fr = frames[(h, w)] = PreviewFrame(baked, h, w, args.white_bkgd, args.step, args.t_min, footprint=footprint)
             rays = path[idx]
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             out = fr.render(rays)
             torch.cuda.synchronize()
             times.append(1e3 * (time.perf_counter() - t0))
+            if fr.mip:
+                hit = out[2].reshape(-1) > 0
+                lod_sum, lod_rays = lod_sum + float(fr.lod[hit].sum()), lod_rays + int(hit.sum())
             save_images(*fr.images(*out), os.path.join(folder, str(int(args.base_size[0] / w))), idx % nums)
         generate_video(folder)
-        print("preview: lattice {0} x {1} x {2}, degree {3}, baked share {4:.4f}, {5:.1f} MiB, {6} {7:.1f} ms, mean {8:.3f} ms per frame "
-              "({9} frames)".format(*baked.dims, baked.degree, baked.baked_share(), baked.nbytes / 2 ** 20,
-                                    "loaded in" if args.baked is not None else "baked in", bake_ms, float(np.mean(times)), len(times)))
+        if args.mip is None:
+            print("preview: lattice {0} x {1} x {2}, degree {3}, baked share {4:.4f}, {5:.1f} MiB, {6} {7:.1f} ms, mean {8:.3f} ms per frame "
+                  "({9} frames)".format(*baked.dims, baked.degree, baked.baked_share(), baked.nbytes / 2 ** 20,
+                                        "loaded in" if args.baked is not None else "baked in", bake_ms, float(np.mean(times)), len(times)))
+        else:
+            print("preview: pyramid of {0} levels {1}, degree {2}, baked share {3:.4f}, {4:.1f} MiB, {5} {6:.1f} ms, mean {7:.3f} ms per frame "
+                  "({8} frames), footprint {9:.4f}, mean lod {10:.3f} over {11} hit rays".format(
+                      len(baked), ", ".join("{0} x {1} x {2}".format(*b.dims) for b in baked.levels), baked.degree,
+                      baked.levels[0].baked_share(), baked.nbytes / 2 ** 20, "loaded in" if args.baked is not None else "baked in", bake_ms,
+                      float(np.mean(times)), len(times), footprint, lod_sum / max(lod_rays, 1), lod_rays))
         if dataset is not None:
             white = bool(hp["val.white_bkgd"])
-            mlp_frames, p_baked, p_mlp, p_both = {}, [], [], []
+            single = baked if args.mip is None else baked.levels[0]
+            mlp_frames, p_baked, p_mlp, p_both, p_mip, p_mip_both = {}, [], [], [], [], []
             for idx in range(len(dataset)):
                 rays, gt = dataset[idx]
                 h, w = int(gt.shape[0]), int(gt.shape[1])
                 if (h, w) not in mlp_frames:
                     mlp_frames[(h, w)] = (FrameEvaluator(system.mip_nerf, h, w, args.chunk_size, white, dev),
-                                          PreviewFrame(baked, h, w, white, args.step, args.t_min))
-                ev, fr = mlp_frames[(h, w)]
+                                          PreviewFrame(single, h, w, white, args.step, args.t_min),
+                                          None if args.mip is None else PreviewFrame(baked, h, w, white, args.step, args.t_min,
+                                                                                     footprint=footprint))
+                ev, fr, fr_mip = mlp_frames[(h, w)]
                 want = ev.render(rays)[0]
                 got = fr.render(rays)[0]
+                if fr_mip is not None:
+                    mip = fr_mip.render(rays)[0]
+                    p_mip.append(_psnr(mip, gt[..., :3]))
+                    p_mip_both.append(_psnr(mip, want))
                 p_baked.append(_psnr(got, gt[..., :3]))
                 p_mlp.append(_psnr(want, gt[..., :3]))
                 p_both.append(_psnr(got, want))
-            print("preview: mean PSNR over {0} test images: baked vs photos {1:.3f}, MLP vs photos {2:.3f}, baked vs MLP {3:.3f}".format(
-                len(dataset), float(np.mean(p_baked)), float(np.mean(p_mlp)), float(np.mean(p_both))))
+            if args.mip is None:
+                print("preview: mean PSNR over {0} test images: baked vs photos {1:.3f}, MLP vs photos {2:.3f}, baked vs MLP {3:.3f}".format(
+                    len(dataset), float(np.mean(p_baked)), float(np.mean(p_mlp)), float(np.mean(p_both))))
+            else:
+                print("preview: mean PSNR over {0} test images: single lattice vs photos {1:.3f}, pyramid vs photos {2:.3f}, MLP vs photos "
+                      "{3:.3f}, single lattice vs MLP {4:.3f}, pyramid vs MLP {5:.3f}".format(
+                          len(dataset), float(np.mean(p_baked)), float(np.mean(p_mip)), float(np.mean(p_mlp)), float(np.mean(p_both)),
+                          float(np.mean(p_mip_both))))
     return folder
 
 
