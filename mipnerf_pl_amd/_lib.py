@@ -198,112 +198,17 @@ PREVIEW_MIP_SIGNATURES = {
                                             _P, _P]),
 }
 
-_lib = None
-_diag = None
-_preview = None
-_preview_mip = None
+_handles = {}
 
 
-def preview_lib():
-    """Load (once) libmipnerf_preview.so.  No fallback: a missing library is an error."""
-    global _preview
-    if _preview is None:
-        if not os.path.exists(PREVIEW_LIB_PATH):
-            raise RuntimeError(f"{PREVIEW_LIB_PATH} is missing: the baked-lattice renderer has no fallback. "
-                               "Build it with `python -m mipnerf_pl_amd.build` (needs hipcc / ROCm).")
-        try:
-            import torch  # noqa: F401  (same HIP runtime instance, see lib())
-        except ImportError:
-            pass
-        h = C.CDLL(PREVIEW_LIB_PATH)
-        for name, (res, args) in PREVIEW_SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        if h.mipnerf_preview_abi_version() != PREVIEW_ABI:
-            raise RuntimeError(f"{PREVIEW_LIB_PATH}: ABI {h.mipnerf_preview_abi_version()}, this binding speaks {PREVIEW_ABI}: rebuild")
-        _preview = h
-    return _preview
-
-
-def preview_check(rc: int, what: str = "") -> None:
-    if rc == OK:
-        return
-    msg = (preview_lib().mipnerf_preview_last_error() or b"").decode(errors="replace")
-    msg = f"{what}: {msg}" if what else msg
-    if rc == E_UNSUPPORTED:
-        raise NotImplementedError(msg)
-    if rc == E_INVALID:
-        raise ValueError(msg)
-    raise RuntimeError(f"{msg} (code {rc})")
-
-
-def preview_mip_lib():
-    """Load (once) libmipnerf_preview_mip.so.  No fallback: a missing library is an error."""
-    global _preview_mip
-    if _preview_mip is None:
-        if not os.path.exists(PREVIEW_MIP_LIB_PATH):
-            raise RuntimeError(f"{PREVIEW_MIP_LIB_PATH} is missing: the pyramid renderer has no fallback. "
-                               "Build it with `python -m mipnerf_pl_amd.build` (needs hipcc / ROCm).")
-        try:
-            import torch  # noqa: F401  (same HIP runtime instance, see lib())
-        except ImportError:
-            pass
-        h = C.CDLL(PREVIEW_MIP_LIB_PATH)
-        for name, (res, args) in PREVIEW_MIP_SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        if h.mipnerf_preview_mip_abi_version() != PREVIEW_MIP_ABI:
-            raise RuntimeError(f"{PREVIEW_MIP_LIB_PATH}: ABI {h.mipnerf_preview_mip_abi_version()}, this binding speaks {PREVIEW_MIP_ABI}: "
-                               "rebuild")
-        _preview_mip = h
-    return _preview_mip
-
-
-def preview_mip_check(rc: int, what: str = "") -> None:
-    if rc == OK:
-        return
-    msg = (preview_mip_lib().mipnerf_preview_mip_last_error() or b"").decode(errors="replace")
-    msg = f"{what}: {msg}" if what else msg
-    if rc == E_UNSUPPORTED:
-        raise NotImplementedError(msg)
-    if rc == E_INVALID:
-        raise ValueError(msg)
-    raise RuntimeError(f"{msg} (code {rc})")
-
-
-def diag_lib():
-    """libmipnerf_diag.so or None when it was not built (callers report the diagnostics as absent)."""
-    global _diag
-    if _diag is None and os.path.exists(DIAG_LIB_PATH):
-        try:
-            import torch  # noqa: F401  (same HIP runtime instance, see lib())
-        except ImportError:
-            pass
-        h = C.CDLL(DIAG_LIB_PATH)
-        for name, (res, args) in DIAG_SIGNATURES.items():
-            fn = getattr(h, name)
-            fn.restype = res
-            fn.argtypes = args
-        _diag = h
-    return _diag
-
-
-def diag_check(rc: int, what: str = "") -> None:
-    if rc != OK:
-        msg = (diag_lib().mipnerf_diag_last_error() or b"").decode(errors="replace")
-        raise (ValueError if rc == E_INVALID else RuntimeError)(f"{what}: {msg} (code {rc})")
-
-
-def lib():
-    """Load (once) and return the ctypes handle with argtypes set."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: the MI355X-native Mip-NeRF path has no CPU fallback. "
-                "Build it with `python -m mipnerf_pl_amd.build` (needs hipcc / ROCm).")
+def _load(path, signatures, missing=None, abi=None):
+    """Load (once) the library at `path` and set the argtypes of `signatures`.  `missing`: what the RuntimeError says after the path when
+    the file is absent (None: return None instead).  `abi`: (name of the version getter, the version this binding speaks)."""
+    if path not in _handles:
+        if not os.path.exists(path):
+            if missing is None:
+                return None
+            raise RuntimeError(f"{path} is missing: {missing} Build it with `python -m mipnerf_pl_amd.build` (needs hipcc / ROCm).")
         try:
             # PyTorch-ROCm bundles its own HIP runtime (soname-less libamdhip64.so): map it FIRST so the
             # library's DT_NEEDED "libamdhip64.so" binds to the same runtime instance torch uses
@@ -311,13 +216,63 @@ def lib():
             import torch  # noqa: F401
         except ImportError:
             pass
-        h = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        h = C.CDLL(path)
+        for name, (res, args) in signatures.items():
             fn = getattr(h, name)       # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
-        _lib = h
-    return _lib
+        if abi is not None and getattr(h, abi[0])() != abi[1]:
+            raise RuntimeError(f"{path}: ABI {getattr(h, abi[0])()}, this binding speaks {abi[1]}: rebuild")
+        _handles[path] = h
+    return _handles[path]
+
+
+def _check(rc, last_error_fn, what):
+    """Turn a C error code into the exception the reference would raise."""
+    if rc == OK:
+        return
+    msg = (last_error_fn() or b"").decode(errors="replace")
+    msg = f"{what}: {msg}" if what else msg
+    if rc == E_UNSUPPORTED:
+        raise NotImplementedError(msg)
+    if rc == E_INVALID:
+        raise ValueError(msg)
+    raise RuntimeError(f"{msg} (code {rc})")
+
+
+def lib():
+    """Load (once) and return the ctypes handle with argtypes set."""
+    return _load(LIB_PATH, SIGNATURES, "the MI355X-native Mip-NeRF path has no CPU fallback.")
+
+
+def diag_lib():
+    """libmipnerf_diag.so or None when it was not built (callers report the diagnostics as absent)."""
+    return _load(DIAG_LIB_PATH, DIAG_SIGNATURES)
+
+
+def preview_lib():
+    """Load (once) libmipnerf_preview.so.  No fallback: a missing library is an error."""
+    return _load(PREVIEW_LIB_PATH, PREVIEW_SIGNATURES, "the baked-lattice renderer has no fallback.", ("mipnerf_preview_abi_version", PREVIEW_ABI))
+
+
+def preview_mip_lib():
+    """Load (once) libmipnerf_preview_mip.so.  No fallback: a missing library is an error."""
+    return _load(PREVIEW_MIP_LIB_PATH, PREVIEW_MIP_SIGNATURES, "the pyramid renderer has no fallback.",
+                 ("mipnerf_preview_mip_abi_version", PREVIEW_MIP_ABI))
+
+
+def preview_check(rc: int, what: str = "") -> None:
+    _check(rc, lambda: preview_lib().mipnerf_preview_last_error(), what)
+
+
+def preview_mip_check(rc: int, what: str = "") -> None:
+    _check(rc, lambda: preview_mip_lib().mipnerf_preview_mip_last_error(), what)
+
+
+def diag_check(rc: int, what: str = "") -> None:
+    if rc != OK:
+        msg = (diag_lib().mipnerf_diag_last_error() or b"").decode(errors="replace")
+        raise (ValueError if rc == E_INVALID else RuntimeError)(f"{what}: {msg} (code {rc})")
 
 
 def num_camera_modes() -> int:
@@ -331,11 +286,4 @@ def last_error() -> str:
 
 def check(rc: int, what: str = "") -> None:
     """Turn a C error code into the exception the reference would raise."""
-    if rc == OK:
-        return
-    msg = f"{what}: {last_error()}" if what else last_error()
-    if rc == E_UNSUPPORTED:
-        raise NotImplementedError(msg)
-    if rc == E_INVALID:
-        raise ValueError(msg)
-    raise RuntimeError(f"{msg} (code {rc})")
+    _check(rc, lambda: lib().mipnerf_last_error(), what)

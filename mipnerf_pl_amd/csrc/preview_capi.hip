@@ -9,7 +9,7 @@
 #include "preview_field_host.hpp"
 
 namespace mip {
-hipError_t launch_preview_march(const PreviewField& f, const PreviewMarch& p, int degree, int64_t n_rays, const float* origins,
+hipError_t launch_preview_march(const PreviewField& f, float hmin, const PreviewMarch& p, int degree, int64_t n_rays, const float* origins,
                                 const float* directions, const float* near, const float* far, float* rgb, float* acc, float* distance,
                                 int32_t* steps, hipStream_t stream);
 hipError_t launch_preview_pack(int64_t n, int degree, const float* sigma, const float* coef, const uint8_t* mask, uint16_t* rows,
@@ -61,10 +61,7 @@ int mipnerf_preview_march(const mipnerf_preview_field_t* field, const mipnerf_pr
     if (!field || !params) return fail(PV_E_INVALID, "preview_march: field and params must not be null");
     const char* why = "";
     if (const int code = mip::preview_field_check(field, &why)) return fail(code, std::string("preview_march: ") + why);
-    if (!(params->step_scale > 0.0f) || !isfinite(params->step_scale)) return fail(PV_E_INVALID, "preview_march: step_scale must be positive and finite");
-    if (params->max_steps < 1) return fail(PV_E_INVALID, "preview_march: max_steps must be at least 1");
-    if (!(params->t_min >= 0.0f && params->t_min < 1.0f)) return fail(PV_E_INVALID, "preview_march: t_min must lie in [0, 1)");
-    if (n_rays < 0 || n_rays > 0x7fffffffll) return fail(PV_E_INVALID, "preview_march: n_rays must lie in [0, 2^31)");
+    if (const int code = mip::preview_call_check(params, n_rays, &why)) return fail(code, std::string("preview_march: ") + why);
     if (n_rays == 0) return PV_OK;
     if (!origins || !directions || !near || !far || !rgb || !acc || !distance)
         return fail(PV_E_INVALID, "preview_march: origins, directions, near, far, rgb, acc and distance must not be null");
@@ -72,12 +69,9 @@ int mipnerf_preview_march(const mipnerf_preview_field_t* field, const mipnerf_pr
     mip::PreviewField f;
     const float hmin = mip::preview_field_derive(field, &f);
     mip::PreviewMarch p;
-    p.s = params->step_scale * hmin;
-    p.t_min = params->t_min;
-    p.max_steps = params->max_steps;
-    for (int a = 0; a < 3; ++a) p.background[a] = params->background[a];
-    if (!(p.s > 0.0f) || !isfinite(p.s)) return fail(PV_E_INVALID, "preview_march: the world step step_scale * min(h) must be positive and finite");
-    return hip_result(mip::launch_preview_march(f, p, field->degree, n_rays, origins, directions, near, far, rgb, acc, distance, steps, S(stream)),
+    if (!mip::preview_march_derive(params, hmin, &p))
+        return fail(PV_E_INVALID, "preview_march: the world step step_scale * min(h) must be positive and finite");
+    return hip_result(mip::launch_preview_march(f, hmin, p, field->degree, n_rays, origins, directions, near, far, rgb, acc, distance, steps, S(stream)),
                       "preview_march");
 }
 

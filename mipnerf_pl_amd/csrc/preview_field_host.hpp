@@ -1,5 +1,6 @@
-// Host side of a mipnerf_preview_field_t, stated ONCE for preview_capi.hip and preview_mip_capi.hip: the checks both entry points make on
-// a lattice before any HIP call, and the by-value kernel argument (PreviewField, preview_march.hpp) derived from it.  Compile with
+// Host side of a march, stated ONCE for preview_capi.hip and preview_mip_capi.hip: the checks both entry points make on a lattice
+// (mipnerf_preview_field_t) and on the parameters of a call before any HIP call, and the by-value kernel arguments (PreviewField and
+// PreviewMarch, preview_march.hpp) derived from them.  Each entry point prepends its own name to a message.  Compile with
 // -ffp-contract=off: the spacing (hi - lo) / float(n - 1) and inv_h = float(n - 1) / (hi - lo) round once, as the header states them.
 #pragma once
 
@@ -53,6 +54,25 @@ inline float preview_field_derive(const mipnerf_preview_field_t* field, PreviewF
     f->occ = field->occupancy;
     f->words_x = (field->dims[0] - 1 + 31) / 32;
     return hmin;
+}
+
+// everything about a call that does not depend on the field: PV_OK, or the code with *why set (no entry-point prefix)
+inline int preview_call_check(const mipnerf_preview_params_t* params, int64_t n_rays, const char** why) {
+    *why = nullptr;
+    if (!(params->step_scale > 0.0f) || !isfinite(params->step_scale)) *why = "step_scale must be positive and finite";
+    else if (params->max_steps < 1) *why = "max_steps must be at least 1";
+    else if (!(params->t_min >= 0.0f && params->t_min < 1.0f)) *why = "t_min must lie in [0, 1)";
+    else if (n_rays < 0 || n_rays > 0x7fffffffll) *why = "n_rays must lie in [0, 2^31)";
+    return *why ? PV_E_INVALID : PV_OK;
+}
+
+// the kernel argument of checked parameters, with the world step step_scale * s0; false: that step is not positive and finite
+inline bool preview_march_derive(const mipnerf_preview_params_t* params, float s0, PreviewMarch* p) {
+    p->s = params->step_scale * s0;
+    p->t_min = params->t_min;
+    p->max_steps = params->max_steps;
+    for (int a = 0; a < 3; ++a) p->background[a] = params->background[a];
+    return p->s > 0.0f && isfinite(p->s);
 }
 
 }  // namespace mip

@@ -1,5 +1,5 @@
 // The per-sample rules of mipnerf_preview_march (include/mipnerf_preview.h), stated ONCE.  MIP_HD like raymath.hpp: the same source is
-// inlined into k_preview_march (kernels_preview.hip) and compiled with g++ by tests/hostmath/preview.cpp; both with -ffp-contract=off, so
+// inlined into k_preview_wave_march (preview_wave_march.hpp) and compiled with g++ by tests/hostmath/preview.cpp; both with -ffp-contract=off, so
 // every product and sum below rounds once, as written.  The cell index and the trilinear fractions are lattice_sample.hpp's
 // (lattice_cell); nothing here restates them.  How the samples of a ray are spread over lanes is the kernel's business, not this file's.
 // preview_mip.hpp (mipnerf_preview_mip_march) builds on this file: it calls preview_row and preview_shade, the two halves of

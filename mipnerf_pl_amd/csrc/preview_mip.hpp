@@ -1,6 +1,6 @@
 // What mipnerf_preview_mip_march (include/mipnerf_preview_mip.h) adds to the per-sample rules of preview_march.hpp, stated ONCE: the
 // extra miss test of P2, the footprint of P3, the level rule of P4 and the mix of two blended rows of P5.  MIP_HD like preview_march.hpp:
-// the same source is inlined into k_preview_mip_march (kernels_preview_mip.hip) and compiled with g++ by tests/hostmath/preview_mip.cpp;
+// the same source is inlined into k_preview_wave_march (preview_wave_march.hpp) and compiled with g++ by tests/hostmath/preview_mip.cpp;
 // both with -ffp-contract=off.  The ray, the samples, the cell, the occupancy bit, the row blend and the shading are preview_march.hpp's
 // and lattice_sample.hpp's; nothing here restates them.  How a ray's samples and levels are spread over lanes is the kernel's business.
 #pragma once

@@ -60,10 +60,8 @@ int mipnerf_preview_mip_march(const mipnerf_preview_pyramid_t* pyramid, const mi
     }
     for (int l = L; l < kMipMaxLevels; ++l) pyr.spacing[l] = pyr.spacing[L - 1];      // never read
     if (!(footprint >= 0.0f) || !isfinite(footprint)) return fail(PV_E_INVALID, std::string(kWho) + "footprint must be finite and >= 0");
-    if (!(params->step_scale > 0.0f) || !isfinite(params->step_scale)) return fail(PV_E_INVALID, std::string(kWho) + "step_scale must be positive and finite");
-    if (params->max_steps < 1) return fail(PV_E_INVALID, std::string(kWho) + "max_steps must be at least 1");
-    if (!(params->t_min >= 0.0f && params->t_min < 1.0f)) return fail(PV_E_INVALID, std::string(kWho) + "t_min must lie in [0, 1)");
-    if (n_rays < 0 || n_rays > 0x7fffffffll) return fail(PV_E_INVALID, std::string(kWho) + "n_rays must lie in [0, 2^31)");
+    const char* why = "";
+    if (const int code = preview_call_check(params, n_rays, &why)) return fail(code, std::string(kWho) + why);
     if (n_rays == 0) return PV_OK;
     if (!origins || !directions || !radii || !near || !far || !rgb || !acc || !distance)
         return fail(PV_E_INVALID, std::string(kWho) + "origins, directions, radii, near, far, rgb, acc and distance must not be null");
@@ -71,11 +69,8 @@ int mipnerf_preview_mip_march(const mipnerf_preview_pyramid_t* pyramid, const mi
         if (!preview_rows_aligned(&pyramid->level[l]))
             return fail(PV_E_INVALID, std::string(kWho) + "level " + std::to_string(l) + ": field.rows must be 16-byte aligned (8 for degree 0)");
     PreviewMarch p;
-    p.s = params->step_scale * pyr.spacing[0];
-    p.t_min = params->t_min;
-    p.max_steps = params->max_steps;
-    for (int a = 0; a < 3; ++a) p.background[a] = params->background[a];
-    if (!(p.s > 0.0f) || !isfinite(p.s)) return fail(PV_E_INVALID, std::string(kWho) + "the world step step_scale * s_0 must be positive and finite");
+    if (!preview_march_derive(params, pyr.spacing[0], &p))
+        return fail(PV_E_INVALID, std::string(kWho) + "the world step step_scale * s_0 must be positive and finite");
     const hipError_t e = launch_preview_mip_march(pyr, p, footprint, pyramid->level[0].degree, n_rays, origins, directions, radii, near, far, rgb,
                                                   acc, distance, steps, lod, reinterpret_cast<hipStream_t>(stream));
     if (e == hipSuccess) return PV_OK;

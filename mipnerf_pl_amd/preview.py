@@ -409,24 +409,34 @@ def _background(white_bkgd):
     return tuple(float(v) for v in white_bkgd)
 
 
+def _march_args(who, fields, tensors, background, step_scale, t_min, max_steps, out, steps, use_occupancy):
+    """What `march` and `march_pyramid` (`who`, as the messages name it) do with their arguments: the checks of the flat ray `tensors`
+    {name: tensor} and of `steps`, the outputs, one `PreviewField` struct per `BakedField` of `fields`, the `PreviewParams`."""
+    B = tensors["origins"].shape[0]
+    dev = fields[0].rows.device
+    for name, t in tensors.items():
+        shape = (B, 3) if name in ("origins", "directions") else (B,)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != int(np.prod(shape)):
+            raise ValueError(f"{who}: {name} must be a contiguous fp32 tensor of {shape} on {dev}")
+    if out is None:
+        out = (torch.empty(B, 3, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev))
+    if steps is not None and (steps.dtype != torch.int32 or steps.numel() != B or not steps.is_contiguous()):
+        raise ValueError(f"{who}: steps must be a contiguous int32 tensor with one entry per ray")
+    structs = []
+    for b in fields:
+        occ = b.occupancy if use_occupancy else None
+        structs.append(L.PreviewField((C.c_int32 * 3)(*b.dims), (C.c_float * 3)(*b.lo), (C.c_float * 3)(*b.hi), b.degree, b.rows.data_ptr(),
+                                      None if occ is None else occ.bits.data_ptr()))
+    params = L.PreviewParams(float(step_scale), float(t_min), int(max_steps), (C.c_float * 3)(*_background(background)))
+    return B, dev, out, structs, params
+
+
 def march(baked, origins, directions, near, far, background, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS,
           out=None, steps=None, use_occupancy=True):
     """mipnerf_preview_march on flat fp32 device tensors: origins / directions [B, 3], near / far [B] -> (rgb [B, 3], acc [B], distance
     [B]) (`out`: these three, preallocated).  `steps`: an int32 [B] tensor that receives the samples evaluated per ray."""
-    B = origins.shape[0]
-    dev = baked.rows.device
-    for name, t, shape in (("origins", origins, (B, 3)), ("directions", directions, (B, 3)), ("near", near, (B,)), ("far", far, (B,))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != int(np.prod(shape)):
-            raise ValueError(f"march: {name} must be a contiguous fp32 tensor of {shape} on {dev}")
-    if out is None:
-        out = (torch.empty(B, 3, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev))
-    rgb, acc, dist = out
-    if steps is not None and (steps.dtype != torch.int32 or steps.numel() != B or not steps.is_contiguous()):
-        raise ValueError("march: steps must be a contiguous int32 tensor with one entry per ray")
-    occ = baked.occupancy if use_occupancy else None
-    field = L.PreviewField((C.c_int32 * 3)(*baked.dims), (C.c_float * 3)(*baked.lo), (C.c_float * 3)(*baked.hi), baked.degree,
-                           baked.rows.data_ptr(), None if occ is None else occ.bits.data_ptr())
-    params = L.PreviewParams(float(step_scale), float(t_min), int(max_steps), (C.c_float * 3)(*_background(background)))
+    B, dev, (rgb, acc, dist), (field,), params = _march_args("march", [baked], dict(origins=origins, directions=directions, near=near, far=far),
+                                                             background, step_scale, t_min, max_steps, out, steps, use_occupancy)
     with torch.cuda.device(dev):
         L.preview_check(L.preview_lib().mipnerf_preview_march(C.byref(field), C.byref(params), B, origins.data_ptr(), directions.data_ptr(),
                                                               near.data_ptr(), far.data_ptr(), rgb.data_ptr(), acc.data_ptr(), dist.data_ptr(),
@@ -440,26 +450,15 @@ def march_pyramid(pyramid, origins, directions, radii, near, far, background, fo
     """mipnerf_preview_mip_march on flat fp32 device tensors: origins / directions [B, 3], radii / near / far [B] -> (rgb [B, 3], acc [B],
     distance [B]) (`out`: these three, preallocated).  `steps`: an int32 [B] tensor that receives the samples evaluated per ray; `lod`: an
     fp32 [B] tensor that receives each ray's weighted mean level.  The step is `step_scale` times the spacing of level 0."""
-    B = origins.shape[0]
-    dev = pyramid.device
-    for name, t, shape in (("origins", origins, (B, 3)), ("directions", directions, (B, 3)), ("radii", radii, (B,)), ("near", near, (B,)),
-                           ("far", far, (B,))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != int(np.prod(shape)):
-            raise ValueError(f"march_pyramid: {name} must be a contiguous fp32 tensor of {shape} on {dev}")
-    if out is None:
-        out = (torch.empty(B, 3, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev))
-    rgb, acc, dist = out
-    if steps is not None and (steps.dtype != torch.int32 or steps.numel() != B or not steps.is_contiguous()):
-        raise ValueError("march_pyramid: steps must be a contiguous int32 tensor with one entry per ray")
+    B, dev, (rgb, acc, dist), structs, params = _march_args(
+        "march_pyramid", pyramid.levels, dict(origins=origins, directions=directions, radii=radii, near=near, far=far), background, step_scale,
+        t_min, max_steps, out, steps, use_occupancy)
     if lod is not None and (lod.dtype != torch.float32 or lod.numel() != B or not lod.is_contiguous() or lod.device != dev):
         raise ValueError("march_pyramid: lod must be a contiguous fp32 tensor with one entry per ray")
     pyr = L.PreviewPyramid()
-    pyr.levels = len(pyramid)
-    for i, b in enumerate(pyramid.levels):
-        occ = b.occupancy if use_occupancy else None
-        pyr.level[i] = L.PreviewField((C.c_int32 * 3)(*b.dims), (C.c_float * 3)(*b.lo), (C.c_float * 3)(*b.hi), b.degree, b.rows.data_ptr(),
-                                      None if occ is None else occ.bits.data_ptr())
-    params = L.PreviewParams(float(step_scale), float(t_min), int(max_steps), (C.c_float * 3)(*_background(background)))
+    pyr.levels = len(structs)
+    for i, field in enumerate(structs):
+        pyr.level[i] = field
     with torch.cuda.device(dev):
         L.preview_mip_check(L.preview_mip_lib().mipnerf_preview_mip_march(
             C.byref(pyr), C.byref(params), float(footprint), B, origins.data_ptr(), directions.data_ptr(), radii.data_ptr(), near.data_ptr(),
@@ -468,19 +467,23 @@ def march_pyramid(pyramid, origins, directions, radii, near, far, background, fo
     return rgb, acc, dist
 
 
+def _march_rays(baked, rays, n, white_bkgd, footprint, step_scale, t_min, max_steps, **kw):
+    """The `n` rays of `rays` (a `Rays` of [..., k] tensors) through `baked` by the entry point of its kind: `march` for a `BakedField`,
+    `march_pyramid` with `rays.radii` and `footprint` for a `BakedPyramid` (`kw`: out, steps and, for a pyramid, lod)."""
+    o, d, near, far = (t.reshape(n, t.shape[-1]).float().contiguous() for t in (rays.origins, rays.directions, rays.near, rays.far))
+    if isinstance(baked, BakedPyramid):
+        return march_pyramid(baked, o, d, rays.radii.reshape(n).float().contiguous(), near.reshape(n), far.reshape(n), white_bkgd, footprint,
+                             step_scale, t_min, max_steps, **kw)
+    return march(baked, o, d, near.reshape(n), far.reshape(n), white_bkgd, step_scale, t_min, max_steps, **kw)
+
+
 def render_rays(baked, rays, white_bkgd, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS,
                 footprint=DEFAULT_FOOTPRINT):
     """`rays` (a `Rays` of [..., k] tensors) marched through `baked`: (rgb [..., 3], distance [...], acc [...]).  A `BakedField` is
     marched with point samples by mipnerf_preview_march; a `BakedPyramid` by mipnerf_preview_mip_march with `rays.radii` and `footprint`.
     The defaults of `step_scale`, `t_min` and `footprint` are choices (see the top of this module), not measurements."""
     shape = rays.origins.shape[:-1]
-    flat = [t.reshape(-1, t.shape[-1]).float().contiguous() for t in (rays.origins, rays.directions, rays.near, rays.far)]
-    if isinstance(baked, BakedPyramid):
-        radii = rays.radii.reshape(-1).float().contiguous()
-        rgb, acc, dist = march_pyramid(baked, flat[0], flat[1], radii, flat[2].reshape(-1), flat[3].reshape(-1), white_bkgd, footprint,
-                                       step_scale, t_min, max_steps)
-    else:
-        rgb, acc, dist = march(baked, flat[0], flat[1], flat[2].reshape(-1), flat[3].reshape(-1), white_bkgd, step_scale, t_min, max_steps)
+    rgb, acc, dist = _march_rays(baked, rays, int(np.prod(shape)), white_bkgd, footprint, step_scale, t_min, max_steps)
     return rgb.reshape(*shape, 3), dist.reshape(shape), acc.reshape(shape)
 
 
@@ -506,16 +509,9 @@ class PreviewFrame:
 
     def render(self, rays):
         """Rays [H, W, k] -> (rgb [H, W, 3], distance [H, W], acc [H, W]): views of the frame's static outputs."""
-        n = self.h * self.w
-        o, d = rays.origins.reshape(n, 3).float().contiguous(), rays.directions.reshape(n, 3).float().contiguous()
-        near, far = rays.near.reshape(n).float().contiguous(), rays.far.reshape(n).float().contiguous()
-        if self.mip:
-            rgb, acc, dist = march_pyramid(self.baked, o, d, rays.radii.reshape(n).float().contiguous(), near, far, self.white_bkgd,
-                                           self.footprint, self.step_scale, self.t_min, self.max_steps, out=self.out, steps=self.steps,
-                                           lod=self.lod)
-        else:
-            rgb, acc, dist = march(self.baked, o, d, near, far, self.white_bkgd, self.step_scale, self.t_min, self.max_steps, out=self.out,
-                                   steps=self.steps)
+        kw = dict(lod=self.lod) if self.mip else {}
+        rgb, acc, dist = _march_rays(self.baked, rays, self.h * self.w, self.white_bkgd, self.footprint, self.step_scale, self.t_min,
+                                     self.max_steps, out=self.out, steps=self.steps, **kw)
         return rgb.view(self.h, self.w, 3), dist.view(self.h, self.w), acc.view(self.h, self.w)
 
     def images(self, rgb, dist, acc):

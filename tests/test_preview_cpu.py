@@ -156,7 +156,12 @@ def test_the_build_units_are_compiled_without_contraction_into_a_third_library()
     csrc = os.path.join(REPO, "mipnerf_pl_amd", "csrc")
     rules = open(os.path.join(csrc, "preview_march.hpp")).read()
     assert '#include "lattice_sample.hpp"' in rules and "floorf" not in rules and "inv_h[" not in rules      # the index rule is not restated
-    kernel = open(os.path.join(csrc, "kernels_preview.hip")).read()
+    unit = open(os.path.join(csrc, "kernels_preview.hip")).read()
+    assert '#include "preview_wave_march.hpp"' in unit                     # the march kernel is the shared header's: the unit and it are one text
+    kernel = unit + open(os.path.join(csrc, "preview_wave_march.hpp")).read()
+    for f in os.listdir(csrc):                                             # and the only one: neither entry point has a kernel of its own
+        if f.endswith((".hip", ".hpp", ".py")):
+            assert not re.search(r"k_preview_march|k_preview_mip_march", open(os.path.join(csrc, f)).read()), f
     assert '#include "preview_march.hpp"' in kernel and "lattice_cell(" in kernel and not re.search(r"atomic\w*\s*\(|\basm\b", kernel)
     capi = open(os.path.join(csrc, "preview_capi.hip")).read()
     assert not re.search(r"hipMalloc|hipFree|Synchronize|hipMemcpy", capi + kernel)          # never allocates, never synchronises

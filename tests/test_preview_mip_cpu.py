@@ -222,7 +222,15 @@ def test_the_build_units_are_compiled_without_contraction_into_a_fourth_library(
     rules = open(os.path.join(CSRC, "preview_mip.hpp")).read()
     assert '#include "preview_march.hpp"' in rules
     assert not re.search(r"floorf|inv_h\[|expf|half_bits_to_float", rules)                 # restates neither the index rule nor rule 4
-    kernel = open(os.path.join(CSRC, "kernels_preview_mip.hip")).read()
+    unit = open(os.path.join(CSRC, "kernels_preview_mip.hip")).read()
+    assert '#include "preview_wave_march.hpp"' in unit                     # the march kernel is the shared header's: the unit and it are one text
+    kernel = unit + open(os.path.join(CSRC, "preview_wave_march.hpp")).read()
+    for f in os.listdir(CSRC):                                             # and the only one: neither entry point has a kernel of its own
+        if f.endswith((".hip", ".hpp", ".py")):
+            assert not re.search(r"k_preview_march|k_preview_mip_march", open(os.path.join(CSRC, f)).read()), f
+    sources = [open(os.path.join(CSRC, f)).read() for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
+    assert sum(len(re.findall(r"__global__[^;{]*k_preview\w*_march\s*\(", t)) for t in sources) == 1      # one march kernel,
+    assert sum(len(re.findall(r"float \w*incl_prod_dpp\s*\(float", t)) for t in sources) == 1                # one product scan
     assert '#include "preview_mip.hpp"' in kernel and "lattice_cell(" in kernel and "preview_row<" in kernel and "preview_shade<" in kernel
     assert not re.search(r"atomic\w*\s*\(|\basm\b|__shared__", kernel)
     capi = open(os.path.join(CSRC, "preview_mip_capi.hip")).read()
