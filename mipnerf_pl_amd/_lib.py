@@ -198,6 +198,31 @@ PREVIEW_MIP_SIGNATURES = {
                                             _P, _P]),
 }
 
+# include/mipnerf_preview_sparse.h: the preview over lattices that store only the rows next to an occupied cell, in a fifth library; the
+# other two preview libraries keep their ABI versions and their entry points
+PREVIEW_SPARSE_LIB_PATH = os.environ.get("MIPNERF_PREVIEW_SPARSE_LIB", os.path.join(HERE, "csrc", "libmipnerf_preview_sparse.so"))
+PREVIEW_SPARSE_ABI = 1
+
+
+class PreviewSparseField(C.Structure):
+    _fields_ = [("field", PreviewField), ("table", _P), ("n_rows", _I64)]
+
+
+class PreviewSparsePyramid(C.Structure):
+    _fields_ = [("levels", _I32), ("level", PreviewSparseField * PREVIEW_MIP_MAX_LEVELS)]
+
+
+PREVIEW_SPARSE_SIGNATURES = {
+    "mipnerf_preview_sparse_abi_version": (C.c_int, []),
+    "mipnerf_preview_sparse_last_error": (C.c_char_p, []),
+    "mipnerf_preview_sparse_scratch_bytes": (_SZ, [C.POINTER(_I32)]),
+    "mipnerf_preview_sparse_index": (C.c_int, [C.POINTER(_I32), _P, _P, _P, _P, _P]),
+    "mipnerf_preview_sparse_gather": (C.c_int, [C.POINTER(_I32), _I32, _P, _P, _P, _P]),
+    "mipnerf_preview_sparse_pack": (C.c_int, [_I64, _I32, _P, _P, _P, _P]),
+    "mipnerf_preview_sparse_march": (C.c_int, [C.POINTER(PreviewSparsePyramid), C.POINTER(PreviewParams), _F, _I64, _P, _P, _P, _P, _P, _P, _P,
+                                               _P, _P, _P, _P]),
+}
+
 _handles = {}
 
 
@@ -259,6 +284,16 @@ def preview_mip_lib():
     """Load (once) libmipnerf_preview_mip.so.  No fallback: a missing library is an error."""
     return _load(PREVIEW_MIP_LIB_PATH, PREVIEW_MIP_SIGNATURES, "the pyramid renderer has no fallback.",
                  ("mipnerf_preview_mip_abi_version", PREVIEW_MIP_ABI))
+
+
+def preview_sparse_lib():
+    """Load (once) libmipnerf_preview_sparse.so.  No fallback: a missing library is an error."""
+    return _load(PREVIEW_SPARSE_LIB_PATH, PREVIEW_SPARSE_SIGNATURES, "the sparse-lattice renderer has no fallback.",
+                 ("mipnerf_preview_sparse_abi_version", PREVIEW_SPARSE_ABI))
+
+
+def preview_sparse_check(rc: int, what: str = "") -> None:
+    _check(rc, lambda: preview_sparse_lib().mipnerf_preview_sparse_last_error(), what)
 
 
 def preview_check(rc: int, what: str = "") -> None:

@@ -15,13 +15,8 @@ k_preview_pack(const int64_t n, const int degree, const float* __restrict__ sigm
                const uint8_t* __restrict__ mask, uint16_t* __restrict__ rows) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int W = preview_row_halves(degree), used = 3 * preview_basis(degree);
-    const bool keep = mask == nullptr || mask[i] != 0;
-    uint16_t* row = rows + i * W;
-    row[0] = preview_half_bits(sigma[i], true);
-    const float* cf = coef + i * used;
-    for (int k = 0; k < used; ++k) row[1 + k] = keep ? preview_half_bits(cf[k], false) : (uint16_t)0;
-    for (int k = 1 + used; k < W; ++k) row[k] = 0;
+    preview_pack_row(degree, sigma[i], coef + i * (3 * preview_basis(degree)), mask == nullptr || mask[i] != 0,
+                     rows + i * preview_row_halves(degree));
 }
 
 // one lattice is a pyramid of one level: footprint 0, no radii, no lod (preview_wave_march.hpp); `hmin` is the field's min(h)

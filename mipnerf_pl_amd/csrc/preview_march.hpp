@@ -128,19 +128,28 @@ struct alignas(2 * N) HalfChunk {      // N = 4: one 8-byte load; N = 8: one 16-
     uint16_t h[N];
 };
 
-// rule 4 on an occupied cell, first half: the trilinear blend of the 8 corner rows
+// how a row of degree DEG is loaded: CH chunks of N halves
 template <int DEG>
-MIP_HD void preview_row(const PreviewField& f, const int c[3], const float fr[3], float (&row)[preview_row_halves(DEG)]) {
-    constexpr int W = preview_row_halves(DEG), N = W < 8 ? W : 8, CH = W / N;
+struct PreviewRowChunks {
+    static constexpr int W = preview_row_halves(DEG), N = W < 8 ? W : 8, CH = W / N;
     typedef HalfChunk<N> Chunk;
-    const int64_t sy = (int64_t)f.box.nx * CH, sz = sy * f.box.ny;        // in chunks
-    const Chunk* q = reinterpret_cast<const Chunk*>(f.rows) + (((int64_t)c[2] * f.box.ny + c[1]) * f.box.nx + c[0]) * CH;
+};
+
+// rule 4 on an occupied cell, first half: the trilinear blend of the 8 corner rows, whatever the storage.  q00, q10, q01, q11: the row of
+// the cell's low-x corner on its four x-lines (y, z), (y + 1, z), (y, z + 1), (y + 1, z + 1); the high-x corner's row is the NEXT row of
+// the same line in both storages (dense: the next lattice point; compact: preview_sparse.hpp's invariant).
+template <int DEG>
+MIP_HD void preview_blend(const typename PreviewRowChunks<DEG>::Chunk* q00, const typename PreviewRowChunks<DEG>::Chunk* q10,
+                          const typename PreviewRowChunks<DEG>::Chunk* q01, const typename PreviewRowChunks<DEG>::Chunk* q11,
+                          const float fr[3], float (&row)[preview_row_halves(DEG)]) {
+    constexpr int N = PreviewRowChunks<DEG>::N, CH = PreviewRowChunks<DEG>::CH;
+    typedef typename PreviewRowChunks<DEG>::Chunk Chunk;
     const float gx = 1.0f - fr[0], gy = 1.0f - fr[1], gz = 1.0f - fr[2];
 #pragma unroll
     for (int k = 0; k < CH; ++k) {
         // the 8 corner loads of this chunk first, then the blend
-        const Chunk v000 = q[k], v100 = q[CH + k], v010 = q[sy + k], v110 = q[sy + CH + k];
-        const Chunk v001 = q[sz + k], v101 = q[sz + CH + k], v011 = q[sz + sy + k], v111 = q[sz + sy + CH + k];
+        const Chunk v000 = q00[k], v100 = q00[CH + k], v010 = q10[k], v110 = q10[CH + k];
+        const Chunk v001 = q01[k], v101 = q01[CH + k], v011 = q11[k], v111 = q11[CH + k];
 #pragma unroll
         for (int e = 0; e < N; ++e) {
             const float v00 = gx * half_bits_to_float(v000.h[e]) + fr[0] * half_bits_to_float(v100.h[e]);
@@ -152,6 +161,16 @@ MIP_HD void preview_row(const PreviewField& f, const int c[3], const float fr[3]
             row[k * N + e] = gz * v0 + fr[2] * v1;
         }
     }
+}
+
+// the dense storage's addresses: point (i, j, k) has the row (k * ny + j) * nx + i
+template <int DEG>
+MIP_HD void preview_row(const PreviewField& f, const int c[3], const float fr[3], float (&row)[preview_row_halves(DEG)]) {
+    constexpr int CH = PreviewRowChunks<DEG>::CH;
+    typedef typename PreviewRowChunks<DEG>::Chunk Chunk;
+    const int64_t sy = (int64_t)f.box.nx * CH, sz = sy * f.box.ny;        // in chunks
+    const Chunk* q = reinterpret_cast<const Chunk*>(f.rows) + (((int64_t)c[2] * f.box.ny + c[1]) * f.box.nx + c[0]) * CH;
+    preview_blend<DEG>(q, q + sy, q + sz, q + sz + sy, fr, row);
 }
 
 // rule 4, second half: a blended row's alpha and clamped colour
@@ -210,6 +229,15 @@ MIP_HD uint16_t preview_half_bits(float v, bool saturate) {
     const uint32_t base = e < -14 ? 0u : (uint32_t)(e + 15 - 1) << 10;            // m still carries the hidden bit when normal
     return (uint16_t)(sign | (base + m));
 #endif
+}
+
+// one packed row (the ROWS paragraph of mipnerf_preview.h) from a point's sigma and its 3 (degree + 1)^2 coefficients; `keep` false: the
+// colour coefficients are written as zeros
+MIP_HD void preview_pack_row(int degree, float sigma, const float* cf, bool keep, uint16_t* row) {
+    const int W = preview_row_halves(degree), used = 3 * preview_basis(degree);
+    row[0] = preview_half_bits(sigma, true);
+    for (int k = 0; k < used; ++k) row[1 + k] = keep ? preview_half_bits(cf[k], false) : (uint16_t)0;
+    for (int k = 1 + used; k < W; ++k) row[k] = 0;
 }
 
 }  // namespace mip

@@ -1,5 +1,6 @@
-// THE march kernel of the baked preview, stated ONCE for libmipnerf_preview.so (kernels_preview.hip: one lattice) and
-// libmipnerf_preview_mip.so (kernels_preview_mip.hip: a pyramid of lattices).  Each unit includes this header and instantiates the kernel
+// THE march kernel of the baked preview, stated ONCE for libmipnerf_preview.so (kernels_preview.hip: one lattice),
+// libmipnerf_preview_mip.so (kernels_preview_mip.hip: a pyramid of lattices) and libmipnerf_preview_sparse.so (kernels_preview_sparse.hip:
+// a pyramid whose levels store only the rows next to an occupied cell).  Each unit includes this header and instantiates the kernel
 // for itself (the libraries are linked separately, -fno-gpu-rdc).  The per-sample arithmetic is preview_march.hpp's and preview_mip.hpp's;
 // this file only spreads a ray's samples, and the levels they read, over a wavefront.  Compile with -ffp-contract=off (preview_march.hpp).
 //
@@ -46,10 +47,11 @@ __device__ __forceinline__ float wave_incl_prod_dpp(float v) {
     return v;
 }
 
-// `radii`, `steps` and `lod` may be null
-template <int DEG>
+// `radii`, `steps` and `lod` may be null.  PYR: PreviewPyramid (dense rows, preview_mip.hpp) or PreviewSparsePyramid (compact rows behind a
+// row table, preview_sparse.hpp); the two differ in the overloads of preview_occupied and preview_row their level type selects, nowhere else.
+template <typename PYR, int DEG>
 __global__ void __launch_bounds__(64 * kPreviewRaysPerBlock)
-k_preview_wave_march(const PreviewPyramid pyr, const PreviewMarch p, const float footprint, const int64_t n_rays,
+k_preview_wave_march(const PYR pyr, const PreviewMarch p, const float footprint, const int64_t n_rays,
                      const float* __restrict__ origins, const float* __restrict__ directions, const float* __restrict__ radii,
                      const float* __restrict__ near, const float* __restrict__ far, float* __restrict__ rgb, float* __restrict__ acc,
                      float* __restrict__ distance, int32_t* __restrict__ steps, float* __restrict__ lod) {
@@ -95,7 +97,7 @@ k_preview_wave_march(const PreviewPyramid pyr, const PreviewMarch p, const float
         for (int lv = 0; lv < L; ++lv) {
             const bool lower = exists && l == lv, upper = exists && two && l + 1 == lv;
             if (__ballot(lower || upper) == 0ull) continue;      // wave-uniform: nobody reads this level
-            const PreviewField& f = pyr.level[lv];               // lv is wave-uniform: scalar loads
+            const auto& f = pyr.level[lv];                       // lv is wave-uniform: scalar loads
             if (lower || upper) {
                 int c[3];
                 float fr[3];
@@ -119,7 +121,7 @@ k_preview_wave_march(const PreviewPyramid pyr, const PreviewMarch p, const float
             for (int lv = 0; lv < L; ++lv) {
                 const bool lower = occupied && l == lv, upper = occupied && two && l + 1 == lv;
                 if (__ballot(lower || upper) == 0ull) continue;
-                const PreviewField& f = pyr.level[lv];
+                const auto& f = pyr.level[lv];
                 if (lower || upper) {
                     const int c[3] = {lower ? ca[0] : cb[0], lower ? ca[1] : cb[1], lower ? ca[2] : cb[2]};
                     const float fr[3] = {lower ? fa[0] : fb[0], lower ? fa[1] : fb[1], lower ? fa[2] : fb[2]};
@@ -172,11 +174,12 @@ k_preview_wave_march(const PreviewPyramid pyr, const PreviewMarch p, const float
 }
 
 // the degree switch; static: every unit launches the instantiations of its own library
-static hipError_t launch_preview_wave_march(const PreviewPyramid& pyr, const PreviewMarch& p, float footprint, int degree, int64_t n_rays,
+template <typename PYR>
+static hipError_t launch_preview_wave_march(const PYR& pyr, const PreviewMarch& p, float footprint, int degree, int64_t n_rays,
                                             const float* origins, const float* directions, const float* radii, const float* near,
                                             const float* far, float* rgb, float* acc, float* distance, int32_t* steps, float* lod,
                                             hipStream_t stream) {
-    const auto kernel = degree == 0 ? k_preview_wave_march<0> : degree == 1 ? k_preview_wave_march<1> : k_preview_wave_march<2>;
+    const auto kernel = degree == 0 ? k_preview_wave_march<PYR, 0> : degree == 1 ? k_preview_wave_march<PYR, 1> : k_preview_wave_march<PYR, 2>;
     const dim3 grid((unsigned)((n_rays + kPreviewRaysPerBlock - 1) / kPreviewRaysPerBlock)), block(64 * kPreviewRaysPerBlock);
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, pyr, p, footprint, n_rays, origins, directions, radii, near, far, rgb, acc, distance,
                        steps, lod);

@@ -7,13 +7,16 @@ The PlenOctrees / Plenoxels idea in its simplest dense form (include/mipnerf_pre
     render_rays(baked, rays)    mipnerf_preview_march: no MLP, one wavefront per ray
     PreviewFrame                the frame-shaped wrapper (`render` / `images` like `evaluate.FrameEvaluator`)
 
+    bake_field(system, sparse=True) / BakedField.to_sparse()    a `SparseField`: only the rows next to an occupied cell, behind a row table
+                                (include/mipnerf_preview_sparse.h); marched by mipnerf_preview_sparse_march to the same bytes
+
     bake_pyramid(system)        `bake_field` at grid, then at about half the points per axis, ...: a `BakedPyramid`
     march_pyramid / render_rays of a pyramid    mipnerf_preview_mip_march (include/mipnerf_preview_mip.h): every sample reads the level (or
                                 the two levels) whose spacing brackets footprint * radius * t, the width of the ray's cone there
 
     python -m mipnerf_pl_amd.preview --ckpt CKPT --out_dir OUT [--grid 256 | --grid NX NY NZ] [--sh_degree 0|1|2] [--bound B]
         [--threshold 0.01] [--dilate 1] [--step 0.5] [--t_min 1e-3] [--precision fp32|bf16] [--n_poses 120] [--scale 1]
-        [--save_baked] [--baked FILE] [--data DIR --compare] [--mip [L]] [--footprint F]
+        [--save_baked] [--baked FILE] [--data DIR --compare] [--mip [L]] [--footprint F] [--sparse]
 
 renders the spherical path of `render_video` to OUT/preview_spheric/<exp_name>/ and prints one `preview:` line.
 
@@ -173,21 +176,289 @@ class BakedField:
     @classmethod
     def load(cls, path, device="cuda"):
         with np.load(path) as z:
+            if "sparse_rows" in z.files:
+                raise ValueError(f"{path} holds a sparse lattice, not a dense one: load it with SparseField.load")
             if "rows" not in z.files:
                 raise ValueError(f"{path} holds a pyramid of lattices, not a single one: load it with BakedPyramid.load")
             return cls._from_arrays({k: z[k] for k in z.files}, device)
 
-    @classmethod
-    def _from_arrays(cls, z, device):
+    @staticmethod
+    def _stored_occupancy(z, dims, lo, hi, device):
+        """The `ops.Occupancy` of saved arrays (None when they hold none) and the threshold."""
         from .ops import Occupancy
-        dims, lo, hi = tuple(int(v) for v in z["dims"]), z["lo"], z["hi"]
-        rows = torch.from_numpy(z["rows"]).to(device)
         thr = float(z["threshold"])
         occ = None
         if "occupancy" in z:
             occ = Occupancy(torch.from_numpy(z["occupancy"].view(np.int32)).to(device).view(torch.uint32), dims, lo, hi)
             occ.threshold, occ.dilate = (None if np.isnan(thr) else thr), (None if int(z["dilate"]) < 0 else int(z["dilate"]))
-        return cls(rows, dims, lo, hi, int(z["degree"]), occ, None if np.isnan(thr) else thr)
+        return occ, (None if np.isnan(thr) else thr)
+
+    @classmethod
+    def _from_arrays(cls, z, device):
+        dims, lo, hi = tuple(int(v) for v in z["dims"]), z["lo"], z["hi"]
+        rows = torch.from_numpy(z["rows"]).to(device)
+        occ, thr = cls._stored_occupancy(z, dims, lo, hi, device)
+        return cls(rows, dims, lo, hi, int(z["degree"]), occ, thr)
+
+    def to_sparse(self, stored=None):
+        """The same lattice as a `SparseField`: mipnerf_preview_sparse_index on the occupancy words (or on the words of `stored`, an
+        `ops.Occupancy` of the cells whose corners are kept: a level of a pyramid keeps more than its own occupied cells, see
+        `pyramid_storage`), mipnerf_preview_sparse_gather on the rows.  Marching it gives the bytes marching this one gives.  Refused
+        without an occupancy: every row would be stored."""
+        if self.occupancy is None:
+            raise ValueError("BakedField.to_sparse: a lattice without an occupancy grid marches every cell, so every row is read: it stays dense")
+        table, m = index_table(self.occupancy if stored is None else stored)
+        return SparseField(gather_rows(self.rows, table, m, self.degree), table, self.dims, self.lo, self.hi, self.degree, self.occupancy,
+                           self.threshold, stored=stored, _table_is_ours=True)
+
+
+def table_words(nx) -> int:
+    """Table words per x-line of POINTS, ceil(nx / 32): not the occupancy grid's ceil((nx - 1) / 32)."""
+    return (int(nx) + 31) // 32
+
+
+def table_of_points(points):
+    """The row table of include/mipnerf_preview_sparse.h restated in torch, on any device: int32 [nz, ny, words_p, 2] (the bits of uint32
+    words) of the stored points bool [nz, ny, nx], and the stored count.  `SparseField` checks a foreign table against it; the tables the
+    bake uses come from mipnerf_preview_sparse_index."""
+    nz, ny, nx = points.shape
+    wp = table_words(nx)
+    bits = torch.zeros(nz, ny, wp * 32, dtype=torch.int64, device=points.device)
+    bits[..., :nx] = points
+    bits = bits.view(nz, ny, wp, 32)
+    mask = (bits << torch.arange(32, dtype=torch.int64, device=points.device)).sum(-1)
+    count = bits.sum(-1)
+    rank = (torch.cumsum(count.reshape(-1), 0) - count.reshape(-1)).view(nz, ny, wp)
+    mask = torch.where(mask >= 2 ** 31, mask - 2 ** 32, mask)           # the uint32 word's bits as an int32
+    return torch.stack([mask, rank], -1).to(torch.int32).contiguous(), int(count.sum())
+
+
+def index_table(occ):
+    """mipnerf_preview_sparse_index: (table int32 [nz, ny, ceil(nx / 32), 2], M) of an `ops.Occupancy`; M is read back."""
+    nx, ny, nz = occ.dims
+    dev = occ.bits.device
+    cdims = (C.c_int32 * 3)(nx, ny, nz)
+    lib = L.preview_sparse_lib()
+    table = torch.empty(nz, ny, table_words(nx), 2, dtype=torch.int32, device=dev)
+    total = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(max(1, (int(lib.mipnerf_preview_sparse_scratch_bytes(cdims)) + 3) // 4), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.preview_sparse_check(lib.mipnerf_preview_sparse_index(cdims, occ.bits.data_ptr(), table.data_ptr(), total.data_ptr(),
+                                                                scratch.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                               "preview_sparse_index")
+    return table, int(total.item())
+
+
+def gather_rows(dense_rows, table, m, degree):
+    """mipnerf_preview_sparse_gather: the rows fp16 [m, W] of the stored points of dense rows [nz, ny, nx, W]."""
+    nz, ny, nx, W = dense_rows.shape
+    rows = torch.empty(m, W, dtype=torch.float16, device=dense_rows.device)
+    if m > 0:
+        with torch.cuda.device(dense_rows.device):
+            L.preview_sparse_check(L.preview_sparse_lib().mipnerf_preview_sparse_gather(
+                (C.c_int32 * 3)(nx, ny, nz), degree, table.data_ptr(), dense_rows.data_ptr(), rows.data_ptr(),
+                torch.cuda.current_stream().cuda_stream), "preview_sparse_gather")
+    return rows
+
+
+def sparse_pack(sigma, coef, degree, out):
+    """mipnerf_preview_sparse_pack: fp16 rows `out` [n, W] of sigma fp32 [n] and coef fp32 [n, (degree + 1)^2, 3], one stored point each."""
+    degree = _check_degree(degree, "sparse_pack")
+    n = sigma.numel()
+    if sigma.dtype != torch.float32 or coef.dtype != torch.float32 or not sigma.is_contiguous() or not coef.is_contiguous() or \
+            coef.numel() != n * (degree + 1) ** 2 * 3:
+        raise ValueError("sparse_pack: sigma fp32 [n] and coef fp32 [n, (degree + 1)^2, 3], contiguous")
+    if out.dtype != torch.float16 or tuple(out.shape) != (n, ROW_HALVES[degree]) or not out.is_contiguous():
+        raise ValueError(f"sparse_pack: out must be contiguous fp16 [n, W] = {(n, ROW_HALVES[degree])}")
+    with torch.cuda.device(sigma.device):
+        L.preview_sparse_check(L.preview_sparse_lib().mipnerf_preview_sparse_pack(n, degree, sigma.data_ptr(), coef.data_ptr(), out.data_ptr(),
+                                                                                  torch.cuda.current_stream().cuda_stream),
+                               "preview_sparse_pack")
+    return out
+
+
+def cells_to_bits(cells):
+    """The words of `ops.Occupancy` of cells bool [nz - 1, ny - 1, nx - 1]: uint32 [nz - 1, ny - 1, ceil((nx - 1) / 32)] on their device."""
+    cz, cy, cx = cells.shape
+    wx = (cx + 31) // 32
+    bits = torch.zeros(cz, cy, wx * 32, dtype=torch.int64, device=cells.device)
+    bits[..., :cx] = cells
+    words = (bits.view(cz, cy, wx, 32) << torch.arange(32, dtype=torch.int64, device=cells.device)).sum(-1)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous().view(torch.uint32)
+
+
+# Two lattices over one box find the cell of a point with fp32 arithmetic each (lattice_sample.hpp): (x - lo) * inv_h carries a relative
+# error of a few 1e-7, so a point within that distance of a cell face may land on either side of it.  Cells count as sharing a point when
+# their intervals come closer than this share of the box edge: 40 times that error, and far below the 1 / 1024 of the smallest cell.
+STORAGE_EPS = 1e-5
+
+
+def _axis_overlap(n_to, n_from, device):
+    """float [n_to - 1, n_from - 1]: 1 where cell a of n_to points and cell b of n_from points over one edge share a point (widened by
+    STORAGE_EPS), formed in float64."""
+    a = torch.arange(n_to, dtype=torch.float64) / (n_to - 1)
+    b = torch.arange(n_from, dtype=torch.float64) / (n_from - 1)
+    share = (a[:-1, None] < b[None, 1:] + STORAGE_EPS) & (b[None, :-1] < a[1:, None] + STORAGE_EPS)
+    return share.to(device=device, dtype=torch.float32)
+
+
+def pyramid_storage(occupancies):
+    """The cells each level of a sparse pyramid must keep the corners of, as one `ops.Occupancy` per level.
+
+    A sample between two levels is occupied when the bit of EITHER level's cell is set (P5 of include/mipnerf_preview_mip.h) and then
+    reads BOTH levels, so a level is also read in cells whose own bit is clear: wherever a point of such a cell lies in an occupied cell
+    of the level below or above.  Per level: its own occupied cells, plus every cell that shares a point with an occupied cell of a
+    neighbouring level (the overlap per axis, widened by STORAGE_EPS for the fp32 index rule; three small matrix products per
+    neighbour).  A single level keeps its own occupied cells: the grid itself is returned."""
+    from .ops import Occupancy
+    occupancies = list(occupancies)
+    if len(occupancies) == 1:
+        return occupancies
+    cells = [occupied_cells(o) for o in occupancies]
+    out = []
+    for i, occ in enumerate(occupancies):
+        keep = cells[i].clone()
+        for j in (i - 1, i + 1):
+            if not 0 <= j < len(occupancies):
+                continue
+            v = cells[j].to(torch.float32)
+            ax, ay, az = (_axis_overlap(occ.dims[a], occupancies[j].dims[a], v.device) for a in range(3))
+            v = torch.matmul(v, ax.t())                                             # [z', y', x]
+            v = torch.matmul(ay, v)                                                 # [z', y, x]
+            v = torch.matmul(az, v.reshape(v.shape[0], -1)).view(az.shape[0], ay.shape[0], ax.shape[0])
+            keep |= v > 0
+        stored = Occupancy(cells_to_bits(keep), occ.dims, occ.lo, occ.hi)
+        stored.threshold, stored.dilate = occ.threshold, None
+        out.append(stored)
+    return out
+
+
+def _covers(stored, needed) -> bool:
+    """Whether every set bit of `needed` is set in `stored` (two `ops.Occupancy` over one lattice)."""
+    return not bool((needed.bits.view(torch.int32) & ~stored.bits.view(torch.int32)).any())
+
+
+class SparseField:
+    """A baked lattice that stores only the rows a march reads (include/mipnerf_preview_sparse.h): `rows` fp16 [M, W], one per lattice
+    point next to an occupied cell, in flat point order; `table` int32 [nz, ny, ceil(nx / 32), 2] (the bits of uint32 words: per 32 points
+    of an x-line their stored bits and the number of stored points before them); `occupancy` (an `ops.Occupancy`, never None) and the
+    rest as in `BakedField`.  Marching it gives the bytes marching the dense lattice with the same occupancy gives.
+
+    `stored` (an `ops.Occupancy` over the same lattice, or None = `occupancy`): the cells whose corners have rows.  It holds at least the
+    occupied cells; a level of a pyramid holds more (`pyramid_storage`).  The march reads `occupancy`; `stored` only says what the table
+    was built from.  The table must be the one of `stored`'s bits: a constructor given a table recomputes it and refuses another."""
+
+    def __init__(self, rows, table, dims, lo, hi, degree, occupancy, threshold=None, stored=None, _table_is_ours=False):
+        self.degree = _check_degree(degree, "SparseField")
+        self.dims = check_lattice(dims, "SparseField")
+        self.lo, self.hi = _box3(lo), _box3(hi)
+        if not all(h > l for l, h in zip(self.lo, self.hi)):
+            raise ValueError(f"SparseField: the box needs hi > lo on every axis (got {self.lo} .. {self.hi})")
+        nx, ny, nz = self.dims
+        if occupancy is None:
+            raise ValueError("SparseField: a sparse lattice needs its occupancy grid (without one every row is read: use BakedField)")
+        if tuple(occupancy.dims) != self.dims or tuple(occupancy.bits.shape) != (nz - 1, ny - 1, (nx + 30) // 32):
+            raise ValueError("SparseField: the occupancy grid must lie on the rows' lattice")
+        if stored is occupancy:
+            stored = None
+        if stored is not None:
+            if tuple(stored.dims) != self.dims or stored.bits.shape != occupancy.bits.shape or stored.bits.device != occupancy.bits.device:
+                raise ValueError("SparseField: the stored cells must lie on the rows' lattice")
+            if not _covers(stored, occupancy):
+                raise ValueError("SparseField: an occupied cell is not among the stored cells (a march would read rows that are not there)")
+        if table.dtype != torch.int32 or tuple(table.shape) != (nz, ny, table_words(nx), 2) or not table.is_contiguous():
+            raise ValueError(f"SparseField: table must be contiguous int32 [nz, ny, ceil(nx / 32), 2] = {(nz, ny, table_words(nx), 2)}, "
+                             f"got {table.dtype} {tuple(table.shape)}")
+        if rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != ROW_HALVES[self.degree] or not rows.is_contiguous():
+            raise ValueError(f"SparseField: rows must be contiguous fp16 [M, W], W = {ROW_HALVES[self.degree]}, got {rows.dtype} "
+                             f"{tuple(rows.shape)}")
+        if not (rows.device == table.device == occupancy.bits.device):
+            raise ValueError("SparseField: rows, table and occupancy live on one device")
+        if not _table_is_ours:
+            cells = occupancy if stored is None else stored
+            want, m = index_table(cells) if rows.is_cuda else table_of_points(baked_points(cells))
+            if not torch.equal(want, table):
+                raise ValueError("SparseField: the table is not the one of the stored cells' bits (a march would read rows of other points)")
+            if rows.shape[0] != m:
+                raise ValueError(f"SparseField: the stored cells have {m} corner points, rows holds {rows.shape[0]}")
+        self.rows, self.table, self.occupancy, self.stored = rows, table, occupancy, stored
+        self.threshold = None if threshold is None else float(threshold)
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.rows.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of what a march reads: the rows, the table and the occupancy words."""
+        return self.rows.numel() * 2 + self.table.numel() * 4 + self.occupancy.bits.numel() * 4
+
+    @property
+    def dense_nbytes(self) -> int:
+        """Bytes the dense lattice takes: `BakedField.nbytes` of `to_dense()`."""
+        nx, ny, nz = self.dims
+        return nx * ny * nz * ROW_HALVES[self.degree] * 2 + self.occupancy.bits.numel() * 4
+
+    def stored_share(self) -> float:
+        """Share of the lattice points that have a row."""
+        nx, ny, nz = self.dims
+        return self.n_rows / float(nx * ny * nz)
+
+    def baked_share(self) -> float:
+        """Share of the lattice points that carry colour coefficients, as `BakedField.baked_share` (a read-back)."""
+        if self.rows.shape[-1] <= 1 or self.n_rows == 0:
+            return 0.0
+        nx, ny, nz = self.dims
+        return float((self.rows[:, 1:4] != 0).any(-1).sum()) / float(nx * ny * nz)
+
+    def stored_points(self):
+        """bool [nz, ny, nx]: the points that have a row (`baked_points` of the stored cells)."""
+        return baked_points(self.occupancy if self.stored is None else self.stored)
+
+    def to_dense(self):
+        """A `BakedField` with the stored rows at their points and ZEROS elsewhere.  That is not what `bake_field` leaves at an unstored
+        point (it keeps the point's sigma there), so the result equals the dense bake in the stored rows only -- which are the only rows
+        a march with this occupancy reads."""
+        nx, ny, nz = self.dims
+        dense = torch.zeros(nz * ny * nx, ROW_HALVES[self.degree], dtype=torch.float16, device=self.rows.device)
+        dense[self.stored_points().reshape(-1)] = self.rows
+        return BakedField(dense.view(nz, ny, nx, -1), self.dims, self.lo, self.hi, self.degree, self.occupancy, self.threshold)
+
+    def save(self, path):
+        """Everything in one .npz with keys of its own (`sparse_rows` and `table` where a dense lattice has `rows`)."""
+        with open(path, "wb") as f:
+            np.savez(f, **self._arrays())
+        return path
+
+    def _arrays(self):
+        occ = self.occupancy
+        arrays = dict(sparse_rows=self.rows.cpu().numpy(), table=self.table.cpu().numpy().view(np.uint32), dims=np.array(self.dims, np.int32),
+                      lo=np.array(self.lo, np.float32), hi=np.array(self.hi, np.float32), degree=np.int32(self.degree),
+                      threshold=np.float32(np.nan if self.threshold is None else self.threshold),
+                      occupancy=occ.bits.cpu().numpy().view(np.uint32), dilate=np.int32(-1 if occ.dilate is None else occ.dilate))
+        if self.stored is not None:
+            arrays["stored"] = self.stored.bits.cpu().numpy().view(np.uint32)
+        return arrays
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        with np.load(path) as z:
+            if "levels" in z.files:
+                raise ValueError(f"{path} holds a pyramid of lattices, not a single one: load it with BakedPyramid.load")
+            if "sparse_rows" not in z.files:
+                raise ValueError(f"{path} holds a dense lattice, not a sparse one: load it with BakedField.load")
+            return cls._from_arrays({k: z[k] for k in z.files}, device)
+
+    @classmethod
+    def _from_arrays(cls, z, device):
+        dims, lo, hi = tuple(int(v) for v in z["dims"]), z["lo"], z["hi"]
+        from .ops import Occupancy
+        occ, thr = BakedField._stored_occupancy(z, dims, lo, hi, device)
+        stored = None
+        if "stored" in z:
+            stored = Occupancy(torch.from_numpy(z["stored"].view(np.int32)).to(device).view(torch.uint32), dims, lo, hi)
+        return cls(torch.from_numpy(z["sparse_rows"]).to(device), torch.from_numpy(z["table"].view(np.int32)).to(device), dims, lo, hi,
+                   int(z["degree"]), occ, thr, stored=stored)
 
 
 def lattice_spacing(dims, lo, hi) -> float:
@@ -197,13 +468,17 @@ def lattice_spacing(dims, lo, hi) -> float:
 
 
 class BakedPyramid:
-    """`levels`: 1 .. 8 `BakedField`s over ONE box (lo and hi equal bit for bit) with one degree, the finest first; the smallest axis
-    spacing increases strictly from level to level (rule P1 of include/mipnerf_preview_mip.h)."""
+    """`levels`: 1 .. 8 `BakedField`s -- or 1 .. 8 `SparseField`s, never a mix -- over ONE box (lo and hi equal bit for bit) with one
+    degree, the finest first; the smallest axis spacing increases strictly from level to level (rule P1 of
+    include/mipnerf_preview_mip.h)."""
 
     def __init__(self, levels):
         levels = list(levels)
-        if not 1 <= len(levels) <= MAX_MIP_LEVELS or not all(isinstance(b, BakedField) for b in levels):
+        if not 1 <= len(levels) <= MAX_MIP_LEVELS or not all(isinstance(b, (BakedField, SparseField)) for b in levels):
             raise ValueError(f"BakedPyramid: 1 .. {MAX_MIP_LEVELS} BakedField levels (got {len(levels)})")
+        if len({isinstance(b, SparseField) for b in levels}) != 1:
+            raise ValueError("BakedPyramid: the levels are all dense (BakedField) or all sparse (SparseField), not a mix: one kernel "
+                             "instantiation marches them all")
         first = levels[0]
         for i, b in enumerate(levels[1:], 1):
             if np.asarray(b.lo, np.float32).tobytes() != np.asarray(first.lo, np.float32).tobytes() or \
@@ -216,6 +491,11 @@ class BakedPyramid:
         self.spacings = tuple(lattice_spacing(b.dims, b.lo, b.hi) for b in levels)
         if not all(a < b for a, b in zip(self.spacings, self.spacings[1:])):
             raise ValueError(f"BakedPyramid: the smallest spacing must increase strictly from level to level (got {self.spacings})")
+        if isinstance(first, SparseField) and len(levels) > 1:
+            for i, (b, need) in enumerate(zip(levels, pyramid_storage([b.occupancy for b in levels]))):
+                if not _covers(b.occupancy if b.stored is None else b.stored, need):
+                    raise ValueError(f"BakedPyramid: level {i} does not store the rows a sample between two levels reads (a level is read "
+                                     "wherever its neighbour's cell is occupied): make its `stored` cells with pyramid_storage")
         self.levels = levels
 
     def __len__(self):
@@ -225,15 +505,36 @@ class BakedPyramid:
     hi = property(lambda self: self.levels[0].hi)
     degree = property(lambda self: self.levels[0].degree)
     device = property(lambda self: self.levels[0].rows.device)
+    sparse = property(lambda self: isinstance(self.levels[0], SparseField))
 
     @property
     def nbytes(self) -> int:
-        """Bytes of the rows and the occupancy words of every level."""
+        """Bytes of the rows and the occupancy words (and, when sparse, the tables) of every level."""
         return sum(b.nbytes for b in self.levels)
 
+    @property
+    def dense_nbytes(self) -> int:
+        """Bytes the pyramid takes with dense levels."""
+        return sum(b.dense_nbytes if self.sparse else b.nbytes for b in self.levels)
+
+    def stored_share(self) -> float:
+        """Share of the lattice points of all levels that have a row (1 for dense levels)."""
+        if not self.sparse:
+            return 1.0
+        return sum(b.n_rows for b in self.levels) / float(sum(int(np.prod(b.dims)) for b in self.levels))
+
+    def to_sparse(self):
+        """Every level through `BakedField.to_sparse`, keeping the cells of `pyramid_storage`."""
+        if any(b.occupancy is None for b in self.levels):
+            raise ValueError("BakedPyramid.to_sparse: a level without an occupancy grid marches every cell, so every row is read: it stays dense")
+        return BakedPyramid([b.to_sparse(stored) for b, stored in zip(self.levels, pyramid_storage([b.occupancy for b in self.levels]))])
+
     def save(self, path):
-        """Every level in one .npz: `levels` and the shared `degree`, then the arrays of `BakedField.save` of level i as `l<i>_<name>`."""
+        """Every level in one .npz: `levels` and the shared `degree`, then the arrays of `BakedField.save` (or `SparseField.save`, and then
+        `sparse` = 1 beside `levels`) of level i as `l<i>_<name>`."""
         arrays = dict(levels=np.int32(len(self.levels)), degree=np.int32(self.degree))
+        if self.sparse:
+            arrays["sparse"] = np.int32(1)
         for i, b in enumerate(self.levels):
             for k, v in b._arrays().items():
                 arrays[f"l{i}_{k}"] = v
@@ -247,12 +548,20 @@ class BakedPyramid:
         with np.load(path) as z:
             return int(z["levels"]) if "levels" in z.files else None
 
+    @staticmethod
+    def stored_sparse(path) -> bool:
+        """Whether a saved lattice or pyramid is sparse, without reading its rows."""
+        with np.load(path) as z:
+            return "sparse" in z.files or "sparse_rows" in z.files
+
     @classmethod
     def load(cls, path, device="cuda"):
         with np.load(path) as z:
             if "levels" not in z.files:
-                raise ValueError(f"{path} holds a single lattice, not a pyramid: load it with BakedField.load")
-            return cls([BakedField._from_arrays({k[len(f"l{i}_"):]: z[k] for k in z.files if k.startswith(f"l{i}_")}, device)
+                raise ValueError("{0} holds a single lattice, not a pyramid: load it with {1}".format(
+                    path, "SparseField.load" if "sparse_rows" in z.files else "BakedField.load"))
+            kind = SparseField if "sparse" in z.files else BakedField
+            return cls([kind._from_arrays({k[len(f"l{i}_"):]: z[k] for k in z.files if k.startswith(f"l{i}_")}, device)
                         for i in range(int(z["levels"]))])
 
 
@@ -326,8 +635,13 @@ def pack_rows(sigma, coef, degree, mask=None, out=None):
 
 
 def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=0.01, dilate=1, n_dirs=DEFAULT_N_DIRS, cov_scale=1.0,
-               precision=None, chunk=None):
-    """Bake the field of a bounded two-level model into a `BakedField` of `grid`^3 (or (nx, ny, nz)) points over lo .. hi.
+               precision=None, chunk=None, sparse=False, _grids=None, _stored=None):
+    """Bake the field of a bounded two-level model into a `BakedField` of `grid`^3 (or (nx, ny, nz)) points over lo .. hi; with
+    `sparse=True` into a `SparseField`, the bytes of `bake_field(...).to_sparse()`, without ever allocating dense rows or dense
+    coefficients: after sigma and the bits come the table (mipnerf_preview_sparse_index) and the stored points in slot order, and every
+    chunk of them goes through `ops.field_at`, `fit_sh` and mipnerf_preview_sparse_pack straight into its rows.  (`bake_pyramid` hands
+    in what it has made already: `_grids` = (sigma, bits) and `_stored` = the level's cells of `pyramid_storage`; a stored point that is
+    not a baked point gets its sigma and zero coefficients, as in the dense rows.)
 
     sigma = `ops.density_grid`; bits = `ops.occupancy_grid(sigma, threshold, dilate)`; a point is baked iff any of the up to 8 cells around
     it is occupied; at the baked points `ops.field_at` runs once per direction of `bake_directions(n_dirs)` on the lattice Gaussian
@@ -348,12 +662,41 @@ def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=
     nx, ny, nz = dims
     nb = (degree + 1) ** 2
     with torch.no_grad():
-        sigma = ops.density_grid(model_or_system, dims, lo, hi, cov_scale=cov_scale, precision=precision)
+        if _grids is None:
+            sigma = ops.density_grid(model_or_system, dims, lo, hi, cov_scale=cov_scale, precision=precision)
+            occ = ops.occupancy_grid(sigma, threshold, lo, hi, dilate=dilate)
+        else:
+            sigma, occ = _grids
         dev = sigma.device
-        occ = ops.occupancy_grid(sigma, threshold, lo, hi, dilate=dilate)
         mask = baked_points(occ)
         dirs = bake_directions(n_dirs)
         dirs32 = dirs.to(device=dev, dtype=torch.float32)
+
+        def coefficients(idx):
+            means, var = lattice_gaussians(dims, lo, hi, cov_scale, idx)
+            rgb = torch.empty(idx.numel(), n_dirs, 3, dtype=torch.float32, device=dev)
+            for k in range(n_dirs):
+                rgb[:, k] = ops.field_at(model_or_system, means, var, dirs32[k].expand(idx.numel(), 3), precision=precision)[:, :3]
+            return fit_sh(rgb, dirs, degree)
+
+        if sparse:
+            table, m = index_table(occ if _stored is None else _stored)
+            stored = mask if _stored is None else baked_points(_stored)
+            index = torch.nonzero(stored.reshape(-1)).reshape(-1)       # flat order is slot order
+            baked = None if _stored is None else mask.reshape(-1)[index]
+            del mask, stored
+            rows = torch.empty(m, ROW_HALVES[degree], dtype=torch.float16, device=dev)
+            for c0 in range(0, m, chunk):
+                idx = index[c0:c0 + chunk]
+                if baked is None:
+                    coef = coefficients(idx).contiguous()
+                else:
+                    coef = torch.zeros(idx.numel(), nb, 3, dtype=torch.float32, device=dev)
+                    keep = baked[c0:c0 + chunk]
+                    if bool(keep.any()):
+                        coef[keep] = coefficients(idx[keep])
+                sparse_pack(sigma.reshape(-1)[idx], coef, degree, rows[c0:c0 + chunk])
+            return SparseField(rows, table, dims, lo, hi, degree, occ, threshold, stored=_stored, _table_is_ours=True)
         rows = torch.empty(nz, ny, nx, ROW_HALVES[degree], dtype=torch.float16, device=dev)
         # dense coefficients only for a slab of z layers at a time (at least 2: the library's smallest lattice)
         layers = min(nz, max(2, (1 << 24) // (nx * ny)))
@@ -366,11 +709,7 @@ def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=
             index = torch.nonzero(mask[z0:z1].reshape(-1)).reshape(-1) + z0 * ny * nx
             for c0 in range(0, index.numel(), chunk):
                 idx = index[c0:c0 + chunk]
-                means, var = lattice_gaussians(dims, lo, hi, cov_scale, idx)
-                rgb = torch.empty(idx.numel(), n_dirs, 3, dtype=torch.float32, device=dev)
-                for k in range(n_dirs):
-                    rgb[:, k] = ops.field_at(model_or_system, means, var, dirs32[k].expand(idx.numel(), 3), precision=precision)[:, :3]
-                coef.view(-1, nb, 3)[idx - z0 * ny * nx] = fit_sh(rgb, dirs, degree)
+                coef.view(-1, nb, 3)[idx - z0 * ny * nx] = coefficients(idx)
             pack_rows(sigma[z0:z1], coef, degree, mask=mask[z0:z1], out=rows[z0:z1])
     return BakedField(rows, dims, lo, hi, degree, occ, threshold)
 
@@ -391,11 +730,31 @@ def pyramid_dims(grid, levels, lo, hi):
 
 def bake_pyramid(model_or_system, grid=256, levels=DEFAULT_MIP_LEVELS, degree=1, lo=None, hi=None, **kwargs):
     """`bake_field` at `grid` and at each coarser lattice of `pyramid_dims`, over the same box and with the same arguments (`kwargs`:
-    threshold, dilate, n_dirs, cov_scale, precision, chunk), as a `BakedPyramid`.  Every level is what `bake_field` returns at its dims:
-    its lattice Gaussians have its own spacing, so a coarser level is the field pre-filtered at that spacing by the model's own integrated
-    encoding.  Level 0 is baked first, so `bake_field`'s refusals come from `bake_field`."""
+    threshold, dilate, n_dirs, cov_scale, precision, chunk, sparse), as a `BakedPyramid`.  Every level is what `bake_field` returns at its
+    dims: its lattice Gaussians have its own spacing, so a coarser level is the field pre-filtered at that spacing by the model's own
+    integrated encoding.  Level 0 is baked first, so `bake_field`'s refusals come from `bake_field`.
+
+    With `sparse=True` the levels are `SparseField`s and the result is `bake_pyramid(...).to_sparse()` byte for byte: sigma and the bits
+    of every level come first (a level's stored cells depend on its neighbours' bits, `pyramid_storage`), then each level is baked into
+    its compact rows."""
     if not 1 <= int(levels) <= MAX_MIP_LEVELS:
         raise ValueError(f"bake_pyramid: a pyramid has 1 .. {MAX_MIP_LEVELS} levels (got {levels})")
+    if kwargs.get("sparse", False):
+        from . import ops
+        refuse_model(model_or_system, "bake_field")
+        _check_degree(degree, "bake_field")
+        if lo is None or hi is None:
+            raise ValueError("bake_field: give the box lo .. hi the lattice spans (the rays to be rendered are marched inside it only)")
+        all_dims = pyramid_dims(check_lattice(grid, "bake_field"), levels, lo, hi)
+        how = {k: kwargs[k] for k in ("cov_scale", "precision") if k in kwargs}
+        with torch.no_grad():
+            grids = []
+            for dims in all_dims:
+                sigma = ops.density_grid(model_or_system, dims, _box3(lo), _box3(hi), **how)
+                grids.append((sigma, ops.occupancy_grid(sigma, kwargs.get("threshold", 0.01), _box3(lo), _box3(hi), dilate=kwargs.get("dilate", 1))))
+            keep = pyramid_storage([occ for _, occ in grids])
+        return BakedPyramid([bake_field(model_or_system, grid=dims, degree=degree, lo=lo, hi=hi, _grids=g, _stored=(k if len(keep) > 1 else None),
+                                        **kwargs) for dims, g, k in zip(all_dims, grids, keep)])
     first = bake_field(model_or_system, grid=grid, degree=degree, lo=lo, hi=hi, **kwargs)
     fields = [first]
     for dims in pyramid_dims(first.dims, levels, first.lo, first.hi)[1:]:
@@ -422,6 +781,8 @@ def _march_args(who, fields, tensors, background, step_scale, t_min, max_steps, 
         out = (torch.empty(B, 3, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev))
     if steps is not None and (steps.dtype != torch.int32 or steps.numel() != B or not steps.is_contiguous()):
         raise ValueError(f"{who}: steps must be a contiguous int32 tensor with one entry per ray")
+    if not use_occupancy and any(isinstance(b, SparseField) for b in fields):
+        raise ValueError(f"{who}: a sparse lattice has rows next to occupied cells only: it cannot be marched without its occupancy grid")
     structs = []
     for b in fields:
         occ = b.occupancy if use_occupancy else None
@@ -431,12 +792,31 @@ def _march_args(who, fields, tensors, background, step_scale, t_min, max_steps, 
     return B, dev, out, structs, params
 
 
+def _march_sparse(who, fields, structs, params, footprint, B, dev, origins, directions, radii, near, far, out, steps, lod):
+    """mipnerf_preview_sparse_march over the `SparseField`s `fields` (`structs`: their `PreviewField` structs from `_march_args`)."""
+    rgb, acc, dist = out
+    pyr = L.PreviewSparsePyramid()
+    pyr.levels = len(fields)
+    for i, (b, field) in enumerate(zip(fields, structs)):
+        pyr.level[i] = L.PreviewSparseField(field, b.table.data_ptr(), b.n_rows)
+    with torch.cuda.device(dev):
+        L.preview_sparse_check(L.preview_sparse_lib().mipnerf_preview_sparse_march(
+            C.byref(pyr), C.byref(params), float(footprint), B, origins.data_ptr(), directions.data_ptr(),
+            None if radii is None else radii.data_ptr(), near.data_ptr(), far.data_ptr(), rgb.data_ptr(), acc.data_ptr(), dist.data_ptr(),
+            None if steps is None else steps.data_ptr(), None if lod is None else lod.data_ptr(), torch.cuda.current_stream().cuda_stream), who)
+    return rgb, acc, dist
+
+
 def march(baked, origins, directions, near, far, background, step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS,
           out=None, steps=None, use_occupancy=True):
     """mipnerf_preview_march on flat fp32 device tensors: origins / directions [B, 3], near / far [B] -> (rgb [B, 3], acc [B], distance
-    [B]) (`out`: these three, preallocated).  `steps`: an int32 [B] tensor that receives the samples evaluated per ray."""
+    [B]) (`out`: these three, preallocated).  `steps`: an int32 [B] tensor that receives the samples evaluated per ray.  A `SparseField`
+    goes through mipnerf_preview_sparse_march as a pyramid of one level, with no radii and footprint 0: the same bytes."""
     B, dev, (rgb, acc, dist), (field,), params = _march_args("march", [baked], dict(origins=origins, directions=directions, near=near, far=far),
                                                              background, step_scale, t_min, max_steps, out, steps, use_occupancy)
+    if isinstance(baked, SparseField):
+        return _march_sparse("preview_sparse_march", [baked], [field], params, 0.0, B, dev, origins, directions, None, near, far,
+                             (rgb, acc, dist), steps, None)
     with torch.cuda.device(dev):
         L.preview_check(L.preview_lib().mipnerf_preview_march(C.byref(field), C.byref(params), B, origins.data_ptr(), directions.data_ptr(),
                                                               near.data_ptr(), far.data_ptr(), rgb.data_ptr(), acc.data_ptr(), dist.data_ptr(),
@@ -447,7 +827,7 @@ def march(baked, origins, directions, near, far, background, step_scale=DEFAULT_
 
 def march_pyramid(pyramid, origins, directions, radii, near, far, background, footprint=DEFAULT_FOOTPRINT, step_scale=DEFAULT_STEP_SCALE,
                   t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS, out=None, steps=None, lod=None, use_occupancy=True):
-    """mipnerf_preview_mip_march on flat fp32 device tensors: origins / directions [B, 3], radii / near / far [B] -> (rgb [B, 3], acc [B],
+    """mipnerf_preview_mip_march (mipnerf_preview_sparse_march for a pyramid of `SparseField`s) on flat fp32 device tensors: origins / directions [B, 3], radii / near / far [B] -> (rgb [B, 3], acc [B],
     distance [B]) (`out`: these three, preallocated).  `steps`: an int32 [B] tensor that receives the samples evaluated per ray; `lod`: an
     fp32 [B] tensor that receives each ray's weighted mean level.  The step is `step_scale` times the spacing of level 0."""
     B, dev, (rgb, acc, dist), structs, params = _march_args(
@@ -455,6 +835,9 @@ def march_pyramid(pyramid, origins, directions, radii, near, far, background, fo
         t_min, max_steps, out, steps, use_occupancy)
     if lod is not None and (lod.dtype != torch.float32 or lod.numel() != B or not lod.is_contiguous() or lod.device != dev):
         raise ValueError("march_pyramid: lod must be a contiguous fp32 tensor with one entry per ray")
+    if pyramid.sparse:
+        return _march_sparse("preview_sparse_march", pyramid.levels, structs, params, footprint, B, dev, origins, directions, radii, near, far,
+                             (rgb, acc, dist), steps, lod)
     pyr = L.PreviewPyramid()
     pyr.levels = len(structs)
     for i, field in enumerate(structs):
@@ -555,6 +938,8 @@ def build_parser():
     p.add_argument("--mip", help="anti-alias the preview with a pyramid of L lattices (1 .. 8), each with about half the points per axis of "
                    "the one before, the level of every sample chosen by the ray's cone radius; the bare flag means 4 levels (a choice: they "
                    "reach 8 times the finest spacing)", type=int, nargs="?", const=DEFAULT_MIP_LEVELS, default=None, metavar="L")
+    p.add_argument("--sparse", help="store only the rows next to an occupied cell, behind a row table: the same pictures from a fraction of the "
+                   "memory (with and without --mip)", action="store_true")
     p.add_argument("--footprint", help="--mip: the cone is footprint * radius * t wide (a choice: the default sqrt(3) is one pixel's width)",
                    type=float, default=None, metavar="F")
     return p
@@ -614,6 +999,17 @@ def refuse_baked_levels(args):
             "nothing; drop --mip" if stored is None else stored))
 
 
+def refuse_baked_kind(args):
+    """--baked of a sparse file without --sparse, or of a dense one with it: refused after reading the file's key names alone."""
+    if args.baked is None:
+        return
+    stored = BakedPyramid.stored_sparse(args.baked)
+    if stored and not args.sparse:
+        raise SystemExit(f"--baked {args.baked} holds sparse rows: give --sparse to render it")
+    if args.sparse and not stored:
+        raise SystemExit(f"--baked {args.baked} holds dense rows, --sparse asks for sparse ones: drop --sparse")
+
+
 def refuse_checkpoint(system):
     """Captured-scene and unbounded checkpoints, and one-level models: refused before anything is moved to the device."""
     from .render_video import is_scene360
@@ -640,6 +1036,7 @@ def main(argv=None):
     dims = refuse_arguments(args)
     refuse_baked_degree(args)
     refuse_baked_levels(args)
+    refuse_baked_kind(args)
     footprint = DEFAULT_FOOTPRINT if args.footprint is None else args.footprint
     system = load_system(args)
     refuse_checkpoint(system)
@@ -662,7 +1059,8 @@ def main(argv=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if args.baked is not None:
-            baked = BakedField.load(args.baked, dev) if args.mip is None else BakedPyramid.load(args.baked, dev)
+            single = SparseField if args.sparse else BakedField
+            baked = single.load(args.baked, dev) if args.mip is None else BakedPyramid.load(args.baked, dev)
         else:
             bound = args.bound
             if bound is None:
@@ -671,7 +1069,7 @@ def main(argv=None):
                 frames = [path[i] for i in range(len(path))] + ([dataset[i][0] for i in range(len(dataset))] if dataset is not None else [])
                 bound = cull_box(frames, min(dims))
             how = dict(grid=dims, degree=1 if args.sh_degree is None else args.sh_degree, lo=-float(bound), hi=float(bound),
-                       threshold=args.threshold, dilate=args.dilate, n_dirs=args.n_dirs, precision=args.precision)
+                       threshold=args.threshold, dilate=args.dilate, n_dirs=args.n_dirs, precision=args.precision, sparse=args.sparse)
             baked = bake_field(system, **how) if args.mip is None else bake_pyramid(system, levels=args.mip, **how)
         torch.cuda.synchronize()
         bake_ms = 1e3 * (time.perf_counter() - t0)
@@ -695,16 +1093,19 @@ def main(argv=None):
                 lod_sum, lod_rays = lod_sum + float(fr.lod[hit].sum()), lod_rays + int(hit.sum())
             save_images(*fr.images(*out), os.path.join(folder, str(int(args.base_size[0] / w))), idx % nums)
         generate_video(folder)
+        # --sparse: the stored share and what the dense rows would take, after everything the line says without it
+        tail = ", stored share {0:.4f}, sparse {1:.1f} MiB against {2:.1f} MiB dense".format(
+            baked.stored_share(), baked.nbytes / 2 ** 20, baked.dense_nbytes / 2 ** 20) if args.sparse else ""
         if args.mip is None:
             print("preview: lattice {0} x {1} x {2}, degree {3}, baked share {4:.4f}, {5:.1f} MiB, {6} {7:.1f} ms, mean {8:.3f} ms per frame "
                   "({9} frames)".format(*baked.dims, baked.degree, baked.baked_share(), baked.nbytes / 2 ** 20,
-                                        "loaded in" if args.baked is not None else "baked in", bake_ms, float(np.mean(times)), len(times)))
+                                        "loaded in" if args.baked is not None else "baked in", bake_ms, float(np.mean(times)), len(times)) + tail)
         else:
             print("preview: pyramid of {0} levels {1}, degree {2}, baked share {3:.4f}, {4:.1f} MiB, {5} {6:.1f} ms, mean {7:.3f} ms per frame "
                   "({8} frames), footprint {9:.4f}, mean lod {10:.3f} over {11} hit rays".format(
                       len(baked), ", ".join("{0} x {1} x {2}".format(*b.dims) for b in baked.levels), baked.degree,
                       baked.levels[0].baked_share(), baked.nbytes / 2 ** 20, "loaded in" if args.baked is not None else "baked in", bake_ms,
-                      float(np.mean(times)), len(times), footprint, lod_sum / max(lod_rays, 1), lod_rays))
+                      float(np.mean(times)), len(times), footprint, lod_sum / max(lod_rays, 1), lod_rays) + tail)
         if dataset is not None:
             white = bool(hp["val.white_bkgd"])
             single = baked if args.mip is None else baked.levels[0]
