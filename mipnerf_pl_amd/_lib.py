@@ -223,6 +223,18 @@ PREVIEW_SPARSE_SIGNATURES = {
                                                _P, _P, _P, _P]),
 }
 
+# include/mipnerf_preview_tune.h: the gradient of the single-lattice march with respect to the rows and an Adam step on them, in a sixth
+# library; the three preview libraries keep their ABI versions and their entry points
+PREVIEW_TUNE_LIB_PATH = os.environ.get("MIPNERF_PREVIEW_TUNE_LIB", os.path.join(HERE, "csrc", "libmipnerf_preview_tune.so"))
+PREVIEW_TUNE_ABI = 1
+PREVIEW_TUNE_SIGNATURES = {
+    "mipnerf_preview_tune_abi_version": (C.c_int, []),
+    "mipnerf_preview_tune_last_error": (C.c_char_p, []),
+    "mipnerf_preview_tune_grad": (C.c_int, [C.POINTER(PreviewField), C.POINTER(PreviewParams), _I64, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P,
+                                            _P, _P]),
+    "mipnerf_preview_tune_adam": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _F, _P]),
+}
+
 _handles = {}
 
 
@@ -290,6 +302,16 @@ def preview_sparse_lib():
     """Load (once) libmipnerf_preview_sparse.so.  No fallback: a missing library is an error."""
     return _load(PREVIEW_SPARSE_LIB_PATH, PREVIEW_SPARSE_SIGNATURES, "the sparse-lattice renderer has no fallback.",
                  ("mipnerf_preview_sparse_abi_version", PREVIEW_SPARSE_ABI))
+
+
+def preview_tune_lib():
+    """Load (once) libmipnerf_preview_tune.so.  No fallback: a missing library is an error."""
+    return _load(PREVIEW_TUNE_LIB_PATH, PREVIEW_TUNE_SIGNATURES, "tuning the baked lattice has no fallback.",
+                 ("mipnerf_preview_tune_abi_version", PREVIEW_TUNE_ABI))
+
+
+def preview_tune_check(rc: int, what: str = "") -> None:
+    _check(rc, lambda: preview_tune_lib().mipnerf_preview_tune_last_error(), what)
 
 
 def preview_sparse_check(rc: int, what: str = "") -> None:

@@ -687,6 +687,12 @@ class RenderGen(torch.utils.data.Dataset):
     def __len__(self):
         return self.n_sample
 
+    def pixel_rays(self, cam_idx, pix_idx):
+        """Rays [n, k] of single pixels: `pix_idx` (row-major within the image) of the cameras `cam_idx`, both integer device tensors [n]."""
+        if self._cams_dev is None:
+            raise RuntimeError("RenderGen: no HIP device; rays are computed by k_generate_rays")
+        return ops.generate_rays(self._cams_dev, cam_idx=cam_idx.to(self.device, torch.int32), pix_idx=pix_idx.to(self.device, torch.int32))
+
     def __getitem__(self, index):
         if self._cams_dev is None:
             raise RuntimeError("RenderGen: no HIP device; rays are computed by k_generate_rays")

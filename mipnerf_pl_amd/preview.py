@@ -10,6 +10,10 @@ The PlenOctrees / Plenoxels idea in its simplest dense form (include/mipnerf_pre
     bake_field(system, sparse=True) / BakedField.to_sparse()    a `SparseField`: only the rows next to an occupied cell, behind a row table
                                 (include/mipnerf_preview_sparse.h); marched by mipnerf_preview_sparse_march to the same bytes
 
+    march_grad / TuneState / tune_field    mipnerf_preview_tune_grad + mipnerf_preview_tune_adam (include/mipnerf_preview_tune.h): the
+                                gradient of `march` with respect to the rows and Adam steps on them against photos or the MLP's renders;
+                                a single dense `BakedField` only, and the float-atomic sums are not bitwise reproducible
+
     bake_pyramid(system)        `bake_field` at grid, then at about half the points per axis, ...: a `BakedPyramid`
     march_pyramid / render_rays of a pyramid    mipnerf_preview_mip_march (include/mipnerf_preview_mip.h): every sample reads the level (or
                                 the two levels) whose spacing brackets footprint * radius * t, the width of the ray's cone there
@@ -17,6 +21,7 @@ The PlenOctrees / Plenoxels idea in its simplest dense form (include/mipnerf_pre
     python -m mipnerf_pl_amd.preview --ckpt CKPT --out_dir OUT [--grid 256 | --grid NX NY NZ] [--sh_degree 0|1|2] [--bound B]
         [--threshold 0.01] [--dilate 1] [--step 0.5] [--t_min 1e-3] [--precision fp32|bf16] [--n_poses 120] [--scale 1]
         [--save_baked] [--baked FILE] [--data DIR --compare] [--mip [L]] [--footprint F] [--sparse]
+        [--tune STEPS [--tune_batch 65536] [--tune_lr_sigma 0.2] [--tune_lr_colour 0.01] [--tune_target photos|mlp] [--tune_seed 0]]
 
 renders the spherical path of `render_video` to OUT/preview_spheric/<exp_name>/ and prints one `preview:` line.
 
@@ -825,6 +830,205 @@ def march(baked, origins, directions, near, far, background, step_scale=DEFAULT_
     return rgb, acc, dist
 
 
+# ---- tuning the lattice through the renderer (include/mipnerf_preview_tune.h) --------------------------------------------------------
+# Choices, not measurements: Adam's usual betas and eps; a density step of 0.2 against densities of tens to hundreds, a coefficient step
+# of 0.01 against colours in [0, 1] (Plenoxels' ratio of the two is larger still).
+DEFAULT_TUNE_LR_SIGMA = 0.2
+DEFAULT_TUNE_LR_COLOUR = 0.01
+DEFAULT_TUNE_BETAS = (0.9, 0.999)
+DEFAULT_TUNE_EPS = 1e-8
+DEFAULT_TUNE_BATCH = 65536
+
+
+def _refuse_tuning(baked, who):
+    if isinstance(baked, SparseField):
+        raise NotImplementedError(f"{who}: a SparseField is not a tuning target (the gradient is scattered into dense rows): tune the dense "
+                                  "BakedField, then .to_sparse()")
+    if isinstance(baked, BakedPyramid):
+        raise NotImplementedError(f"{who}: a BakedPyramid is not a tuning target (the gradient of the level mix is not implemented): "
+                                  "tune a single BakedField")
+    if not isinstance(baked, BakedField):
+        raise TypeError(f"{who}: expected a BakedField, got {type(baked).__name__}")
+
+
+def march_grad(baked, origins, directions, near, far, background, grad_rgb=None, grad_acc=None, target=None, loss_scale=None, grad_rows=None,
+               step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS, use_occupancy=True, out=None, counters=None):
+    """mipnerf_preview_tune_grad: the march of `march` and its gradient with respect to the rows in one launch -> (grad_rows, rgb, acc).
+    The loss side is `grad_rgb` [B, 3], or `target` [B, 3] with `loss_scale` (G = loss_scale * (rgb - target), rgb this launch's own);
+    `grad_acc` [B] is optional.  `grad_rows` fp32 [nz, ny, nx, W] is ADDED INTO (None: a fresh zero tensor); rgb and acc are the bytes
+    `march` gives (`out`: the two, preallocated).  `counters`: an int64 [2] tensor that is added to (samples, flushes).  The sums over
+    rays use float atomics: two runs may differ in the last bits of grad_rows."""
+    _refuse_tuning(baked, "march_grad")
+    B, dev, _, (field,), params = _march_args("march_grad", [baked], dict(origins=origins, directions=directions, near=near, far=far),
+                                              background, step_scale, t_min, max_steps, (None, None, None), None, use_occupancy)
+    if (grad_rgb is None) == (target is None):
+        raise ValueError("march_grad: give exactly one of grad_rgb and target")
+    if target is not None and loss_scale is None:
+        raise ValueError("march_grad: target needs loss_scale")
+    for name, t, shape in (("grad_rgb", grad_rgb, (B, 3)), ("target", target, (B, 3)), ("grad_acc", grad_acc, (B,))):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or tuple(t.shape) != shape):
+            raise ValueError(f"march_grad: {name} must be a contiguous fp32 tensor of {shape} on {dev}")
+    if grad_rows is None:
+        grad_rows = torch.zeros(baked.rows.shape, dtype=torch.float32, device=dev)
+    elif grad_rows.dtype != torch.float32 or grad_rows.shape != baked.rows.shape or not grad_rows.is_contiguous() or grad_rows.device != dev:
+        raise ValueError(f"march_grad: grad_rows must be a contiguous fp32 tensor of {tuple(baked.rows.shape)} on {dev}")
+    if counters is not None and (counters.dtype != torch.int64 or counters.numel() != 2 or counters.device != dev):
+        raise ValueError("march_grad: counters must be an int64 tensor of 2 entries")
+    rgb, acc = (torch.empty(B, 3, device=dev), torch.empty(B, device=dev)) if out is None else out
+    for name, t, shape in (("out[0] (rgb)", rgb, (B, 3)), ("out[1] (acc)", acc, (B,))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or tuple(t.shape) != shape:
+            raise ValueError(f"march_grad: {name} must be a contiguous fp32 tensor of {shape} on {dev}")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        L.preview_tune_check(L.preview_tune_lib().mipnerf_preview_tune_grad(
+            C.byref(field), C.byref(params), B, origins.data_ptr(), directions.data_ptr(), near.data_ptr(), far.data_ptr(), ptr(grad_rgb),
+            ptr(target), 0.0 if loss_scale is None else float(loss_scale), ptr(grad_acc), rgb.data_ptr(), acc.data_ptr(), grad_rows.data_ptr(),
+            ptr(counters), torch.cuda.current_stream().cuda_stream), "preview_tune_grad")
+    return grad_rows, rgb, acc
+
+
+def tune_adam(master, m, v, grad, rows, degree, mask, lr_sigma, lr_colour, beta1, beta2, eps, c1, c2):
+    """mipnerf_preview_tune_adam on fp32 [..., W] tensors and the fp16 `rows` [..., W], in place: one Adam step on the used entries of every
+    point whose `mask` byte (uint8 per point, or None) is not 0, the new rows rounded as `pack_rows` rounds them, grad cleared."""
+    degree = _check_degree(degree, "tune_adam")
+    W = ROW_HALVES[degree]
+    n = rows.numel() // W
+    for name, t in (("master", master), ("m", m), ("v", v), ("grad", grad)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != rows.shape or t.device != rows.device:
+            raise ValueError(f"tune_adam: {name} must be a contiguous fp32 tensor of the rows' shape on their device")
+    if rows.dtype != torch.float16 or not rows.is_contiguous() or rows.shape[-1] != W:
+        raise ValueError(f"tune_adam: rows must be contiguous fp16 [..., {W}]")
+    if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != n or not mask.is_contiguous() or mask.device != rows.device):
+        raise ValueError("tune_adam: one contiguous uint8 mask byte per point")
+    with torch.cuda.device(rows.device):
+        L.preview_tune_check(L.preview_tune_lib().mipnerf_preview_tune_adam(
+            n, degree, master.data_ptr(), m.data_ptr(), v.data_ptr(), grad.data_ptr(), rows.data_ptr(), None if mask is None else mask.data_ptr(),
+            float(lr_sigma), float(lr_colour), float(beta1), float(beta2), float(eps), float(c1), float(c2),
+            torch.cuda.current_stream().cuda_stream), "preview_tune_adam")
+
+
+class TuneState:
+    """What tuning a `BakedField` keeps beside it: fp32 master rows made from the fp16 rows, Adam's `m` and `v`, the gradient buffer and
+    the point mask (`baked_points` of the occupancy: only points next to an occupied cell ever receive a gradient; None without an
+    occupancy).  `step` updates `baked.rows` in place; the occupancy never changes.  The two learning rates are choices, not measurements."""
+
+    def __init__(self, baked, lr_sigma=DEFAULT_TUNE_LR_SIGMA, lr_colour=DEFAULT_TUNE_LR_COLOUR, betas=DEFAULT_TUNE_BETAS, eps=DEFAULT_TUNE_EPS,
+                 step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS):
+        _refuse_tuning(baked, "TuneState")
+        if not (lr_sigma >= 0 and lr_colour >= 0 and 0 <= betas[0] < 1 and 0 <= betas[1] < 1 and eps >= 0):
+            raise ValueError("TuneState: learning rates and eps must not be negative, the betas must lie in [0, 1)")
+        self.baked = baked
+        self.lr_sigma, self.lr_colour, self.betas, self.eps = float(lr_sigma), float(lr_colour), (float(betas[0]), float(betas[1])), float(eps)
+        self.step_scale, self.t_min, self.max_steps = float(step_scale), float(t_min), int(max_steps)
+        self.master = baked.rows.float()
+        self.m, self.v, self.grad = torch.zeros_like(self.master), torch.zeros_like(self.master), torch.zeros_like(self.master)
+        self.mask = None if baked.occupancy is None else baked_points(baked.occupancy).to(torch.uint8).contiguous()
+        self.steps = 0
+        self.counters = None         # an int64 [2] tensor here makes every step count its samples and flushes
+
+    def step(self, rays, target, white_bkgd):
+        """One step on a batch: `rays` (a `Rays` of [..., k] tensors), `target` [..., 3] -> the batch's mean squared error BEFORE the step,
+        a 0-d device tensor.  mipnerf_preview_tune_grad in target mode with loss_scale = 2 / (3 B), then mipnerf_preview_tune_adam."""
+        n = int(np.prod(rays.origins.shape[:-1]))
+        o, d, near, far = (t.reshape(n, t.shape[-1]).float().contiguous() for t in (rays.origins, rays.directions, rays.near, rays.far))
+        target = target.reshape(n, 3).float().contiguous()
+        _, rgb, _ = march_grad(self.baked, o, d, near.reshape(n), far.reshape(n), white_bkgd, target=target, loss_scale=2.0 / (3.0 * n),
+                               grad_rows=self.grad, step_scale=self.step_scale, t_min=self.t_min, max_steps=self.max_steps,
+                               counters=self.counters)
+        loss = ((rgb - target) ** 2).mean()
+        self.steps += 1
+        b1, b2 = self.betas
+        tune_adam(self.master, self.m, self.v, self.grad, self.baked.rows, self.baked.degree, self.mask, self.lr_sigma, self.lr_colour, b1, b2,
+                  self.eps, 1.0 / (1.0 - b1 ** self.steps), 1.0 / (1.0 - b2 ** self.steps))
+        return loss
+
+    def state_dict(self):
+        return dict(master=self.master, m=self.m, v=self.v, steps=self.steps, lr_sigma=self.lr_sigma, lr_colour=self.lr_colour,
+                    betas=self.betas, eps=self.eps)
+
+    def load_state_dict(self, state):
+        for k in ("master", "m", "v"):
+            if tuple(state[k].shape) != tuple(self.master.shape):
+                raise ValueError(f"TuneState.load_state_dict: {k} has shape {tuple(state[k].shape)}, the lattice {tuple(self.master.shape)}")
+            getattr(self, k).copy_(state[k])
+        self.steps = int(state["steps"])
+        self.lr_sigma, self.lr_colour, self.eps = float(state["lr_sigma"]), float(state["lr_colour"]), float(state["eps"])
+        self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+        self.grad.zero_()
+        self.baked.rows.copy_(pack_master(self.master, self.baked.degree))
+
+
+def pack_master(master, degree):
+    """fp32 master rows -> fp16 rows with the pack's rounding (sigma saturates at the fp16 maximum), pure torch."""
+    rows = master.clone()
+    rows[..., 0] = torch.clamp(rows[..., 0], max=65504.0)
+    return rows.to(torch.float16)
+
+
+def tune_field(baked, rays_and_targets, steps, white_bkgd=True, state=None, **kwargs):
+    """`steps` steps of `TuneState.step` on `baked`: `rays_and_targets(step)` -> (Rays, target [B, 3]).  Returns (state, losses), the losses
+    a [steps] device tensor of each batch's mean squared error before its step.  `kwargs` go to `TuneState`."""
+    if steps < 1:
+        raise ValueError("tune_field: at least one step")
+    state = TuneState(baked, **kwargs) if state is None else state
+    losses = []
+    for k in range(int(steps)):
+        rays, target = rays_and_targets(k)
+        losses.append(state.step(rays, target, white_bkgd))
+    return state, torch.stack(losses)
+
+
+def photo_batches(train_dataset, batch, seed=0):
+    """Batches of a train split: uniform pixel ids from a seeded device generator through `dataset.rays_at` -> (Rays, pixels [B, 3])."""
+    dev = train_dataset.device if getattr(train_dataset, "device", None) is not None else torch.device("cuda", torch.cuda.current_device())
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    total = int(train_dataset.num_pixels)
+
+    def draw(step):
+        ids = torch.randint(0, total, (int(batch),), generator=gen, device=dev, dtype=torch.int64)
+        rays, pixels = train_dataset.rays_at(ids)
+        return rays, (None if pixels is None else pixels[..., :3])      # (a `PathPixels` has no photos: `mlp_batches` supplies the target)
+    return draw
+
+
+class PathPixels:
+    """The pixels of the frames of a camera path (`datasets.RenderGen`) as one ray source: `num_pixels` and `rays_at(ids)` like a train
+    split's, without photos.  `frames`: the indices of the frames to draw from (default: all)."""
+
+    def __init__(self, path, frames=None):
+        self.path, self.device = path, path.device
+        self.frames = torch.as_tensor(list(range(len(path))) if frames is None else list(frames), dtype=torch.int64, device=self.device)
+        counts = np.array([path.sizes[int(i)][0] * path.sizes[int(i)][1] for i in self.frames.tolist()], np.int64)
+        self.offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)])).to(self.device)
+        self.num_pixels = int(counts.sum())
+
+    def rays_at(self, ids):
+        ids = ids.to(self.device, torch.int64).reshape(-1)
+        cam = torch.searchsorted(self.offsets, ids, right=True) - 1
+        pix = ids - self.offsets[cam]
+        return self.path.pixel_rays(self.frames[cam], pix), None
+
+
+def mlp_batches(model, ray_source, batch, seed=0, white_bkgd=True, chunk=None):
+    """The rays `photo_batches` would draw from `ray_source` (a train split or a `PathPixels`), with the target taken from the fine level of
+    `model` under torch.no_grad() -> (Rays, rgb [B, 3])."""
+    from .evaluate import DEFAULT_CHUNK
+    from .model import GraphedFrame
+    draw = photo_batches(ray_source, batch, seed)
+    frame = []
+
+    def batch_of(step):
+        rays, _ = draw(step)
+        with torch.no_grad():
+            if not frame:
+                frame.append(GraphedFrame(model, int(batch), DEFAULT_CHUNK if chunk is None else chunk, white_bkgd, rays.origins.device,
+                                          capture=False))
+            _, rgb, _ = frame[0](rays)
+            return rays, rgb.reshape(int(batch), 3).clone()
+    return batch_of
+
+
 def march_pyramid(pyramid, origins, directions, radii, near, far, background, footprint=DEFAULT_FOOTPRINT, step_scale=DEFAULT_STEP_SCALE,
                   t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS, out=None, steps=None, lod=None, use_occupancy=True):
     """mipnerf_preview_mip_march (mipnerf_preview_sparse_march for a pyramid of `SparseField`s) on flat fp32 device tensors: origins / directions [B, 3], radii / near / far [B] -> (rgb [B, 3], acc [B],
@@ -942,7 +1146,47 @@ def build_parser():
                    "memory (with and without --mip)", action="store_true")
     p.add_argument("--footprint", help="--mip: the cone is footprint * radius * t wide (a choice: the default sqrt(3) is one pixel's width)",
                    type=float, default=None, metavar="F")
+    p.add_argument("--tune", help="fine-tune the baked lattice through its own renderer for STEPS Adam steps before rendering: with --data "
+                   "against the train split's photos (or the MLP's renders of those rays), without --data against the MLP's renders of random "
+                   "pixels of the spherical path's own frames, i.e. ON THE RENDERED POSES; either way on the background of --white_bkgd, the "
+                   "one the frames are rendered on.  A single dense lattice only; with --sparse the lattice is baked dense, tuned, then made sparse, so the peak memory is the dense bake's.  The float-atomic gradient sums "
+                   "make two runs differ in the last bits", type=int, default=None, metavar="STEPS")
+    p.add_argument("--tune_batch", help=f"--tune: rays per step (default {DEFAULT_TUNE_BATCH})", type=int, default=None, metavar="B")
+    p.add_argument("--tune_lr_sigma", help=f"--tune: Adam step of the density entries (a choice, not a measurement: default "
+                   f"{DEFAULT_TUNE_LR_SIGMA})", type=float, default=None)
+    p.add_argument("--tune_lr_colour", help=f"--tune: Adam step of the colour coefficients (a choice, not a measurement: default "
+                   f"{DEFAULT_TUNE_LR_COLOUR})", type=float, default=None)
+    p.add_argument("--tune_target", help="--tune: what the lattice is tuned against (default: photos with --data, else mlp)",
+                   choices=["photos", "mlp"], default=None)
+    p.add_argument("--tune_seed", help="--tune: seed of the batch draws (default 0)", type=int, default=None)
     return p
+
+
+TUNE_FLAGS = ("tune_batch", "tune_lr_sigma", "tune_lr_colour", "tune_target", "tune_seed")
+
+
+def refuse_tune_arguments(args):
+    """What --tune and its flags refuse from the command line alone."""
+    given = [f for f in TUNE_FLAGS if getattr(args, f) is not None]
+    if args.tune is None:
+        if given:
+            raise SystemExit(f"--{given[0]} belongs to --tune STEPS: give --tune as well")
+        return
+    if args.tune < 1:
+        raise SystemExit(f"--tune {args.tune}: at least one step")
+    if args.mip is not None:
+        raise SystemExit("--tune with --mip: a pyramid of lattices is not a tuning target (not implemented): drop one of them")
+    if args.baked is not None and args.sparse:
+        raise SystemExit("--tune with a sparse --baked file: sparse rows are not a tuning target (not implemented); tune the dense lattice "
+                         "and give --sparse without --baked, or render the file without --tune")
+    if args.tune_target == "photos" and args.data is None:
+        raise SystemExit("--tune_target photos tunes against the train split of a data set: give --data")
+    if args.tune_batch is not None and args.tune_batch < 1:
+        raise SystemExit(f"--tune_batch {args.tune_batch}: at least one ray")
+    for f in ("tune_lr_sigma", "tune_lr_colour"):
+        v = getattr(args, f)
+        if v is not None and not (v >= 0 and np.isfinite(v)):
+            raise SystemExit(f"--{f} {v}: must be finite and >= 0")
 
 
 def refuse_arguments(args):
@@ -972,6 +1216,7 @@ def refuse_arguments(args):
         raise SystemExit("--footprint scales the cone that chooses a pyramid level: give --mip as well")
     if args.footprint is not None and not (args.footprint >= 0 and np.isfinite(args.footprint)):
         raise SystemExit(f"--footprint {args.footprint}: must be finite and >= 0")
+    refuse_tune_arguments(args)
     if args.ckpt is None:
         raise SystemExit("give --ckpt: the checkpoint names the experiment (and is what --compare renders with the MLP)")
     return dims
@@ -1029,6 +1274,32 @@ def _psnr(a, b):
     return float(ops.eval_errors(a, b)[0])
 
 
+def _tune_command(args, system, baked, path, hp, dev):
+    """--tune: the batch source, the steps and the `preview: tuned` line; returns the lattice to render (a `SparseField` with --sparse)."""
+    from .datasets import dataset_dict
+    batch = DEFAULT_TUNE_BATCH if args.tune_batch is None else args.tune_batch
+    seed = 0 if args.tune_seed is None else args.tune_seed
+    against = args.tune_target if args.tune_target is not None else ("photos" if args.data is not None else "mlp")
+    white = bool(args.white_bkgd)         # the background the frames are rendered on: photos composited, MLP rendered and lattice tuned on it
+    if args.data is not None:
+        source = dataset_dict[hp["dataset_name"]](data_dir=args.data, split="train", white_bkgd=white, batch_type="all_images", device=dev)
+    else:
+        source = PathPixels(path)
+    batches = photo_batches(source, batch, seed) if against == "photos" else \
+        mlp_batches(system.mip_nerf, source, batch, seed, white, args.chunk_size)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    _, losses = tune_field(baked, batches, args.tune, white,
+                           lr_sigma=DEFAULT_TUNE_LR_SIGMA if args.tune_lr_sigma is None else args.tune_lr_sigma,
+                           lr_colour=DEFAULT_TUNE_LR_COLOUR if args.tune_lr_colour is None else args.tune_lr_colour,
+                           step_scale=args.step, t_min=args.t_min)
+    torch.cuda.synchronize()
+    secs = time.perf_counter() - t0
+    print("preview: tuned {0} steps of {1} rays against the {2} in {3:.2f} s ({4:.2f} ms per step), batch loss {5:.3e} -> {6:.3e}".format(
+        args.tune, batch, "photos" if against == "photos" else "MLP", secs, 1e3 * secs / args.tune, float(losses[0]), float(losses[-1])))
+    return baked.to_sparse() if args.sparse else baked
+
+
 def main(argv=None):
     from .evaluate import FrameEvaluator, cull_box, generate_video, save_images
     from .render_video import load_system
@@ -1069,10 +1340,16 @@ def main(argv=None):
                 frames = [path[i] for i in range(len(path))] + ([dataset[i][0] for i in range(len(dataset))] if dataset is not None else [])
                 bound = cull_box(frames, min(dims))
             how = dict(grid=dims, degree=1 if args.sh_degree is None else args.sh_degree, lo=-float(bound), hi=float(bound),
-                       threshold=args.threshold, dilate=args.dilate, n_dirs=args.n_dirs, precision=args.precision, sparse=args.sparse)
+                       threshold=args.threshold, dilate=args.dilate, n_dirs=args.n_dirs, precision=args.precision,
+                       sparse=args.sparse and args.tune is None)           # --tune --sparse: baked dense, tuned, then made sparse
             baked = bake_field(system, **how) if args.mip is None else bake_pyramid(system, levels=args.mip, **how)
         torch.cuda.synchronize()
         bake_ms = 1e3 * (time.perf_counter() - t0)
+        untuned = None
+        if args.tune is not None:
+            untuned = BakedField(baked.rows.clone(), baked.dims, baked.lo, baked.hi, baked.degree, baked.occupancy, baked.threshold) \
+                if dataset is not None else None                            # --compare: the untuned rows beside the tuned ones
+            baked = _tune_command(args, system, baked, path, hp, dev)
         if args.save_baked:
             print("preview: lattice saved to {}".format(baked.save(os.path.join(folder, "baked.npz"))))
         frames, times = {}, []
@@ -1110,6 +1387,7 @@ def main(argv=None):
             white = bool(hp["val.white_bkgd"])
             single = baked if args.mip is None else baked.levels[0]
             mlp_frames, p_baked, p_mlp, p_both, p_mip, p_mip_both = {}, [], [], [], [], []
+            untuned_frames, p_untuned, p_untuned_both = {}, [], []         # --tune: the lattice as it was baked, beside the tuned one
             for idx in range(len(dataset)):
                 rays, gt = dataset[idx]
                 h, w = int(gt.shape[0]), int(gt.shape[1])
@@ -1128,6 +1406,15 @@ def main(argv=None):
                 p_baked.append(_psnr(got, gt[..., :3]))
                 p_mlp.append(_psnr(want, gt[..., :3]))
                 p_both.append(_psnr(got, want))
+                if untuned is not None:
+                    if (h, w) not in untuned_frames:
+                        untuned_frames[(h, w)] = PreviewFrame(untuned, h, w, white, args.step, args.t_min)
+                    before = untuned_frames[(h, w)].render(rays)[0]
+                    p_untuned.append(_psnr(before, gt[..., :3]))
+                    p_untuned_both.append(_psnr(before, want))
+            if untuned is not None:
+                print("preview: tuning moved the mean PSNR over {0} test images: vs photos {1:.3f} -> {2:.3f}, vs MLP {3:.3f} -> {4:.3f}".format(
+                    len(dataset), float(np.mean(p_untuned)), float(np.mean(p_baked)), float(np.mean(p_untuned_both)), float(np.mean(p_both))))
             if args.mip is None:
                 print("preview: mean PSNR over {0} test images: baked vs photos {1:.3f}, MLP vs photos {2:.3f}, baked vs MLP {3:.3f}".format(
                     len(dataset), float(np.mean(p_baked)), float(np.mean(p_mlp)), float(np.mean(p_both))))
