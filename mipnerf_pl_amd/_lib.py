@@ -235,6 +235,18 @@ PREVIEW_TUNE_SIGNATURES = {
     "mipnerf_preview_tune_adam": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _F, _P]),
 }
 
+# include/mipnerf_preview_360.h: the preview of the unbounded-scene model, a lattice over the contracted space marched along world rays, in
+# a seventh library; the four preview libraries keep their ABI versions and their entry points
+PREVIEW_360_LIB_PATH = os.environ.get("MIPNERF_PREVIEW_360_LIB", os.path.join(HERE, "csrc", "libmipnerf_preview_360.so"))
+PREVIEW_360_ABI = 1
+PREVIEW_360_SIGNATURES = {
+    "mipnerf_preview_360_abi_version": (C.c_int, []),
+    "mipnerf_preview_360_last_error": (C.c_char_p, []),
+    "mipnerf_preview_360_march": (C.c_int, [C.POINTER(PreviewField), _F, C.POINTER(PreviewParams), _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mipnerf_preview_360_march_sparse": (C.c_int, [C.POINTER(PreviewSparseField), _F, C.POINTER(PreviewParams), _I64, _P, _P, _P, _P, _P, _P,
+                                                   _P, _P, _P]),
+}
+
 _handles = {}
 
 
@@ -285,6 +297,16 @@ def lib():
 def diag_lib():
     """libmipnerf_diag.so or None when it was not built (callers report the diagnostics as absent)."""
     return _load(DIAG_LIB_PATH, DIAG_SIGNATURES)
+
+
+def preview_360_lib():
+    """Load (once) libmipnerf_preview_360.so.  No fallback: a missing library is an error."""
+    return _load(PREVIEW_360_LIB_PATH, PREVIEW_360_SIGNATURES, "the contracted-lattice renderer has no fallback.",
+                 ("mipnerf_preview_360_abi_version", PREVIEW_360_ABI))
+
+
+def preview_360_check(rc: int, what: str = "") -> None:
+    _check(rc, lambda: preview_360_lib().mipnerf_preview_360_last_error(), what)
 
 
 def preview_lib():

@@ -1,7 +1,8 @@
 """Build libmipnerf_hip.so (the drop-in library), libmipnerf_diag.so (measurement tooling), libmipnerf_preview.so (the baked-lattice
 preview renderer), libmipnerf_preview_mip.so (the same renderer over a pyramid of lattices), libmipnerf_preview_sparse.so (the same
 renderer over lattices that store only the rows next to an occupied cell) and libmipnerf_preview_tune.so (the gradient of that renderer
-with respect to the lattice and an Adam step on it) for gfx950 in-tree (hipcc cross-compiles without a GPU).
+with respect to the lattice and an Adam step on it) and libmipnerf_preview_360.so (the renderer of the unbounded-scene model: a lattice over
+the contracted space) for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
     python -m mipnerf_pl_amd.build [--force]
 
@@ -108,6 +109,11 @@ PREVIEW_SPARSE_UNITS = [("kernels_preview_sparse.hip", ["-ffp-contract=off"]),  
 PREVIEW_TUNE_LIB = os.path.join(CSRC, "libmipnerf_preview_tune.so")
 PREVIEW_TUNE_UNITS = [("kernels_preview_tune.hip", ["-ffp-contract=off"]),   # sweep A is the march of kernels_preview.hip, bit for bit
                       ("preview_tune_capi.hip", ["-ffp-contract=off"])]       # the world step step_scale * min(h) is formed on the host
+# the preview of the unbounded-scene model, a lattice over the contracted space (include/mipnerf_preview_360.h): a seventh library, so the
+# four preview libraries keep their entry points
+PREVIEW_360_LIB = os.path.join(CSRC, "libmipnerf_preview_360.so")
+PREVIEW_360_UNITS = [("kernels_preview_360.hip", ["-ffp-contract=off"]),   # the warp, the contraction and the row blend round as stated in preview_march_360.hpp
+                     ("preview_360_capi.hip", ["-ffp-contract=off"])]       # the contracted step step_scale * min(h) is formed on the host
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall",
           "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result"]
 
@@ -170,18 +176,19 @@ def build(force: bool = False, verbose: bool = True) -> str:
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_preview_mip.h"))
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_preview_sparse.h"))
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_preview_tune.h"))
+    deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_preview_360.h"))
     stamp = os.path.join(CSRC, ".build_stamp_" + os.path.basename(LIB))
     units = UNITS[:-1] + variant_units() + UNITS[-1:]          # capi.hip last
-    dig = _digest(deps, COMMON + sum((f for _, f in units + PREVIEW_UNITS + PREVIEW_MIP_UNITS + PREVIEW_SPARSE_UNITS + PREVIEW_TUNE_UNITS), []))
+    dig = _digest(deps, COMMON + sum((f for _, f in units + PREVIEW_UNITS + PREVIEW_MIP_UNITS + PREVIEW_SPARSE_UNITS + PREVIEW_TUNE_UNITS + PREVIEW_360_UNITS), []))
     if not force and os.path.exists(LIB) and os.path.exists(DIAG_LIB) and os.path.exists(PREVIEW_LIB) and os.path.exists(PREVIEW_MIP_LIB) and \
-            os.path.exists(PREVIEW_SPARSE_LIB) and os.path.exists(PREVIEW_TUNE_LIB) and os.path.exists(stamp) and open(stamp).read() == dig:
+            os.path.exists(PREVIEW_SPARSE_LIB) and os.path.exists(PREVIEW_TUNE_LIB) and os.path.exists(PREVIEW_360_LIB) and os.path.exists(stamp) and open(stamp).read() == dig:
         if verbose:
             print(f"[build] {LIB} is up to date")
         return LIB
     cc = hipcc()
     objs = []
     procs = []
-    for src, extra in units + DIAG_UNITS + PREVIEW_UNITS + PREVIEW_MIP_UNITS + PREVIEW_SPARSE_UNITS + PREVIEW_TUNE_UNITS:
+    for src, extra in units + DIAG_UNITS + PREVIEW_UNITS + PREVIEW_MIP_UNITS + PREVIEW_SPARSE_UNITS + PREVIEW_TUNE_UNITS + PREVIEW_360_UNITS:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
         cmd = [cc] + COMMON + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
@@ -198,6 +205,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
             print(f"[build] FAILED: {src}")
     if failed:
         raise RuntimeError("hipcc failed")
+    p360_objs = objs[len(objs) - len(PREVIEW_360_UNITS):]
+    objs = objs[:len(objs) - len(PREVIEW_360_UNITS)]
     tune_objs = objs[len(objs) - len(PREVIEW_TUNE_UNITS):]
     objs = objs[:len(objs) - len(PREVIEW_TUNE_UNITS)]
     sparse_objs = objs[len(objs) - len(PREVIEW_SPARSE_UNITS):]
@@ -220,7 +229,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     subprocess.check_call(["gcc", "-shared", "-fPIC", "-o", os.path.join(stub_dir, "libamdhip64.so"), stub_c])
     rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
     # The dynamic symbol table is the C ABI and nothing else: a linker version script keeps `mipnerf_*` (the entry points
-    # include/mipnerf_hip.h / mipnerf_diag.h / mipnerf_preview.h / mipnerf_preview_mip.h / mipnerf_preview_sparse.h / mipnerf_preview_tune.h declare) and makes every C++ launcher, kernel handle and table blob local.
+    # include/mipnerf_hip.h / mipnerf_diag.h / mipnerf_preview.h / mipnerf_preview_mip.h / mipnerf_preview_sparse.h / mipnerf_preview_tune.h / mipnerf_preview_360.h declare) and makes every C++ launcher, kernel handle and table blob local.
     vers = os.path.join(stub_dir, "exports.map")
     with open(vers, "w") as f:
         f.write("{ global: mipnerf_*; local: *; };\n")
@@ -247,6 +256,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
         print("[build]", " ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)
     cmd = ["g++", "-shared", "-fPIC", "-o", PREVIEW_TUNE_LIB] + tune_objs + cmd[cmd.index("-Wl,--version-script=" + vers):]
+    if verbose:
+        print("[build]", " ".join(cmd))
+    subprocess.check_call(cmd, cwd=CSRC)
+    cmd = ["g++", "-shared", "-fPIC", "-o", PREVIEW_360_LIB] + p360_objs + cmd[cmd.index("-Wl,--version-script=" + vers):]
     if verbose:
         print("[build]", " ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)

@@ -22,6 +22,8 @@ The PlenOctrees / Plenoxels idea in its simplest dense form (include/mipnerf_pre
         [--threshold 0.01] [--dilate 1] [--step 0.5] [--t_min 1e-3] [--precision fp32|bf16] [--n_poses 120] [--scale 1]
         [--save_baked] [--baked FILE] [--data DIR --compare] [--mip [L]] [--footprint F] [--sparse]
         [--tune STEPS [--tune_batch 65536] [--tune_lr_sigma 0.2] [--tune_lr_colour 0.01] [--tune_target photos|mlp] [--tune_seed 0]]
+    python -m mipnerf_pl_amd.preview --ckpt CKPT --data DIR --out_dir OUT --space contracted [--far_radius R] [--bound B] [--split test]
+        [--n_views 30] [--factor F] [--sparse] [--compare] [--save_baked] [--baked FILE]      (a llff / realdata360 checkpoint: the unbounded-scene model)
 
 renders the spherical path of `render_video` to OUT/preview_spheric/<exp_name>/ and prints one `preview:` line.
 
@@ -29,7 +31,9 @@ THE BAKED PICTURE IS NOT THE MLP'S PICTURE: colour is a low-order expansion in t
 and colour are blended trilinearly between lattice points, and without `--mip` the march takes point samples of one lattice (no cones:
 that preview is not anti-aliased).  With `--mip` the coarser lattices, baked at their own lattice Gaussians, are the field pre-filtered
 at their spacing, and the cone radius chooses between them.  `--data DIR --compare` measures how far below the MLP either scores.
-Bounded two-level models only.
+Two-level models only.  Without `--space` the model must be bounded; `--space contracted` bakes the unbounded-scene model into a lattice
+over its contracted space and marches it along straight world rays (include/mipnerf_preview_360.h): `bake_field(..., space='contracted',
+far_radius=R)`, the interpolated path of `render_video`, frames in OUT/preview_path/<exp_name>/1/.
 """
 from __future__ import annotations
 
@@ -124,12 +128,50 @@ def _box3(v):
     return tuple(float(np.float32(x)) for x in (v if hasattr(v, "__len__") else (v,) * 3))
 
 
+def _check_space(space, far_radius, who):
+    """(space, far_radius) of a lattice: (None, None) in world coordinates, ('contracted', R) with a finite R > 1 otherwise."""
+    if space not in (None, "contracted"):
+        raise ValueError(f"{who}: space must be None or 'contracted', got {space!r}")
+    if space is None:
+        if far_radius is not None:
+            raise ValueError(f"{who}: far_radius belongs to space='contracted' (a lattice in world coordinates is cut by its box)")
+        return None, None
+    if far_radius is None or not (float(far_radius) > 1.0 and np.isfinite(float(far_radius))):
+        raise ValueError(f"{who}: a contracted lattice needs far_radius, finite and > 1 (got {far_radius!r})")
+    return space, float(np.float32(far_radius))
+
+
+def _space_arrays(baked):
+    """The two .npz keys a contracted lattice adds (a lattice in world coordinates keeps its key set)."""
+    if baked.space is None:
+        return {}
+    return dict(space=np.array(baked.space), far_radius=np.float32(baked.far_radius))
+
+
+def _stored_space(z):
+    """(space, far_radius) of saved arrays."""
+    if "space" not in z:
+        return None, None
+    return str(z["space"]), float(z["far_radius"])
+
+
+def refuse_contracted(baked, who):
+    """What is not implemented for a lattice of the contracted space (a pyramid of them, their gradient, tuning them)."""
+    fields = baked.levels if isinstance(baked, BakedPyramid) else [baked]
+    if any(getattr(b, "space", None) is not None for b in fields):
+        raise NotImplementedError(f"{who}: a contracted lattice (space='contracted', the unbounded-scene model) is not supported here: "
+                                  "a contracted pyramid, contracted tuning and its gradient are not implemented")
+
+
 class BakedField:
     """A baked lattice: `rows` fp16 [nz, ny, nx, W] (W = 4 / 16 / 32 for degree 0 / 1 / 2; row[0] = sigma, row[1 + 3k + c] = coefficient k
     of channel c), `dims` = (nx, ny, nz), the box `lo` .. `hi` in (x, y, z) order, `degree`, `occupancy` (an `ops.Occupancy` over the
-    same lattice, or None: every cell is marched) and the density `threshold` its bits were built with."""
+    same lattice, or None: every cell is marched) and the density `threshold` its bits were built with.  `space`: None -- the box lies in
+    world coordinates (the bounded model) -- or 'contracted' -- in the contracted coordinates of the unbounded-scene model, with
+    `far_radius` the world radius its rays are cut at (include/mipnerf_preview_360.h); `march` dispatches on it."""
 
-    def __init__(self, rows, dims, lo, hi, degree, occupancy=None, threshold=None):
+    def __init__(self, rows, dims, lo, hi, degree, occupancy=None, threshold=None, space=None, far_radius=None):
+        self.space, self.far_radius = _check_space(space, far_radius, "BakedField")
         self.degree = _check_degree(degree, "BakedField")
         self.dims = check_lattice(dims, "BakedField")
         self.lo, self.hi = _box3(lo), _box3(hi)
@@ -170,7 +212,14 @@ class BakedField:
         if occ is not None:
             arrays["occupancy"] = occ.bits.cpu().numpy().view(np.uint32)
             arrays["dilate"] = np.int32(-1 if occ.dilate is None else occ.dilate)
+        arrays.update(_space_arrays(self))
         return arrays
+
+    @staticmethod
+    def stored_space(path):
+        """The space of a saved lattice or pyramid (None or 'contracted'), without reading its rows."""
+        with np.load(path) as z:
+            return str(z["space"]) if "space" in z.files else None
 
     @staticmethod
     def stored_degree(path) -> int:
@@ -194,7 +243,8 @@ class BakedField:
         thr = float(z["threshold"])
         occ = None
         if "occupancy" in z:
-            occ = Occupancy(torch.from_numpy(z["occupancy"].view(np.int32)).to(device).view(torch.uint32), dims, lo, hi)
+            occ = Occupancy(torch.from_numpy(z["occupancy"].view(np.int32)).to(device).view(torch.uint32), dims, lo, hi,
+                            space=_stored_space(z)[0])
             occ.threshold, occ.dilate = (None if np.isnan(thr) else thr), (None if int(z["dilate"]) < 0 else int(z["dilate"]))
         return occ, (None if np.isnan(thr) else thr)
 
@@ -203,7 +253,7 @@ class BakedField:
         dims, lo, hi = tuple(int(v) for v in z["dims"]), z["lo"], z["hi"]
         rows = torch.from_numpy(z["rows"]).to(device)
         occ, thr = cls._stored_occupancy(z, dims, lo, hi, device)
-        return cls(rows, dims, lo, hi, int(z["degree"]), occ, thr)
+        return cls(rows, dims, lo, hi, int(z["degree"]), occ, thr, *_stored_space(z))
 
     def to_sparse(self, stored=None):
         """The same lattice as a `SparseField`: mipnerf_preview_sparse_index on the occupancy words (or on the words of `stored`, an
@@ -214,7 +264,7 @@ class BakedField:
             raise ValueError("BakedField.to_sparse: a lattice without an occupancy grid marches every cell, so every row is read: it stays dense")
         table, m = index_table(self.occupancy if stored is None else stored)
         return SparseField(gather_rows(self.rows, table, m, self.degree), table, self.dims, self.lo, self.hi, self.degree, self.occupancy,
-                           self.threshold, stored=stored, _table_is_ours=True)
+                           self.threshold, stored=stored, _table_is_ours=True, space=self.space, far_radius=self.far_radius)
 
 
 def table_words(nx) -> int:
@@ -353,7 +403,9 @@ class SparseField:
     occupied cells; a level of a pyramid holds more (`pyramid_storage`).  The march reads `occupancy`; `stored` only says what the table
     was built from.  The table must be the one of `stored`'s bits: a constructor given a table recomputes it and refuses another."""
 
-    def __init__(self, rows, table, dims, lo, hi, degree, occupancy, threshold=None, stored=None, _table_is_ours=False):
+    def __init__(self, rows, table, dims, lo, hi, degree, occupancy, threshold=None, stored=None, _table_is_ours=False, space=None,
+                 far_radius=None):
+        self.space, self.far_radius = _check_space(space, far_radius, "SparseField")      # as in `BakedField`
         self.degree = _check_degree(degree, "SparseField")
         self.dims = check_lattice(dims, "SparseField")
         self.lo, self.hi = _box3(lo), _box3(hi)
@@ -427,7 +479,8 @@ class SparseField:
         nx, ny, nz = self.dims
         dense = torch.zeros(nz * ny * nx, ROW_HALVES[self.degree], dtype=torch.float16, device=self.rows.device)
         dense[self.stored_points().reshape(-1)] = self.rows
-        return BakedField(dense.view(nz, ny, nx, -1), self.dims, self.lo, self.hi, self.degree, self.occupancy, self.threshold)
+        return BakedField(dense.view(nz, ny, nx, -1), self.dims, self.lo, self.hi, self.degree, self.occupancy, self.threshold, self.space,
+                          self.far_radius)
 
     def save(self, path):
         """Everything in one .npz with keys of its own (`sparse_rows` and `table` where a dense lattice has `rows`)."""
@@ -443,6 +496,7 @@ class SparseField:
                       occupancy=occ.bits.cpu().numpy().view(np.uint32), dilate=np.int32(-1 if occ.dilate is None else occ.dilate))
         if self.stored is not None:
             arrays["stored"] = self.stored.bits.cpu().numpy().view(np.uint32)
+        arrays.update(_space_arrays(self))
         return arrays
 
     @classmethod
@@ -461,9 +515,11 @@ class SparseField:
         occ, thr = BakedField._stored_occupancy(z, dims, lo, hi, device)
         stored = None
         if "stored" in z:
-            stored = Occupancy(torch.from_numpy(z["stored"].view(np.int32)).to(device).view(torch.uint32), dims, lo, hi)
+            stored = Occupancy(torch.from_numpy(z["stored"].view(np.int32)).to(device).view(torch.uint32), dims, lo, hi,
+                               space=_stored_space(z)[0])
+        space, far_radius = _stored_space(z)
         return cls(torch.from_numpy(z["sparse_rows"]).to(device), torch.from_numpy(z["table"].view(np.int32)).to(device), dims, lo, hi,
-                   int(z["degree"]), occ, thr, stored=stored)
+                   int(z["degree"]), occ, thr, stored=stored, space=space, far_radius=far_radius)
 
 
 def lattice_spacing(dims, lo, hi) -> float:
@@ -485,6 +541,9 @@ class BakedPyramid:
             raise ValueError("BakedPyramid: the levels are all dense (BakedField) or all sparse (SparseField), not a mix: one kernel "
                              "instantiation marches them all")
         first = levels[0]
+        if any(b.space is not None for b in levels):
+            raise NotImplementedError("BakedPyramid: a contracted lattice (space='contracted') cannot be a level: a contracted pyramid is "
+                                      "not implemented")
         for i, b in enumerate(levels[1:], 1):
             if np.asarray(b.lo, np.float32).tobytes() != np.asarray(first.lo, np.float32).tobytes() or \
                     np.asarray(b.hi, np.float32).tobytes() != np.asarray(first.hi, np.float32).tobytes():
@@ -570,10 +629,16 @@ class BakedPyramid:
                         for i in range(int(z["levels"]))])
 
 
-def refuse_model(model_or_system, who):
-    """The bake covers the bounded two-level model; anything else is refused with the reason."""
+def refuse_model(model_or_system, who, space=None):
+    """The bake covers the bounded two-level model, and with space='contracted' the unbounded-scene two-level model; anything else is
+    refused with the reason."""
     m = getattr(model_or_system, "mip_nerf", model_or_system)
-    if bool(getattr(m, "unbounded", False)):
+    if space not in (None, "contracted"):
+        raise ValueError(f"{who}: space must be None or 'contracted', got {space!r}")
+    if space == "contracted" and not bool(getattr(m, "unbounded", False)):
+        raise ValueError(f"{who}: space='contracted' bakes the unbounded-scene model (unbounded=True); this model is bounded: its lattice "
+                         "lies in world coordinates (drop space=)")
+    if space is None and bool(getattr(m, "unbounded", False)):
         raise NotImplementedError(f"{who}: unbounded=True models are not supported (their field lives in a contracted space; a contracted "
                                   "lattice is not implemented)")
     if int(getattr(m, "num_levels", 2)) != 2:
@@ -640,7 +705,7 @@ def pack_rows(sigma, coef, degree, mask=None, out=None):
 
 
 def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=0.01, dilate=1, n_dirs=DEFAULT_N_DIRS, cov_scale=1.0,
-               precision=None, chunk=None, sparse=False, _grids=None, _stored=None):
+               precision=None, chunk=None, sparse=False, space=None, far_radius=None, _grids=None, _stored=None):
     """Bake the field of a bounded two-level model into a `BakedField` of `grid`^3 (or (nx, ny, nz)) points over lo .. hi; with
     `sparse=True` into a `SparseField`, the bytes of `bake_field(...).to_sparse()`, without ever allocating dense rows or dense
     coefficients: after sigma and the bits come the table (mipnerf_preview_sparse_index) and the stored points in slot order, and every
@@ -651,11 +716,20 @@ def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=
     sigma = `ops.density_grid`; bits = `ops.occupancy_grid(sigma, threshold, dilate)`; a point is baked iff any of the up to 8 cells around
     it is occupied; at the baked points `ops.field_at` runs once per direction of `bake_directions(n_dirs)` on the lattice Gaussian
     (variance cov_scale h^2 / 12), `chunk` points at a time (default 2^20), then `fit_sh` and mipnerf_preview_pack.  The MLP is reached
-    through those public ops only.  `precision`: 'fp32' / 'bf16' (default: the model's)."""
+    through those public ops only.  `precision`: 'fp32' / 'bf16' (default: the model's).
+
+    `space='contracted'` (with `far_radius`, finite and > 1) bakes the unbounded-scene model: the lattice spans lo .. hi of the CONTRACTED
+    space (default [-2, 2]^3, all of it), sigma = `ops.density_grid(space='contracted', far_radius=far_radius)`, and `ops.field_at(space=
+    'contracted')` runs on the lattice Gaussians (variance cov_scale h^2 / 12 in contracted coordinates) with world view directions.
+    The result carries `space` and `far_radius`, and `march` sends it through mipnerf_preview_360_march."""
     from . import ops
-    refuse_model(model_or_system, "bake_field")
+    refuse_model(model_or_system, "bake_field", space)
+    space, far_radius = _check_space(space, far_radius, "bake_field")
     degree = _check_degree(degree, "bake_field")
     dims = check_lattice(grid, "bake_field")
+    if space is not None:
+        lo, hi = -2.0 if lo is None else lo, 2.0 if hi is None else hi
+    where = {} if space is None else dict(space=space, far_radius=far_radius)
     if lo is None or hi is None:
         raise ValueError("bake_field: give the box lo .. hi the lattice spans (the rays to be rendered are marched inside it only)")
     if (degree + 1) ** 2 > n_dirs:
@@ -668,8 +742,9 @@ def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=
     nb = (degree + 1) ** 2
     with torch.no_grad():
         if _grids is None:
-            sigma = ops.density_grid(model_or_system, dims, lo, hi, cov_scale=cov_scale, precision=precision)
+            sigma = ops.density_grid(model_or_system, dims, lo, hi, cov_scale=cov_scale, precision=precision, **where)
             occ = ops.occupancy_grid(sigma, threshold, lo, hi, dilate=dilate)
+            occ.space = space
         else:
             sigma, occ = _grids
         dev = sigma.device
@@ -681,7 +756,7 @@ def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=
             means, var = lattice_gaussians(dims, lo, hi, cov_scale, idx)
             rgb = torch.empty(idx.numel(), n_dirs, 3, dtype=torch.float32, device=dev)
             for k in range(n_dirs):
-                rgb[:, k] = ops.field_at(model_or_system, means, var, dirs32[k].expand(idx.numel(), 3), precision=precision)[:, :3]
+                rgb[:, k] = ops.field_at(model_or_system, means, var, dirs32[k].expand(idx.numel(), 3), precision=precision, space=space)[:, :3]
             return fit_sh(rgb, dirs, degree)
 
         if sparse:
@@ -701,7 +776,7 @@ def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=
                     if bool(keep.any()):
                         coef[keep] = coefficients(idx[keep])
                 sparse_pack(sigma.reshape(-1)[idx], coef, degree, rows[c0:c0 + chunk])
-            return SparseField(rows, table, dims, lo, hi, degree, occ, threshold, stored=_stored, _table_is_ours=True)
+            return SparseField(rows, table, dims, lo, hi, degree, occ, threshold, stored=_stored, _table_is_ours=True, **where)
         rows = torch.empty(nz, ny, nx, ROW_HALVES[degree], dtype=torch.float16, device=dev)
         # dense coefficients only for a slab of z layers at a time (at least 2: the library's smallest lattice)
         layers = min(nz, max(2, (1 << 24) // (nx * ny)))
@@ -716,7 +791,7 @@ def bake_field(model_or_system, grid=256, degree=1, lo=None, hi=None, threshold=
                 idx = index[c0:c0 + chunk]
                 coef.view(-1, nb, 3)[idx - z0 * ny * nx] = coefficients(idx)
             pack_rows(sigma[z0:z1], coef, degree, mask=mask[z0:z1], out=rows[z0:z1])
-    return BakedField(rows, dims, lo, hi, degree, occ, threshold)
+    return BakedField(rows, dims, lo, hi, degree, occ, threshold, **where)
 
 
 def pyramid_dims(grid, levels, lo, hi):
@@ -744,6 +819,9 @@ def bake_pyramid(model_or_system, grid=256, levels=DEFAULT_MIP_LEVELS, degree=1,
     its compact rows."""
     if not 1 <= int(levels) <= MAX_MIP_LEVELS:
         raise ValueError(f"bake_pyramid: a pyramid has 1 .. {MAX_MIP_LEVELS} levels (got {levels})")
+    if kwargs.get("space") is not None:
+        raise NotImplementedError(f"bake_pyramid: space={kwargs['space']!r}: a contracted pyramid is not implemented (bake_field bakes a "
+                                  "single contracted lattice)")
     if kwargs.get("sparse", False):
         from . import ops
         refuse_model(model_or_system, "bake_field")
@@ -816,9 +894,20 @@ def march(baked, origins, directions, near, far, background, step_scale=DEFAULT_
           out=None, steps=None, use_occupancy=True):
     """mipnerf_preview_march on flat fp32 device tensors: origins / directions [B, 3], near / far [B] -> (rgb [B, 3], acc [B], distance
     [B]) (`out`: these three, preallocated).  `steps`: an int32 [B] tensor that receives the samples evaluated per ray.  A `SparseField`
-    goes through mipnerf_preview_sparse_march as a pyramid of one level, with no radii and footprint 0: the same bytes."""
+    goes through mipnerf_preview_sparse_march as a pyramid of one level, with no radii and footprint 0: the same bytes.  A lattice of the
+    contracted space (`baked.space == 'contracted'`, dense or sparse) goes through mipnerf_preview_360_march[_sparse]: `step_scale` then
+    scales a step of the CONTRACTED space and the rays are cut by the ball of `baked.far_radius`, not by the box."""
     B, dev, (rgb, acc, dist), (field,), params = _march_args("march", [baked], dict(origins=origins, directions=directions, near=near, far=far),
                                                              background, step_scale, t_min, max_steps, out, steps, use_occupancy)
+    if baked.space is not None:
+        lib, sparse = L.preview_360_lib(), isinstance(baked, SparseField)
+        arg = L.PreviewSparseField(field, baked.table.data_ptr(), baked.n_rows) if sparse else field
+        with torch.cuda.device(dev):
+            L.preview_360_check((lib.mipnerf_preview_360_march_sparse if sparse else lib.mipnerf_preview_360_march)(
+                C.byref(arg), baked.far_radius, C.byref(params), B, origins.data_ptr(), directions.data_ptr(), near.data_ptr(), far.data_ptr(),
+                rgb.data_ptr(), acc.data_ptr(), dist.data_ptr(), None if steps is None else steps.data_ptr(),
+                torch.cuda.current_stream().cuda_stream), "preview_360_march_sparse" if sparse else "preview_360_march")
+        return rgb, acc, dist
     if isinstance(baked, SparseField):
         return _march_sparse("preview_sparse_march", [baked], [field], params, 0.0, B, dev, origins, directions, None, near, far,
                              (rgb, acc, dist), steps, None)
@@ -841,6 +930,7 @@ DEFAULT_TUNE_BATCH = 65536
 
 
 def _refuse_tuning(baked, who):
+    refuse_contracted(baked, who)
     if isinstance(baked, SparseField):
         raise NotImplementedError(f"{who}: a SparseField is not a tuning target (the gradient is scattered into dense rows): tune the dense "
                                   "BakedField, then .to_sparse()")
@@ -1034,6 +1124,7 @@ def march_pyramid(pyramid, origins, directions, radii, near, far, background, fo
     """mipnerf_preview_mip_march (mipnerf_preview_sparse_march for a pyramid of `SparseField`s) on flat fp32 device tensors: origins / directions [B, 3], radii / near / far [B] -> (rgb [B, 3], acc [B],
     distance [B]) (`out`: these three, preallocated).  `steps`: an int32 [B] tensor that receives the samples evaluated per ray; `lod`: an
     fp32 [B] tensor that receives each ray's weighted mean level.  The step is `step_scale` times the spacing of level 0."""
+    refuse_contracted(pyramid, "march_pyramid")
     B, dev, (rgb, acc, dist), structs, params = _march_args(
         "march_pyramid", pyramid.levels, dict(origins=origins, directions=directions, radii=radii, near=near, far=far), background, step_scale,
         t_min, max_steps, out, steps, use_occupancy)
@@ -1159,6 +1250,18 @@ def build_parser():
     p.add_argument("--tune_target", help="--tune: what the lattice is tuned against (default: photos with --data, else mlp)",
                    choices=["photos", "mlp"], default=None)
     p.add_argument("--tune_seed", help="--tune: seed of the batch draws (default 0)", type=int, default=None)
+    p.add_argument("--space", help="'contracted': bake a llff / realdata360 checkpoint (the unbounded-scene model) into a lattice over the "
+                   "contracted space and render the interpolated path through the poses of --data (required) to "
+                   "<out_dir>/preview_path/<exp_name>/1/; --grid, --sh_degree, --sparse, --compare, --save_baked and --baked work as for a "
+                   "bounded checkpoint, --bound is the half-width of the lattice in the contracted space (default 2, all of it)",
+                   choices=["contracted"], default=None)
+    p.add_argument("--far_radius", help="--space contracted: rays are cut, and the density is 0, beyond this distance from the centre (default: "
+                   "the largest distance any ray of the frames to be rendered reaches, plus one cell's allowance)", type=float, default=None,
+                   metavar="R")
+    p.add_argument("--split", help="--space contracted: the split whose poses the path runs through (default test)", choices=["train", "test"],
+                   default=None)
+    p.add_argument("--n_views", help="--space contracted: three times the poses per pair of consecutive poses (default 30)", type=int, default=None)
+    p.add_argument("--factor", help="--space contracted: the data set's shrink factor (default: the checkpoint's)", type=int, default=None)
     return p
 
 
@@ -1189,6 +1292,40 @@ def refuse_tune_arguments(args):
             raise SystemExit(f"--{f} {v}: must be finite and >= 0")
 
 
+def refuse_space_arguments(args):
+    """What --space and its flags refuse from the command line alone."""
+    if args.space is None:
+        for flag in ("far_radius", "split", "n_views", "factor"):
+            if getattr(args, flag) is not None:
+                raise SystemExit(f"--{flag} belongs to --space contracted: give --space as well")
+        return
+    args.split = "test" if args.split is None else args.split
+    args.n_views = 30 if args.n_views is None else args.n_views
+    if args.mip is not None:
+        raise SystemExit("--space contracted with --mip: a contracted pyramid is not implemented: drop --mip")
+    if args.tune is not None:
+        raise SystemExit("--space contracted with --tune: tuning a contracted lattice is not implemented: drop --tune")
+    if args.far_radius is not None and not (args.far_radius > 1 and np.isfinite(args.far_radius)):
+        raise SystemExit(f"--far_radius {args.far_radius}: must be finite and > 1")
+    if args.bound is not None and args.bound > 2:
+        raise SystemExit(f"--bound {args.bound}: the contracted space ends at 2")
+    if args.n_views < 1:
+        raise SystemExit(f"--n_views {args.n_views}: at least one")
+    if args.data is None:
+        raise SystemExit("--space contracted renders the interpolated path through the poses of a data set: give --data")
+
+
+def refuse_baked_space(args):
+    """--baked of a contracted lattice without --space contracted, or of a bounded one with it: refused after reading the file's keys."""
+    if args.baked is None:
+        return
+    stored = BakedField.stored_space(args.baked)
+    if stored != args.space:
+        raise SystemExit("--baked {0} holds a lattice of {1}, {2}".format(
+            args.baked, "world coordinates (a bounded scene)" if stored is None else f"the {stored} space",
+            "--space contracted asks for a contracted one: drop --space" if stored is None else f"give --space {stored} to render it"))
+
+
 def refuse_arguments(args):
     """Everything that can be refused from the command line alone, before any file is opened."""
     if len(args.grid) not in (1, 3):
@@ -1217,6 +1354,7 @@ def refuse_arguments(args):
     if args.footprint is not None and not (args.footprint >= 0 and np.isfinite(args.footprint)):
         raise SystemExit(f"--footprint {args.footprint}: must be finite and >= 0")
     refuse_tune_arguments(args)
+    refuse_space_arguments(args)
     if args.ckpt is None:
         raise SystemExit("give --ckpt: the checkpoint names the experiment (and is what --compare renders with the MLP)")
     return dims
@@ -1255,15 +1393,22 @@ def refuse_baked_kind(args):
         raise SystemExit(f"--baked {args.baked} holds dense rows, --sparse asks for sparse ones: drop --sparse")
 
 
-def refuse_checkpoint(system):
-    """Captured-scene and unbounded checkpoints, and one-level models: refused before anything is moved to the device."""
+def refuse_checkpoint(system, space=None):
+    """Captured-scene and unbounded checkpoints (unless `space='contracted'` names their lattice), bounded ones with it, and one-level
+    models: refused before anything is moved to the device."""
     from .render_video import is_scene360
-    if is_scene360(system.hparams) or bool(getattr(system.mip_nerf, "unbounded", False)):
+    unbounded = bool(getattr(system.mip_nerf, "unbounded", False))
+    if space is None and (is_scene360(system.hparams) or unbounded):
         raise SystemExit("preview: this checkpoint holds a captured scene ({}); the baked lattice is implemented for bounded (Blender) "
-                         "checkpoints only -- its rays leave any box and the unbounded-scene model lives in a contracted space".format(
+                         "checkpoints only -- its rays leave any box and the unbounded-scene model lives in a contracted space.  Give "
+                         "--space contracted (with --data) to bake the unbounded-scene model into a lattice over that space".format(
                              system.hparams.get("dataset_name")))
+    if space is not None and not (is_scene360(system.hparams) and unbounded):
+        raise SystemExit("preview: --space {0} bakes the unbounded-scene model of a llff / realdata360 checkpoint; this checkpoint ({1}) "
+                         "holds a bounded model, whose lattice lies in world coordinates: drop --space".format(
+                             space, system.hparams.get("dataset_name")))
     try:
-        refuse_model(system, "preview")
+        refuse_model(system, "preview", space)
     except NotImplementedError as e:
         raise SystemExit(str(e))
 
@@ -1300,6 +1445,85 @@ def _tune_command(args, system, baked, path, hp, dev):
     return baked.to_sparse() if args.sparse else baked
 
 
+def _contracted_command(args, argv, system, dims, dev):
+    """--space contracted: the interpolated path of `render_video` through the poses of --data, every frame from a lattice over the
+    contracted space; prints the `preview:` line and, with --compare, the PSNR line of the test split.  Returns the output folder."""
+    from .datasets import PathGen, RealData360
+    from .evaluate import FrameEvaluator, cull_far_radius, generate_video, save_images
+    from .render_video import flag_given
+    hp = system.hparams
+    factor = args.factor if args.factor is not None else int(hp.get("factor", 4))
+    white = bool(args.white_bkgd) if flag_given(argv, "--white_bkgd") else bool(hp["val.white_bkgd"])
+
+    def split(name):
+        return RealData360(args.data, split=name, white_bkgd=hp["val.white_bkgd"], batch_type="all_images" if name == "train" else "single_image",
+                           factor=factor, device=dev)
+    poses = split(args.split)
+    path = PathGen(poses, args.n_views, device=dev)
+    dataset = (poses if args.split == "test" else split("test")) if args.compare else None
+    folder = os.path.join(args.out_dir, "preview_path", hp["exp_name"])
+    os.makedirs(os.path.join(folder, "1"), exist_ok=True)
+    with torch.no_grad():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if args.baked is not None:
+            baked = (SparseField if args.sparse else BakedField).load(args.baked, dev)
+            if args.far_radius is not None and float(np.float32(args.far_radius)) != baked.far_radius:
+                raise SystemExit(f"--baked {args.baked} was baked with far radius {baked.far_radius:g}, --far_radius asks for {args.far_radius:g}: "
+                                 "drop one of them")
+        else:
+            radius = args.far_radius
+            if radius is None:
+                if min(dims) < 4:
+                    raise SystemExit("--grid: the default far radius needs at least 4 points per axis; give --far_radius")
+                frames = [path[i] for i in range(len(path))] + ([dataset[i][0] for i in range(len(dataset))] if dataset is not None else [])
+                radius = cull_far_radius(frames, min(dims))
+            bound = 2.0 if args.bound is None else float(args.bound)
+            baked = bake_field(system, grid=dims, degree=1 if args.sh_degree is None else args.sh_degree, lo=-bound, hi=bound,
+                               threshold=args.threshold, dilate=args.dilate, n_dirs=args.n_dirs, precision=args.precision, sparse=args.sparse,
+                               space=args.space, far_radius=radius)
+        torch.cuda.synchronize()
+        bake_ms = 1e3 * (time.perf_counter() - t0)
+        if args.save_baked:
+            print("preview: lattice saved to {}".format(baked.save(os.path.join(folder, "baked.npz"))))
+        frames, times, samples, rays_seen = {}, [], 0, 0
+        for idx in range(len(path)):
+            h, w = path.sizes[idx]
+            fr = frames.get((h, w))
+            if fr is None:
+                fr = frames[(h, w)] = PreviewFrame(baked, h, w, white, args.step, args.t_min)
+            rays = path[idx]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fr.render(rays)
+            torch.cuda.synchronize()
+            times.append(1e3 * (time.perf_counter() - t0))
+            samples, rays_seen = samples + int(fr.steps.sum()), rays_seen + h * w
+            save_images(*fr.images(*out), os.path.join(folder, "1"), idx)
+        generate_video(folder)
+        tail = ", stored share {0:.4f}, sparse {1:.1f} MiB against {2:.1f} MiB dense".format(
+            baked.stored_share(), baked.nbytes / 2 ** 20, baked.dense_nbytes / 2 ** 20) if args.sparse else ""
+        print("preview: lattice {0} x {1} x {2}, degree {3}, baked share {4:.4f}, {5:.1f} MiB, {6} {7:.1f} ms, mean {8:.3f} ms per frame "
+              "({9} frames), contracted, far radius {10:.4g}, mean {11:.1f} evaluated samples per ray".format(
+                  *baked.dims, baked.degree, baked.baked_share(), baked.nbytes / 2 ** 20, "loaded in" if args.baked is not None else "baked in",
+                  bake_ms, float(np.mean(times)), len(times), baked.far_radius, samples / max(rays_seen, 1)) + tail)
+        if dataset is not None:
+            both, p_baked, p_mlp, p_both = {}, [], [], []
+            for idx in range(len(dataset)):
+                rays, gt = dataset[idx]
+                h, w = int(gt.shape[0]), int(gt.shape[1])
+                if (h, w) not in both:
+                    both[(h, w)] = (FrameEvaluator(system.mip_nerf, h, w, args.chunk_size, white, dev), PreviewFrame(baked, h, w, white, args.step, args.t_min))
+                ev, fr = both[(h, w)]
+                want, got = ev.render(rays)[0], fr.render(rays)[0]
+                p_baked.append(_psnr(got, gt[..., :3]))
+                p_mlp.append(_psnr(want, gt[..., :3]))
+                p_both.append(_psnr(got, want))
+            print("preview: mean PSNR over {0} test images: baked vs photos {1:.3f}, MLP vs photos {2:.3f}, baked vs MLP {3:.3f}".format(
+                len(dataset), float(np.mean(p_baked)), float(np.mean(p_mlp)), float(np.mean(p_both))))
+    return folder
+
+
 def main(argv=None):
     from .evaluate import FrameEvaluator, cull_box, generate_video, save_images
     from .render_video import load_system
@@ -1308,11 +1532,14 @@ def main(argv=None):
     refuse_baked_degree(args)
     refuse_baked_levels(args)
     refuse_baked_kind(args)
+    refuse_baked_space(args)
     footprint = DEFAULT_FOOTPRINT if args.footprint is None else args.footprint
     system = load_system(args)
-    refuse_checkpoint(system)
+    refuse_checkpoint(system, args.space)
     dev = torch.device("cuda", torch.cuda.current_device())
     system = system.to(dev).eval()
+    if args.space is not None:
+        return _contracted_command(args, argv, system, dims, dev)
     hp = system.hparams
     exp_name = hp["exp_name"]
     from .datasets import RenderGen, dataset_dict
