@@ -247,6 +247,16 @@ PREVIEW_360_SIGNATURES = {
                                                    _P, _P, _P]),
 }
 
+# include/mipnerf_preview_reg.h: the gradient of a total-variation term and of an SH decay on the tuned lattice's fp32 master rows, in an
+# eighth library; the five preview libraries keep their ABI versions and their entry points
+PREVIEW_REG_LIB_PATH = os.environ.get("MIPNERF_PREVIEW_REG_LIB", os.path.join(HERE, "csrc", "libmipnerf_preview_reg.so"))
+PREVIEW_REG_ABI = 1
+PREVIEW_REG_SIGNATURES = {
+    "mipnerf_preview_reg_abi_version": (C.c_int, []),
+    "mipnerf_preview_reg_last_error": (C.c_char_p, []),
+    "mipnerf_preview_reg_grad": (C.c_int, [C.POINTER(_I32), _I32, C.POINTER(_F), _P, _P, _P, _F, _F, _F, _F, _P]),
+}
+
 _handles = {}
 
 
@@ -334,6 +344,16 @@ def preview_tune_lib():
 
 def preview_tune_check(rc: int, what: str = "") -> None:
     _check(rc, lambda: preview_tune_lib().mipnerf_preview_tune_last_error(), what)
+
+
+def preview_reg_lib():
+    """Load (once) libmipnerf_preview_reg.so.  No fallback: a missing library is an error."""
+    return _load(PREVIEW_REG_LIB_PATH, PREVIEW_REG_SIGNATURES, "regularising the tuning of the baked lattice has no fallback.",
+                 ("mipnerf_preview_reg_abi_version", PREVIEW_REG_ABI))
+
+
+def preview_reg_check(rc: int, what: str = "") -> None:
+    _check(rc, lambda: preview_reg_lib().mipnerf_preview_reg_last_error(), what)
 
 
 def preview_sparse_check(rc: int, what: str = "") -> None:

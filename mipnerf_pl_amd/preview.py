@@ -13,6 +13,8 @@ The PlenOctrees / Plenoxels idea in its simplest dense form (include/mipnerf_pre
     march_grad / TuneState / tune_field    mipnerf_preview_tune_grad + mipnerf_preview_tune_adam (include/mipnerf_preview_tune.h): the
                                 gradient of `march` with respect to the rows and Adam steps on them against photos or the MLP's renders;
                                 a single dense `BakedField` only, and the float-atomic sums are not bitwise reproducible
+    tune_regularise             mipnerf_preview_reg_grad (include/mipnerf_preview_reg.h): the gradient of a total-variation term and of
+                                an SH decay on the master rows, added between the two by `TuneState(tv_sigma=, tv_colour=, sh_decay=)`
 
     bake_pyramid(system)        `bake_field` at grid, then at about half the points per axis, ...: a `BakedPyramid`
     march_pyramid / render_rays of a pyramid    mipnerf_preview_mip_march (include/mipnerf_preview_mip.h): every sample reads the level (or
@@ -21,7 +23,8 @@ The PlenOctrees / Plenoxels idea in its simplest dense form (include/mipnerf_pre
     python -m mipnerf_pl_amd.preview --ckpt CKPT --out_dir OUT [--grid 256 | --grid NX NY NZ] [--sh_degree 0|1|2] [--bound B]
         [--threshold 0.01] [--dilate 1] [--step 0.5] [--t_min 1e-3] [--precision fp32|bf16] [--n_poses 120] [--scale 1]
         [--save_baked] [--baked FILE] [--data DIR --compare] [--mip [L]] [--footprint F] [--sparse]
-        [--tune STEPS [--tune_batch 65536] [--tune_lr_sigma 0.2] [--tune_lr_colour 0.01] [--tune_target photos|mlp] [--tune_seed 0]]
+        [--tune STEPS [--tune_batch 65536] [--tune_lr_sigma 0.2] [--tune_lr_colour 0.01] [--tune_target photos|mlp] [--tune_seed 0]
+                      [--tune_tv_sigma 0] [--tune_tv_colour 0] [--tune_sh_decay 0] [--tune_tv_eps 1e-4]]
     python -m mipnerf_pl_amd.preview --ckpt CKPT --data DIR --out_dir OUT --space contracted [--far_radius R] [--bound B] [--split test]
         [--n_views 30] [--factor F] [--sparse] [--compare] [--save_baked] [--baked FILE]      (a llff / realdata360 checkpoint: the unbounded-scene model)
 
@@ -927,6 +930,9 @@ DEFAULT_TUNE_LR_COLOUR = 0.01
 DEFAULT_TUNE_BETAS = (0.9, 0.999)
 DEFAULT_TUNE_EPS = 1e-8
 DEFAULT_TUNE_BATCH = 65536
+# A choice as well: the total variation's eps keeps the norm differentiable where a row equals its neighbours; 1e-4 is (1e-2)^2, small
+# against squared differences of densities (tens) and of coefficients (tenths).  The three weights default to 0: the regulariser is off.
+DEFAULT_TUNE_TV_EPS = 1e-4
 
 
 def _refuse_tuning(baked, who):
@@ -997,16 +1003,58 @@ def tune_adam(master, m, v, grad, rows, degree, mask, lr_sigma, lr_colour, beta1
             torch.cuda.current_stream().cuda_stream), "preview_tune_adam")
 
 
+def lattice_axis_scale(dims, lo, hi):
+    """r_a = hmin / h_a of a lattice in fp32, h_a = (hi_a - lo_a) / float(n_a - 1) as the libraries form the spacings: 1 on a cubic lattice"""
+    h = (np.asarray(hi, np.float32) - np.asarray(lo, np.float32)) / (np.asarray(dims) - 1).astype(np.float32)
+    return (h.min() / h).astype(np.float32)
+
+
+def tune_regularise(master, mask, dims, lo, hi, degree, grad, tv_sigma, tv_colour, sh_decay, tv_eps, n_points=None):
+    """mipnerf_preview_reg_grad: ADD the gradient of `tv_sigma` x the total variation of the density, `tv_colour` x that of the colour
+    coefficients and 0.5 `sh_decay` x the squared coefficients of k >= 1 into `grad`, each divided by `n_points`; master and grad fp32
+    [nz, ny, nx, W], `mask` one uint8 per point or None.  `n_points` is the number of masked points, counted ONCE by the caller (this call
+    does not synchronise); None stands for every point of the lattice and is refused with a mask.  A gather: two calls give the same bytes."""
+    degree = _check_degree(degree, "tune_regularise")
+    dims = check_lattice(dims, "tune_regularise")
+    shape = (dims[2], dims[1], dims[0], ROW_HALVES[degree])
+    for name, t in (("master", master), ("grad", grad)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != master.device:
+            raise ValueError(f"tune_regularise: {name} must be a contiguous fp32 tensor of {shape} on the master rows' device")
+    n = dims[0] * dims[1] * dims[2]
+    if mask is not None and (mask.dtype != torch.uint8 or mask.numel() != n or not mask.is_contiguous() or mask.device != master.device):
+        raise ValueError("tune_regularise: one contiguous uint8 mask byte per point")
+    if n_points is None:
+        if mask is not None:
+            raise ValueError("tune_regularise: with a mask, n_points (the number of masked points, counted once) must be given")
+        n_points = n
+    weights = [float(w) for w in (tv_sigma, tv_colour, sh_decay)]
+    if not all(w >= 0 and np.isfinite(w) for w in weights) or not (tv_eps > 0 and np.isfinite(tv_eps)) or int(n_points) < 1:
+        raise ValueError("tune_regularise: the weights must be finite and >= 0, tv_eps finite and > 0, n_points at least 1")
+    scale = lattice_axis_scale(dims, lo, hi)
+    with torch.cuda.device(master.device):
+        L.preview_reg_check(L.preview_reg_lib().mipnerf_preview_reg_grad(
+            (C.c_int32 * 3)(*dims), degree, (C.c_float * 3)(*[float(x) for x in scale]), master.data_ptr(),
+            None if mask is None else mask.data_ptr(), grad.data_ptr(), *[w / int(n_points) for w in weights], float(tv_eps),
+            torch.cuda.current_stream().cuda_stream), "preview_reg_grad")
+    return grad
+
+
 class TuneState:
     """What tuning a `BakedField` keeps beside it: fp32 master rows made from the fp16 rows, Adam's `m` and `v`, the gradient buffer and
     the point mask (`baked_points` of the occupancy: only points next to an occupied cell ever receive a gradient; None without an
-    occupancy).  `step` updates `baked.rows` in place; the occupancy never changes.  The two learning rates are choices, not measurements."""
+    occupancy).  `step` updates `baked.rows` in place; the occupancy never changes.  The two learning rates are choices, not measurements.
+    `tv_sigma`, `tv_colour`, `sh_decay` (default 0: off) weigh the regulariser of `tune_regularise`, per masked point; `tv_eps` is a choice."""
 
     def __init__(self, baked, lr_sigma=DEFAULT_TUNE_LR_SIGMA, lr_colour=DEFAULT_TUNE_LR_COLOUR, betas=DEFAULT_TUNE_BETAS, eps=DEFAULT_TUNE_EPS,
-                 step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS):
+                 step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS, tv_sigma=0.0, tv_colour=0.0, sh_decay=0.0,
+                 tv_eps=DEFAULT_TUNE_TV_EPS):
         _refuse_tuning(baked, "TuneState")
         if not (lr_sigma >= 0 and lr_colour >= 0 and 0 <= betas[0] < 1 and 0 <= betas[1] < 1 and eps >= 0):
             raise ValueError("TuneState: learning rates and eps must not be negative, the betas must lie in [0, 1)")
+        if not all(w >= 0 and np.isfinite(w) for w in (tv_sigma, tv_colour, sh_decay)) or not (tv_eps > 0 and np.isfinite(tv_eps)):
+            raise ValueError("TuneState: tv_sigma, tv_colour and sh_decay must be finite and >= 0, tv_eps finite and > 0")
+        self.tv_sigma, self.tv_colour, self.sh_decay, self.tv_eps = float(tv_sigma), float(tv_colour), float(sh_decay), float(tv_eps)
+        self._n_points = None        # the masked points, counted (one synchronisation) by the first regularised step
         self.baked = baked
         self.lr_sigma, self.lr_colour, self.betas, self.eps = float(lr_sigma), float(lr_colour), (float(betas[0]), float(betas[1])), float(eps)
         self.step_scale, self.t_min, self.max_steps = float(step_scale), float(t_min), int(max_steps)
@@ -1027,14 +1075,29 @@ class TuneState:
                                counters=self.counters)
         loss = ((rgb - target) ** 2).mean()
         self.steps += 1
+        if self.regularised:
+            tune_regularise(self.master, self.mask, self.baked.dims, self.baked.lo, self.baked.hi, self.baked.degree, self.grad, self.tv_sigma,
+                            self.tv_colour, self.sh_decay, self.tv_eps, self.n_points)
         b1, b2 = self.betas
         tune_adam(self.master, self.m, self.v, self.grad, self.baked.rows, self.baked.degree, self.mask, self.lr_sigma, self.lr_colour, b1, b2,
                   self.eps, 1.0 / (1.0 - b1 ** self.steps), 1.0 / (1.0 - b2 ** self.steps))
         return loss
 
+    @property
+    def regularised(self) -> bool:
+        return self.tv_sigma != 0.0 or self.tv_colour != 0.0 or self.sh_decay != 0.0
+
+    @property
+    def n_points(self) -> int:
+        """the points the regulariser's weights are divided by: the masked ones (all without a mask), counted once"""
+        if self._n_points is None:
+            self._n_points = int(self.master[..., 0].numel() if self.mask is None else self.mask.sum())
+        return self._n_points
+
     def state_dict(self):
         return dict(master=self.master, m=self.m, v=self.v, steps=self.steps, lr_sigma=self.lr_sigma, lr_colour=self.lr_colour,
-                    betas=self.betas, eps=self.eps)
+                    betas=self.betas, eps=self.eps, tv_sigma=self.tv_sigma, tv_colour=self.tv_colour, sh_decay=self.sh_decay,
+                    tv_eps=self.tv_eps)
 
     def load_state_dict(self, state):
         for k in ("master", "m", "v"):
@@ -1044,6 +1107,9 @@ class TuneState:
         self.steps = int(state["steps"])
         self.lr_sigma, self.lr_colour, self.eps = float(state["lr_sigma"]), float(state["lr_colour"]), float(state["eps"])
         self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+        for k in ("tv_sigma", "tv_colour", "sh_decay", "tv_eps"):      # a dict saved without them says nothing about them: they stay
+            if k in state:
+                setattr(self, k, float(state[k]))
         self.grad.zero_()
         self.baked.rows.copy_(pack_master(self.master, self.baked.degree))
 
@@ -1250,6 +1316,15 @@ def build_parser():
     p.add_argument("--tune_target", help="--tune: what the lattice is tuned against (default: photos with --data, else mlp)",
                    choices=["photos", "mlp"], default=None)
     p.add_argument("--tune_seed", help="--tune: seed of the batch draws (default 0)", type=int, default=None)
+    p.add_argument("--tune_tv_sigma", help="--tune: weight of the total variation of the density, per tuned point (default 0: off; a choice, "
+                   "not a measurement: Adam rescales the gradient, so a weight counts only against the photometric gradient; on the one "
+                   "scene of DESIGN 4.20, 1e-3 .. 1e-2 kept most of what held-out poses otherwise lose and 1e-1 cost more than it gave)", type=float, default=None, metavar="X")
+    p.add_argument("--tune_tv_colour", help="--tune: weight of the total variation of the colour coefficients, per tuned point (default 0: off; "
+                   "a choice, not a measurement)", type=float, default=None, metavar="X")
+    p.add_argument("--tune_sh_decay", help="--tune: weight of 0.5 x the squared view-dependent coefficients (k >= 1), per tuned point (default "
+                   "0: off; a choice, not a measurement)", type=float, default=None, metavar="X")
+    p.add_argument("--tune_tv_eps", help=f"--tune: the eps under the total variation's root (a choice, not a measurement: default "
+                   f"{DEFAULT_TUNE_TV_EPS})", type=float, default=None, metavar="X")
     p.add_argument("--space", help="'contracted': bake a llff / realdata360 checkpoint (the unbounded-scene model) into a lattice over the "
                    "contracted space and render the interpolated path through the poses of --data (required) to "
                    "<out_dir>/preview_path/<exp_name>/1/; --grid, --sh_degree, --sparse, --compare, --save_baked and --baked work as for a "
@@ -1265,7 +1340,8 @@ def build_parser():
     return p
 
 
-TUNE_FLAGS = ("tune_batch", "tune_lr_sigma", "tune_lr_colour", "tune_target", "tune_seed")
+TUNE_FLAGS = ("tune_batch", "tune_lr_sigma", "tune_lr_colour", "tune_target", "tune_seed", "tune_tv_sigma", "tune_tv_colour", "tune_sh_decay",
+              "tune_tv_eps")
 
 
 def refuse_tune_arguments(args):
@@ -1286,10 +1362,12 @@ def refuse_tune_arguments(args):
         raise SystemExit("--tune_target photos tunes against the train split of a data set: give --data")
     if args.tune_batch is not None and args.tune_batch < 1:
         raise SystemExit(f"--tune_batch {args.tune_batch}: at least one ray")
-    for f in ("tune_lr_sigma", "tune_lr_colour"):
+    for f in ("tune_lr_sigma", "tune_lr_colour", "tune_tv_sigma", "tune_tv_colour", "tune_sh_decay"):
         v = getattr(args, f)
         if v is not None and not (v >= 0 and np.isfinite(v)):
             raise SystemExit(f"--{f} {v}: must be finite and >= 0")
+    if args.tune_tv_eps is not None and not (args.tune_tv_eps > 0 and np.isfinite(args.tune_tv_eps)):
+        raise SystemExit(f"--tune_tv_eps {args.tune_tv_eps}: must be finite and > 0")
 
 
 def refuse_space_arguments(args):
@@ -1434,14 +1512,19 @@ def _tune_command(args, system, baked, path, hp, dev):
         mlp_batches(system.mip_nerf, source, batch, seed, white, args.chunk_size)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    _, losses = tune_field(baked, batches, args.tune, white,
-                           lr_sigma=DEFAULT_TUNE_LR_SIGMA if args.tune_lr_sigma is None else args.tune_lr_sigma,
-                           lr_colour=DEFAULT_TUNE_LR_COLOUR if args.tune_lr_colour is None else args.tune_lr_colour,
-                           step_scale=args.step, t_min=args.t_min)
+    reg = {k: v for k, v in (("tv_sigma", args.tune_tv_sigma), ("tv_colour", args.tune_tv_colour), ("sh_decay", args.tune_sh_decay),
+                             ("tv_eps", args.tune_tv_eps)) if v is not None}
+    state, losses = tune_field(baked, batches, args.tune, white,
+                               lr_sigma=DEFAULT_TUNE_LR_SIGMA if args.tune_lr_sigma is None else args.tune_lr_sigma,
+                               lr_colour=DEFAULT_TUNE_LR_COLOUR if args.tune_lr_colour is None else args.tune_lr_colour,
+                               step_scale=args.step, t_min=args.t_min, **reg)
     torch.cuda.synchronize()
     secs = time.perf_counter() - t0
     print("preview: tuned {0} steps of {1} rays against the {2} in {3:.2f} s ({4:.2f} ms per step), batch loss {5:.3e} -> {6:.3e}".format(
         args.tune, batch, "photos" if against == "photos" else "MLP", secs, 1e3 * secs / args.tune, float(losses[0]), float(losses[-1])))
+    if state.regularised:
+        print("preview: regularised with tv_sigma {0:g}, tv_colour {1:g}, sh_decay {2:g} (tv_eps {3:g}), each divided by the {4} tuned "
+              "points".format(state.tv_sigma, state.tv_colour, state.sh_decay, state.tv_eps, state.n_points))
     return baked.to_sparse() if args.sparse else baked
 
 
