@@ -55,7 +55,9 @@ k_cast_ipe_bwd(int64_t B, int N, int min_deg, int ndeg, int disable_integration,
             const float yv = disable_integration ? 0.0f : g.cov[a] * (scale * scale);
             const double e = exp(-0.5 * (double)yv);
             const double gs = ge[l * 3 + a], gc = ge[3 * ndeg + l * 3 + a];        // sin half, "cos" half
-            const double ys = y, yc = y + kHalfPiF;
+            // the phase of the "cos" half in double: the forward's fl32(y + fl32(pi/2)) is off by up to half an ulp of y, 0.1 rad at
+            // y = 3e6, which is nothing to a feature but rotates its derivative (tests/ipe_jacobian.py)
+            const double ys = y, yc = (double)y + (double)kHalfPiF;
             const double ss = sin(ys), cs = cos(ys), sc = sin(yc), cc = cos(yc);
             dmean[a] += (double)scale * e * (gs * cs + gc * cc);
             dcov[a] += -0.5 * (double)scale * (double)scale * e * (gs * ss + gc * sc);
