@@ -257,6 +257,17 @@ PREVIEW_REG_SIGNATURES = {
     "mipnerf_preview_reg_grad": (C.c_int, [C.POINTER(_I32), _I32, C.POINTER(_F), _P, _P, _P, _F, _F, _F, _F, _P]),
 }
 
+# include/mipnerf_preview_tune_360.h: the gradient of the contracted lattice's march with respect to the rows, in a ninth library; the
+# other eight keep their ABI versions and their entry points
+PREVIEW_TUNE_360_LIB_PATH = os.environ.get("MIPNERF_PREVIEW_TUNE_360_LIB", os.path.join(HERE, "csrc", "libmipnerf_preview_tune_360.so"))
+PREVIEW_TUNE_360_ABI = 1
+PREVIEW_TUNE_360_SIGNATURES = {
+    "mipnerf_preview_tune_360_abi_version": (C.c_int, []),
+    "mipnerf_preview_tune_360_last_error": (C.c_char_p, []),
+    "mipnerf_preview_tune_360_grad": (C.c_int, [C.POINTER(PreviewField), _F, C.POINTER(PreviewParams), _I64, _P, _P, _P, _P, _P, _P, _F, _P,
+                                                _P, _P, _P, _P, _P]),
+}
+
 _handles = {}
 
 
@@ -344,6 +355,16 @@ def preview_tune_lib():
 
 def preview_tune_check(rc: int, what: str = "") -> None:
     _check(rc, lambda: preview_tune_lib().mipnerf_preview_tune_last_error(), what)
+
+
+def preview_tune_360_lib():
+    """Load (once) libmipnerf_preview_tune_360.so.  No fallback: a missing library is an error."""
+    return _load(PREVIEW_TUNE_360_LIB_PATH, PREVIEW_TUNE_360_SIGNATURES, "tuning a contracted lattice has no fallback.",
+                 ("mipnerf_preview_tune_360_abi_version", PREVIEW_TUNE_360_ABI))
+
+
+def preview_tune_360_check(rc: int, what: str = "") -> None:
+    _check(rc, lambda: preview_tune_360_lib().mipnerf_preview_tune_360_last_error(), what)
 
 
 def preview_reg_lib():

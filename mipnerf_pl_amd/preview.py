@@ -163,7 +163,9 @@ def refuse_contracted(baked, who):
     fields = baked.levels if isinstance(baked, BakedPyramid) else [baked]
     if any(getattr(b, "space", None) is not None for b in fields):
         raise NotImplementedError(f"{who}: a contracted lattice (space='contracted', the unbounded-scene model) is not supported here: "
-                                  "a contracted pyramid, contracted tuning and its gradient are not implemented")
+                                  "a contracted pyramid is not implemented; the gradient and the tuning of a contracted lattice live in "
+                                  "mipnerf_pl_amd.preview_tune360 (march_grad, TuneState360, tune_field; the command "
+                                  "`python -m mipnerf_pl_amd.preview_tune360`)")
 
 
 class BakedField:
@@ -1048,7 +1050,7 @@ class TuneState:
     def __init__(self, baked, lr_sigma=DEFAULT_TUNE_LR_SIGMA, lr_colour=DEFAULT_TUNE_LR_COLOUR, betas=DEFAULT_TUNE_BETAS, eps=DEFAULT_TUNE_EPS,
                  step_scale=DEFAULT_STEP_SCALE, t_min=DEFAULT_T_MIN, max_steps=DEFAULT_MAX_STEPS, tv_sigma=0.0, tv_colour=0.0, sh_decay=0.0,
                  tv_eps=DEFAULT_TUNE_TV_EPS):
-        _refuse_tuning(baked, "TuneState")
+        self._refuse(baked)
         if not (lr_sigma >= 0 and lr_colour >= 0 and 0 <= betas[0] < 1 and 0 <= betas[1] < 1 and eps >= 0):
             raise ValueError("TuneState: learning rates and eps must not be negative, the betas must lie in [0, 1)")
         if not all(w >= 0 and np.isfinite(w) for w in (tv_sigma, tv_colour, sh_decay)) or not (tv_eps > 0 and np.isfinite(tv_eps)):
@@ -1064,15 +1066,23 @@ class TuneState:
         self.steps = 0
         self.counters = None         # an int64 [2] tensor here makes every step count its samples and flushes
 
+    # the two things that depend on the space the lattice lives in (preview_tune360.TuneState360 overrides them): which lattices are
+    # refused, and the call that marches a batch and adds its gradient into self.grad
+    def _refuse(self, baked):
+        _refuse_tuning(baked, "TuneState")
+
+    def _march_grad(self, *args, **kwargs):
+        return march_grad(*args, **kwargs)
+
     def step(self, rays, target, white_bkgd):
         """One step on a batch: `rays` (a `Rays` of [..., k] tensors), `target` [..., 3] -> the batch's mean squared error BEFORE the step,
         a 0-d device tensor.  mipnerf_preview_tune_grad in target mode with loss_scale = 2 / (3 B), then mipnerf_preview_tune_adam."""
         n = int(np.prod(rays.origins.shape[:-1]))
         o, d, near, far = (t.reshape(n, t.shape[-1]).float().contiguous() for t in (rays.origins, rays.directions, rays.near, rays.far))
         target = target.reshape(n, 3).float().contiguous()
-        _, rgb, _ = march_grad(self.baked, o, d, near.reshape(n), far.reshape(n), white_bkgd, target=target, loss_scale=2.0 / (3.0 * n),
-                               grad_rows=self.grad, step_scale=self.step_scale, t_min=self.t_min, max_steps=self.max_steps,
-                               counters=self.counters)
+        _, rgb, _ = self._march_grad(self.baked, o, d, near.reshape(n), far.reshape(n), white_bkgd, target=target, loss_scale=2.0 / (3.0 * n),
+                                     grad_rows=self.grad, step_scale=self.step_scale, t_min=self.t_min, max_steps=self.max_steps,
+                                     counters=self.counters)
         loss = ((rgb - target) ** 2).mean()
         self.steps += 1
         if self.regularised:
@@ -1382,7 +1392,8 @@ def refuse_space_arguments(args):
     if args.mip is not None:
         raise SystemExit("--space contracted with --mip: a contracted pyramid is not implemented: drop --mip")
     if args.tune is not None:
-        raise SystemExit("--space contracted with --tune: tuning a contracted lattice is not implemented: drop --tune")
+        raise SystemExit("--space contracted with --tune: this command does not tune a contracted lattice: drop --tune, tune with "
+                         "`python -m mipnerf_pl_amd.preview_tune360` and render its file with --space contracted --baked")
     if args.far_radius is not None and not (args.far_radius > 1 and np.isfinite(args.far_radius)):
         raise SystemExit(f"--far_radius {args.far_radius}: must be finite and > 1")
     if args.bound is not None and args.bound > 2:
