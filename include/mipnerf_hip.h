@@ -713,6 +713,23 @@ int mipnerf_train_step(mipnerf_ctx* ctx, int64_t num_rays, const mipnerf_rays* r
                        size_t workspace_bytes, float* grad_flat, int32_t accumulate, float* out_scalars,
                        const mipnerf_level_out* out, void* stream);
 
+/* ---- the fused per-ray launches as stage entry points (ABI 6 grows; nothing above changes) ----
+ * What mipnerf_forward (option 4) and mipnerf_train_step run behind the MLP of a level, on the caller's rays: one launch each, the same
+ * per-ray device functions as the stand-alone entry points, so the same bits.  Inputs and the four compositing outputs as
+ * mipnerf_volumetric_rendering (all four required).  mipnerf_composite_resample then draws t_new [B, N+1] as
+ * mipnerf_resample_along_rays does from those weights, inverting over `bins` [B, N+1] (t_samples itself for a bounded scene) with
+ * u_rand [B, N+1] or NULL.  mipnerf_composite_train also writes ray_loss [B] and d_w [B, N] = g_const * d ray_loss / d w as
+ * mipnerf_distloss does with g_ray[b] = g_const; t_new = NULL is a last level (no resampling: u_rand, resample_padding and bins are not
+ * read), bins = NULL inverts over t_samples.  num_samples > MIPNERF_MAX_SAMPLES is MIPNERF_E_INVALID before anything is launched. */
+int mipnerf_composite_resample(int64_t num_rays, int32_t num_samples, const float* rgb_sigma, const float* t_samples,
+                               const float* directions, int32_t white_bkgd, float* comp_rgb, float* distance, float* acc,
+                               float* weights, const float* bins, const float* u_rand, float resample_padding, float* t_new,
+                               void* stream);
+int mipnerf_composite_train(int64_t num_rays, int32_t num_samples, const float* rgb_sigma, const float* t_samples,
+                            const float* directions, int32_t white_bkgd, float* comp_rgb, float* distance, float* acc,
+                            float* weights, float* ray_loss, float g_const, float* d_w, const float* u_rand, float resample_padding,
+                            float* t_new /* NULL: last level */, const float* bins /* NULL: t_samples */, void* stream);
+
 /* ---- instrumentation ------------------------------------------------------------------ */
 /* Times `iters` launches of the bf16 MLP kernel with hipEvents on `stream`; returns the
  * average milliseconds per launch in *ms (used by bench.py for roofline.achieved). */

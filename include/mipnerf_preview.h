@@ -1,5 +1,5 @@
 /* mipnerf_preview.h -- C ABI of libmipnerf_preview.so: a trained field BAKED into a dense lattice of fp16 rows (density + spherical-
- * harmonic colour) and ray-marched without the MLP.  Not part of the drop-in library (include/mipnerf_hip.h keeps its 91 entry points).
+ * harmonic colour) and ray-marched without the MLP.  Not part of the drop-in library (include/mipnerf_hip.h keeps its 93 entry points).
  *
  * Built next to libmipnerf_hip.so by `python -m mipnerf_pl_amd.build` from csrc/kernels_preview.hip + csrc/preview_capi.hip;
  * csrc/preview_march.hpp states the per-sample rules once, for the device and for a host compiler, and takes the cell index and the

@@ -1,6 +1,6 @@
 /* mipnerf_preview_mip.h -- C ABI of libmipnerf_preview_mip.so: the baked preview marched through a PYRAMID of lattices, the level of every
  * sample chosen by the width of the ray's cone there, so the preview is anti-aliased.  A fourth library: libmipnerf_preview.so
- * (include/mipnerf_preview.h) keeps its 4 entry points and the drop-in library (include/mipnerf_hip.h) its 91.
+ * (include/mipnerf_preview.h) keeps its 4 entry points and the drop-in library (include/mipnerf_hip.h) its 93.
  *
  * Built by `python -m mipnerf_pl_amd.build` from csrc/kernels_preview_mip.hip + csrc/preview_mip_capi.hip; csrc/preview_mip.hpp states
  * the level rule and the mix of two rows once, for the device and for a host compiler, and takes everything else from

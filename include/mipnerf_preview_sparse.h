@@ -1,6 +1,6 @@
 /* mipnerf_preview_sparse.h -- C ABI of libmipnerf_preview_sparse.so: the baked preview over lattices that STORE ONLY THE ROWS THE MARCH
  * READS.  A fifth library: libmipnerf_preview.so (include/mipnerf_preview.h) keeps its 4 entry points, libmipnerf_preview_mip.so
- * (include/mipnerf_preview_mip.h) its 3 and the drop-in library (include/mipnerf_hip.h) its 91.
+ * (include/mipnerf_preview_mip.h) its 3 and the drop-in library (include/mipnerf_hip.h) its 93.
  *
  * Built by `python -m mipnerf_pl_amd.build` from csrc/kernels_preview_sparse.hip + csrc/preview_sparse_capi.hip; csrc/preview_sparse.hpp
  * states the storage rule once, for the device and for a host compiler, and takes everything else from csrc/preview_march.hpp and

@@ -1,6 +1,6 @@
 /* mipnerf_preview_tune.h -- C ABI of libmipnerf_preview_tune.so: FINE-TUNING THE BAKED LATTICE THROUGH ITS OWN RENDERER.  A sixth library:
  * libmipnerf_preview.so (include/mipnerf_preview.h) keeps its 4 entry points, libmipnerf_preview_mip.so (include/mipnerf_preview_mip.h) its
- * 3, libmipnerf_preview_sparse.so (include/mipnerf_preview_sparse.h) its 7 and the drop-in library (include/mipnerf_hip.h) its 91.
+ * 3, libmipnerf_preview_sparse.so (include/mipnerf_preview_sparse.h) its 7 and the drop-in library (include/mipnerf_hip.h) its 93.
  *
  * Built by `python -m mipnerf_pl_amd.build` from csrc/kernels_preview_tune.hip + csrc/preview_tune_capi.hip; csrc/preview_tune.hpp states
  * rules 8 - 10 and the Adam rule once, for the device and for a host compiler, and takes rules 1 - 5 from csrc/preview_march.hpp by call.

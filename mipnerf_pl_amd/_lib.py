@@ -141,6 +141,8 @@ SIGNATURES = {
     "mipnerf_train_workspace_bytes": (_SZ, [_P, _I64]),
     "mipnerf_train_step": (C.c_int, [_P, _I64, C.POINTER(RaysPtrs), _P, _P, _P, _P, C.c_uint32, _F, _F, _I32, _P, _SZ, _P, _I32, _P,
                                      C.POINTER(LevelOut), _P]),
+    "mipnerf_composite_resample": (C.c_int, [_I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
+    "mipnerf_composite_train": (C.c_int, [_I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _F, _P, _P, _F, _P, _P, _P]),
     "mipnerf_time_mlp": (C.c_int, [_P, _I64, _I32, _P, _P, C.c_int, _P, C.c_int, C.POINTER(_F), _P]),
     "mipnerf_selftest": (C.c_int, [_P]),
     "mipnerf_set_option": (C.c_int, [_P, C.c_int, C.c_int]),

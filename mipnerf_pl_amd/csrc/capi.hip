@@ -1348,6 +1348,29 @@ int mipnerf_distloss(int64_t B, int32_t N, const float* weights, const float* t,
     return MIPNERF_OK;
 }
 
+// ---- the fused per-ray launches of mipnerf_forward / mipnerf_train_step as stage entry points: the same launchers, fed by the caller ----
+int mipnerf_composite_resample(int64_t B, int32_t N, const float* rgb_sigma, const float* t, const float* dirs, int32_t white_bkgd,
+                               float* comp_rgb, float* distance, float* acc, float* weights, const float* bins, const float* u_rand,
+                               float resample_padding, float* t_new, void* stream) {
+    if (B < 1 || N < 1 || N > MIPNERF_MAX_SAMPLES || !rgb_sigma || !t || !dirs || !comp_rgb || !distance || !acc || !weights || !bins ||
+        !t_new)
+        return fail(MIPNERF_E_INVALID, "composite_resample: bad argument");
+    HIP_TRY(mip::launch_composite_resample(B, N, rgb_sigma, t, dirs, white_bkgd, comp_rgb, distance, acc, weights, bins, u_rand,
+                                           resample_padding, t_new, S(stream)));
+    return MIPNERF_OK;
+}
+
+int mipnerf_composite_train(int64_t B, int32_t N, const float* rgb_sigma, const float* t, const float* dirs, int32_t white_bkgd,
+                            float* comp_rgb, float* distance, float* acc, float* weights, float* ray_loss, float g_const, float* d_w,
+                            const float* u_rand, float resample_padding, float* t_new, const float* bins, void* stream) {
+    if (B < 1 || N < 1 || N > MIPNERF_MAX_SAMPLES || !rgb_sigma || !t || !dirs || !comp_rgb || !distance || !acc || !weights || !ray_loss ||
+        !d_w)
+        return fail(MIPNERF_E_INVALID, "composite_train: bad argument");
+    HIP_TRY(mip::launch_composite_train(B, N, rgb_sigma, t, dirs, white_bkgd, comp_rgb, distance, acc, weights, ray_loss, g_const, d_w,
+                                        u_rand, resample_padding, t_new, S(stream), bins));
+    return MIPNERF_OK;
+}
+
 // ---- gradient through the resampler (stop_resample_grad=False, mip.py:265-279): the pieces autograd chains ------------------
 int mipnerf_volumetric_rendering_bwd_t(int64_t B, int32_t N, const float* rgb_sigma, const float* t, const float* dirs,
                                        int32_t white_bkgd, const float* g_rgb, const float* g_dist, const float* g_acc,

@@ -232,6 +232,8 @@ def test_one_sample_too_many_is_refused_before_any_launch():
     rp = L.RaysPtrs(*[p] * 7)
     calls = {
         "mipnerf_volumetric_rendering": (B, N, p, p, p, 1, p, p, p, p, None),
+        "mipnerf_composite_resample": (B, N, p, p, p, 1, p, p, p, p, p, p, 0.01, p, None),
+        "mipnerf_composite_train": (B, N, p, p, p, 1, p, p, p, p, p, 0.5, p, p, 0.01, p, p, None),
         "mipnerf_resample_along_rays": (B, N, p, p, p, 0.01, p, None),
         "mipnerf_sorted_piecewise_constant_pdf": (B, N, p, p, N + 1, p, p, None),
         "mipnerf_volumetric_rendering_bwd": (B, N, p, p, p, 1, p, p, p, p, 0.001, p, None),

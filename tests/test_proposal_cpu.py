@@ -128,7 +128,7 @@ def test_entry_points_are_declared_bound_and_exported():
         assert len(proto.split(",")) == len(L.SIGNATURES[name][1]), name
         assert hasattr(lib, name)
     assert len(L.SIGNATURES["mipnerf_lattice_density"][1]) == 12 and len(L.SIGNATURES["mipnerf_forward_proposal"][1]) == 15
-    assert len(L.SIGNATURES) == 91
+    assert len(L.SIGNATURES) == 93
     assert lib.mipnerf_abi_version() == 6
     h = re.sub(r"[\s*]+", " ", hdr)
     for phrase in ["i0 = min(int(floorf(u)), n - 2)", "inv_h = float(n - 1) / (hi - lo)", "A non-finite coordinate gives 0",
@@ -187,7 +187,10 @@ def test_the_unit_is_built_without_contraction_and_is_not_a_per_ray_kernel():
     hdr = open(os.path.join(REPO, "mipnerf_pl_amd", "csrc", "lattice_sample.hpp")).read()
     assert "MIP_HD float lattice_trilinear(" in hdr and " / " not in re.sub(r"//.*", "", hdr)      # no division on the device
     capi = open(os.path.join(REPO, "mipnerf_pl_amd", "csrc", "capi.hip")).read()
-    assert capi.count("mip::launch_composite_resample(") == 1 and "static int forward_levels(" in capi        # one level loop, shared
+    levels = capi[capi.index("static int forward_levels("):capi.index("int mipnerf_forward(")]
+    assert levels.count("mip::launch_composite_resample(") == 1                                               # one level loop, shared
+    stage = capi[capi.index("int mipnerf_composite_resample("):capi.index("int mipnerf_composite_train(")]
+    assert stage.count("mip::launch_composite_resample(") == 1 and capi.count("mip::launch_composite_resample(") == 2   # and the stage entry point
 
 
 # ---- Python surface --------------------------------------------------------------------------------------------------------------
