@@ -395,7 +395,9 @@ int mipnerf_density_grid(mipnerf_ctx* ctx, const int32_t* dims_host, const float
  * and 4 apply as there: same bits either way).  Level 0's outputs are what compositing yields for colour 0 and the lattice's density:
  * comp_rgb = the background times (1 - acc) -- the lattice's silhouette, not a coarse render --, acc, distance, weights and t_samples as
  * usual; level 1 draws its samples from those weights.  The picture is NOT mipnerf_forward's: the fine samples sit elsewhere.  Needs
- * mipnerf_workspace_bytes and no more.  MIPNERF_E_UNSUPPORTED for cfg.unbounded = 1 (a contracted lattice is not implemented) and for
+ * mipnerf_workspace_bytes and no more.  MIPNERF_E_UNSUPPORTED for cfg.unbounded = 1 (that model's proposal pyramid is read by
+ * mipnerf_lattice_density_360 of include/mipnerf_proposal_360.h, a library of its own, and its level loop is composed of the stage entry
+ * points around that call; there is no single entry point for it) and for
  * num_levels != 2; MIPNERF_E_INVALID for the lattice argument errors above.  No density noise.  Graph-capturable like mipnerf_forward. */
 int mipnerf_lattice_density(const int32_t* dims_host, const float* lo_host, const float* hi_host, const float* lattice, int64_t num_rays,
                             int32_t num_samples, const float* t_samples, const float* origins, const float* directions, const float* radii,

@@ -270,6 +270,25 @@ PREVIEW_TUNE_360_SIGNATURES = {
                                                 _P, _P, _P, _P, _P]),
 }
 
+# include/mipnerf_proposal_360.h: the proposal density of the unbounded-scene model from a pyramid of contracted density lattices, in a
+# tenth library; the other nine keep their ABI versions and their entry points
+PROPOSAL_360_LIB_PATH = os.environ.get("MIPNERF_PROPOSAL_360_LIB", os.path.join(HERE, "csrc", "libmipnerf_proposal_360.so"))
+PROPOSAL_360_ABI = 1
+PROPOSAL_MAX_LEVELS = 4
+
+
+class ProposalPyramid(C.Structure):
+    _fields_ = [("levels", _I32), ("dims", (_I32 * 3) * PROPOSAL_MAX_LEVELS), ("lattice", _P * PROPOSAL_MAX_LEVELS), ("lo", _F * 3),
+                ("hi", _F * 3)]
+
+
+PROPOSAL_360_SIGNATURES = {
+    "mipnerf_proposal_360_abi_version": (C.c_int, []),
+    "mipnerf_proposal_360_last_error": (C.c_char_p, []),
+    "mipnerf_lattice_density_360": (C.c_int, [C.POINTER(ProposalPyramid), _F, _I64, _I32, _P, _P, _P, _P, _P, _P]),
+    "mipnerf_reciprocal_360": (C.c_int, [_I64, _P, _P, _P]),
+}
+
 _handles = {}
 
 
@@ -367,6 +386,16 @@ def preview_tune_360_lib():
 
 def preview_tune_360_check(rc: int, what: str = "") -> None:
     _check(rc, lambda: preview_tune_360_lib().mipnerf_preview_tune_360_last_error(), what)
+
+
+def proposal_360_lib():
+    """Load (once) libmipnerf_proposal_360.so.  No fallback: a missing library is an error."""
+    return _load(PROPOSAL_360_LIB_PATH, PROPOSAL_360_SIGNATURES, "the contracted proposal lattice has no fallback.",
+                 ("mipnerf_proposal_360_abi_version", PROPOSAL_360_ABI))
+
+
+def proposal_360_check(rc: int, what: str = "") -> None:
+    _check(rc, lambda: proposal_360_lib().mipnerf_proposal_360_last_error(), what)
 
 
 def preview_reg_lib():

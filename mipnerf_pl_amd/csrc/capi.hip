@@ -2101,7 +2101,7 @@ int mipnerf_forward_proposal(mipnerf_ctx* c, int64_t B, const mipnerf_rays* rays
     prop.lattice = lattice;
     if (!c) return fail(MIPNERF_E_INVALID, "forward_proposal: null argument (ctx)");
     if (c->cfg.unbounded)
-        return fail(MIPNERF_E_UNSUPPORTED, "forward_proposal: the unbounded-scene model lives in a contracted space; a lattice proposal for it is not implemented");
+        return fail(MIPNERF_E_UNSUPPORTED, "forward_proposal: the unbounded-scene model lives in a contracted space; its proposal pyramid is read by mipnerf_lattice_density_360 (mipnerf_proposal_360.h) and the level loop around it is composed of the stage entry points, not by this call");
     if (c->cfg.num_levels != 2)
         return fail(MIPNERF_E_UNSUPPORTED, "forward_proposal: the lattice replaces the coarse level of a two-level model (num_levels = %d)", c->cfg.num_levels);
     if (B >= (1LL << 31)) return fail(MIPNERF_E_INVALID, "forward_proposal: bad ray count %lld", (long long)B);

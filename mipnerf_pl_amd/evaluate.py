@@ -171,23 +171,48 @@ def scene_occupancy(system, frames=None, grid=128, threshold=0.01, dilate=1, bou
     return occ
 
 
-def scene_proposal(system, frames=None, grid=256, bound=None, verbose=True, distorted=None):
+def scene_proposal(system, frames=None, grid=256, bound=None, verbose=True, distorted=None, space=None, far_radius=None, levels=1,
+                   footprint=1.0):
     """`ops.field_proposal` of the system's field on grid^3 points over [-bound, bound]^3 (default: `cull_box` of `frames`, the box that
-    holds every ray segment plus one cell), printing the lattice size and its build time once.  The unbounded-scene model is refused."""
+    holds every ray segment plus one cell), printing the lattice size and its build time once.  The unbounded-scene model is refused
+    unless `space='contracted'`: the result is then `ops.field_proposal_360` -- a pyramid of `levels` contracted lattices, the finest with
+    grid^3 points, over [-bound, bound]^3 of the contracted space (default 2, all of it), with the density 0 beyond |z| = 2 - 1 / far_radius
+    (default: `cull_far_radius` of `frames`) and the level picked with `footprint` -- and a bounded model is refused.  `levels` = 1 and
+    `footprint` = 1 are choices, not measurements."""
     import time
-    if bool(getattr(system.mip_nerf, "unbounded", False)):
-        raise NotImplementedError("lattice proposals: unbounded=True models are not supported (their field lives in a contracted space; a "
-                                  "contracted proposal lattice is not implemented)")
-    if bound is None:
+    unbounded = bool(getattr(system.mip_nerf, "unbounded", False))
+    if space is None:
+        if unbounded:
+            raise NotImplementedError("lattice proposals: unbounded=True models are not supported (their field lives in a contracted space) "
+                                      "unless the lattice lies there too: space='contracted'")
+        if bound is None:
+            if frames is None:
+                raise ValueError("scene_proposal: give the frames to be rendered or a bound")
+            bound = cull_box(frames, grid, distorted)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        prop = ops.field_proposal(system, grid=grid, lo=-float(bound), hi=float(bound))
+        torch.cuda.synchronize()
+        if verbose:
+            print("proposal: {0}^3 density lattice over +-{1:.4f} built in {2:.1f} ms".format(grid, float(bound), 1e3 * (time.perf_counter() - t0)))
+        return prop
+    if space != "contracted":
+        raise ValueError(f"scene_proposal: space must be None or 'contracted' (a world box cannot hold an unbounded ray), got {space!r}")
+    if not unbounded:
+        raise ValueError("scene_proposal: space='contracted' belongs to unbounded=True models; a bounded model's lattice lies in world space")
+    ops.proposal_ladder_360(grid, levels)            # a bad ladder is refused before the frames are walked
+    if far_radius is None:
         if frames is None:
-            raise ValueError("scene_proposal: give the frames to be rendered or a bound")
-        bound = cull_box(frames, grid, distorted)
+            raise ValueError("scene_proposal: give the frames to be rendered or a far_radius")
+        far_radius = cull_far_radius(frames, grid, distorted)
+    bound = 2.0 if bound is None else float(bound)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    prop = ops.field_proposal(system, grid=grid, lo=-float(bound), hi=float(bound))
+    prop = ops.field_proposal_360(system, grid=grid, levels=levels, far_radius=float(far_radius), bound=bound, footprint=footprint)
     torch.cuda.synchronize()
     if verbose:
-        print("proposal: {0}^3 density lattice over +-{1:.4f} built in {2:.1f} ms".format(grid, float(bound), 1e3 * (time.perf_counter() - t0)))
+        print("proposal: {0}^3 x {1} levels contracted density lattice over +-{2:.4f}, far radius {3:.4f}, built in {4:.1f} ms".format(
+            grid, int(levels), bound, float(far_radius), 1e3 * (time.perf_counter() - t0)))
     return prop
 
 

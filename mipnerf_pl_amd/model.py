@@ -680,9 +680,11 @@ class MipNerf(torch.nn.Module):
         (uint8, >= mipnerf_workspace_bytes) for a caller that keeps several forwards in flight on different streams.
         `proposal` (optional, an `ops.ProposalGrid`; bounded two-level models, inference): the coarse level's density comes from that
         lattice instead of an encoding + MLP launch (mipnerf_forward_proposal); level 0's comp_rgb is then the lattice's silhouette
-        against the background, not a coarse render, and the fine level is NOT the two-level model's: its samples sit elsewhere."""
+        against the background, not a coarse render, and the fine level is NOT the two-level model's: its samples sit elsewhere.  An
+        unbounded=True model takes an `ops.ProposalGrid360`: there is no entry point for that level loop, so the two levels are composed of
+        the stage entry points (`_forward_proposal_360`), `ws` unused; not meant for a hipGraph capture."""
         if proposal is not None:
-            ops._refuse_proposal_model(self, "MipNerf._forward_native(proposal=)")
+            ops._refuse_proposal_model(self, "MipNerf._forward_native(proposal=)", proposal)
         dev = rays.origins.device
         B, N = rays.origins.shape[0], self.num_samples
         ctx = self.mlp.native(dev)
@@ -716,6 +718,8 @@ class MipNerf(torch.nn.Module):
         if proposal is not None:
             if dz is not None:
                 raise NotImplementedError("MipNerf._forward_native(proposal=): density noise belongs to training; lattice proposals are inference only")
+            if isinstance(proposal, ops.ProposalGrid360):
+                return self._forward_proposal_360(f, proposal, randomized, t_rand, u_rand, white_bkgd, ret)
             L.check(L.lib().mipnerf_forward_proposal(ctx.handle, B, C.byref(rp), proposal.cdims, proposal.clo, proposal.chi,
                                                      proposal.lattice.data_ptr(), t_rand.data_ptr() if randomized else None,
                                                      u_rand.data_ptr() if randomized else None, flags, self.precision, ws.data_ptr(),
@@ -724,6 +728,40 @@ class MipNerf(torch.nn.Module):
         L.check(L.lib().mipnerf_forward(ctx.handle, B, C.byref(rp), t_rand.data_ptr() if randomized else None,
                                         u_rand.data_ptr() if randomized else None, None if dz is None else dz.data_ptr(),
                                         flags, self.precision, ws.data_ptr(), ws.numel(), outs, ops._stream()), "mipnerf_forward")
+        return ret
+
+    def _forward_proposal_360(self, f, grid, randomized, t_rand, u_rand, white_bkgd, ret):
+        """The two levels of an unbounded=True model with the coarse density read from a `ProposalGrid360`, through the stage entry points
+        (the drop-in library has no entry point for this level loop): sample_along_rays_360 -> lattice_density_360 -> volumetric_rendering ->
+        resample_along_rays on the inverse-depth posts -> reciprocal_360 -> cast_ipe_360 -> the MLP -> volumetric_rendering.  Every stage is
+        the kernel mipnerf_forward launches for it (its per-stage route), level 0's encoding and MLP launch excepted; writes into `ret`.
+        Cost: five device tensors are allocated per call (both levels' inverse-depth posts, the packed density, the fine encoding and the
+        MLP's output) and the caller's workspace is not used; the per-stage MLP entry point serves one stream at a time per context."""
+        origins, directions, viewdirs, radii, _, near, far = f
+        (rgb0, dist0, acc0, w0, t0), (rgb1, dist1, acc1, w1, t1) = ret
+        B, N = origins.shape[0], self.num_samples
+        if B == 0:
+            return ret
+        dev, lib, st = origins.device, L.lib(), ops._stream()
+        t_inv0, t_inv1 = torch.empty(B, N + 1, device=dev), torch.empty(B, N + 1, device=dev)
+        packed = torch.empty(B, N, 4, device=dev)
+        tr = t_rand.data_ptr() if randomized else None
+        ur = u_rand.data_ptr() if randomized else None
+        white = int(bool(white_bkgd))
+        L.check(lib.mipnerf_sample_along_rays_360(B, N, near.data_ptr(), far.data_ptr(), tr, t_inv0.data_ptr(), t0.data_ptr(), st), "sample_along_rays_360")
+        L.proposal_360_check(L.proposal_360_lib().mipnerf_lattice_density_360(C.byref(grid.cpyramid), grid.footprint, B, N, t0.data_ptr(),
+                                                                              origins.data_ptr(), directions.data_ptr(), radii.data_ptr(),
+                                                                              packed.data_ptr(), st), "lattice_density_360")
+        L.check(lib.mipnerf_volumetric_rendering(B, N, packed.data_ptr(), t0.data_ptr(), directions.data_ptr(), white, rgb0.data_ptr(),
+                                                 dist0.data_ptr(), acc0.data_ptr(), w0.data_ptr(), st), "volumetric_rendering")
+        L.check(lib.mipnerf_resample_along_rays(B, N, t_inv0.data_ptr(), w0.data_ptr(), ur, float(self.resample_padding), t_inv1.data_ptr(), st),
+                "resample_along_rays")
+        ops.reciprocal_360(t_inv1, out=t1)
+        enc = ops.cast_ipe_360(t1, origins, directions, radii, self.min_deg_point, self.max_deg_point, precision=self.precision)
+        venc = ops.pos_enc(viewdirs, 0, self.deg_view) if self.mlp._cfg_extra.get("use_viewdirs", 1) else None
+        act = self.mlp(enc, venc, return_activated=True)[2]
+        L.check(lib.mipnerf_volumetric_rendering(B, N, act.data_ptr(), t1.data_ptr(), directions.data_ptr(), white, rgb1.data_ptr(),
+                                                 dist1.data_ptr(), acc1.data_ptr(), w1.data_ptr(), st), "volumetric_rendering")
         return ret
 
 
@@ -816,12 +854,18 @@ class GraphedFrame:
     `proposal` (opt-in, an `ops.ProposalGrid`; None launches exactly what it launched before): every chunk forward takes its coarse
     density from that lattice (`MipNerf._forward_native(proposal=)`).  The returned `rgb[0]` is then the lattice's silhouette against the
     background, not a coarse render, and the frame is NOT the two-level frame.  The captured graph bakes in the lattice pointer: assigning
-    another `ProposalGrid` object to `.proposal` forces a recapture, as a changed precision does."""
+    another `ProposalGrid` object to `.proposal` forces a recapture, as a changed precision does.  An unbounded=True model takes an
+    `ops.ProposalGrid360` instead (the grid's type must fit the model): its chunk forwards are composed of stage calls
+    (`MipNerf._forward_native`), and such a frame is NEVER captured -- it runs them eagerly on one lane whatever `capture` says."""
 
     def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, lanes: Optional[int] = None,
                  capture: bool = True, proposal=None):
         if proposal is not None:
-            ops._refuse_proposal_model(model, "GraphedFrame(proposal=)")
+            ops._refuse_proposal_model(model, "GraphedFrame(proposal=)", proposal)
+            if capture and isinstance(proposal, ops.ProposalGrid360):
+                import warnings
+                warnings.warn("GraphedFrame(proposal=ProposalGrid360): this frame is not captured into a hipGraph (its chunk forwards are "
+                              "composed of stage calls); capture=True is ignored and the chunks run eagerly on one lane", stacklevel=2)
         self.proposal = proposal
         self.model, self.n, self.chunk, self.white_bkgd, self.dev = model, int(num_rays), int(chunk), bool(white_bkgd), device
         self.capture = bool(capture)
@@ -853,7 +897,8 @@ class GraphedFrame:
         bounds = [(m, lo, min(hi, lo + self.chunk)) for m, start, hi in jobs for lo in range(int(start), int(hi), self.chunk)]
         if not bounds:
             return
-        lanes = min(self.lanes, len(bounds))
+        # a ProposalGrid360's chunk forward goes through the per-stage MLP entry point: one stream at a time per context
+        lanes = 1 if isinstance(self.proposal, ops.ProposalGrid360) else min(self.lanes, len(bounds))
         need = 0
         for m in {id(m): m for m, _, _ in bounds}.values():
             ctx = m.mlp.native(self.dev)
@@ -911,10 +956,10 @@ class GraphedFrame:
             self.graph = None                   # another ProposalGrid (or none) since the capture: the graph holds the other lattice's pointer
         if self.graph is None:
             self._captured_precision, self._captured_proposal = self.model.precision, self.proposal
-            if self.capture:
+            if self.capture and not isinstance(self.proposal, ops.ProposalGrid360):
                 self._capture()
             else:
-                self.graph = False
+                self.graph = False              # (a ProposalGrid360's chunk forwards are composed of stage calls: never captured)
         for dst, src in zip(self.static_in, rays):
             dst.copy_(src)
         if self.graph is False:
@@ -995,7 +1040,7 @@ class CulledFrame:
     live rays -- plain, tightened or adaptive, the siblings included, all with the same grid -- takes its coarse density from that lattice
     (`GraphedFrame(proposal=)`).  Live pixels are bit for bit what `GraphedFrame(proposal=)` yields on the same (tightened) rays; the
     returned `rgb[0]` is then the lattice's silhouette against the background, not a coarse render.  `.proposal` may be reassigned
-    between calls."""
+    between calls.  With a contracted `ops.Occupancy` and an unbounded=True model the grid is an `ops.ProposalGrid360`."""
 
     def __init__(self, model: "MipNerf", num_rays: int, chunk: int, white_bkgd: bool, device: torch.device, occupancy,
                  lanes: Optional[int] = None, outside_occupied: bool = True, cone_scale: float = 1.0, tighten: bool = False,
@@ -1050,7 +1095,7 @@ class CulledFrame:
     @proposal.setter
     def proposal(self, grid) -> None:
         if grid is not None:
-            ops._refuse_proposal_model(self.model, "CulledFrame(proposal=)")
+            ops._refuse_proposal_model(self.model, "CulledFrame(proposal=)", grid)
         self._compact.proposal = grid
 
     @property

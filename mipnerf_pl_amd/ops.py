@@ -626,19 +626,28 @@ class ProposalGrid:
             raise ValueError(f"ProposalGrid: the box needs hi > lo on every axis (got {self.lo} .. {self.hi})")
 
 
-def _refuse_proposal_model(model, name):
-    """lattice proposals replace the coarse level of a bounded two-level model: anything else is refused with a message"""
-    if bool(getattr(model, "unbounded", False)):
-        raise NotImplementedError(f"{name}: unbounded=True models are not supported (their field lives in a contracted space; a contracted "
-                                  "proposal lattice is not implemented)")
+def _refuse_proposal_model(model, name, grid=None):
+    """A lattice proposal replaces the coarse level of a two-level model, and the grid's type says which: a `ProposalGrid` (or no grid: the
+    two-argument call of before) goes with a bounded model, a `ProposalGrid360` with an unbounded=True one.  Every mismatch is refused."""
+    unbounded = bool(getattr(model, "unbounded", False))
+    if isinstance(grid, ProposalGrid360):
+        if not unbounded:
+            raise NotImplementedError(f"{name}: a ProposalGrid360 lies in the contracted space of unbounded=True models; this model is "
+                                      "bounded (its lattice is ops.field_proposal's ProposalGrid)")
+    elif unbounded:
+        raise NotImplementedError(f"{name}: unbounded=True models are not supported by a ProposalGrid (their field lives in a contracted "
+                                  "space): they take the ProposalGrid360 of ops.field_proposal_360")
     if int(getattr(model, "num_levels", 2)) != 2:
         raise NotImplementedError(f"{name}: the lattice replaces the coarse level of a two-level model (num_levels = {model.num_levels})")
 
 
 def field_proposal(model_or_system, grid=256, lo=None, hi=None, cov_scale=1.0, precision=None):
     """`density_grid` of the field on grid^3 (or (nx, ny, nz)) points over lo .. hi, wrapped into a `ProposalGrid`.  unbounded=True
-    models are refused (their field lives in a contracted space)."""
-    _field_mlp(model_or_system, "field_proposal")
+    models are refused (their field lives in a contracted space: `field_proposal_360`)."""
+    try:
+        _field_mlp(model_or_system, "field_proposal")
+    except NotImplementedError as e:
+        raise NotImplementedError(f"{e}; for a proposal lattice of such a model: field_proposal_360") from None
     if lo is None or hi is None:
         raise ValueError("field_proposal: give the box lo .. hi the lattice spans (the rays to be rendered should stay inside it: outside, a "
                          "sample takes the value of the nearest face)")
@@ -657,6 +666,114 @@ def lattice_density(grid, t_samples, origins, directions, radii):
         L.check(L.lib().mipnerf_lattice_density(grid.cdims, grid.clo, grid.chi, _ptr(grid.lattice), B, N1 - 1, _ptr(t_samples), _ptr(o), _ptr(d),
                                                 _ptr(r), _ptr(out), _stream()), "lattice_density")
     return out[..., 3]
+
+
+# ---- the proposal density of the unbounded-scene model: a pyramid of contracted lattices (csrc/kernels_proposal_360.hip) -----------
+class ProposalGrid360:
+    """A pyramid of 1 .. 4 fp32 device lattices [nz_l, ny_l, nx_l] (finest first; the layout of `density_grid`), all over the box lo .. hi
+    of the CONTRACTED space, that stands in for the coarse level's density of an unbounded=True model: `lattice_density_360` reads, per
+    sample, the level(s) whose spacing matches the sample's own contracted covariance (include/mipnerf_proposal_360.h, rules Q1 - Q4).
+    Not a `ProposalGrid`: `space` is 'contracted', `far_radius` is the radius the levels were baked with (beyond |z| = 2 - 1 / far_radius
+    their density is 0) and `footprint` scales the yardstick that picks the level (0: always level 0).  Keeps the host struct the C ABI
+    reads (`cpyramid`) next to the tensors, which must stay alive and in place while it is in use."""
+
+    space = "contracted"
+
+    def __init__(self, lattices, lo, hi, far_radius, footprint=1.0):
+        lattices = [lattices] if torch.is_tensor(lattices) else list(lattices)
+        if not 1 <= len(lattices) <= L.PROPOSAL_MAX_LEVELS:
+            raise ValueError(f"ProposalGrid360: a pyramid has 1 .. {L.PROPOSAL_MAX_LEVELS} levels (got {len(lattices)})")
+        self.lattices = [_f32c(g, "lattice") for g in lattices]
+        _, _, clo, chi = _lattice_args("ProposalGrid360", (2, 2, 2), lo, hi)
+        self.lo, self.hi = tuple(float(v) for v in clo), tuple(float(v) for v in chi)
+        if not all(h > l for l, h in zip(self.lo, self.hi)):
+            raise ValueError(f"ProposalGrid360: the box needs hi > lo on every axis (got {self.lo} .. {self.hi})")
+        self.far_radius, self.footprint = float(far_radius), float(footprint)
+        if not self.far_radius > 1.0:
+            raise ValueError(f"ProposalGrid360: far_radius must exceed 1, the radius of the uncontracted ball (got {far_radius})")
+        if not (self.footprint >= 0.0 and self.footprint < float("inf")):
+            raise ValueError(f"ProposalGrid360: footprint must be finite and >= 0 (got {footprint})")
+        self.dims, self.spacing = [], []
+        self.cpyramid = L.ProposalPyramid()
+        self.cpyramid.levels = len(self.lattices)
+        span = torch.tensor(self.hi, dtype=torch.float32) - torch.tensor(self.lo, dtype=torch.float32)
+        for l, g in enumerate(self.lattices):
+            if g.dim() != 3 or min(g.shape) < 2:
+                raise ValueError(f"ProposalGrid360: level {l}: expected a [nz, ny, nx] lattice with at least 2 points per axis, got {tuple(g.shape)}")
+            dims = (g.shape[2], g.shape[1], g.shape[0])
+            self.dims.append(dims)
+            self.spacing.append(float((span / (torch.tensor(dims, dtype=torch.float32) - 1.0)).max()))       # fp32, as the library forms it
+            if l > 0 and not self.spacing[l] > self.spacing[l - 1]:
+                raise ValueError(f"ProposalGrid360: the spacing must increase strictly from level to level (level {l}: {self.spacing[l]} "
+                                 f"after {self.spacing[l - 1]})")
+            for a in range(3):
+                self.cpyramid.dims[l][a] = dims[a]
+            self.cpyramid.lattice[l] = g.data_ptr()
+        for a in range(3):
+            self.cpyramid.lo[a], self.cpyramid.hi[a] = self.lo[a], self.hi[a]
+
+    def __len__(self):
+        return len(self.lattices)
+
+
+def proposal_ladder_360(grid, levels):
+    """Points per axis of the levels of `field_proposal_360`: n_0 = grid, n_l = max(2, ((n_{l-1} - 1) >> 1) + 1) -- every other point of the
+    level below when n - 1 is even.  A level that would repeat the one below (the ladder has reached 2 points) is an error."""
+    grid, levels = int(grid), int(levels)
+    if not 1 <= levels <= L.PROPOSAL_MAX_LEVELS:
+        raise ValueError(f"field_proposal_360: levels must be in 1 .. {L.PROPOSAL_MAX_LEVELS} (got {levels})")
+    if grid < 2:
+        raise ValueError(f"field_proposal_360: a lattice needs at least 2 points per axis (got {grid})")
+    n = [grid]
+    for l in range(1, levels):
+        n.append(max(2, ((n[-1] - 1) >> 1) + 1))
+        if n[-1] >= n[-2]:
+            raise ValueError(f"field_proposal_360: grid = {grid} has no level {l}: the ladder {n[:-1]} ends at {n[-2]} points per axis")
+    return n
+
+
+def field_proposal_360(model_or_system, grid=256, levels=1, far_radius=64.0, bound=2.0, cov_scale=1.0, footprint=1.0, precision=None):
+    """A `ProposalGrid360` of an unbounded=True model's own density: level l is ONE `density_grid(..., space='contracted', far_radius=,
+    cov_scale=)` call on n_l^3 points (`proposal_ladder_360`) over [-bound, bound]^3 at its own spacing -- a coarser lattice baked at its own
+    lattice Gaussian is the field pre-filtered at that spacing by the model's own encoding, so there is no bake code of its own.
+    `levels` = 1 and `footprint` = 1 are choices, not measurements."""
+    _field_mlp(model_or_system, "field_proposal_360", "contracted")
+    ladder = proposal_ladder_360(grid, levels)
+    bound = float(bound)
+    if not bound > 0.0:
+        raise ValueError(f"field_proposal_360: the half-width of the box must be positive (got {bound})")
+    lattices = [density_grid(model_or_system, n, -bound, bound, cov_scale=cov_scale, precision=precision, space="contracted",
+                             far_radius=far_radius) for n in ladder]
+    return ProposalGrid360(lattices, -bound, bound, far_radius, footprint)
+
+
+def lattice_density_360(grid, t_samples, origins, directions, radii):
+    """The proposal density of the unbounded-scene model on its own (mipnerf_lattice_density_360): per conical frustum [t_i, t_{i+1}] the
+    value of `grid` (a `ProposalGrid360`) at the contracted Gaussian `cast_rays_360(contracted=True)` returns -- the trilinear value of the
+    level its covariance selects at its mean, mixed with the next level's in between two spacings -- as [B, N].  A non-finite mean gives 0
+    (the rules of include/mipnerf_proposal_360.h)."""
+    if not isinstance(grid, ProposalGrid360):
+        raise TypeError(f"lattice_density_360: expected a ProposalGrid360, got {type(grid).__name__}")
+    t_samples = _f32c(t_samples, "t_samples")
+    B, N1 = t_samples.shape
+    out = torch.empty(B, N1 - 1, 4, device=t_samples.device, dtype=torch.float32)
+    o, d, r = _f32c(origins, "origins"), _f32c(directions, "directions"), _f32c(radii, "radii")
+    import ctypes as C
+    with torch.cuda.device(t_samples.device):
+        L.proposal_360_check(L.proposal_360_lib().mipnerf_lattice_density_360(C.byref(grid.cpyramid), grid.footprint, B, N1 - 1, _ptr(t_samples),
+                                                                              _ptr(o), _ptr(d), _ptr(r), _ptr(out), _stream()),
+                             "lattice_density_360")
+    return out[..., 3]
+
+
+def reciprocal_360(t_inv, out=None):
+    """t = 1 / t_inv per fence post (mipnerf_reciprocal_360): the bits of the native forward's own step between the inverse-depth
+    resampling and the fine level's encoding."""
+    t_inv = _f32c(t_inv, "t_inv")
+    out = torch.empty_like(t_inv) if out is None else out
+    with torch.cuda.device(t_inv.device):
+        L.proposal_360_check(L.proposal_360_lib().mipnerf_reciprocal_360(t_inv.numel(), _ptr(t_inv), _ptr(out), _stream()), "reciprocal_360")
+    return out
 
 
 def lattice_ipe_360(dims, lo, hi, cov_scale=1.0, space="contracted", min_deg=0, max_deg=16, precision=L.PREC_FP32, fragments=False,

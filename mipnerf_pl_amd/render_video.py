@@ -156,6 +156,16 @@ def add_common_args(p):
                    metavar="N")
     p.add_argument("--proposal_bound", help="--proposal_grid: the lattice spans [-B, B]^3 (default: the largest coordinate any ray of the "
                    "cameras to be rendered reaches between near and far, plus one cell)", type=float, default=None)
+    p.add_argument("--proposal_space", help="--proposal_grid on a checkpoint of the unbounded-scene model: 'contracted' lays the lattice out in "
+                   "the contracted space (a pyramid of --proposal_levels lattices over [-2, 2]^3, or [-B, B]^3 with --proposal_bound), read at "
+                   "every sample's own contracted Gaussian", choices=["contracted"], default=None)
+    p.add_argument("--proposal_far_radius", help="--proposal_space contracted: the lattice's density is 0 beyond this world radius (default: "
+                   "the farthest point any ray of the cameras to be rendered reaches, plus one cell)", type=float, default=None, metavar="R")
+    p.add_argument("--proposal_levels", help="--proposal_space contracted: levels of the pyramid, 1 to 4, each with every other point of the one "
+                   "below and baked at its own spacing; a sample reads the level(s) as wide as its own Gaussian (default 1: a choice, not a "
+                   "measurement)", type=int, default=None, metavar="L")
+    p.add_argument("--proposal_footprint", help="--proposal_space contracted: scales the width that picks the level; 0 always reads the finest "
+                   "(default 1: a choice, not a measurement)", type=float, default=None, metavar="F")
     p.add_argument("--render_samples", help="samples per ray and level to render with (default: the checkpoint's num_samples; the parameters do "
                    "not depend on it); independent of --cull", type=int, default=None)
     return p
@@ -227,23 +237,52 @@ def refuse_proposal_without_grid(args):
         raise SystemExit(f"--proposal_grid {grid}: the lattice needs at least 4 points per axis")
     if getattr(args, "proposal_bound", None) is not None and not args.proposal_bound > 0:
         raise SystemExit(f"--proposal_bound {args.proposal_bound}: the half-width of the box must be positive")
+    space = getattr(args, "proposal_space", None)
+    if space is not None and grid is None:
+        raise SystemExit("--proposal_space describes the lattice of --proposal_grid: give --proposal_grid as well")
+    for flag in ("proposal_far_radius", "proposal_levels", "proposal_footprint"):
+        if getattr(args, flag, None) is not None and space != "contracted":
+            raise SystemExit(f"--{flag} belongs to --proposal_space contracted")
+    levels, footprint, far = (getattr(args, k, None) for k in ("proposal_levels", "proposal_footprint", "proposal_far_radius"))
+    if levels is not None and not 1 <= levels <= 4:
+        raise SystemExit(f"--proposal_levels {levels}: a pyramid has 1 to 4 levels")
+    if footprint is not None and not (footprint >= 0 and footprint < float("inf")):
+        raise SystemExit(f"--proposal_footprint {footprint}: must be finite and >= 0")
+    if far is not None and not far > 1:
+        raise SystemExit(f"--proposal_far_radius {far}: must exceed 1, the radius of the uncontracted ball")
+    if space is not None:
+        from .ops import proposal_ladder_360
+        try:
+            proposal_ladder_360(grid, 1 if levels is None else levels)
+        except ValueError as e:
+            raise SystemExit(f"--proposal_grid {grid} --proposal_levels {levels}: {e}")
 
 
 def refuse_scene360_proposal(args, system):
-    """--proposal_grid belongs to bounded checkpoints: a llff / realdata360 checkpoint (and any unbounded-scene model) exits with a
-    message before anything is rendered."""
+    """--proposal_grid and the checkpoint's model must agree on the space: a llff / realdata360 checkpoint (and any unbounded-scene model)
+    needs --proposal_space contracted, a bounded one must not have it.  Exits with a message before anything is rendered."""
     if getattr(args, "proposal_grid", None) is None:
         return
-    if is_scene360(system.hparams) or bool(getattr(system.mip_nerf, "unbounded", False)):
-        raise SystemExit("--proposal_grid: this checkpoint holds a captured scene ({}); the proposal lattice is implemented for bounded "
-                         "(Blender) checkpoints only -- its rays leave any box and the unbounded-scene model lives in a contracted space.  "
-                         "Render it without --proposal_grid".format(system.hparams.get("dataset_name")))
+    unbounded, space = bool(getattr(system.mip_nerf, "unbounded", False)), getattr(args, "proposal_space", None)
+    if space is None and (is_scene360(system.hparams) or unbounded):
+        raise SystemExit("--proposal_grid: this checkpoint holds a captured scene ({}); its rays leave any box and the unbounded-scene model "
+                         "lives in a contracted space -- give --proposal_space contracted (and optionally --proposal_levels L, "
+                         "--proposal_far_radius R, --proposal_footprint F) for a lattice laid out there, or render it without "
+                         "--proposal_grid".format(system.hparams.get("dataset_name")))
+    if space is not None and not unbounded:
+        raise SystemExit(f"--proposal_space {space}: this checkpoint holds a bounded model; its proposal lattice lies in world space -- drop "
+                         "--proposal_space")
 
 
 def cli_proposal(args, system, frames, distorted=None):
     """The proposal lattice the --proposal flags ask for (None without --proposal_grid); `frames` / `distorted` as in `cli_occupancy`."""
     if getattr(args, "proposal_grid", None) is None:
         return None
+    if getattr(args, "proposal_space", None) is not None:
+        levels, footprint = getattr(args, "proposal_levels", None), getattr(args, "proposal_footprint", None)
+        return scene_proposal(system, frames if args.proposal_far_radius is None else None, grid=args.proposal_grid, bound=args.proposal_bound,
+                              distorted=distorted, space=args.proposal_space, far_radius=args.proposal_far_radius,
+                              levels=1 if levels is None else levels, footprint=1.0 if footprint is None else footprint)
     return scene_proposal(system, frames if args.proposal_bound is None else None, grid=args.proposal_grid, bound=args.proposal_bound,
                           distorted=distorted)
 
