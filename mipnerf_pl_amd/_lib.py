@@ -289,6 +289,24 @@ PROPOSAL_360_SIGNATURES = {
     "mipnerf_reciprocal_360": (C.c_int, [_I64, _P, _P, _P]),
 }
 
+# include/mipnerf_fuse.h: rendered depth fused into a truncated signed distance volume, in an eleventh library; the other ten keep their
+# ABI versions and their entry points
+FUSE_LIB_PATH = os.environ.get("MIPNERF_FUSE_LIB", os.path.join(HERE, "csrc", "libmipnerf_fuse.so"))
+FUSE_ABI = 1
+FUSE_MAX_QUANTILES = 4
+FUSE_FRAME_FLOATS = 16
+FUSE_FRAMES_PER_LAUNCH = 8
+_FUSE_VOLUME = [C.POINTER(_I32), C.POINTER(_F), C.POINTER(_F), _F, _I32, _I64, _P, _P, _P, _I64, _P, _P]
+FUSE_SIGNATURES = {
+    "mipnerf_fuse_abi_version": (C.c_int, []),
+    "mipnerf_fuse_last_error": (C.c_char_p, []),
+    "mipnerf_fuse_depth_quantile": (C.c_int, [_I64, _I32, _P, _P, _I32, C.POINTER(_F), _P, _P]),
+    "mipnerf_fuse_projection": (C.c_int, [_P, _P]),
+    "mipnerf_fuse_integrate": (C.c_int, _FUSE_VOLUME + [_P]),
+    "mipnerf_fuse_finalise": (C.c_int, [C.POINTER(_I32), _P, _P, _F, _P, _P]),
+    "mipnerf_fuse_integrate_host": (C.c_int, list(_FUSE_VOLUME)),
+}
+
 _handles = {}
 
 
@@ -396,6 +414,16 @@ def proposal_360_lib():
 
 def proposal_360_check(rc: int, what: str = "") -> None:
     _check(rc, lambda: proposal_360_lib().mipnerf_proposal_360_last_error(), what)
+
+
+def fuse_lib():
+    """Load (once) libmipnerf_fuse.so.  No fallback: a missing library is an error."""
+    return _load(FUSE_LIB_PATH, FUSE_SIGNATURES, "fusing depth into a signed distance volume has no fallback.",
+                 ("mipnerf_fuse_abi_version", FUSE_ABI))
+
+
+def fuse_check(rc: int, what: str = "") -> None:
+    _check(rc, lambda: fuse_lib().mipnerf_fuse_last_error(), what)
 
 
 def preview_reg_lib():

@@ -4,7 +4,8 @@ renderer over lattices that store only the rows next to an occupied cell) and li
 with respect to the lattice and an Adam step on it) and libmipnerf_preview_360.so (the renderer of the unbounded-scene model: a lattice over
 the contracted space) and libmipnerf_preview_reg.so (the gradient of a total-variation term and an SH decay on the tuned lattice) and
 libmipnerf_preview_tune_360.so (the gradient of the contracted-space renderer with respect to its lattice) and libmipnerf_proposal_360.so
-(the proposal density of the unbounded-scene model from a pyramid of contracted lattices) for gfx950 in-tree (hipcc cross-compiles without a GPU).
+(the proposal density of the unbounded-scene model from a pyramid of contracted lattices) and libmipnerf_fuse.so (rendered depth fused into a
+truncated signed distance volume) for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
     python -m mipnerf_pl_amd.build [--force]
 
@@ -130,6 +131,11 @@ PREVIEW_TUNE_360_UNITS = [("kernels_preview_tune_360.hip", ["-ffp-contract=off"]
 PROPOSAL_360_LIB = os.path.join(CSRC, "libmipnerf_proposal_360.so")
 PROPOSAL_360_UNITS = [("kernels_proposal_360.hip", ["-ffp-contract=off"]),   # the Gaussian rounds as in k_cast_ipe_360, the blends as stated in lattice_sample_360.hpp
                       ("proposal_360_capi.hip", ["-ffp-contract=off"])]       # the spacings and inv_h are formed on the host
+# rendered depth fused into a truncated signed distance volume (include/mipnerf_fuse.h): an eleventh library, so the other ten keep their
+# entry points and their bytes
+FUSE_LIB = os.path.join(CSRC, "libmipnerf_fuse.so")
+FUSE_UNITS = [("kernels_fuse.hip", ["-ffp-contract=off"]),   # the projection rows, D - t and s / trunc round as stated in fuse_rules.hpp
+              ("fuse_capi.hip", ["-ffp-contract=off"])]       # the spacing is formed on the host; the host build of rules T rounds like the kernel
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall",
           "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result"]
 
@@ -196,19 +202,20 @@ def build(force: bool = False, verbose: bool = True) -> str:
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_preview_reg.h"))
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_preview_tune_360.h"))
     deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_proposal_360.h"))
+    deps.append(os.path.join(os.path.dirname(HERE), "include", "mipnerf_fuse.h"))
     stamp = os.path.join(CSRC, ".build_stamp_" + os.path.basename(LIB))
     units = UNITS[:-1] + variant_units() + UNITS[-1:]          # capi.hip last
-    dig = _digest(deps, COMMON + sum((f for _, f in units + PREVIEW_UNITS + PREVIEW_MIP_UNITS + PREVIEW_SPARSE_UNITS + PREVIEW_TUNE_UNITS + PREVIEW_360_UNITS + PREVIEW_REG_UNITS + PREVIEW_TUNE_360_UNITS + PROPOSAL_360_UNITS), []))
+    dig = _digest(deps, COMMON + sum((f for _, f in units + PREVIEW_UNITS + PREVIEW_MIP_UNITS + PREVIEW_SPARSE_UNITS + PREVIEW_TUNE_UNITS + PREVIEW_360_UNITS + PREVIEW_REG_UNITS + PREVIEW_TUNE_360_UNITS + PROPOSAL_360_UNITS + FUSE_UNITS), []))
     if not force and os.path.exists(LIB) and os.path.exists(DIAG_LIB) and os.path.exists(PREVIEW_LIB) and os.path.exists(PREVIEW_MIP_LIB) and \
             os.path.exists(PREVIEW_SPARSE_LIB) and os.path.exists(PREVIEW_TUNE_LIB) and os.path.exists(PREVIEW_360_LIB) and os.path.exists(PREVIEW_REG_LIB) and \
-            os.path.exists(PREVIEW_TUNE_360_LIB) and os.path.exists(PROPOSAL_360_LIB) and os.path.exists(stamp) and open(stamp).read() == dig:
+            os.path.exists(PREVIEW_TUNE_360_LIB) and os.path.exists(PROPOSAL_360_LIB) and os.path.exists(FUSE_LIB) and os.path.exists(stamp) and open(stamp).read() == dig:
         if verbose:
             print(f"[build] {LIB} is up to date")
         return LIB
     cc = hipcc()
     objs = []
     procs = []
-    for src, extra in units + DIAG_UNITS + PREVIEW_UNITS + PREVIEW_MIP_UNITS + PREVIEW_SPARSE_UNITS + PREVIEW_TUNE_UNITS + PREVIEW_360_UNITS + PREVIEW_REG_UNITS + PREVIEW_TUNE_360_UNITS + PROPOSAL_360_UNITS:
+    for src, extra in units + DIAG_UNITS + PREVIEW_UNITS + PREVIEW_MIP_UNITS + PREVIEW_SPARSE_UNITS + PREVIEW_TUNE_UNITS + PREVIEW_360_UNITS + PREVIEW_REG_UNITS + PREVIEW_TUNE_360_UNITS + PROPOSAL_360_UNITS + FUSE_UNITS:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
         cmd = [cc] + COMMON + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
@@ -225,6 +232,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
             print(f"[build] FAILED: {src}")
     if failed:
         raise RuntimeError("hipcc failed")
+    fuse_objs = objs[len(objs) - len(FUSE_UNITS):]
+    objs = objs[:len(objs) - len(FUSE_UNITS)]
     prop360_objs = objs[len(objs) - len(PROPOSAL_360_UNITS):]
     objs = objs[:len(objs) - len(PROPOSAL_360_UNITS)]
     tune360_objs = objs[len(objs) - len(PREVIEW_TUNE_360_UNITS):]
@@ -255,7 +264,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     subprocess.check_call(["gcc", "-shared", "-fPIC", "-o", os.path.join(stub_dir, "libamdhip64.so"), stub_c])
     rocm_lib = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib")
     # The dynamic symbol table is the C ABI and nothing else: a linker version script keeps `mipnerf_*` (the entry points
-    # include/mipnerf_hip.h / mipnerf_diag.h / mipnerf_preview.h / mipnerf_preview_mip.h / mipnerf_preview_sparse.h / mipnerf_preview_tune.h / mipnerf_preview_360.h / mipnerf_preview_reg.h / mipnerf_preview_tune_360.h / mipnerf_proposal_360.h declare) and makes every C++ launcher, kernel handle and table blob local.
+    # include/mipnerf_hip.h / mipnerf_diag.h / mipnerf_preview.h / mipnerf_preview_mip.h / mipnerf_preview_sparse.h / mipnerf_preview_tune.h / mipnerf_preview_360.h / mipnerf_preview_reg.h / mipnerf_preview_tune_360.h / mipnerf_proposal_360.h / mipnerf_fuse.h declare) and makes every C++ launcher, kernel handle and table blob local.
     vers = os.path.join(stub_dir, "exports.map")
     with open(vers, "w") as f:
         f.write("{ global: mipnerf_*; local: *; };\n")
@@ -298,6 +307,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
         print("[build]", " ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)
     cmd = ["g++", "-shared", "-fPIC", "-o", PROPOSAL_360_LIB] + prop360_objs + cmd[cmd.index("-Wl,--version-script=" + vers):]
+    if verbose:
+        print("[build]", " ".join(cmd))
+    subprocess.check_call(cmd, cwd=CSRC)
+    cmd = ["g++", "-shared", "-fPIC", "-o", FUSE_LIB] + fuse_objs + cmd[cmd.index("-Wl,--version-script=" + vers):]
     if verbose:
         print("[build]", " ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)

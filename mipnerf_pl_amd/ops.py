@@ -1316,3 +1316,97 @@ def guided_draw(state, r, order, ring_start=0):
                                             _ptr(state.header), _ptr(order), _ptr(state.weight), _ptr(state.cell), state.ring_len,
                                             int(ring_start), _stream()), "guided_draw")
     return order
+
+
+# ---- rendered depth fused into a truncated signed distance volume (csrc/kernels_fuse.hip, include/mipnerf_fuse.h) ---------------------
+def depth_quantile(weights, t_samples, q=0.5, out=None):
+    """The depth at which a ray's opacity reaches `q` (mipnerf_fuse_depth_quantile, rule D of include/mipnerf_fuse.h): `weights` [B, N] and
+    `t_samples` [B, N + 1] as `MipNerf.forward` returns a level's (world distances, for the unbounded-scene model too) -> [B], or [B, Q]
+    for a sequence of up to 4 quantiles.  q = 0.5 is the median depth; a ray whose weights sum to less than q has the depth +inf: `q` is an
+    opacity, not a share of acc, so a ray that misses the object has no depth."""
+    import ctypes as C
+    single = not hasattr(q, "__len__")
+    qs = [float(q)] if single else [float(v) for v in q]
+    if not 1 <= len(qs) <= L.FUSE_MAX_QUANTILES:
+        raise ValueError(f"depth_quantile: 1 to {L.FUSE_MAX_QUANTILES} quantiles per call, got {len(qs)}")
+    w, t = _f32c(weights, "weights"), _f32c(t_samples, "t_samples")
+    if w.dim() != 2 or t.dim() != 2 or t.shape[0] != w.shape[0] or t.shape[1] != w.shape[1] + 1:
+        raise ValueError(f"depth_quantile: expected weights [B, N] and t_samples [B, N + 1], got {tuple(w.shape)} and {tuple(t.shape)}")
+    B, N = w.shape
+    shape = (B,) if single else (B, len(qs))
+    if out is None:
+        out = torch.empty(shape, device=w.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != w.device:
+        raise ValueError(f"depth_quantile: bad preallocated output {tuple(out.shape)} (want {shape}, contiguous fp32 on {w.device})")
+    with torch.cuda.device(w.device):
+        L.fuse_check(L.fuse_lib().mipnerf_fuse_depth_quantile(B, N, _ptr(w), _ptr(t), len(qs), (C.c_float * len(qs))(*qs), _ptr(out), _stream()),
+                     "depth_quantile")
+    return out
+
+
+def fuse_projection(cameras):
+    """The frame records of `camera_record` rows (mipnerf_fuse_projection, rule P of include/mipnerf_fuse.h; host only): [F, 32] ->
+    [F, 16] float32 on the CPU, each P[3][4] | W, H, near, far with (a, b, t) = P (p, 1), t the ray parameter of the world point p and
+    (a / t, b / t) its continuous pixel coordinate.  Camera modes 0 and 1; a distorted camera (modes 2 and 3) is refused
+    (NotImplementedError): fuse ideal pinhole frames of the capture's K instead, as `render_video.PathGen` builds them."""
+    import numpy as np
+    cams = np.ascontiguousarray(torch.as_tensor(cameras).detach().cpu().reshape(-1, 32).to(torch.float32).numpy())
+    frames = np.zeros((cams.shape[0], L.FUSE_FRAME_FLOATS), np.float32)
+    for f in range(cams.shape[0]):
+        L.fuse_check(L.fuse_lib().mipnerf_fuse_projection(cams[f].ctypes.data, frames[f].ctypes.data), f"fuse_projection (camera {f})")
+    return torch.from_numpy(frames)
+
+
+class TSDF:
+    """A truncated signed distance volume over the lattice dims = (nx, ny, nz) of the box lo .. hi (include/mipnerf_fuse.h, rules T and F):
+    two fp32 planes `sum` and `count` [nz, ny, nx] on the device.  `integrate` adds depth frames, in order and without atomics, so the
+    bytes do not depend on how the frames are split over calls; `lattice` is the volume whose zero level set `isosurface(v, 0.0, lo, hi)`
+    cuts -- no density threshold.  `trunc`: the truncation distance in world units."""
+
+    def __init__(self, dims, lo, hi, trunc, device="cuda"):
+        self.dims, self.cdims, self.clo, self.chi = _lattice_args("TSDF", dims, lo, hi)
+        self.lo, self.hi, self.trunc = tuple(self.clo), tuple(self.chi), float(trunc)
+        if min(self.dims) < 2 or 7 * self.dims[0] * self.dims[1] * self.dims[2] >= 2 ** 31:
+            raise ValueError(f"TSDF: a lattice needs 2 points per axis and 7 nx ny nz < 2^31, got {self.dims}")
+        if not (self.trunc > 0.0 and self.trunc < float("inf")):
+            raise ValueError(f"TSDF: trunc must be finite and > 0, got {trunc!r}")
+        shape = (self.dims[2], self.dims[1], self.dims[0])
+        self.sum = torch.zeros(shape, device=device, dtype=torch.float32)
+        self.count = torch.zeros(shape, device=device, dtype=torch.float32)
+
+    def integrate(self, frames, depth, offsets=None, carve=True):
+        """frames [F, 16] (`fuse_projection`; CPU or device), depth: one fp32 device buffer that holds frame f's [H_f, W_f] image at
+        offsets[f] (int64 [F]; None: the images lie one behind the other).  A pixel's depth is the ray parameter of its surface (what
+        `depth_quantile` returns): +inf carves the ray free over [near, far] (carve=False: skipped), NaN / 0 / negative are skipped."""
+        fr = torch.as_tensor(frames).detach().to(torch.float32).reshape(-1, L.FUSE_FRAME_FLOATS)
+        host = fr.cpu()
+        F = host.shape[0]
+        depth = _f32c(depth, "depth").reshape(-1)
+        pixels = (host[:, 12].double() * host[:, 13].double()).to(torch.int64)
+        if offsets is None:
+            off = torch.cumsum(pixels, 0) - pixels
+        else:
+            off = torch.as_tensor(offsets).detach().cpu().to(torch.int64).reshape(-1)
+        if off.shape[0] != F:
+            raise ValueError(f"TSDF.integrate: one offset per frame ({F}), got {off.shape[0]}")
+        if F and (bool((off < 0).any()) or bool((off + pixels > depth.numel()).any()) or bool((pixels < 1).any())):
+            raise ValueError(f"TSDF.integrate: a frame's image does not lie inside the depth buffer ({depth.numel()} floats)")
+        dev = self.sum.device
+        fr, off = fr.to(dev).contiguous(), off.to(dev).contiguous()
+        with torch.cuda.device(dev):
+            L.fuse_check(L.fuse_lib().mipnerf_fuse_integrate(self.cdims, self.clo, self.chi, self.trunc, int(bool(carve)), F, _ptr(fr), _ptr(off),
+                                                             _ptr(depth), depth.numel(), _ptr(self.sum), _ptr(self.count), _stream()),
+                         "TSDF.integrate")
+        return self
+
+    def lattice(self, unseen="inside"):
+        """[nz, ny, nx] fp32: -(sum / count) where a frame updated the point, else +1 (unseen='inside', the default: space carving -- a
+        point deeper than trunc behind every view's surface is never updated, and calling it outside wraps the object in a second, inner
+        shell) or -1 ('outside').  Inside is > 0, the convention of `isosurface`."""
+        if unseen not in ("inside", "outside"):
+            raise ValueError(f"TSDF.lattice: unseen must be 'inside' or 'outside', got {unseen!r}")
+        out = torch.empty_like(self.sum)
+        with torch.cuda.device(out.device):
+            L.fuse_check(L.fuse_lib().mipnerf_fuse_finalise(self.cdims, _ptr(self.sum), _ptr(self.count), 1.0 if unseen == "inside" else -1.0,
+                                                            _ptr(out), _stream()), "TSDF.lattice")
+        return out
