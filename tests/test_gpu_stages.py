@@ -286,7 +286,9 @@ def test_mipnerf360_path(G, contracted, randomized):
     mean and covariance, off-axis IPE) on the GPU against oracle/mipnerf360_oracle.py.  PARITY UNPINNED: the oracle
     restates Barron et al. 2022 (the reference's own code for this path is dead and wrong, see the oracle header);
     stated tolerances: t 1e-6 relative, means 2e-6, covariances 3e-4 of the largest entry (fp32 limit at |x| ~ 1e3: measured 1.5e-4),
-    features 1e-4 when contracted (|y| <= 2), and the structure properties below."""
+    features 1e-4 when contracted (|y| <= 2), and the structure properties below.  This is the parity statement against the oracle at 6
+    degrees; the per-entry statement -- every fence post, mean, covariance and feature against float64 with its own budget, at the
+    shipped 16 degrees, on the tiled kernel and the fragments too -- is tests/test_gpu_ipe360_forward.py (fixture: tests/ipe360_forward.py)."""
     from mipnerf_pl_amd import ops, _lib as L
     from oracle import mipnerf360_oracle as o360
     DEV = G.DEV

@@ -246,7 +246,9 @@ def test_bf16_off_axis_encoding_vs_the_gaussian_expectation(G):
     sine / exp2); round 4 compared them with the sibling per-direction kernel only.  Here: against the closed-form Gaussian expectation
     E[sin(2^l p.x)] = sin(2^l p.mu) exp(-0.5 4^l p^T Sigma p) (and cos) evaluated in FLOAT64 on the oracle's contracted Gaussians, degree by
     degree.  Error budget per feature: half a bf16 ulp of a value <= 1 (2^-9) + the fp32 phase: the kernel forms y = 2^l fl32(p.mu) in fp32,
-    |p.mu| <= 2 after the contraction, so the phase is off by up to 2^l x 2.4e-7 rad (what the fp32 rows and the oracle carry as well)."""
+    |p.mu| <= 2 after the contraction, so the phase is off by up to 2^l x 2.4e-7 rad (what the fp32 rows and the oracle carry as well).
+    One bound per degree over the batch; the per-entry statement -- half a bf16 ulp at each feature's own truth plus its own phase and
+    damping terms, from the kernel's own fp32 Gaussians -- is tests/test_gpu_ipe360_forward.py (fixture: tests/ipe360_forward.py)."""
     from mipnerf_pl_amd import _lib as L
     from mipnerf_pl_amd import ops
     from oracle import mipnerf360_oracle as o360
